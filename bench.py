@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: Flipped-VQA training samples/s on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N --steps K --warmup W]          (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if asked and prints the line;
+everything that takes runs or legs of its own (the instrumented `roofline` passes, `other_configs`, `cpu_baseline`) runs only
+with --full.
+
+--dump-outputs DIR: after the timed steps (before anything --full adds), rank 0 writes what the last timed step handed its
+caller as DIR/<name>.npy (float32, 64 MB at most, see OUTPUTS): the three losses, the gradient norm, the trainables after
+AdamW and their gradients. Weights are closed-form and batches seeded, so equal arguments give equal inputs on every run.
 
 One step = one full training step of the hot path on one synthetic batch already resident in
 HBM: LLaMA-Adapter forward over the frame-spliced token stream, the flipped loss(es), backward,
@@ -10,7 +18,7 @@ Workload at N=1 = BASELINE configs[1]: LLaMA-7B (random-init, closed-form), bf16
 batch 8 per GPU, max_feats 10, VQA loss only. N>1 = the same per-GPU work on every rank (weak
 scaling), one all-reduce(mean) of 4.5 M fp32 gradients per step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields and step_roofline, plus with --full
   roofline     — the dominant kernel family (the bf16 projection GEMMs: the 4-wave whole-tile kernel gemm4w_k
                  and the split-K kernel gemm_sk_256, every launch of every instantiation): algorithmic
                  FLOPs / launch time against the 2.5 PFLOP/s dense bf16 MFMA peak. Launch times come from
@@ -23,7 +31,7 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                  measured reads 5 % long (`frac_brackets_as_measured`). Kernel durations cover ~96.5 % of a step; the rest
                  are the ~480 kernel boundaries of a step (~1.9 us each), which `non_gemm_ms_per_step` contains; `alg_bytes_per_launch` (operands + outputs of each launch, from its shape)
                  stands beside `traffic` (fabric bytes per launch from the committed PMC passes);
-  step_roofline— algorithmic FLOPs of the whole step (SURVEY §8d formula) / step time;
+  step_roofline— (every run) algorithmic FLOPs of the whole step (SURVEY §8d formula) / step time;
   cpu_baseline — the CPU oracle (oracle/ref_cpu.py) timed on this host's cores on BASELINE configs[0]:
                  full-depth 7B, B=2, all three losses, forward+backward+AdamW, one warm-up + timed steps within a
                  host-time budget (rank 0, N=1 only; ONE timed step while the other-config legs are on);
@@ -121,6 +129,40 @@ def launch_alg_bytes(kind, flops, R, D, Hf, V):
                 b += 2.0 * R * 2 * N + 2.0 * R * N      # reads (s, t) rows of 2N, writes d(a|b) rows of 2N instead of N
             return b
     return None
+
+
+DUMP_BUDGET = 60 * 10**6     # array bytes --dump-outputs may write; with the .npy headers the files stay under 64 MB
+OUTPUTS = ("losses", "grad_norm", "trainables", "grads")
+
+
+def step_outputs(outs, opt):
+    """What one training step hands its caller, as host float32 arrays: the (vqa, vaq, qav) losses, the gradient norm the loss
+    scaler returns, the flat trainables after AdamW and their (unscaled) flat gradient."""
+    import numpy as np
+    vqa, vaq, qav, norm = outs
+    f32 = lambda t: t.detach().float().reshape(-1).cpu().numpy()
+    return {"losses": np.concatenate([f32(vqa), f32(vaq), f32(qav)]), "grad_norm": f32(norm),
+            "trainables": f32(opt.flat.flat), "grads": f32(opt.flat.flat_grad)}
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET, seed=0):
+    """Writes {name: array} as out_dir/<name>.npy (float32 / float64 kept, anything else as float32). If they hold more than
+    `budget` bytes, every array is cut to the same fraction of its elements by a sample fixed by `seed` and its size (the same
+    indices on every run), flattened. Returns {name: elements written}."""
+    import numpy as np
+    arrays = {n: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, budget / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for n, a in arrays.items():
+        if keep < 1.0:
+            k = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+        written[n] = int(a.size)
+    return written
 
 
 def _cpu_extrapolated(seq_len, max_feats):
@@ -367,10 +409,17 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"],
                     help="storage type of activations / frozen weights: bf16 (BASELINE configs), fp16 (the reference's own), fp32 (exact)")
     ap.add_argument("--n_layers", type=int, default=0, help="debug only: reduced depth (marks the line invalid)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs or legs of its own: the instrumented roofline passes, the other BASELINE "
+                         "configs and the CPU baseline (a plain run times the steps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no_other_configs", action="store_true",
-                    help="skip the short C3 / C4 / C5 legs that follow the default (C2) workload at N = 1")
+                    help="with --full: skip the short C3 / C4 / C5 legs that follow the default (C2) workload at N = 1")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this parent has made no GPU call; it starts the N ranks as a CHILD
@@ -468,8 +517,8 @@ def main():
         opt.zero_grad()
         vqa, vaq, qav = net(batches[i % n_batches])
         loss = vqa + vaq + qav
-        scaler(loss, opt, parameters=None, update_grad=True)
-        return loss
+        norm = scaler(loss, opt, parameters=None, update_grad=True)
+        return loss, (vqa, vaq, qav, norm)
 
     def fence():
         torch.cuda.synchronize()
@@ -490,9 +539,12 @@ def main():
         net.comm_events = []                 # an event pair around every gradient all-reduce of the timed steps
     t0 = time.perf_counter()
     for i in range(a.steps):
-        loss = one_step(i)
+        loss, outs = one_step(i)
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:         # the last timed step's results, before --full's passes step the model further
+        written = write_outputs(a.dump_outputs, step_outputs(outs, opt))
+        print(f"[bench] outputs of timed step {a.steps} -> {a.dump_outputs}: {written}", file=sys.stderr, flush=True)
     comm = None
     if world > 1:
         ev, net.comm_events = net.comm_events, None
@@ -545,8 +597,10 @@ def main():
         return ms_pass, rec
 
     roof = None
-    ms_sparse, rec_sparse = instrumented(STRIDE)
-    ms_dense, rec_dense = instrumented(1)
+    ms_sparse, rec_sparse, ms_dense, rec_dense = None, [], None, []
+    if a.full:
+        ms_sparse, rec_sparse = instrumented(STRIDE)
+        ms_dense, rec_dense = instrumented(1)
     if rank == 0 and rec_sparse:
         # calibration: what an event pair with NOTHING between reads on this stream (the record-to-record spacing that
         # every bracketed launch also contains); taken off per launch so that the figure is the kernel's own duration — checked
@@ -681,9 +735,10 @@ def main():
                        "global_batch": a.batch_size * world, "seq_len": a.seq_len,
                        "parallelism": f"dp{world}" if world > 1 else "single"},
             "loss": loss_val,
-            "roofline": roof,
-            "step_roofline": step_roofline_of(fl, ms, peak, model, batches, a.batch_size, a.seq_len, tasks),
         }
+        if a.full:
+            out["roofline"] = roof
+        out["step_roofline"] = step_roofline_of(fl, ms, peak, model, batches, a.batch_size, a.seq_len, tasks)
         if comm is not None:
             out["comm"] = comm
         if diag is not None:
@@ -701,7 +756,7 @@ def main():
             out["value_per_gpu"] = value / world         # the N = 1-equivalent rate: read it against BENCH's `value`
         default_workload = (a.model == "7B" and a.batch_size == 8 and a.seq_len == 128 and a.dtype == "bf16"
                             and not (a.vaq or a.qav) and not a.n_layers)
-        legs_on = world == 1 and default_workload and not a.no_other_configs
+        legs_on = a.full and world == 1 and default_workload and not a.no_other_configs
         if legs_on:
             # BASELINE configs[2..4] as one GPU runs them, driver-timed with the C2 line (round-4 verdict #3): free the C2
             # model first (7B: ~30 GiB with the transposed copies; the 13B leg needs ~58)
@@ -720,7 +775,7 @@ def main():
                 except Exception as e:   # a leg must never take the headline measurement down
                     out["other_configs"][name] = {"error": repr(e)[:300]}
                 print(f"[bench] {name}: {out['other_configs'][name]}", file=sys.stderr, flush=True)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 # with the legs on, ONE timed oracle step (warm-up + one: ~170 s on the box's 128 threads) keeps the command < 450 s
                 out["cpu_baseline"] = cpu_baseline_leg(a.seq_len, 10, max_timed=1 if legs_on else 3)

@@ -61,7 +61,9 @@ def _tiny_model():
     return cfg, llama.Transformer(ma, args)
 
 
-def test_model_has_reference_state_dict_and_no_cpu_path():
+def test_model_has_reference_state_dict_and_no_cpu_path(monkeypatch):
+    # the synthetic-tokenizer switch off, whatever the process set before (tests/dp_worker.py sets it on import)
+    monkeypatch.delenv("FVQA_SYNTHETIC_TOKENIZER", raising=False)
     cfg, model = _tiny_model()
     want = {n: s for n, s, _ in synth.state_spec(cfg)}
     have = {n: tuple(p.shape) for n, p in model.named_parameters()}
@@ -232,6 +234,34 @@ def test_bench_launcher_command_and_env():
     assert env["FVQA_DIST_BACKEND"] == "gloo" and env["FVQA_BENCH_REHEARSAL"] == "1"
     env = bench.launcher_env(2, 0, env={})                     # no device visible: nothing to rehearse on
     assert "FVQA_DIST_BACKEND" not in env
+
+
+def test_bench_dump_outputs_files_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: what a step hands its caller as float32 arrays; written whole under the budget, and above it
+    every array cut to the same fraction by a sample that is the same on every call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    flat = types.SimpleNamespace(flat=torch.arange(1000, dtype=torch.float32), flat_grad=-torch.arange(1000.0))
+    outs = (torch.tensor(2.5, dtype=torch.bfloat16), torch.tensor(0.0), torch.tensor(1.0), torch.tensor(7.0))
+    arrays = bench.step_outputs(outs, types.SimpleNamespace(flat=flat))
+    assert sorted(arrays) == sorted(bench.OUTPUTS) and all(a.dtype == np.float32 for a in arrays.values())
+    assert arrays["losses"].tolist() == [2.5, 0.0, 1.0] and arrays["grad_norm"].tolist() == [7.0]
+    whole = bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert whole == {"losses": 3, "grad_norm": 1, "trainables": 1000, "grads": 1000}
+    for n in bench.OUTPUTS:
+        got = np.load(tmp_path / "whole" / f"{n}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, arrays[n])
+    big = {"a": np.arange(10**6, dtype=np.float64), "b": np.ones(10**5, dtype=np.int32)}
+    cut = bench.write_outputs(str(tmp_path / "cut1"), big, budget=80000)
+    assert bench.write_outputs(str(tmp_path / "cut2"), big, budget=80000) == cut
+    assert sum(np.load(tmp_path / "cut1" / f"{n}.npy").nbytes for n in big) <= 80000
+    a1, a2 = np.load(tmp_path / "cut1" / "a.npy"), np.load(tmp_path / "cut2" / "a.npy")
+    assert a1.dtype == np.float64 and np.array_equal(a1, a2) and np.all(np.diff(a1) > 0)   # same sorted sample both times
+    assert np.load(tmp_path / "cut1" / "b.npy").dtype == np.float32
+    assert bench.DUMP_BUDGET <= 64 * 10**6
 
 
 def _sk_plan(M, N, K, dtype, n_cu=256):

@@ -1,13 +1,14 @@
 #!/bin/bash
 # usage: tools/ab_bench.sh OUTDIR TAG_A LIB_A TAG_B LIB_B [rounds]   — interleaved same-box A/B of two library builds on
-# the default bench (C2); LIB "-" = the in-tree libfvqa_hip.so. Prints one line per run.
+# the default bench (C2, --full: with the roofline passes and the other-config legs); LIB "-" = the in-tree libfvqa_hip.so.
+# Prints one line per run.
 out=$1; ta=$2; la=$3; tb=$4; lb=$5; n=${6:-3}
 mkdir -p $out
 for i in $(seq 1 $n); do
   for pair in "$ta:$la" "$tb:$lb"; do
     t=${pair%%:*}; l=${pair#*:}
     if [ "$l" = "-" ]; then unset FVQA_LIB; else export FVQA_LIB=$PWD/flipped-vqa_amd/fvqa/$l; fi
-    python bench.py --steps 20 --warmup 5 --no_cpu_baseline 2>/dev/null | grep "^{" > $out/ab_${t}_$i.json
+    python bench.py --steps 20 --warmup 5 --full --no_cpu_baseline 2>/dev/null | grep "^{" > $out/ab_${t}_$i.json
   done
 done
 unset FVQA_LIB

@@ -77,7 +77,7 @@ def main():
     # run this in the SAME gpurun call as the counter passes: the tag is the code the counters were collected on
     doc = {"fvqa_version": int(_lib.load().fvqa_version()), "source_hash": build.source_hash(),
            "command": "rocprofv3 --kernel-trace --pmc <one counter set per pass> -- python3 bench.py --steps 2 --warmup 1 "
-                      "--no_cpu_baseline (C2: LLaMA-7B bf16 B=8 S=128 VQA)",
+                      "--full --no_cpu_baseline (C2: LLaMA-7B bf16 B=8 S=128 VQA)",
            "kernels": res}
     json.dump(doc, open(out, "w"), indent=1)
     print(json.dumps(doc, indent=1))

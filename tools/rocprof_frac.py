@@ -3,7 +3,7 @@
 
     python tools/rocprof_frac.py <kernel_stats.csv> <bench_under_rocprof.json> [out.json]
 
-kernel_stats.csv: the `rocprofv3 --kernel-trace --stats` summary of `python3 bench.py --steps K --warmup W ...` (every step of
+kernel_stats.csv: the `rocprofv3 --kernel-trace --stats` summary of `python3 bench.py --steps K --warmup W --full ...` (every step of
 the command: warm-up, timed, sparse-probe and dense-probe passes — all the same step); the json: the line that command printed.
 Output: steps the trace covers (GEMM calls / launches per step), GEMM ms per step (sum of the gemm4w_k / gemm4w_sk_k /
 gemm_sk_256 rows / steps), frac_rocprof = the line's GEMM FLOPs per step / that time / the MFMA peak, the sum of ALL kernel
