@@ -423,6 +423,238 @@ __global__ __launch_bounds__(256) void qav_bwd_v_k(const T* __restrict__ xn, con
   }
 }
 
+
+// ---- audio-visual front end (reference llama/model.py:209-227,306-324) ------------------------------------------------
+// The projections of the audio modes: out[r,d] = sum over 1..2 sources of X_s[r,:]·W_s[d,:] (+ bias[d]), every operand read
+// where it lies — a source is (pointer, row pitch, K), its weight (pointer, row pitch): `concat` is two sources against two
+// column ranges of one weight, `sum` two sources against two weights, `audio_only` and the projections of `attention` one.
+struct AvSrc { const float* x; const float* w; int ldx, ldw, k; };
+struct AvSrcs { AvSrc s[2]; int n; };
+
+// visual_proj_fwd_mfma_k grown to pitched sources: one workgroup per 16 output features, its 4 waves split EACH source's K
+// (K_s % 64 == 0), the R <= 128 rows as 16-row MFMA blocks, partials meet in LDS. Per output the fma chain of a wave is source
+// 0's k ascending, then source 1's; the four partials are added in wave order: fixed, bitwise repeatable.
+template <int VU>
+__device__ __forceinline__ void av_accumulate(f32x4 (&acc)[8], const AvSrc& S, int R, int nrb, int bn, int w, int li, int g) {
+  const int kw = S.k / 4;                                  // this wave's K range of the source
+  const float* bp = S.w + (size_t)bn * S.ldw + (size_t)w * kw + 4 * g;
+  const float* ap[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    int ar = b * 16 + li; ar = ar < R ? ar : R - 1;
+    ap[b] = S.x + (size_t)ar * S.ldx + (size_t)w * kw + 4 * g;
+  }
+  for (int k0 = 0; k0 < kw; k0 += 16 * VU) {               // every load of a trip in flight before its first MFMA
+    float4 bf[VU], af[VU][8];
+#pragma unroll
+    for (int u = 0; u < VU; ++u) {
+      const int k = k0 + 16 * u;
+      const bool in = k < kw;
+      bf[u] = in ? *reinterpret_cast<const float4*>(bp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+        af[u][b] = (in && b < nrb) ? *reinterpret_cast<const float4*>(ap[b] + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < VU; ++u) {
+      if (k0 + 16 * u >= kw) break;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        if (b >= nrb) break;
+        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].x, bf[u].x, acc[b], 0, 0, 0);     // D[row 4g+e][feature li]
+        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].y, bf[u].y, acc[b], 0, 0, 0);
+        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].z, bf[u].z, acc[b], 0, 0, 0);
+        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].w, bf[u].w, acc[b], 0, 0, 0);
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void av_proj_fwd_mfma_k(AvSrcs S, const float* __restrict__ bias,
+                                                          const float* __restrict__ temporal, float* __restrict__ raw,
+                                                          T* __restrict__ tok, int R, int F, int D) {
+  __shared__ float part[4][8][16][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int li = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+  const int nrb = (R + 15) >> 4;
+  int bn = n0 + li; bn = bn < D ? bn : D - 1;
+  f32x4 acc[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  av_accumulate<4>(acc, S.s[0], R, nrb, bn, w, li, g);
+  if (S.n > 1) av_accumulate<4>(acc, S.s[1], R, nrb, bn, w, li, g);
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) part[w][b][4 * g + e][li] = acc[b][e];
+  __syncthreads();
+  for (int i = threadIdx.x; i < nrb * 256; i += 256) {
+    const int b = i >> 8, rr = (i >> 4) & 15, c = i & 15;
+    const int r = b * 16 + rr, d = n0 + c;
+    if (r < R && d < D) {
+      float v = ((part[0][b][rr][c] + part[1][b][rr][c]) + part[2][b][rr][c]) + part[3][b][rr][c];
+      if (bias) v += bias[d];
+      raw[(size_t)r * D + d] = v;
+      if (tok) tok[(size_t)r * D + d] = from_f32<T>(v + temporal[(size_t)(r % F) * D + d]);
+    }
+  }
+}
+
+// any row count, K_s % 4 == 0: one wave per output feature sweeps the rows (the fallback beyond 128 rows, as visual_proj_fwd_k is)
+template <typename T>
+__global__ __launch_bounds__(256) void av_proj_fwd_k(AvSrcs S, const float* __restrict__ bias,
+                                                     const float* __restrict__ temporal, float* __restrict__ raw,
+                                                     T* __restrict__ tok, int R, int F, int D) {
+  const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (d >= D) return;
+  const int lane = threadIdx.x & 63;
+  for (int r = 0; r < R; ++r) {
+    float acc = 0.f;
+    for (int s = 0; s < S.n; ++s) {
+      const float* x = S.s[s].x + (size_t)r * S.s[s].ldx;
+      const float* wr = S.s[s].w + (size_t)d * S.s[s].ldw;
+      for (int k = lane * 4; k < S.s[s].k; k += 256) {
+        float a[4], b[4];
+        Vec4<float>::load(x + k, a);
+        Vec4<float>::load(wr + k, b);
+        acc += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+      }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      if (bias) acc += bias[d];
+      raw[(size_t)r * D + d] = acc;
+      if (tok) tok[(size_t)r * D + d] = from_f32<T>(acc + temporal[(size_t)(r % F) * D + d]);
+    }
+  }
+}
+
+// X[n,f,:] = softmax_t(Q[n,f,:]·K[n,t,:] * scale) · V[n,:,:] over the T <= 16 keys of the same sample (reference
+// llama/model.py:153-169), fp32 throughout, max subtracted. One workgroup per query row; scores are block sums in key order.
+__global__ __launch_bounds__(256) void av_cross_attn_fwd_k(const float* __restrict__ q, const float* __restrict__ k,
+                                                           const float* __restrict__ v, float* __restrict__ x, int nq,
+                                                           int T, int dim, int ldq, int ldk, int ldv, float scale) {
+  __shared__ float red[4];
+  const int row = blockIdx.x;
+  const int n = row / nq;
+  const float* qr = q + (size_t)row * ldq;
+  float sc[16];
+  float m = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    sc[t] = -INFINITY;
+    if (t < T) {
+      const float* kr = k + ((size_t)n * T + t) * ldk;
+      float a = 0.f;
+      for (int c = threadIdx.x * 4; c < dim; c += 1024) {
+        float qa[4], ka[4];
+        Vec4<float>::load(qr + c, qa);
+        Vec4<float>::load(kr + c, ka);
+        a += qa[0] * ka[0] + qa[1] * ka[1] + qa[2] * ka[2] + qa[3] * ka[3];
+      }
+      sc[t] = block_sum_256(a, red) * scale;
+      m = fmaxf(m, sc[t]);
+    }
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 16; ++t)
+    if (t < T) { sc[t] = expf(sc[t] - m); sum += sc[t]; }
+  const float inv = 1.f / sum;
+  for (int c = threadIdx.x * 4; c < dim; c += 1024) {
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+      if (t < T) {
+        float va[4];
+        Vec4<float>::load(v + ((size_t)n * T + t) * ldv + c, va);
+        const float p = sc[t] * inv;
+        o[0] += p * va[0]; o[1] += p * va[1]; o[2] += p * va[2]; o[3] += p * va[3];
+      }
+    Vec4<float>::store(x + (size_t)row * dim + c, o);
+  }
+}
+
+// visual_proj_bwd_k with pitches: dW_s[d, k] += sum_r (d_tok[r,d] + d_qav[r,d]) * X_s[r,k] for source blockIdx.y, dW_s a column
+// range of a weight gradient with its own row pitch (S.s[].w / ldw). Same fma chain per output: rows ascending.
+template <int KMAX, int DB, int RT>
+__global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d_tok, const float* __restrict__ d_qav,
+                                                     AvSrcs S, int R, int D) {
+  const AvSrc src = blockIdx.y == 0 ? S.s[0] : S.s[1];
+  const float* __restrict__ X = src.x;
+  float* __restrict__ dW = const_cast<float*>(src.w);
+  const int K = src.k, ldx = src.ldx, ldw = src.ldw;
+  const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * DB;
+  if (d0 >= D) return;
+  const int lane = threadIdx.x & 63;
+  float acc[DB][KMAX];
+#pragma unroll
+  for (int j = 0; j < DB; ++j)
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t) acc[j][t] = 0.f;
+  for (int r0 = 0; r0 < R; r0 += RT) {
+    float g[RT][DB];
+    float v[RT][KMAX];
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr) {
+      const int r = r0 + rr < R ? r0 + rr : R - 1;
+      const float live = r0 + rr < R ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < DB; ++j) {
+        const int d = d0 + j < D ? d0 + j : D - 1;
+        float gv = d_tok[(size_t)r * D + d];
+        if (d_qav) gv += d_qav[(size_t)r * D + d];
+        g[rr][j] = gv * live;
+      }
+#pragma unroll
+      for (int t = 0; t < KMAX / 4; ++t) {
+        const int k = t * 256 + lane * 4;
+        float q[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k < K) Vec4<float>::load(X + (size_t)r * ldx + k, q);
+        v[rr][4 * t] = q[0]; v[rr][4 * t + 1] = q[1]; v[rr][4 * t + 2] = q[2]; v[rr][4 * t + 3] = q[3];
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+      for (int j = 0; j < DB; ++j)
+#pragma unroll
+        for (int t = 0; t < KMAX; ++t) acc[j][t] += g[rr][j] * v[rr][t];
+  }
+#pragma unroll
+  for (int j = 0; j < DB; ++j) {
+    if (d0 + j >= D) break;
+#pragma unroll
+    for (int t = 0; t < KMAX / 4; ++t) {
+      const int k = t * 256 + lane * 4;
+      if (k < K) {
+        float v[4];
+        Vec4<float>::load(dW + (size_t)(d0 + j) * ldw + k, v);
+        v[0] += acc[j][4 * t]; v[1] += acc[j][4 * t + 1]; v[2] += acc[j][4 * t + 2]; v[3] += acc[j][4 * t + 3];
+        Vec4<float>::store(dW + (size_t)(d0 + j) * ldw + k, v);
+      }
+    }
+  }
+}
+
+// host side: the C sources checked and packed for a launch (16-byte rows everywhere: float4 loads)
+static int av_pack(const fvqa_proj_src* src, int n_src, AvSrcs* out, bool* mfma_ok) {
+  if (n_src < 1 || n_src > 2 || !src) return FVQA_EINVAL;
+  *mfma_ok = true;
+  out->n = n_src;
+  for (int s = 0; s < n_src; ++s) {
+    if (!src[s].x || !src[s].w) return FVQA_EINVAL;
+    if (src[s].k <= 0 || src[s].k % 4 || src[s].ldx < src[s].k || src[s].ldw < src[s].k) return FVQA_ESHAPE;
+    if (src[s].ldx % 4 || src[s].ldw % 4 || (((uintptr_t)src[s].x | (uintptr_t)src[s].w) & 15)) return FVQA_EALIGN;
+    if (src[s].k % 64) *mfma_ok = false;
+    out->s[s] = AvSrc{src[s].x, src[s].w, src[s].ldx, src[s].ldw, src[s].k};
+  }
+  if (n_src == 1) out->s[1] = out->s[0];
+  return FVQA_OK;
+}
+
 }  // namespace
 
 extern "C" int fvqa_visual_proj_fwd(const float* video, const float* W, const float* temporal, float* vf_raw,
@@ -474,6 +706,77 @@ extern "C" int fvqa_visual_proj_bwd(const float* d_tok, const float* d_qav, cons
                        n_frames_total, in_dim, dim);
   hipLaunchKernelGGL(temporal_bwd_k, dim3((max_feats * dim + 255) / 256), dim3(256), 0, st, d_tok, dtemporal,
                      n_frames_total / max_feats, max_feats, dim);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_proj_fwd(const fvqa_proj_src* src, int n_src, const float* bias, const float* temporal,
+                                float* out_raw, void* out_tok, int rows, int max_feats, int dim, int dtype, void* stream) {
+  if (!out_raw || (temporal != nullptr) != (out_tok != nullptr)) return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (rows <= 0 || dim <= 0 || (temporal && max_feats <= 0)) return FVQA_ESHAPE;
+  AvSrcs S;
+  bool mfma_ok;
+  if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int F = max_feats > 0 ? max_feats : 1;
+  const dim3 block(256);
+  if (mfma_ok && rows <= 128) {
+    const dim3 g16((dim + 15) / 16);
+    if (dtype == FVQA_H16)
+      hipLaunchKernelGGL(av_proj_fwd_mfma_k<bf16_t>, g16, block, 0, st, S, bias, temporal, out_raw, (bf16_t*)out_tok, rows, F, dim);
+    else
+      hipLaunchKernelGGL(av_proj_fwd_mfma_k<float>, g16, block, 0, st, S, bias, temporal, out_raw, (float*)out_tok, rows, F, dim);
+  } else {
+    const dim3 grid((dim + 3) / 4);
+    if (dtype == FVQA_H16)
+      hipLaunchKernelGGL(av_proj_fwd_k<bf16_t>, grid, block, 0, st, S, bias, temporal, out_raw, (bf16_t*)out_tok, rows, F, dim);
+    else
+      hipLaunchKernelGGL(av_proj_fwd_k<float>, grid, block, 0, st, S, bias, temporal, out_raw, (float*)out_tok, rows, F, dim);
+  }
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_cross_attn_fwd(const float* q, const float* k, const float* v, float* x, int n_samples, int n_query,
+                                      int n_key, int dim, int ldq, int ldk, int ldv, float scale, void* stream) {
+  if (!q || !k || !v || !x) return FVQA_EINVAL;
+  if (n_samples <= 0 || n_query <= 0 || n_key <= 0 || n_key > 16 || dim <= 0 || dim % 4 || ldq < dim || ldk < dim || ldv < dim)
+    return FVQA_ESHAPE;
+  if (ldq % 4 || ldk % 4 || ldv % 4 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)x) & 15)) return FVQA_EALIGN;
+  hipLaunchKernelGGL(av_cross_attn_fwd_k, dim3(n_samples * n_query), dim3(256), 0, (hipStream_t)stream, q, k, v, x, n_query,
+                     n_key, dim, ldq, ldk, ldv, scale);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_proj_bwd(const float* d_tok, const float* d_qav, const fvqa_proj_src* src, int n_src, float* dtemporal,
+                                int rows, int max_feats, int dim, void* stream) {
+  if (!d_tok || !dtemporal) return FVQA_EINVAL;
+  if (rows <= 0 || max_feats <= 0 || rows % max_feats || dim <= 0) return FVQA_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_src) {                                              // (audio_only has no trainable projection: the temporal sum alone)
+    AvSrcs S;
+    bool mfma_ok;
+    if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
+    bool narrow = true;
+    for (int s = 0; s < n_src; ++s) {
+      if (src[s].k > 2048) return FVQA_ESHAPE;
+      narrow = narrow && src[s].k <= 1024;
+    }
+    if (narrow) {              // every source in one launch (grid.y)
+      hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, d_tok, d_qav, S, rows, dim);
+    } else {
+      for (int s = 0; s < n_src; ++s) {
+        AvSrcs one = S;
+        one.s[0] = S.s[s];
+        one.n = 1;
+        hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, d_tok, d_qav, one, rows, dim);
+      }
+    }
+  }
+  hipLaunchKernelGGL(temporal_bwd_k, dim3((max_feats * dim + 255) / 256), dim3(256), 0, st, d_tok, dtemporal,
+                     rows / max_feats, max_feats, dim);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

@@ -1,16 +1,17 @@
 """Batch producer in front of the hot path: `load_data` / `batch_collate` with the reference's names
-and collate schema (reference dataloader/__init__.py:15-90). Only NExT-QA is built (the dataset the
-BASELINE configs are quoted on); the other readers of the reference are host-side file formats
-outside SURVEY §8."""
+and collate schema (reference dataloader/__init__.py:15-90). NExT-QA (the dataset the BASELINE configs
+are quoted on) and MusicAVQA (the audio-visual one: CLIP frames + ImageBind audio) are built; the other
+readers of the reference are host-side file formats outside SURVEY §8."""
 import torch
 
 from util import misc
 
 from .base_dataset import TASKS, BaseDataset   # noqa: F401
+from .musicavqa import MusicAVQA
 from .nextqa import NextQA
 
-dataset_mapping = {"nextqa": NextQA}
-num_options_mapping = {"nextqa": 5}
+dataset_mapping = {"nextqa": NextQA, "musicavqa": MusicAVQA}
+num_options_mapping = {"nextqa": 5, "musicavqa": 1}
 
 
 def _worker_init(worker_id):
@@ -52,6 +53,9 @@ def batch_collate(batch):
     if "video" in batch[0]:
         out["video"] = torch.stack([s["video"] for s in batch])
         out["video_len"] = torch.tensor([s["video_len"] for s in batch], dtype=torch.long)
+    if "audio" in batch[0]:                                 # (the audio-only batch has no "video", reference :79-82)
+        out["audio"] = torch.stack([s["audio"] for s in batch])
+        out["audio_len"] = torch.tensor([s["audio_len"] for s in batch], dtype=torch.long)
     out["text"] = [s["text"] for s in batch]
     for key in ("text_id", "label", "video_index", "label_mask"):
         out[key] = {t: stack(key, t) for t in TASKS}

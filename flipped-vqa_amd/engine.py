@@ -114,7 +114,12 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
             os.makedirs(os.path.join(args.output_dir, "extracted_answers"), exist_ok=True)
             misc.save_result(extracted, os.path.join(args.output_dir, "extracted_answers"),
                              "extracted_answers_epoch%d" % epoch)
-        hit = answer.to(best.device) == best
+        if getattr(args, "dataset", None) == "musicavqa":
+            # one free-text option: a hit is a generated answer that starts with it (reference engine.py:100-116)
+            hit = torch.tensor([g["generated_answer"].startswith(t["options"][0]) for t, g in zip(data["text"], extracted)],
+                               device=best.device)
+        else:
+            hit = answer.to(best.device) == best
         misc.log_qtype(data, hit, log, args)
         log.update(lr=optimizer.param_groups[0]["lr"])
         log.update(n=bsz, acc=hit.sum().item() / bsz)

@@ -12,7 +12,7 @@ from typing import Optional
 
 F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_RESIDUAL, EPI_SWIGLU_BWD, EPI_SWIGLU_BWD_ST = 0, 1, 3, 6
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _p, _i, _f, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 
@@ -50,6 +50,9 @@ SIGNATURES = {
     "fvqa_attn_bwd_rotated": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_visual_proj_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "fvqa_visual_proj_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fvqa_av_proj_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "fvqa_av_cross_attn_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "fvqa_av_proj_bwd": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "fvqa_embed_splice": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_splice_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_ce_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _p]),
@@ -80,6 +83,11 @@ class SkRider(C.Structure):
 class SkRope(C.Structure):
     """Mirror of `fvqa_sk_rope` (include/fvqa.h)."""
     _fields_ = [("cos_t", C.c_void_p), ("sin_t", C.c_void_p)] + [(n, C.c_int32) for n in ("seq_len", "head_dim", "cols")]
+
+
+class ProjSrc(C.Structure):
+    """Mirror of `fvqa_proj_src` (include/fvqa.h)."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p)] + [(n, C.c_int32) for n in ("ldx", "ldw", "k", "reserved_")]
 
 
 class RowSegs(C.Structure):

@@ -24,7 +24,8 @@ from . import scored
 # dicts over tasks (scored_*: the scored-row lists of the LM streams, fvqa/scored.py — made here, where the labels are on the host,
 # so that the step's LM head can run on the scored rows without another copy or a read-back)
 TENSOR_FIELDS = ("text_id", "label", "video_index", "label_mask") + scored.FIELDS
-PLAIN_FIELDS = ("video", "video_len", "answer", "qtype")              # plain tensors
+PLAIN_FIELDS = ("video", "video_len", "audio", "audio_len", "answer", "qtype")   # plain tensors, those the batch has (the
+#                                                                 audio-only batch has no "video"): one staging buffer for all
 HOST_FIELDS = ("video_start", "prefix_index", "vid", "text", "qid", scored.COUNT)   # stay on the host
 
 

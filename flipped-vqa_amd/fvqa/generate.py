@@ -30,9 +30,9 @@ def greedy_decode(eng, data: dict, n_new: int = N_NEW) -> torch.Tensor:
                          "reference llama/model.py:381)")
     ids_all = data["text_id"]["vqa"]
     B, _, S = ids_all.shape
-    sub = {"video": data["video"],
-           "text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-           "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}}
+    sub = {k: data[k] for k in ("video", "audio") if k in data}      # (the audio-only batch has no "video")
+    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+           "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
     saved = (eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows)
     eng.tasks, eng.n_streams, eng._arena, eng._vstart = ["vqa"], 1, eng._gen_arena, {}
     eng.lm_head_rows = "all"                                # the prefill's logits are read at the prefix positions: every row

@@ -6,6 +6,8 @@ PyTorch is only the owner of device memory and streams here; all arithmetic is i
 """
 from __future__ import annotations
 
+import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -610,6 +612,66 @@ def visual_proj_bwd(d_tok, d_qav, video, dW, dtemporal):
     rc = _lib.load().fvqa_visual_proj_bwd(_ptr(d_tok), _ptr(d_qav), _ptr(video), _ptr(dW), _ptr(dtemporal), R, F,
                                           K, D, _stream())
     _lib.check(rc, "fvqa_visual_proj_bwd")
+
+
+def _proj_srcs(srcs, rows: int, dim: int, what: str):
+    """[(x, w)] -> the fvqa_proj_src array: x (rows, k) fp32, w (dim, k) fp32 — a weight or a column range of one (forward),
+    the same range of its gradient (backward); both may be row-pitched views."""
+    arr = (_lib.ProjSrc * max(1, len(srcs)))()
+    for i, (x, w) in enumerate(srcs):
+        _dev(x, w, rows_strided=True)
+        _need(x.dtype == w.dtype == torch.float32, f"{what}: fp32 sources")
+        _need(x.shape[0] == rows and w.shape[0] == dim and x.shape[1] == w.shape[1], f"{what}: source shapes")
+        arr[i].x, arr[i].w, arr[i].ldx, arr[i].ldw, arr[i].k = x.data_ptr(), w.data_ptr(), x.stride(0), w.stride(0), x.shape[1]
+    return arr
+
+
+def av_proj_fwd(srcs, out_raw, *, bias=None, temporal=None, out_tok=None):
+    """out_raw (rows, dim) fp32 = sum of x·w^T over the 1..2 (x, w) sources (+ bias); with `temporal` (F, dim):
+    out_tok = cast(out_raw + temporal[r % F]) in out_tok's dtype (include/fvqa.h fvqa_av_proj_fwd)."""
+    _dev(out_raw, bias, temporal, out_tok)
+    rows, dim = out_raw.shape
+    _need(1 <= len(srcs) <= 2 and out_raw.dtype == torch.float32, "av_proj_fwd: one or two sources, fp32 output")
+    _need((temporal is None) == (out_tok is None), "av_proj_fwd: temporal and out_tok come together")
+    _need(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (dim,)), "av_proj_fwd: bias")
+    F, dtype = 0, torch.float32
+    if temporal is not None:
+        F, dtype = temporal.shape[0], out_tok.dtype
+        _need(temporal.dtype == torch.float32 and temporal.shape[1] == dim and tuple(out_tok.shape) == (rows, dim),
+              "av_proj_fwd: temporal / out_tok shapes")
+    arr = _proj_srcs(srcs, rows, dim, "av_proj_fwd")
+    rc = _lib.load(dtype).fvqa_av_proj_fwd(C.addressof(arr), len(srcs), _ptr(bias), _ptr(temporal), _ptr(out_raw), _ptr(out_tok),
+                                           rows, F, dim, dt_code(dtype), _stream())
+    _lib.check(rc, "fvqa_av_proj_fwd")
+
+
+def av_cross_attn_fwd(q, k, v, x, n_samples: int, n_query: int, n_key: int):
+    """x = softmax(q·k^T / sqrt(dim))·v over the n_key keys of each sample (include/fvqa.h fvqa_av_cross_attn_fwd)."""
+    _dev(q, k, v, rows_strided=True)
+    _dev(x)
+    dim = x.shape[1]
+    _need(q.dtype == k.dtype == v.dtype == x.dtype == torch.float32, "av_cross_attn_fwd: fp32")
+    _need(tuple(q.shape) == (n_samples * n_query, dim) == tuple(x.shape), "av_cross_attn_fwd: q / x shapes")
+    _need(tuple(k.shape) == (n_samples * n_key, dim) == tuple(v.shape), "av_cross_attn_fwd: k / v shapes")
+    rc = _lib.load().fvqa_av_cross_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(x), n_samples, n_query, n_key, dim, q.stride(0),
+                                            k.stride(0), v.stride(0), 1.0 / math.sqrt(dim), _stream())
+    _lib.check(rc, "fvqa_av_cross_attn_fwd")
+
+
+def av_proj_bwd(d_tok, d_qav, srcs, dtemporal):
+    """dW += (d_tok + d_qav)^T·x for each (x, dW) of the 0..2 trainable sources — dW a weight gradient or a column range of
+    one — and dtemporal += sum_b d_tok[b] (include/fvqa.h fvqa_av_proj_bwd)."""
+    _dev(d_tok, d_qav, dtemporal)
+    rows, dim = d_tok.shape
+    F = dtemporal.shape[0]
+    for t in (d_tok, d_qav):
+        _need(t is None or (t.dtype == torch.float32 and tuple(t.shape) == (rows, dim)), "av_proj_bwd: d_tok/d_qav")
+    _need(dtemporal.dtype == torch.float32 and dtemporal.shape[1] == dim and rows % F == 0 and len(srcs) <= 2,
+          "av_proj_bwd: shapes")
+    arr = _proj_srcs(srcs, rows, dim, "av_proj_bwd")
+    rc = _lib.load().fvqa_av_proj_bwd(_ptr(d_tok), _ptr(d_qav), C.addressof(arr), len(srcs), _ptr(dtemporal), rows, F, dim,
+                                      _stream())
+    _lib.check(rc, "fvqa_av_proj_bwd")
 
 
 def embed_splice(ids, emb, vf_tok, h, n_seq, S, F, *, vstart: int = 0, zero_labels=None, index=None, mode: int = 0):

@@ -77,8 +77,15 @@ class DataParallel(torch.nn.Module):
             dist.broadcast(t, src=src, group=self.group)
 
     def broadcast_params(self):
-        """rank 0's flat trainable buffer -> every rank (one 18 MB broadcast for 7B)."""
+        """rank 0's flat trainable buffer -> every rank (one 18 MB broadcast for 7B), and with it the frozen front-end weights
+        of the audio modes (audio_proj, the cross-attention): randomly initialised, outside every checkpoint and — seeded
+        seed+rank — different on every rank until here. torch DDP's constructor broadcasts frozen parameters too."""
         self._bcast(self.module.flat_params().flat)
+        eng = getattr(self.module, "_engine", None)
+        for name in ("w_audio", "w_qkv", "b_qkv"):
+            t = getattr(eng, name, None)
+            if t is not None:
+                self._bcast(t)
 
     def broadcast_optimizer(self, optimizer, loss_scaler=None):
         """After a resume: rank 0's AdamW moments / step counter (and loss-scale state) -> every rank, so

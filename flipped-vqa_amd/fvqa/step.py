@@ -24,6 +24,20 @@ import torch
 from . import _lib, ops, scored
 
 TASKS = ("vqa", "vaq", "qav")
+
+
+def audio_mode(args) -> str:
+    """The front end's mode, decoded once from the reference's three arguments (llama/model.py:209-227): "none" (video only),
+    "only", "concat", "sum" or "attention". The reference tests `audio_merge in 'sum'` — a substring test; train.validate_args
+    restricts the values, so it is read as == "sum" here."""
+    if not getattr(args, "audio", False):
+        return "none"
+    if getattr(args, "audio_only", False):
+        return "only"
+    merge = getattr(args, "audio_merge", None)
+    if merge not in ("concat", "sum", "attention"):
+        raise ValueError(f"--audio needs --audio_only or --audio_merge concat|sum|attention, got {merge!r}")
+    return merge
 class TailRows:
     """The rows a head reads (fvqa/scored.py), for the streams one engine runs, on its device: segment k of the compact layout =
     stream k's rows, [off_k, off_k + rows_k). LM streams come first (vqa [, vaq]), then qav. `gather` / `scatter` are the
@@ -61,7 +75,9 @@ def stage_batch(data: dict, device) -> dict:
     """A batch dict (dataloader/__init__.py:28-90 schema, host tensors) moved to `device` for a resident-batch loop, the
     tail-row lists of its streams (fvqa/scored.py) taken while the labels are on the host and moved with the rest."""
     out = scored.annotate({k: (dict(v) if isinstance(v, dict) else v) for k, v in data.items()})
-    out["video"] = out["video"].to(device)
+    for k in ("video", "audio"):                     # (the audio-only batch has no "video")
+        if k in out:
+            out[k] = out[k].to(device)
     for k in ("text_id", "label", "video_index") + scored.FIELDS:
         if k in out:
             out[k] = {t: v.to(device) for t, v in out[k].items()}
@@ -228,6 +244,89 @@ class StepEngine:
         # "scored": the last layer's post-attention half, the heads and their backward on the rows a head reads (TailRows);
         # "all": every position, as the reference
         self.lm_head_rows = "all" if os.environ.get("FVQA_LM_HEAD", "scored") == "all" else "scored"
+        self.audio = model.audio_mode
+        self._pack_front(model)
+
+    # ------------------------------------------------------------------ front end (llama/model.py:306-324)
+    def _pack_front(self, model):
+        """The audio modes' frozen front-end weights as fp32 device tensors (they are fp32 parameters already unless someone cast
+        the module); `attention`: query | key | value row-concatenated, so that K and V of the audio rows are one projection —
+        the parameters become views of the fused buffers, as the layers' wq / wk / wv are."""
+        self.w_audio = self.w_qkv = self.b_qkv = None
+        if self.audio in ("only", "sum", "attention"):
+            p = model.audio_proj.weight
+            p.data = p.data.to(self.device, torch.float32).contiguous()
+            self.w_audio = p.data
+        if self.audio == "attention":
+            ca = model.video_audio_cross_attn
+            mods = (ca.query, ca.key, ca.value)
+            E = ca.query.weight.shape[0]
+            self.w_qkv = torch.cat([x.weight.data.to(self.device, torch.float32) for x in mods], 0).contiguous()
+            self.b_qkv = torch.cat([x.bias.data.to(self.device, torch.float32) for x in mods], 0).contiguous()
+            for j, x in enumerate(mods):
+                x.weight.data = self.w_qkv[j * E:(j + 1) * E]
+                x.bias.data = self.b_qkv[j * E:(j + 1) * E]
+
+    def _front_fwd(self, data: dict, B: int):
+        """_video_feature (vf_raw, fp32, kept for the QAV head) and the spliced tokens vf_tok = cast(vf_raw + temporal_emb) of the
+        model's mode, plus what the backward needs: [(x, first column, columns)] of the TRAINABLE projection's sources.
+          none       video·Wv^T                         (fvqa_visual_proj_fwd, as ever)
+          only       audio·Wa^T                         no trainable projection
+          concat     [video | audio]·Wv^T               two sources against two column ranges of Wv (D, 1792)
+          sum        audio·Wa^T + video·Wv^T            two sources, two weights; the audio branch is frozen
+          attention  X·Wv^T, X = softmax(Q K^T / sqrt(768)) V with Q = video·Wq^T + bq, [K | V] = a·[Wk | Wv]^T + [bk | bv],
+                     a = audio·Wa^T: five launches; X is kept, nothing trainable lies before it."""
+        m, dev, F, D = self.model, self.device, self.F, self.D
+        f32 = torch.float32
+        mode = self.audio
+        temporal = m.temporal_emb.weight.data
+        vf_raw = torch.empty(B * F, D, dtype=f32, device=dev)
+        vf_tok = torch.empty(B * F, D, dtype=self.dtype, device=dev)
+        video_d = audio_d = None
+        if mode != "only":
+            video_d = data["video"].to(dev, dtype=f32, non_blocking=True).reshape(B * F, -1).contiguous()
+        if mode == "none":
+            ops.visual_proj_fwd(video_d, m.visual_proj.weight.data, temporal, vf_raw, vf_tok)
+            return vf_raw, vf_tok, [(video_d, 0, video_d.shape[1])]
+        audio = data["audio"]
+        T = audio.shape[1]
+        if audio.dim() != 3 or audio.shape[0] != B or not (T == F or (mode == "attention" and 1 <= T <= F)):
+            raise ValueError(f"audio of shape {tuple(audio.shape)}: expected ({B}, {F}, K)" +
+                             (f" or ({B}, 1..{F}, K)" if mode == "attention" else ""))
+        audio_d = audio.to(dev, dtype=f32, non_blocking=True).reshape(B * T, -1).contiguous()
+        Kv = video_d.shape[1] if video_d is not None else 0
+        if mode == "only":
+            ops.av_proj_fwd([(audio_d, self.w_audio)], vf_raw, temporal=temporal, out_tok=vf_tok)
+            return vf_raw, vf_tok, []
+        W = m.visual_proj.weight.data
+        if mode == "concat":
+            ops.av_proj_fwd([(video_d, W[:, :Kv]), (audio_d, W[:, Kv:])], vf_raw, temporal=temporal, out_tok=vf_tok)
+            return vf_raw, vf_tok, [(video_d, 0, Kv), (audio_d, Kv, audio_d.shape[1])]
+        if mode == "sum":
+            ops.av_proj_fwd([(audio_d, self.w_audio), (video_d, W)], vf_raw, temporal=temporal, out_tok=vf_tok)
+            return vf_raw, vf_tok, [(video_d, 0, Kv)]
+        E = self.w_qkv.shape[1]
+        a = torch.empty(B * T, E, dtype=f32, device=dev)
+        q = torch.empty(B * F, E, dtype=f32, device=dev)
+        kv = torch.empty(B * T, 2 * E, dtype=f32, device=dev)
+        x = torch.empty(B * F, E, dtype=f32, device=dev)
+        ops.av_proj_fwd([(audio_d, self.w_audio)], a)
+        ops.av_proj_fwd([(video_d, self.w_qkv[:E])], q, bias=self.b_qkv[:E])
+        ops.av_proj_fwd([(a, self.w_qkv[E:])], kv, bias=self.b_qkv[E:])
+        ops.av_cross_attn_fwd(q, kv[:, :E], kv[:, E:], x, B, F, T)
+        ops.av_proj_fwd([(x, W)], vf_raw, temporal=temporal, out_tok=vf_tok)
+        return vf_raw, vf_tok, [(x, 0, E)]
+
+    def _front_bwd(self, sv: dict, ar: "Arena", grads: "FlatParams", has_qav: bool):
+        """d visual_proj += G^T·(the trainable projection's sources), G = d_tok + d_qav; d temporal_emb += sum_b d_tok[b]. The
+        frozen audio branch (`sum`, `only`) and the cross-attention (`attention`) get no gradient (llama_vqa.py:72)."""
+        d_qav = ar.d_qav if has_qav else None
+        dT = grads.grad_view("temporal_emb.weight")
+        if self.audio == "none":
+            ops.visual_proj_bwd(ar.d_tok, d_qav, sv["front"][0][0], grads.grad_view("visual_proj.weight"), dT)
+            return
+        gW = grads.grad_view("visual_proj.weight") if sv["front"] else None
+        ops.av_proj_bwd(ar.d_tok, d_qav, [(x, gW[:, c0:c0 + k]) for x, c0, k in sv["front"]], dT)
 
     # ------------------------------------------------------------------ native layer schedule
     def layer_plan(self, ar: "Arena", grads: "FlatParams", vstart: torch.Tensor):
@@ -310,8 +409,7 @@ class StepEngine:
         m, pk = self.model, self.pack
         dev = self.device
         F, D, V, A, H, Dh, Hf, L = self.F, self.D, self.V, self.A, self.H, self.Dh, self.Hf, self.L
-        video = data["video"]
-        B = video.shape[0]
+        B = data["text_id"]["vqa"].shape[0]                     # (the audio-only batch has no "video")
         S = data["text_id"]["vqa"].shape[-1]
         n_opt = data["text_id"]["vqa"].shape[1]
         if n_opt != 1:
@@ -326,9 +424,6 @@ class StepEngine:
                 raise ValueError(f"text_id[{t}] outside [0, {V})")
         ids = {t: v.to(dev, non_blocking=True).contiguous() for t, v in ids_h.items()}
         labels = {t: data["label"][t].reshape(B, S).to(dev, non_blocking=True).contiguous() for t in self.tasks}
-        video_d = video.to(dev, dtype=torch.float32, non_blocking=True).reshape(B * F, -1).contiguous()
-        # (with the other host-to-device copies of the batch, not behind the layers: a pageable copy holds the host until the
-        # stream reaches it)
         tl = self._tail(data, B, S) if self.lm_head_rows == "scored" else None
         qidx = None
         if "qav" in self.tasks:
@@ -342,10 +437,8 @@ class StepEngine:
         R, Ra = ar.R, ar.Ra
         vstart = self.vstart_tensor(B, vs["vqa"], vs["vaq"])
 
-        # visual projection + temporal embedding (model.py:322,324)
-        vf_raw = torch.empty(B * F, D, dtype=torch.float32, device=dev)
-        vf_tok = torch.empty(B * F, D, dtype=self.dtype, device=dev)
-        ops.visual_proj_fwd(video_d, m.visual_proj.weight.data, m.temporal_emb.weight.data, vf_raw, vf_tok)
+        # the front end: _video_feature and the spliced tokens of the model's mode (model.py:306-324)
+        vf_raw, vf_tok, front = self._front_fwd(data, B)
 
         # embedding gather + splice per stream (model.py:286-294,326-336)
         for k, t in enumerate(self.tasks):
@@ -387,7 +480,7 @@ class StepEngine:
                                  ar.loss_sum[2], B, S, D, F, self.tau)
             elif tl is None:
                 ops.ce_fwd(ar.logits[rows], labels[t], ar.lse[rows], ar.rowloss[rows], ar.loss_sum[k], B, S, V, 0)
-        self.saved = dict(ar=ar, B=B, S=S, vs=vs, labels=labels, qidx=qidx, video=video_d, vf_raw=vf_raw,
+        self.saved = dict(ar=ar, B=B, S=S, vs=vs, labels=labels, qidx=qidx, front=front, vf_raw=vf_raw,
                           vstart=vstart, tail=tl)
         self.last_scored = tl                                   # (tests: which rows the compact results belong to)
         losses = ar.loss_sum[:, 0] / ar.loss_sum[:, 1]        # mean over scored rows (NaN if none, as torch CE)
@@ -530,8 +623,7 @@ class StepEngine:
                 ops.splice_bwd(dh0, ar.d_tok, B, S, F, index=sv["qidx"], mode=1)
             else:
                 ops.splice_bwd(dh0, ar.d_tok, B, S, F, vstart=vs[t], mode=0)
-        ops.visual_proj_bwd(ar.d_tok, ar.d_qav if has_qav else None, sv["video"],
-                            grads.grad_view("visual_proj.weight"), grads.grad_view("temporal_emb.weight"))
+        self._front_bwd(sv, ar, grads, has_qav)
         self.saved = None
 
 
@@ -587,13 +679,14 @@ class StepEngine:
 class FlatParams:
     """All trainables of the model as views of ONE flat fp32 buffer (and one flat grad buffer).
 
-    Layout: adapter_query | visual_proj | temporal_emb | gates (L_all, 2, H). Parameter objects keep
+    Layout: adapter_query | visual_proj | temporal_emb | gates (L_all, 2, H) — the model names the segments ahead of the gates
+    (the audio-only model has no visual_proj, `concat` a 1792-wide one). Parameter objects keep
     their reference names/shapes (llama_vqa.py:71-76 freeze policy), only their storage moves."""
 
     def __init__(self, model):
         self.model = model
         named = dict(model.named_parameters())
-        self.names = ["adapter_query.weight", "visual_proj.weight", "temporal_emb.weight"]
+        self.names = list(model.flat_trainable_names())
         n_layers = len(model.layers)
         H = model.params.n_heads
         sizes = [named[n].numel() for n in self.names]

@@ -87,6 +87,15 @@ class SynthConfig:
     # walks t -> pi(t) -> pi(pi(t)) ... (31 distinct ids per row, margins as decided as with the identity tie) instead of
     # repeating the token it was fed, and a wrong KV-cache row / position in the token loop changes the next id.
     peaked_perm: bool = False
+    # audio fusion (reference llama/model.py:209-227): none | only | concat | sum | attention. `audio` of a batch is
+    # (B, audio_len, audio_dim); audio_len 0 = max_feats (the `attention` dataset hands one row per sample: audio_len = 1)
+    audio: str = "none"
+    audio_len: int = 0
+    audio_dim: int = 1024
+
+    @property
+    def audio_rows(self) -> int:
+        return self.audio_len or self.max_feats
 
     @property
     def head_dim(self) -> int:
@@ -128,7 +137,19 @@ def state_spec(cfg: SynthConfig) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
     D, Hf, V = cfg.dim, cfg.ffn_dim, cfg.vocab_size
     yield "tok_embeddings.weight", (V, D), "emb"
     yield "adapter_query.weight", (cfg.adapter_len * cfg.adapter_layer, D), "emb"
-    yield "visual_proj.weight", (D, cfg.video_dim), "lin"
+    Kv, Ka = cfg.video_dim, cfg.audio_dim
+    if cfg.audio not in AUDIO_MODES:
+        raise ValueError(f"audio mode {cfg.audio!r} not in {AUDIO_MODES}")
+    if cfg.audio in ("only", "sum"):
+        yield "audio_proj.weight", (D, Ka), "lin"
+    elif cfg.audio == "attention":
+        yield "audio_proj.weight", (Kv, Ka), "lin"
+    if cfg.audio != "only":
+        yield "visual_proj.weight", (D, Kv + Ka if cfg.audio == "concat" else Kv), "lin"
+    if cfg.audio == "attention":
+        for part in ("query", "key", "value"):
+            yield f"video_audio_cross_attn.{part}.weight", (Kv, Kv), "lin"
+            yield f"video_audio_cross_attn.{part}.bias", (Kv,), "lin"
     yield "temporal_emb.weight", (cfg.max_feats, D), "tied_temporal" if (cfg.peaked or cfg.peaked_perm) else "emb"
     for i in range(cfg.n_layers):
         p = f"layers.{i}."
@@ -147,6 +168,7 @@ def state_spec(cfg: SynthConfig) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
     yield "output.weight", (V, D), "tied_out_perm" if cfg.peaked_perm else ("tied_out" if cfg.peaked else "lin")
 
 
+AUDIO_MODES = ("none", "only", "concat", "sum", "attention")
 TRAINABLE_MARKS = ("gate", "adapter", "temporal_emb", "visual_proj")   # reference llama_vqa.py:72
 
 
@@ -253,7 +275,7 @@ def make_batch(cfg: SynthConfig, seed: int = 0, batch_size: Optional[int] = None
         "vaq": torch.arange(vs, vs + F).repeat(B, 1),
         "qav": pq_all[:, None] + torch.arange(F)[None, :],
     }
-    return {
+    out = {
         "vid": [f"synthetic{seed}_{b}" for b in range(B)],
         "video": video,
         "video_len": torch.full((B,), F, dtype=torch.long),
@@ -264,6 +286,13 @@ def make_batch(cfg: SynthConfig, seed: int = 0, batch_size: Optional[int] = None
         "answer": torch.zeros(B, dtype=torch.long),
         "qtype": torch.zeros(B, dtype=torch.long),
     }
+    if cfg.audio != "none":
+        T = cfg.audio_rows
+        out["audio"] = hashed_uniform(tag + ".audio", (B, T, cfg.audio_dim), math.sqrt(3.0))
+        out["audio_len"] = torch.full((B,), T, dtype=torch.long)
+        if cfg.audio == "only":                    # the audio-only batch has no "video" (dataloader/__init__.py collate)
+            del out["video"], out["video_len"]
+    return out
 
 
 class SyntheticLoader:
@@ -273,7 +302,9 @@ class SyntheticLoader:
         self.batches = [make_batch(cfg, seed=1234 + rank + world * i) for i in range(n_batches)]
         if pin and torch.cuda.is_available():
             for b in self.batches:
-                b["video"] = b["video"].pin_memory()
+                for k in ("video", "audio"):
+                    if k in b:
+                        b[k] = b[k].pin_memory()
                 for k in ("text_id", "label", "video_index"):
                     b[k] = {t: v.pin_memory() for t, v in b[k].items()}
 

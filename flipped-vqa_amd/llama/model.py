@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from fvqa.step import FlatParams, StepEngine
+from fvqa.step import FlatParams, StepEngine, audio_mode
 from llama.tokenizer import Tokenizer
 
 
@@ -82,6 +82,15 @@ class _Block(nn.Module):        # reference llama/model.py:178-182
         self.ffn_norm = _Weight(p.dim, init="ones")
 
 
+VIDEO_DIM, AUDIO_DIM = 768, 1024       # CLIP frame / ImageBind audio feature widths (reference llama/model.py:209-223)
+
+
+class _CrossAttention(nn.Module):     # parameter layout of reference llama/model.py:145-150 (fp32, :227)
+    def __init__(self, dim: int):
+        super().__init__()
+        self.query, self.key, self.value = (nn.Linear(dim, dim, dtype=torch.float32) for _ in range(3))
+
+
 class _StepFunction(torch.autograd.Function):
     """forward: losses (3,) from the kernel schedule; backward: launches the backward schedule.
 
@@ -123,8 +132,7 @@ class Transformer(nn.Module):
         self.vocab_size = params.vocab_size
         self.n_layers = params.n_layers
         self.max_feats = args.max_feats
-        if getattr(args, "audio", False):
-            raise NotImplementedError("audio fusion variants are outside the MI355X hot path (video-only)")
+        self.audio_mode = audio_mode(args)         # none | only | concat | sum | attention (reference llama/model.py:209-227)
 
         self.tokenizer = Tokenizer(model_path=f"{args.llama_model_path}./tokenizer.model", args=args)
         self.eos_id = self.tokenizer.eos_id
@@ -133,7 +141,20 @@ class Transformer(nn.Module):
 
         self.tok_embeddings = _Weight(params.vocab_size, params.dim)
         self.adapter_query = _Weight(params.adapter_len * params.adapter_layer, params.dim, init="normal")
-        self.visual_proj = _Weight(params.dim, 768, init="linear")
+        # The front end's projections, registered in the reference's order (llama/model.py:209-227). audio_proj and the
+        # cross-attention are outside the freeze policy's filter (llama_vqa.py:72): they stay at this initialisation — nn.Linear's
+        # own rule, drawn from torch's seeded generator — in every mode, and no checkpoint of trainables holds them. They are
+        # kept in fp32 whatever the storage type: the front end is fp32 arithmetic.
+        f32 = dict(dtype=torch.float32)
+        am = self.audio_mode
+        if am in ("only", "sum"):
+            self.audio_proj = nn.Linear(AUDIO_DIM, params.dim, bias=False, **f32)
+        elif am == "attention":
+            self.audio_proj = nn.Linear(AUDIO_DIM, VIDEO_DIM, bias=False, **f32)
+        if am != "only":
+            self.visual_proj = _Weight(params.dim, VIDEO_DIM + AUDIO_DIM if am == "concat" else VIDEO_DIM, init="linear")
+        if am == "attention":
+            self.video_audio_cross_attn = _CrossAttention(VIDEO_DIM)
         self.temporal_emb = _Weight(self.max_feats, params.dim, init="normal")
         self.adapter_len = params.adapter_len
         self.adapter_layer = params.adapter_layer
@@ -163,6 +184,11 @@ class Transformer(nn.Module):
         li = self.engine_layer_ids()[i]
         g = self._flat.gates
         return g[li, 0], g[li, 1]
+
+    def flat_trainable_names(self):
+        """The trainables FlatParams lays out ahead of the gates, in buffer order (no visual_proj in the audio-only model)."""
+        return ["adapter_query.weight"] + (["visual_proj.weight"] if hasattr(self, "visual_proj") else []) + \
+            ["temporal_emb.weight"]
 
     def trainable_parameters(self):
         return [p for p in self.parameters() if p.requires_grad]

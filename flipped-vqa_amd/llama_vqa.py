@@ -104,7 +104,8 @@ def fill_closed_form(model, cfg=None):
     cfg = cfg or synth.SynthConfig(dim=p.dim, n_heads=p.n_heads, n_layers=p.n_layers, vocab_size=model.vocab_size,
                                    multiple_of=p.multiple_of, norm_eps=p.norm_eps, adapter_len=p.adapter_len,
                                    adapter_layer=p.adapter_layer, max_feats=model.max_feats,
-                                   max_seq_len=p.max_seq_len, bias=model.args.bias, tau=model.args.tau)
+                                   max_seq_len=p.max_seq_len, bias=model.args.bias, tau=model.args.tau,
+                                   audio=model.audio_mode)
     own = dict(model.named_parameters())
     for name, shape, kind in synth.state_spec(cfg):
         t = own[name]

@@ -98,9 +98,10 @@ def build_loaders(args, model):
         p = model.params
         cfg = synth.SynthConfig(dim=p.dim, n_heads=p.n_heads, n_layers=p.n_layers, vocab_size=model.vocab_size,
                                 max_feats=args.max_feats, max_seq_len=args.max_seq_len, batch_size=args.batch_size,
-                                vaq=args.vaq, qav=args.qav)
+                                vaq=args.vaq, qav=args.qav, audio=model.audio_mode,
+                                audio_len=1 if model.audio_mode == "attention" else 0)   # (one audio row per clip, as MusicAVQA hands)
         return synth.SyntheticLoader(cfg, args.synthetic_batches, misc.get_rank(), misc.get_world_size(), pin=True), None
-    from dataloader import load_data          # NExT-QA reader + collate of this package (dataloader/)
+    from dataloader import load_data          # NExT-QA / MusicAVQA readers + collate of this package (dataloader/)
     return load_data(args, model.tokenizer, split="train"), load_data(args, model.tokenizer, split="val")
 
 

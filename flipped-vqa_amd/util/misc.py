@@ -352,23 +352,32 @@ def all_reduce_mean(value: float) -> float:
 
 # ---- validation bookkeeping (reference util/misc.py:343-600) -----------------------------------------
 NEXTQA_GROUPS = {"C": (1, 2), "T": (3, 4, 5), "D": (6, 7, 8)}       # causal / temporal / descriptive type ids
+# MusicAVQA's fifteen types (dataloader/musicavqa.py: 1 + 5 * modality + kind) grouped by modality and by kind
+# (reference util/misc.py:495-524)
+MUSICAVQA_GROUPS = {"audio": (1, 2, 3, 4, 5), "visual": (6, 7, 8, 9, 10), "audio_visual": (11, 12, 13, 14, 15),
+                    "temporal": (1, 6, 11), "existential": (2, 7, 12), "comparative": (3, 8, 13), "location": (4, 9, 14),
+                    "counting": (5, 10, 15)}
+QTYPE_GROUPS = {"nextqa": NEXTQA_GROUPS, "musicavqa": MUSICAVQA_GROUPS}
 
 
 def log_qtype(data, hit, metric_logger: MetricLogger, args):
-    """Per-question-type accuracy meters for NExT-QA: C (CH, CW), T (TN, TC, TP), D (DL, DC, DO), Total — each
-    updated with weight = number of questions of the group in this batch (reference util/misc.py:443-449,526-532).
-    Other datasets of the reference are not built."""
-    if getattr(args, "dataset", "nextqa") != "nextqa":
+    """Per-question-type accuracy meters — NExT-QA: C (CH, CW), T (TN, TC, TP), D (DL, DC, DO), Total; MusicAVQA: the three
+    modalities and the five kinds (no Total: the reference logs none there) — each updated with weight = number of questions
+    of the group in this batch (reference util/misc.py:443-449,495-532). Other datasets of the reference are not built."""
+    dataset = getattr(args, "dataset", "nextqa")
+    if dataset not in QTYPE_GROUPS:
         return
     eps = 1e-10
     qtype = torch.as_tensor(data["qtype"]).cpu()
     hit = torch.as_tensor(hit).cpu().to(torch.float64)
-    for name, ids in NEXTQA_GROUPS.items():
+    for name, ids in QTYPE_GROUPS[dataset].items():
         sel = torch.zeros_like(qtype, dtype=torch.bool)
         for i in ids:
             sel |= qtype == i
         n = float(sel.sum())
         metric_logger.update(n=n + eps, **{name: float(hit[sel].sum()) / (n + eps)})
+    if dataset != "nextqa":
+        return
     n = float(qtype.numel())
     metric_logger.update(n=n + eps, Total=float(hit.sum()) / n if n else 0.0)
 

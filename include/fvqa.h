@@ -273,6 +273,30 @@ int fvqa_visual_proj_bwd(const float* d_tok, const float* d_qav, const float* vi
                          float* dtemporal, int n_frames_total, int max_feats, int in_dim, int dim,
                          void* stream);
 
+/* ---- audio-visual front end (llama/model.py:209-227,306-324: --audio with concat / sum / attention / audio_only) ------
+ * One source of a projection: x (rows, k) fp32 with row pitch ldx, against k columns of a weight w (dim rows) with row pitch
+ * ldw. Every pointer 16-byte aligned, k % 4 == 0, pitches % 4 == 0. */
+typedef struct fvqa_proj_src {
+  const float* x;
+  const float* w; /* forward: the weight's column range; backward: the same range of the weight GRADIENT (written) */
+  int32_t ldx, ldw, k, reserved_;
+} fvqa_proj_src;
+/* out_raw (rows, dim) fp32 = sum_s x_s·w_s^T (+ bias (dim) or NULL), n_src = 1 or 2 — `concat`: two sources against two
+ * column ranges of one weight; `sum`: two weights; `audio_only` and the projections of `attention`: one. temporal (F, dim)
+ * and out_tok (rows, dim, storage dtype) = cast(out_raw + temporal[r % F]) both given or both NULL. Exact-fp32 matrix
+ * cores for rows <= 128 and k % 64 == 0 (one launch), a wave-per-feature kernel otherwise; fixed order, bitwise repeatable. */
+int fvqa_av_proj_fwd(const fvqa_proj_src* src, int n_src, const float* bias, const float* temporal, float* out_raw,
+                     void* out_tok, int rows, int max_feats, int dim, int dtype, void* stream);
+/* x (n_samples*n_query, dim) fp32 = softmax_t(q·k_t * scale)·v over the n_key <= 16 keys of the same sample, maximum
+ * subtracted (llama/model.py:153-169); q (n_samples*n_query, dim | ldq), k, v (n_samples*n_key, dim | ldk, ldv). Forward only:
+ * the module is frozen and nothing trainable lies before it. */
+int fvqa_av_cross_attn_fwd(const float* q, const float* k, const float* v, float* x, int n_samples, int n_query,
+                           int n_key, int dim, int ldq, int ldk, int ldv, float scale, void* stream);
+/* dW_s (dim, k_s | ldw) += (d_tok + d_qav)^T·x_s for each of n_src = 0..2 TRAINABLE sources (src[s].w = where the source's
+ * columns start in the weight gradient, k_s <= 2048), dtemporal (F, dim) += sum_b d_tok[b] as fvqa_visual_proj_bwd. */
+int fvqa_av_proj_bwd(const float* d_tok, const float* d_qav, const fvqa_proj_src* src, int n_src, float* dtemporal,
+                     int rows, int max_feats, int dim, void* stream);
+
 /* ---- token embedding gather + frame splice (llama/model.py:286-294,326-336) -----------
  * h[n,s,:] = emb[ids[n,s]] (zeroed where zero_labels[n,s] >= 0; NULL = never) then
  * mode 0 (vqa/vaq): rows [vstart, vstart+F) := vf_tok[n]           (slice assign, :327,:332)
