@@ -1,0 +1,361 @@
+// Answer-option scoring (reference engine.py:86-93 + llama/model_my_original_mod.py:332-377: every option of a sample is run
+// through the model, per-token cross-entropy with ignore_index 0, the option with the lowest mean loss is chosen).
+//
+// The O option sequences of a sample are equal up to the first answer token, and with causal attention so are their hidden
+// states: the prompt is run ONCE (the training forward, which leaves every layer's k / v in the arena = the KV cache) and
+// each option only recomputes its last T rows, the "suffix" (fvqa/score.py). Two kernels serve that:
+//
+// fvqa_attn_suffix — Attention.forward (llama/model.py:87-128) at the suffix rows. Query row (n, c, j) sits at position
+//   start[n] + j and attends to
+//     * the cached keys / values [0, start[n]) of sample n (read, never written: O continuations share one cache),
+//     * rows 0..j of its OWN option's suffix (rotated here and rounded to the storage type, as the prefill holds them),
+//     * the A adapter keys (no RoPE, own softmax scaled by tanh(gate1[h])),
+//   with gate2[h] added on the frame keys [vs, vs+F) when the query position is >= vs+F.
+//   One 256-thread workgroup per (head, sample): each cached key / value row is loaded ONCE for all O*T queries of the sample
+//   (a workgroup per option would read the prompt O times). Queries are taken in tiles of 32, keys in chunks of 32 staged in
+//   LDS as fp32; a running (max, sum) per query carries the softmax across chunks — the sums run in one fixed order, there
+//   are no atomics, two launches give the same bits. No matrix cores: 20..80 query rows per (head, sample) against <= 128 keys
+//   is a few hundred kFLOP next to the weight streams of the projections around it.
+//   Rows j >= len[n] are padding: never loaded (a NaN there reaches nothing), their output rows are written as zeros.
+//
+// fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
+//   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
+//   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
+#include "attn_decode_body.h"
+
+namespace {
+using namespace fvqa_decode;
+
+constexpr int QT = 32;                   // queries per tile
+constexpr int KC = 32;                   // keys per chunk
+constexpr int KLD = DH + 4;              // LDS row stride of q / k (floats): 16-byte rows, lanes of a key column on distinct banks
+constexpr int TMAX = 16;                 // suffix rows per option
+
+// 16 consecutive head dims [d0, d0 + 16) of a row as floats
+template <typename T> __device__ __forceinline__ void load16(const T* p, float (&v)[16]);
+template <> __device__ __forceinline__ void load16<bf16_t>(const bf16_t* p, float (&v)[16]) {
+  float a[8], b[8];
+  Chunk<bf16_t>::load(p, a);
+  Chunk<bf16_t>::load(p + 8, b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v[e] = a[e]; v[8 + e] = b[e]; }
+}
+template <> __device__ __forceinline__ void load16<float>(const float* p, float (&v)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    float a[4];
+    Chunk<float>::load(p + 4 * u, a);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[4 * u + e] = a[e];
+  }
+}
+
+// rotate 16 head dims starting at d0 (a multiple of 16) of a row at position p, rounded to the storage type
+template <typename T>
+__device__ __forceinline__ void rope16(float (&v)[16], const float* cs, const float* sn, int p, int d0) {
+  const float4* cp = reinterpret_cast<const float4*>(cs + (size_t)p * HP + d0 / 2);
+  const float4* sp = reinterpret_cast<const float4*>(sn + (size_t)p * HP + d0 / 2);
+  const float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+  const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float a = v[2 * e], b = v[2 * e + 1];
+    v[2 * e] = round_to<T>(a * c[e] - b * s[e]);
+    v[2 * e + 1] = round_to<T>(a * s[e] + b * c[e]);
+  }
+}
+
+__device__ __forceinline__ void store16(float* dst, const float (&v)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    *reinterpret_cast<float4*>(dst + 4 * u) = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+}
+
+__device__ __forceinline__ float half_max(float v) {       // over the 32 lanes of an aligned half wave
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, const T* __restrict__ cache,
+                                                     T* __restrict__ o_suf, const float* __restrict__ gate1,
+                                                     const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
+                                                     const int32_t* __restrict__ start_p, const int32_t* __restrict__ len_p,
+                                                     const float* __restrict__ cs, const float* __restrict__ sn, int B, int O,
+                                                     int Tn, int S, int H, int A, int F, int cache_rot) {
+  __shared__ __attribute__((aligned(16))) float Qs[QT][KLD];     // the tile's queries: rotated, rounded
+  __shared__ __attribute__((aligned(16))) float Ks[KC][KLD];     // the chunk's keys, as the prefill holds them
+  __shared__ __attribute__((aligned(16))) float Vs[KC][DH];
+  __shared__ __attribute__((aligned(16))) float Ps[QT][KC];      // the chunk's probabilities (unnormalised)
+  __shared__ float mrun[QT], lrun[QT], alpha[QT];
+  const int tid = threadIdx.x;
+  const int h = blockIdx.x, n = blockIdx.y;
+  const int D = H * DH;
+  const size_t ld = (size_t)3 * D;
+  int start = start_p[n];
+  start = start < 0 ? 0 : (start > S ? S : start);
+  int len = len_p[n];
+  len = len < 0 ? 0 : (len > Tn ? Tn : len);
+  if (len > S - start) len = S - start;
+  const int NQ = O * Tn;
+  const T* seq = cache + (size_t)n * S * ld + h * DH;
+  const T* arow = cache + (size_t)B * S * ld + h * DH;
+  const T* sufn = suf + (size_t)n * NQ * ld + h * DH;
+  const float scale = rsqrtf((float)DH);
+  const int vs = vstart[n];
+  const float g2 = gate2[h];
+  const float tg1 = tanhf(gate1[h]);
+  // staging role: 8 threads per row, 16 head dims each
+  const int srow = tid >> 3, sd0 = (tid & 7) * 16;
+  // score role: key column kk, queries 4*qg .. 4*qg + 3
+  const int kk = tid & 31, qg = tid >> 5;
+  // value role: head dim vd, queries 16*qh .. 16*qh + 15
+  const int vd = tid & 127, qh = tid >> 7;
+
+  for (int q0 = 0; q0 < NQ; q0 += QT) {
+    // ---- the tile's queries
+    {
+      const int qi = q0 + srow;
+      const int j = qi % Tn;
+      float v[16];
+      if (qi < NQ && j < len) {
+        load16<T>(sufn + (size_t)qi * ld + sd0, v);
+        rope16<T>(v, cs, sn, start + j, sd0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = 0.f;
+      }
+      store16(&Qs[srow][sd0], v);
+      if (tid < QT) { mrun[tid] = -1e30f; lrun[tid] = 0.f; }
+    }
+    float acc[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc[u] = 0.f;
+    // what this thread's four score queries are
+    int qj[4], qc[4];
+    bool qok[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int qi = q0 + 4 * qg + u;
+      qc[u] = qi / Tn;
+      qj[u] = qi % Tn;
+      qok[u] = qi < NQ && qj[u] < len;
+    }
+    // the suffix keys a query of this tile can see: the rows of the options the tile touches
+    const int s_lo = (q0 / Tn) * Tn;
+    int s_hi = ((q0 + QT - 1) / Tn + 1) * Tn;
+    if (s_hi > NQ) s_hi = NQ;
+    const int n_pre = (start + KC - 1) / KC, n_suf = (s_hi - s_lo + KC - 1) / KC;
+    // chunks: [0, n_pre) cached prompt keys, [n_pre, n_pre + n_suf) suffix keys, then the adapter keys (own softmax)
+    for (int ch = 0; ch <= n_pre + n_suf; ++ch) {
+      const int kind = ch < n_pre ? 0 : (ch < n_pre + n_suf ? 1 : 2);
+      const int k0 = kind == 0 ? ch * KC : (kind == 1 ? s_lo + (ch - n_pre) * KC : 0);
+      __syncthreads();                                   // the previous chunk's readers are done (and Qs / mrun are written)
+      if (kind == 2 && tid < QT) {                       // text softmax closed: o = acc / l, then the adapter's share is added
+        alpha[tid] = lrun[tid] > 0.f ? 1.f / lrun[tid] : 0.f;
+        mrun[tid] = -1e30f;
+      }
+      // ---- stage the chunk's keys and values
+      {
+        const int ki = k0 + srow;
+        float k[16], v[16];
+        const T* row = nullptr;
+        int pos = 0;
+        bool rot = false;
+        if (kind == 0) {
+          if (ki < start) { row = seq + (size_t)ki * ld; pos = ki; rot = !cache_rot; }
+        } else if (kind == 1) {
+          const int j = ki % Tn;
+          if (ki < s_hi && j < len) { row = sufn + (size_t)ki * ld; pos = start + j; rot = true; }
+        } else if (ki < A) {
+          row = arow + (size_t)ki * ld;
+        }
+        if (row) {
+          load16<T>(row + D + sd0, k);
+          load16<T>(row + 2 * D + sd0, v);
+          if (rot) rope16<T>(k, cs, sn, pos, sd0);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) k[e] = v[e] = 0.f;
+        }
+        store16(&Ks[srow][sd0], k);
+        store16(&Vs[srow][sd0], v);
+      }
+      __syncthreads();
+      // ---- scores of (4 queries) x (key kk)
+      float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int d = 0; d < DH; d += 4) {
+        const float4 k4 = *reinterpret_cast<const float4*>(&Ks[kk][d]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float4 q4 = *reinterpret_cast<const float4*>(&Qs[4 * qg + u][d]);
+          s[u] += q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
+        }
+      }
+      const int ki = k0 + kk;
+      int kpos = ki, kc = -1, kj = 0;
+      bool kok;
+      if (kind == 0) {
+        kok = ki < start;
+      } else if (kind == 1) {
+        kc = ki / Tn;
+        kj = ki % Tn;
+        kpos = start + kj;
+        kok = ki < s_hi && kj < len;
+      } else {
+        kok = ki < A;
+      }
+      const bool frame_key = kind != 2 && vs >= 0 && kpos >= vs && kpos < vs + F;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        bool see = qok[u] && kok;
+        if (kind == 1) see = see && kc == qc[u] && kj <= qj[u];
+        float x = s[u] * scale;
+        if (frame_key && start + qj[u] >= vs + F) x += g2;
+        x = see ? x : -1e30f;
+        const int q = 4 * qg + u;
+        const float m_old = mrun[q];
+        const float m_new = fmaxf(m_old, half_max(x));
+        const float e = see ? __expf(x - m_new) : 0.f;
+        const float sum = half_sum(e);
+        if (kind == 2) {
+          Ps[q][kk] = sum > 0.f ? e / sum * tg1 : 0.f;
+        } else {
+          Ps[q][kk] = e;
+          if (kk == 0) {
+            const float a = __expf(m_old - m_new);
+            alpha[q] = a;
+            lrun[q] = lrun[q] * a + sum;
+          }
+        }
+        if (kk == 0) mrun[q] = m_new;      // (read above by this half wave only: each query belongs to one)
+      }
+      __syncthreads();
+      // ---- values: acc[q] = acc[q] * alpha[q] + sum_k P[q][k] V[k][vd]
+      float vcol[KC];
+#pragma unroll
+      for (int k = 0; k < KC; ++k) vcol[k] = Vs[k][vd];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int q = 16 * qh + u;
+        float a = acc[u] * alpha[q];
+#pragma unroll
+        for (int k = 0; k < KC; k += 4) {
+          const float4 p4 = *reinterpret_cast<const float4*>(&Ps[q][k]);
+          a += p4.x * vcol[k];
+          a += p4.y * vcol[k + 1];
+          a += p4.z * vcol[k + 2];
+          a += p4.w * vcol[k + 3];
+        }
+        acc[u] = a;
+      }
+    }
+    // ---- the tile's output rows (padding rows: zeros)
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int qi = q0 + 16 * qh + u;
+      if (qi < NQ) {
+        const bool ok = qi % Tn < len;
+        o_suf[((size_t)n * NQ + qi) * D + h * DH + vd] = from_f32<T>(ok ? acc[u] : 0.f);
+      }
+    }
+    __syncthreads();                                     // Qs / mrun are rewritten by the next tile
+  }
+}
+
+// one workgroup per sample: clear, scatter, reduce per option, pick
+__global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ rowloss, const int32_t* __restrict__ map, int M,
+                                                     float* __restrict__ il, float* __restrict__ sum_o,
+                                                     int64_t* __restrict__ cnt_o, float* __restrict__ mean_o,
+                                                     int64_t* __restrict__ pred, int O, int S1) {
+  __shared__ float means[64];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int per = O * S1;
+  float* mine = il + (size_t)n * per;
+  for (int i = tid; i < per; i += 256) mine[i] = 0.f;
+  __syncthreads();
+  for (int r = tid; r < M; r += 256) {
+    const int at = map[r] - n * per;                     // (a row listed twice would race: the host lists each once)
+    if (map[r] >= 0 && at >= 0 && at < per) mine[at] = rowloss[r];
+  }
+  __syncthreads();
+  for (int c = w; c < O; c += 4) {
+    float s = 0.f;
+    int k = 0;
+    for (int t = lane; t < S1; t += 64) {
+      const float x = mine[c * S1 + t];
+      s += x;
+      k += (x != 0.f) ? 1 : 0;                           // reference engine.py:88 (a NaN counts, an exact 0 does not)
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
+    if (lane == 0) {
+      const float m = s / (float)k;                      // 0 / 0 = NaN, as torch
+      sum_o[n * O + c] = s;
+      cnt_o[n * O + c] = k;
+      mean_o[n * O + c] = m;
+      means[c] = m;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int best = 0;
+    for (int c = 0; c < O; ++c) {
+      const float x = means[c], b = means[best];
+      if (x != x) { best = c; break; }                   // torch.argmin: the first NaN wins
+      if (x < b) best = c;                               // ties stay with the lowest index
+    }
+    pred[n] = best;
+  }
+}
+
+}  // namespace
+
+extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
+                                const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
+                                const float* cos_t, const float* sin_t, int n_seq, int n_options, int suffix_len,
+                                int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
+                                int dtype, void* stream) {
+  if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !len || !cos_t || !sin_t)
+    return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > TMAX || seq_len <= 0 || n_heads <= 0 ||
+      head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
+    return FVQA_ESHAPE;
+  if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || n_options > 4096) return FVQA_ESHAPE;
+  if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
+  dim3 grid(n_heads, n_seq), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FVQA_H16)
+    hipLaunchKernelGGL(attn_suffix_k<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
+                       (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
+                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
+  else
+    hipLaunchKernelGGL(attn_suffix_k<float>, grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
+                       (float*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
+                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,
+                                float* option_sum, int64_t* option_count, float* option_mean, int64_t* prediction,
+                                int n_seq, int n_options, int seq_len, void* stream) {
+  if (!rowloss || !row_map || !individual_losses || !option_sum || !option_count || !option_mean || !prediction)
+    return FVQA_EINVAL;
+  if (n_rows < 0 || n_seq <= 0 || n_seq > 65535 || n_options <= 0 || n_options > 64 || seq_len < 2) return FVQA_ESHAPE;
+  if ((long long)n_seq * n_options * (seq_len - 1) > 0x7fffffffLL) return FVQA_ESHAPE;
+  hipLaunchKernelGGL(option_pick_k, dim3(n_seq), dim3(256), 0, (hipStream_t)stream, rowloss, row_map, n_rows,
+                     individual_losses, option_sum, option_count, option_mean, prediction, n_options, seq_len - 1);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}

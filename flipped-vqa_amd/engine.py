@@ -95,18 +95,41 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
 
 def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer, epoch: int,
                   args=None):
-    """Validation with the reference's signature and return value (reference engine.py:59-145), generation
-    mode (`--is_generation_task`, the mode every run script of the reference uses): greedy answer generation,
-    nearest-choice matching, accuracy overall and per question type. The per-choice-loss mode calls a model
-    branch the reference no longer has (its `inference` returns the generation tuple), so it is rejected."""
-    if not getattr(args, "is_generation_task", False):
-        raise NotImplementedError("validation is built for --is_generation_task (reference engine.py:78-86)")
+    """Validation with the reference's signature and return value (reference engine.py:59-145), both modes.
+    `--is_generation_task` (the mode every run script of the reference uses): greedy answer generation, nearest-choice matching.
+    Otherwise the original multiple-choice protocol (engine.py:86-93,122-129): every option is scored by its mean
+    cross-entropy over the answer tokens and the lowest wins — `model.score_options(data)` (llama/model.py; a model without it
+    is rejected) returns the reference's `individual_losses` and leaves count / prediction, reduced on the device, in
+    `last_scoring`: one host read per batch. Accuracy overall and per question type either way."""
+    gen = bool(getattr(args, "is_generation_task", False))
+    owner = None
+    if not gen:
+        owner = next((m for m in (model, getattr(model, "module", None)) if hasattr(m, "score_options")), None)
+        if owner is None:
+            raise NotImplementedError("validation without --is_generation_task needs a model with score_options "
+                                      "(reference engine.py:86-93)")
     model.eval()
     log = misc.MetricLogger(delimiter="  ")
     log.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
     for data in log.log_every(data_loader, max(1, len(data_loader) // 4), f"Epoch: [{epoch}]"):
         answer = data["answer"]
         bsz = answer.shape[0]
+        if not gen:
+            with torch.no_grad():
+                individual_losses = owner.score_options(data)
+            last = getattr(owner, "last_scoring", None)
+            if last is not None:
+                prediction = last["prediction"]
+            else:                                            # (a model that only returns the losses: engine.py:88-93)
+                count = (individual_losses != 0).sum(-1)
+                prediction = (individual_losses.sum(-1) / count).argmin(-1)
+            hit = answer.cpu() == prediction.cpu()           # the batch's one device->host read
+            misc.log_qtype(data, hit, log, args)
+            log.update(lr=optimizer.param_groups[0]["lr"])
+            log.update(n=bsz, acc=hit.sum().item() / bsz)
+            if getattr(args, "debug", False):
+                break
+            continue
         with torch.no_grad():
             best, extracted = model(data, inference=True)
         if getattr(args, "output_dir", None):

@@ -10,6 +10,7 @@ The answer is then matched to the choices by cosine similarity of mean token emb
 reference's quirks kept (choices padded with id 0 before averaging, llama/model.py:566-575)."""
 from __future__ import annotations
 
+import contextlib
 from typing import List, Tuple
 
 import torch
@@ -17,6 +18,21 @@ import torch
 from . import ops
 
 N_NEW = 31          # reference llama/model.py:438: positions prefix-1 .. prefix+29
+
+
+@contextlib.contextmanager
+def vqa_stream_only(eng, arenas: str, lm_head_rows: str):
+    """The engine as an evaluation path runs it — the VQA stream alone, in the arenas kept under the attribute `arenas`
+    (`_gen_arena`, `_score_arena`: the training step's activations stay where they are), the LM head on `lm_head_rows` — with
+    the training configuration (tasks / n_streams / _arena / _vstart / lm_head_rows) put back on the way out."""
+    saved = (eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows)
+    eng.tasks, eng.n_streams, eng._arena, eng._vstart = ["vqa"], 1, getattr(eng, arenas), {}
+    eng.lm_head_rows = lm_head_rows
+    try:
+        yield eng
+    finally:
+        setattr(eng, arenas, eng._arena)
+        eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows = saved
 
 
 @torch.no_grad()
@@ -33,10 +49,7 @@ def greedy_decode(eng, data: dict, n_new: int = N_NEW) -> torch.Tensor:
     sub = {k: data[k] for k in ("video", "audio") if k in data}      # (the audio-only batch has no "video")
     sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
            "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    saved = (eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows)
-    eng.tasks, eng.n_streams, eng._arena, eng._vstart = ["vqa"], 1, eng._gen_arena, {}
-    eng.lm_head_rows = "all"                                # the prefill's logits are read at the prefix positions: every row
-    try:
+    with vqa_stream_only(eng, "_gen_arena", "all"):         # the prefill's logits are read at the prefix positions: every row
         eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
         ar = eng.arena(B, S)
         vstart = eng.saved["vstart"]
@@ -76,9 +89,6 @@ def greedy_decode(eng, data: dict, n_new: int = N_NEW) -> torch.Tensor:
             ops.gemm_nt(xn, pk.wout, lg)
             pred = lg.argmax(-1)
         return ids
-    finally:
-        eng._gen_arena = eng._arena
-        eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows = saved
 
 
 @torch.no_grad()

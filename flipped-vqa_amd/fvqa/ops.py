@@ -555,6 +555,54 @@ def attn_decode(qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_se
 DECODE_PTRS = 9
 
 
+SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)
+
+
+def attn_suffix(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
+                cache_rotated: bool):
+    """The option-scoring path's attention at the suffix rows (include/fvqa.h fvqa_attn_suffix): qkv_suf (n_seq*n_options*T,
+    3*D) RAW projections of suffix row j of option c of sample n at position start[n] + j; qkv_cache the layer's prefill buffer
+    (read only). Writes o_suf (n_seq*n_options*T, D); rows j >= length[n] are padding (zeros)."""
+    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_suffix")
+    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
+    R = n_seq * n_options * T
+    _need(cos_t is not None, "attn_suffix: rope tables")
+    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, "attn_suffix: dtype")
+    _need(1 <= T <= SUFFIX_MAX and n_options >= 1, f"attn_suffix: 1 <= suffix rows <= {SUFFIX_MAX}")
+    _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), "attn_suffix: row shapes")
+    for t in (vstart, start, length):
+        _need(t.dtype == torch.int32 and t.numel() == n_seq, "attn_suffix: vstart / start / len are int32 (n_seq)")
+    for t in (gate1, gate2):
+        _need(t.dtype == torch.float32 and t.numel() == H, "attn_suffix: gate shape")
+    rc = _lib.load(qkv_cache.dtype).fvqa_attn_suffix(_ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1), _ptr(gate2),
+                                                     _ptr(vstart), _ptr(start), _ptr(length), _ptr(cos_t), _ptr(sin_t), n_seq,
+                                                     n_options, T, S, H, Dh, A, F, 1 if cache_rotated else 0,
+                                                     dt_code(qkv_suf.dtype), _stream())
+    _lib.check(rc, "fvqa_attn_suffix")
+    return o_suf
+
+
+def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: int):
+    """The per-option reduction (include/fvqa.h fvqa_option_pick): rowloss fp32 compact per-row losses, row_map int32 (entry of
+    (n_seq, n_options, S-1) each of the first n_rows rows belongs to, < 0 none) ->
+    (individual_losses (n_seq, n_options, S-1) fp32, sum, count int64, mean (n_seq, n_options), prediction (n_seq,) int64)."""
+    _dev(rowloss, row_map)
+    _need(rowloss.dtype == torch.float32 and row_map.dtype == torch.int32, "option_pick: fp32 losses, int32 map")
+    _need(0 <= n_rows <= min(rowloss.numel(), row_map.numel()), "option_pick: rows")
+    _need(1 <= n_options <= 64 and S >= 2 and n_seq >= 1, "option_pick: 1..64 options")
+    dev = rowloss.device
+    il = torch.empty(n_seq, n_options, S - 1, dtype=torch.float32, device=dev)
+    s = torch.empty(n_seq, n_options, dtype=torch.float32, device=dev)
+    cnt = torch.empty(n_seq, n_options, dtype=torch.int64, device=dev)
+    mean = torch.empty(n_seq, n_options, dtype=torch.float32, device=dev)
+    pred = torch.empty(n_seq, dtype=torch.int64, device=dev)
+    rc = _lib.load().fvqa_option_pick(_ptr(rowloss), _ptr(row_map), n_rows, _ptr(il), _ptr(s), _ptr(cnt), _ptr(mean),
+                                      _ptr(pred), n_seq, n_options, S, _stream())
+    _lib.check(rc, "fvqa_option_pick")
+    return il, s, cnt, mean, pred
+
+
 def attn_bwd_workspace(n_seq, S, H, Dh, A) -> int:
     return int(_lib.load().fvqa_attn_bwd_workspace(n_seq, S, H, Dh, A))
 

@@ -1,0 +1,229 @@
+"""Validation by scoring the answer options (reference engine.py:86-93,122-129 + llama/model_my_original_mod.py:332-377,506):
+every option of a sample is run through the model, per-token cross-entropy with ignore_index 0, the option with the lowest mean
+loss over its answer tokens is the prediction.
+
+The reference runs B * n_options full sequences that differ only in their last few tokens. Two forms here:
+
+  shared  the prompt is run ONCE per sample (option 0, the training forward in an arena of its own: every layer's k / v stay in
+          the arena = the KV cache; no LM head on it), then only the SUFFIX rows of each option — from the first row that is
+          scored or differs, to the last scored row — go through the layers: RMSNorm -> QKV -> fvqa_attn_suffix (several
+          continuations read one cached prompt, nothing is written to it) -> WO + residual -> RMSNorm -> W1|W3 SwiGLU -> W2 +
+          residual. With causal attention the hidden states in front of the first differing token are those of option 0, and
+          rows behind an option's last scored row are never read, so the scored rows are what the dense form computes.
+          S + n_options * T rows per sample instead of n_options * S (148 against 640 at S = 128, five options, T = 4).
+  dense   the options flattened to (B * n_options, 1, S), front-end inputs repeated per option (model_my_original_mod.py:333),
+          the existing forward with tail rows: the reference's computation on the step's own kernels. The fallback for batches
+          the planner turns down, and what FVQA_SCORE=dense forces.
+
+Both end in the same tail: the scored rows' losses in a compact array (fvqa_ce_fwd, shifted-label convention of fvqa/scored.py)
+-> fvqa_option_pick -> individual_losses (B, n_options, S-1), per-option sum / count / mean, prediction.
+"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import ops, scored
+from .generate import vqa_stream_only
+
+ROUTES = ("shared", "dense")
+DEFAULT_ROUTE = "shared"
+
+
+@dataclass
+class OptionPlan:
+    """What plan_options found. start / length: (B,) int64 host — the suffix of sample n is rows [start[n], start[n] + length[n])
+    of every option; T = max length; shared: whether the batch can take the shared form (why_dense says why not)."""
+    start: torch.Tensor
+    length: torch.Tensor
+    T: int
+    shared: bool
+    why_dense: str
+    rows: torch.Tensor             # (M, 3) int64: (n, c, t) of every scored row, row-major
+
+
+def plan_options(text_id, label, prefix_index=None, video_start=None, F: int = 0) -> OptionPlan:
+    """Host-only integer work. text_id, label: (B, O, S) int64 host tensors; video_start: per-sample first frame slot (or one
+    int); prefix_index is not needed (the labels say where the answers are) and only checked for length when given.
+    Per sample: lcp = the first position where any option differs from option 0 (S if none); row t is scored iff
+    label[t + 1] > 0 (llama/model.py:348-350, ignore_index 0); start = min(lcp, first scored row) — every scored row then lies
+    in the suffix, the prompt pass needs no LM head; length = last scored row of any option + 1 - start.
+    Shared form iff every sample has a scored row, start >= video_start + F + 1 (no frame slot in a suffix: its inputs are token
+    embeddings) and length <= ops.SUFFIX_MAX."""
+    ids = torch.as_tensor(text_id)
+    lab = torch.as_tensor(label)
+    if ids.dim() != 3 or ids.shape != lab.shape:
+        raise ValueError(f"plan_options: text_id {tuple(ids.shape)} and label {tuple(lab.shape)} must be (B, O, S)")
+    B, O, S = ids.shape
+    if prefix_index is not None and len(prefix_index) != B:
+        raise ValueError("plan_options: one prefix index per sample")
+    if video_start is None:
+        vs = torch.zeros(B, dtype=torch.int64)
+    elif isinstance(video_start, int):
+        vs = torch.full((B,), video_start, dtype=torch.int64)
+    else:
+        vs = torch.as_tensor([int(v) for v in video_start], dtype=torch.int64)
+    differs = (ids != ids[:, :1]).any(1)                                  # (B, S)
+    pos = torch.arange(S)
+    lcp = torch.where(differs, pos, torch.full_like(pos, S)).min(1).values
+    ok = lab[:, :, 1:] > 0                                                # (B, O, S-1): row t scored
+    any_t = ok.any(1)                                                     # (B, S-1)
+    has = any_t.any(1)
+    t = torch.arange(S - 1)
+    first = torch.where(any_t, t, torch.full_like(t, S)).min(1).values
+    last = torch.where(any_t, t, torch.full_like(t, -1)).max(1).values
+    start = torch.minimum(lcp, first)
+    length = torch.where(has, last + 1 - start, torch.zeros_like(start))
+    why = ""
+    if not bool(has.all()):
+        why = "a sample has no scored row"
+    elif bool((start < vs + F + 1).any()):
+        why = "an option differs (or is scored) inside or in front of the frame slots"
+    elif int(length.max()) > ops.SUFFIX_MAX:
+        why = f"a suffix of {int(length.max())} rows (> {ops.SUFFIX_MAX})"
+    return OptionPlan(start=start, length=length, T=int(length.max()) if B else 0, shared=not why, why_dense=why,
+                      rows=torch.nonzero(ok))
+
+
+def route_of(plan: OptionPlan) -> str:
+    """FVQA_SCORE=shared|dense picks the form; a batch the planner turns down goes dense whatever was asked."""
+    want = os.environ.get("FVQA_SCORE", "") or DEFAULT_ROUTE
+    if want not in ROUTES:
+        raise ValueError(f"FVQA_SCORE={want!r}: expected one of {ROUTES}")
+    return want if plan.shared else "dense"
+
+
+def _front_inputs(data: dict, repeat: int = 1) -> dict:
+    sub = {}
+    for k in ("video", "audio"):                           # (the audio-only batch has no "video")
+        if k in data:
+            sub[k] = data[k] if repeat == 1 else data[k].repeat_interleave(repeat, 0)
+    return sub
+
+
+def _pick(eng, rowloss, row_map_host, n_rows, B, O, S):
+    row_map = row_map_host.to(torch.int32).to(eng.device, non_blocking=True)
+    return ops.option_pick(rowloss, row_map, n_rows, B, O, S)
+
+
+@torch.no_grad()
+def score_options(eng, data: dict, route: Optional[str] = None, events: Optional[list] = None):
+    """-> dict(individual_losses (B, O, S-1) fp32, sum, count (int64), mean (B, O), prediction (B,) int64 — all on the device —,
+    route, plan). route: None = route_of(plan). events: a list that receives (name, start, end) torch.cuda.Event triples of the
+    passes (tools/score_bench.py)."""
+    ids = data["text_id"]["vqa"]
+    lab = data["label"]["vqa"]
+    ids_h, lab_h = ids.cpu(), lab.cpu()
+    if ids_h.dim() != 3:
+        raise ValueError("score_options: text_id['vqa'] must be (B, n_options, S)")
+    V = eng.V
+    if int(ids_h.min()) < 0 or int(ids_h.max()) >= V:
+        raise ValueError(f"text_id[vqa] outside [0, {V})")
+    vs_list = [int(v) for v in data["video_start"]["vqa"]]
+    plan = plan_options(ids_h, lab_h, data.get("prefix_index", {}).get("vqa"), vs_list, eng.F)
+    route = route or route_of(plan)
+    if route == "shared" and not plan.shared:
+        raise ValueError(f"score_options: this batch cannot take the shared form ({plan.why_dense})")
+    fn = _shared if route == "shared" else _dense
+    il, s, cnt, mean, pred = fn(eng, data, ids_h, lab_h, vs_list, plan, events)
+    return dict(individual_losses=il, sum=s, count=cnt, mean=mean, prediction=pred, route=route, plan=plan)
+
+
+def _mark(events, name):
+    if events is None:
+        return lambda: None
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+
+    def done():
+        b.record()
+        events.append((name, a, b))
+    return done
+
+
+def _dense(eng, data, ids_h, lab_h, vs_list, plan, events):
+    B, O, S = ids_h.shape
+    sub = _front_inputs(data, O)
+    sub.update({"text_id": {"vqa": ids_h.reshape(B * O, 1, S)}, "label": {"vqa": lab_h.reshape(B * O, 1, S)},
+                "video_start": {"vqa": [vs_list[0]] * (B * O), "vaq": [vs_list[0]] * (B * O)}})
+    done = _mark(events, "dense forward")
+    with vqa_stream_only(eng, "_score_arena", "scored"):
+        eng.forward(sub)                                   # tail rows: the last layer's second half and the head on scored rows
+        tl, ar = eng.last_scored, eng.saved["ar"]
+        eng.saved = None                                   # (no backward follows)
+    done()
+    o0, rows = tl.segs[0]
+    m = tl.counts[0]
+    n, c, t = plan.rows.unbind(1)                          # the same row-major order as scored.lists_of over (B*O, S)
+    assert m == n.numel()
+    row_map = torch.full((rows,), -1, dtype=torch.int64)
+    row_map[:m] = (n * O + c) * (S - 1) + t
+    return _pick(eng, ar.rowloss_c[o0:o0 + rows], row_map, rows, B, O, S)
+
+
+def _shared(eng, data, ids_h, lab_h, vs_list, plan, events):
+    m_, pk, dev = eng.model, eng.pack, eng.device
+    B, O, S = ids_h.shape
+    D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
+    T = plan.T
+    # ---- the prompt pass: option 0, no scored row (its labels are all ignored: the head sees pad rows only)
+    sub = _front_inputs(data)
+    sub.update({"text_id": {"vqa": ids_h[:, 0:1]}, "label": {"vqa": torch.zeros(B, 1, S, dtype=torch.int64)},
+                "video_start": {"vqa": vs_list, "vaq": vs_list}})
+    # ---- the suffix rows (host integers, staged while the prompt pass runs)
+    start, length = plan.start, plan.length
+    j = torch.arange(T)
+    pos = (start[:, None] + j[None, :]).clamp(max=S - 1)                                   # (B, T)
+    ids_suf = ids_h.gather(2, pos[:, None, :].expand(B, O, T))
+    ids_suf = torch.where((j[None, :] < length[:, None])[:, None, :], ids_suf, torch.zeros_like(ids_suf))
+    n, c, t = plan.rows.unbind(1)
+    M = int(n.numel())
+    rows = scored.rows_of(M)
+    gidx = torch.zeros(rows, dtype=torch.int32)
+    gidx[:M] = ((n * O + c) * T + (t - start[n])).to(torch.int32)
+    lab_shift = torch.zeros(rows, dtype=torch.int64)
+    lab_shift[1:M + 1] = lab_h[n, c, t + 1]
+    row_map = torch.full((rows,), -1, dtype=torch.int64)
+    row_map[:M] = (n * O + c) * (S - 1) + t
+    done = _mark(events, "prompt pass")
+    with vqa_stream_only(eng, "_score_arena", "scored"):
+        eng.forward(sub)
+        ar, vstart = eng.saved["ar"], eng.saved["vstart"]
+        eng.saved = None                                   # (no backward follows)
+    done()
+    done = _mark(events, "suffix pass")
+    mv = lambda x: x.to(dev, non_blocking=True)            # noqa: E731
+    start_d, len_d = mv(start.to(torch.int32)), mv(length.to(torch.int32))
+    R = B * O * T
+    x = pk.emb[mv(ids_suf.reshape(-1))].contiguous()       # token embeddings: the planner keeps frame slots out of a suffix
+    e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+    xn, hn, h, x2, o = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+    qkv, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
+    fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)    # the prefill left RAW keys in the cache
+    for i in range(L):
+        ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
+        ops.gemm_nt(xn, pk.wqkv[i], qkv)
+        g1, g2 = m_.gate_views(i)
+        ops.attn_suffix(qkv, ar.qkv[i], o, g1, g2, vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, H, Dh, A, F,
+                        cache_rotated=not fused)
+        ops.gemm_nt(o, pk.wo[i], h, residual=x)
+        ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
+        ops.gemm_nt(hn, pk.w13[i], ab)
+        ops.swiglu_fwd(ab, z, R, Hf)
+        ops.gemm_nt(z, pk.w2[i], x2, residual=h)
+        x, x2 = x2, x
+    # ---- the scored rows: final norm, LM head, cross-entropy (one "sequence" of `rows` positions, fvqa/scored.py)
+    xg, xf = e(rows, D), e(rows, D)
+    lg = e(rows, V, dtype=torch.float32)
+    lse, rowloss = e(rows, dtype=torch.float32), e(rows, dtype=torch.float32)
+    loss_sum = torch.zeros(2, dtype=torch.float32, device=dev)
+    ops.gather_rows(x, xg, ops.row_segs([mv(gidx)], [0, rows], R))
+    ops.rmsnorm_fwd(xg, pk.norm, xf, None, eng.eps, rows=rows)
+    ops.gemm_nt(xf, pk.wout, lg)
+    ops.ce_fwd(lg, mv(lab_shift), lse, rowloss, loss_sum, 1, rows, V, 0)
+    out = _pick(eng, rowloss, row_map, rows, B, O, S)
+    done()
+    return out

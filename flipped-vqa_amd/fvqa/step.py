@@ -237,6 +237,7 @@ class StepEngine:
         self.sin = sin.to(self.device).contiguous()
         self._arena: Dict[tuple, Arena] = {}
         self._gen_arena: Dict[tuple, Arena] = {}     # arenas of the generation path (VQA stream only)
+        self._score_arena: Dict[tuple, Arena] = {}   # arenas of the option-scoring path (fvqa/score.py; VQA stream only)
         self._vstart: Dict[tuple, torch.Tensor] = {}
         self.saved = None
         self.last_scored = None

@@ -295,6 +295,55 @@ def make_batch(cfg: SynthConfig, seed: int = 0, batch_size: Optional[int] = None
     return out
 
 
+def make_option_batch(cfg: SynthConfig, n_options: int = 5, seed: int = 0, batch_size: Optional[int] = None) -> dict:
+    """A validation-shaped batch (dataloader/__init__.py schema with n_options > 1; the multiple-choice protocol of reference
+    engine.py:86-93): per sample one prompt shared by all options — prefix, frame slots, question text, one common answer
+    token — then 1..3 tokens that differ per option and an end token, pad behind. Labels keep the ids from the answer's first
+    token on (dataloader/base_dataset.py:63-91), so the scored rows are the 3..5 rows in front of each option's end. Only the VQA
+    stream (the one validation reads); `answer` cycles through the options, `prefix_index` is where the answers start."""
+    B = batch_size or cfg.batch_size
+    S, F, V, O = cfg.max_seq_len, cfg.max_feats, cfg.vocab_size, n_options
+    tag = f"options{seed}"
+    vs = max(2, min(19, S // 4 - 1))
+    assert vs + F + 10 <= S, "sequence too short for the synthetic prompt layout"
+    prefix = _rand_ints(tag + ".prefix", B, max(vs + F + 3, S - 40), S - 6)         # the answer's first position
+    video = hashed_uniform(tag + ".video", (B, F, cfg.video_dim), math.sqrt(3.0))
+    prompt = _rand_ints(tag + ".ids", B * S, 3, V).reshape(B, S)
+    tail = _rand_ints(tag + ".tail", B * O * 3, 3, V).reshape(B, O, 3)
+    n_tail = 1 + _rand_ints(tag + ".ntail", B * O, 0, 3).reshape(B, O)
+    ids = torch.zeros(B, O, S, dtype=torch.int64)
+    lab = torch.zeros(B, O, S, dtype=torch.int64)
+    for b in range(B):
+        p = int(prefix[b])
+        for c in range(O):
+            k = int(n_tail[b, c])
+            ids[b, c, :p + 1] = prompt[b, :p + 1]
+            ids[b, c, vs:vs + F] = 0
+            ids[b, c, p + 1:p + 1 + k] = tail[b, c, :k]
+            ids[b, c, p + 1] = 3 + (int(tail[b, 0, 0]) + c) % (V - 3)              # the first answer token differs per option
+            ids[b, c, p + 1 + k] = 2                                               # the end token
+            lab[b, c, p:p + 2 + k] = ids[b, c, p:p + 2 + k]
+    out = {
+        "vid": [f"options{seed}_{b}" for b in range(B)],
+        "video": video,
+        "video_len": torch.full((B,), F, dtype=torch.long),
+        "text_id": {"vqa": ids},
+        "label": {"vqa": lab},
+        "video_start": {"vqa": [vs] * B},
+        "video_index": {"vqa": torch.arange(vs, vs + F).repeat(B, 1)},
+        "prefix_index": {"vqa": [int(p) for p in prefix]},
+        "answer": torch.arange(B, dtype=torch.long) % O,
+        "qtype": 1 + torch.arange(B, dtype=torch.long) % 8,
+    }
+    if cfg.audio != "none":
+        T = cfg.audio_rows
+        out["audio"] = hashed_uniform(tag + ".audio", (B, T, cfg.audio_dim), math.sqrt(3.0))
+        out["audio_len"] = torch.full((B,), T, dtype=torch.long)
+        if cfg.audio == "only":
+            del out["video"], out["video_len"]
+    return out
+
+
 class SyntheticLoader:
     """A fixed-length iterable of pre-built batches (stands in for DataLoader in tests/bench)."""
 

@@ -222,6 +222,18 @@ class Transformer(nn.Module):
         self.last_generation = {"ids": ids, "similarities": sims}
         return best, extracted
 
+    @torch.no_grad()
+    def score_options(self, data):
+        """The multiple-choice protocol's model half (reference llama/model_my_original_mod.py:332-377,506 with
+        `inference=True`, not a generation task): -> individual_losses (B, n_options, S-1) fp32 on the device, the per-token
+        cross-entropy (ignore_index 0) of every option, zero wherever a row is not scored. The reduction engine.py:86-93 makes of
+        it is done on the device as well and left in `last_scoring`: prediction (B,), per-option mean and count, and the route
+        that ran ("shared": the prompt once + each option's last rows; "dense": every option in full — fvqa/score.py)."""
+        from fvqa import score
+        r = score.score_options(self.ensure_engine(), data)
+        self.last_scoring = {k: r[k] for k in ("prediction", "mean", "count", "route")}
+        return r["individual_losses"]
+
     def forward(self, data, inference=False):
         if inference:
             return self.inference(data)

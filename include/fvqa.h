@@ -236,6 +236,28 @@ int fvqa_attn_decode(const void* qkv_row, void* qkv_cache, void* o_row, const fl
                      const int32_t* vstart, const int64_t* pos, const float* cos_t, const float* sin_t, int n_seq,
                      int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
                      int dtype, void* stream);
+/* Attention of the option-scoring path (fvqa/score.py) at the SUFFIX rows: the O answer options of a sample share their prompt,
+ * which is run once and left in qkv_cache exactly as fvqa_attn_decode takes it (same cache_rotated rule, adapter rows behind the
+ * n_seq*S sequence rows); each option recomputes only its last rows. qkv_suf (n_seq*n_options*suffix_len, 3*dim): RAW q | k | v
+ * of suffix row j of option c of sample n — row (n*n_options + c)*suffix_len + j, sequence position start[n] + j. A query row
+ * attends to the cache rows [0, start[n]) of its sample, to rows 0..j of its OWN option's suffix (rotated here, rounded to the
+ * storage type) and to the adapter keys (own softmax x tanh(gate1)); gate2 is added on the frame keys when the query position is
+ * >= vstart[n] + max_feats. start, len: int32 device arrays (n_seq); rows j >= len[n] are padding — never read, their o rows are
+ * zeros. Writes o_suf (n_seq*n_options*suffix_len, dim) and NOTHING else: the cache is read-only here. One launch, no atomics,
+ * bitwise repeatable. head_dim 128, seq_len <= 4096, suffix_len <= 16. */
+int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                     const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
+                     const float* sin_t, int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim,
+                     int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
+/* The per-option reduction of the multiple-choice protocol (reference engine.py:86-93). rowloss: n_rows compact per-row losses
+ * (fvqa_ce_fwd); row_map[r] = (n*n_options + c)*(seq_len-1) + t, the entry of individual_losses row r belongs to (< 0: a pad
+ * row; each entry listed at most once). Writes individual_losses (n_seq, n_options, seq_len-1) fp32 — zero wherever no row was
+ * scored —, per option the sum, the count of entries != 0 (int64; a scored row whose loss is exactly 0 is not counted, a NaN is)
+ * and mean = sum / count, and prediction (n_seq) int64 = argmin over options of the mean with torch's rule: the first NaN
+ * wins, ties go to the lowest index. Fixed summation order. n_options <= 64. */
+int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,
+                     float* option_sum, int64_t* option_count, float* option_mean, int64_t* prediction, int n_seq,
+                     int n_options, int seq_len, void* stream);
 /* workspace bytes fvqa_attn_bwd needs (fp32 partials for the batch-summed adapter k/v
  * gradients and the per-head gate sums). Its FIRST 1024 BYTES are integer arrival counters of the
  * fused bf16 backward: the caller zeroes them once after allocating the workspace; every call
