@@ -578,10 +578,12 @@ __global__ __launch_bounds__(256) void av_cross_attn_fwd_k(const float* __restri
 }
 
 // visual_proj_bwd_k with pitches: dW_s[d, k] += sum_r (d_tok[r,d] + d_qav[r,d]) * X_s[r,k] for source blockIdx.y, dW_s a column
-// range of a weight gradient with its own row pitch (S.s[].w / ldw). Same fma chain per output: rows ascending.
+// range of a weight gradient with its own row pitch (S.s[].w / ldw). Same fma chain per output: rows ascending. The gradient
+// rows have pitch ldg (fvqa_av_linear_bwd: a column range of a wider matrix); with dbias, dbias[d] += sum_r g[r,d], rows
+// ascending, by the waves of source 0.
 template <int KMAX, int DB, int RT>
 __global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d_tok, const float* __restrict__ d_qav,
-                                                     AvSrcs S, int R, int D) {
+                                                     AvSrcs S, int R, int D, int ldg, float* __restrict__ dbias) {
   const AvSrc src = blockIdx.y == 0 ? S.s[0] : S.s[1];
   const float* __restrict__ X = src.x;
   float* __restrict__ dW = const_cast<float*>(src.w);
@@ -590,10 +592,13 @@ __global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d
   if (d0 >= D) return;
   const int lane = threadIdx.x & 63;
   float acc[DB][KMAX];
+  float bsum[DB];
 #pragma unroll
-  for (int j = 0; j < DB; ++j)
+  for (int j = 0; j < DB; ++j) {
+    bsum[j] = 0.f;
 #pragma unroll
     for (int t = 0; t < KMAX; ++t) acc[j][t] = 0.f;
+  }
   for (int r0 = 0; r0 < R; r0 += RT) {
     float g[RT][DB];
     float v[RT][KMAX];
@@ -604,8 +609,8 @@ __global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d
 #pragma unroll
       for (int j = 0; j < DB; ++j) {
         const int d = d0 + j < D ? d0 + j : D - 1;
-        float gv = d_tok[(size_t)r * D + d];
-        if (d_qav) gv += d_qav[(size_t)r * D + d];
+        float gv = d_tok[(size_t)r * ldg + d];
+        if (d_qav) gv += d_qav[(size_t)r * ldg + d];
         g[rr][j] = gv * live;
       }
 #pragma unroll
@@ -619,9 +624,16 @@ __global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d
 #pragma unroll
     for (int rr = 0; rr < RT; ++rr)
 #pragma unroll
-      for (int j = 0; j < DB; ++j)
+      for (int j = 0; j < DB; ++j) {
+        bsum[j] += g[rr][j];
 #pragma unroll
         for (int t = 0; t < KMAX; ++t) acc[j][t] += g[rr][j] * v[rr][t];
+      }
+  }
+  if (dbias && blockIdx.y == 0 && lane == 0) {
+#pragma unroll
+    for (int j = 0; j < DB; ++j)
+      if (d0 + j < D) dbias[d0 + j] += bsum[j];
   }
 #pragma unroll
   for (int j = 0; j < DB; ++j) {
@@ -637,6 +649,172 @@ __global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d
       }
     }
   }
+}
+
+// ---- --train_audio: the backward of the audio half of the front end ---------------------------------------------------
+// Backward of av_cross_attn_fwd_k, one workgroup per sample: dq, dk, dv (written) from q, k, v and dx; the softmax is recomputed
+// with the maximum subtracted, as the forward does. Queries go through LDS in chunks of 16 (any n_query), columns in tiles of
+// 1024; a thread owns 4 columns of a tile and keeps dk_t, dv_t of the T <= 16 keys for them in registers.
+//   scores / dP: one wave per (f, t) pair, lanes over dim, wave_sum (a fixed shuffle tree)
+//   P, dS = P o (dP - sum_t P dP): one thread per query row, t ascending
+//   dv_t += P_ft dx_f, dk_t += dS_ft q_f: f ascending; dq_f = scale sum_t dS_ft k_t: t ascending
+// With one key P is exactly 1 and dS = 1 * (dP - 1 * dP) exactly 0: dq and dk come out as zeros.
+constexpr int CA_QC = 16;
+__global__ __launch_bounds__(256) void av_cross_attn_bwd_k(const float* __restrict__ q, const float* __restrict__ k,
+                                                           const float* __restrict__ v, const float* __restrict__ dx,
+                                                           float* __restrict__ dq, float* __restrict__ dk,
+                                                           float* __restrict__ dv, int nq, int T, int dim, int ldq, int ldk,
+                                                           int ldv, int lddq, int lddk, int lddv, float scale) {
+  __shared__ float sP[CA_QC][16];      // scores, then P
+  __shared__ float sD[CA_QC][16];      // dP, then dS
+  const int n = blockIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float* kn = k + (size_t)n * T * ldk;
+  const float* vn = v + (size_t)n * T * ldv;
+  for (int c0 = 0; c0 < dim; c0 += 1024) {
+    const int c = c0 + threadIdx.x * 4;
+    const bool live = c < dim;
+    float adk[16][4], adv[16][4];
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) adk[t][e] = adv[t][e] = 0.f;
+    for (int f0 = 0; f0 < nq; f0 += CA_QC) {
+      const int nf = nq - f0 < CA_QC ? nq - f0 : CA_QC;
+      __syncthreads();                                         // the previous chunk's readers are done with sP / sD
+      for (int p = w; p < nf * T; p += 4) {
+        const int f = p / T, t = p - f * T;
+        const size_t row = (size_t)n * nq + f0 + f;
+        const float* qr = q + row * ldq;
+        const float* dr = dx + row * dim;
+        const float* kr = kn + (size_t)t * ldk;
+        const float* vr = vn + (size_t)t * ldv;
+        float s = 0.f, d = 0.f;
+        for (int cc = lane * 4; cc < dim; cc += 256) {
+          float a[4], b[4];
+          Vec4<float>::load(qr + cc, a);
+          Vec4<float>::load(kr + cc, b);
+          s += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+          Vec4<float>::load(dr + cc, a);
+          Vec4<float>::load(vr + cc, b);
+          d += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+        }
+        s = wave_sum(s) * scale;
+        d = wave_sum(d);
+        if (lane == 0) { sP[f][t] = s; sD[f][t] = d; }
+      }
+      __syncthreads();
+      if ((int)threadIdx.x < nf) {
+        const int f = threadIdx.x;
+        float m = -INFINITY;
+        for (int t = 0; t < T; ++t) m = fmaxf(m, sP[f][t]);
+        float e[16], sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+          if (t < T) { e[t] = expf(sP[f][t] - m); sum += e[t]; }
+        const float inv = 1.f / sum;
+        float dot = 0.f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+          if (t < T) { e[t] *= inv; dot += e[t] * sD[f][t]; }
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+          if (t < T) { sD[f][t] = e[t] * (sD[f][t] - dot); sP[f][t] = e[t]; }
+      }
+      __syncthreads();
+      if (live) {
+        for (int f = 0; f < nf; ++f) {
+          const size_t row = (size_t)n * nq + f0 + f;
+          float qa[4], da[4], o[4] = {0.f, 0.f, 0.f, 0.f};
+          Vec4<float>::load(q + row * ldq + c, qa);
+          Vec4<float>::load(dx + row * dim + c, da);
+#pragma unroll
+          for (int t = 0; t < 16; ++t)
+            if (t < T) {
+              const float p = sP[f][t], ds = sD[f][t];
+              float ka[4];
+              Vec4<float>::load(kn + (size_t)t * ldk + c, ka);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                adv[t][e] += p * da[e];
+                adk[t][e] += ds * qa[e];
+                o[e] += ds * ka[e];
+              }
+            }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] *= scale;
+          Vec4<float>::store(dq + row * lddq + c, o);
+        }
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t)
+        if (t < T) {
+          float o[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = adk[t][e] * scale;
+          Vec4<float>::store(dk + ((size_t)n * T + t) * lddk + c, o);
+          Vec4<float>::store(dv + ((size_t)n * T + t) * lddv + c, adv[t]);
+        }
+    }
+  }
+}
+
+// Input gradient of a projection: dx[r, j] = sum_d (g0[r,d] + g1[r,d]) * W[d, j] on the exact-fp32 matrix cores. One workgroup
+// per 16 output columns and 16 rows (grid.y: at 80 rows and k = 768, 240 workgroups; one workgroup per 128 rows took 68 us at
+// dim = 4096, this one 29); its 4 waves split the reduction (dim % 64 == 0), the four partials meet in LDS and are added in
+// wave order. Per output the fma chain of a wave is d ascending in 16-element strides: fixed, bitwise repeatable.
+__global__ __launch_bounds__(256) void av_proj_dx_k(const float* __restrict__ g0, const float* __restrict__ g1,
+                                                    const float* __restrict__ W, float* __restrict__ dx, int R, int D, int K,
+                                                    int ldg, int ldw, int lddx) {
+  __shared__ float part[4][16][17];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int li = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+  const int r0 = blockIdx.y * 16;
+  const int dw = D / 4;                                      // this wave's range of the reduction
+  int bn = n0 + li; bn = bn < K ? bn : K - 1;
+  int ar = r0 + li; ar = ar < R ? ar : R - 1;
+  const float* bp = W + (size_t)(w * dw + 4 * g) * ldw + bn;
+  const size_t aoff = (size_t)ar * ldg + (size_t)w * dw + 4 * g;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int VU = 8;
+  for (int d0 = 0; d0 < dw; d0 += 16 * VU) {                 // every load of a trip in flight before its first MFMA
+    float bf[VU][4];
+    float4 af[VU];
+#pragma unroll
+    for (int u = 0; u < VU; ++u) {
+      const int d = d0 + 16 * u;
+      const bool in = d < dw;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bf[u][e] = in ? bp[(size_t)(d + e) * ldw] : 0.f;
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in) {
+        a = *reinterpret_cast<const float4*>(g0 + aoff + d);
+        if (g1) {
+          const float4 a1 = *reinterpret_cast<const float4*>(g1 + aoff + d);
+          a.x += a1.x; a.y += a1.y; a.z += a1.z; a.w += a1.w;
+        }
+      }
+      af[u] = a;
+    }
+#pragma unroll
+    for (int u = 0; u < VU; ++u) {
+      if (d0 + 16 * u >= dw) break;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u].x, bf[u][0], acc, 0, 0, 0);     // D[row 4g+e][column li]
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u].y, bf[u][1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u].z, bf[u][2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u].w, bf[u][3], acc, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) part[w][4 * g + e][li] = acc[e];
+  __syncthreads();
+  const int rr = threadIdx.x >> 4, c = threadIdx.x & 15;
+  const int r = r0 + rr, j = n0 + c;
+  if (r < R && j < K)
+    dx[(size_t)r * lddx + j] = ((part[0][rr][c] + part[1][rr][c]) + part[2][rr][c]) + part[3][rr][c];
 }
 
 // host side: the C sources checked and packed for a launch (16-byte rows everywhere: float4 loads)
@@ -765,18 +943,78 @@ extern "C" int fvqa_av_proj_bwd(const float* d_tok, const float* d_qav, const fv
       narrow = narrow && src[s].k <= 1024;
     }
     if (narrow) {              // every source in one launch (grid.y)
-      hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, d_tok, d_qav, S, rows, dim);
+      hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, d_tok, d_qav, S, rows, dim, dim,
+                         (float*)nullptr);
     } else {
       for (int s = 0; s < n_src; ++s) {
         AvSrcs one = S;
         one.s[0] = S.s[s];
         one.n = 1;
-        hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, d_tok, d_qav, one, rows, dim);
+        hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, d_tok, d_qav, one, rows, dim, dim,
+                           (float*)nullptr);
       }
     }
   }
   hipLaunchKernelGGL(temporal_bwd_k, dim3((max_feats * dim + 255) / 256), dim3(256), 0, st, d_tok, dtemporal,
                      rows / max_feats, max_feats, dim);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_cross_attn_bwd(const float* q, const float* k, const float* v, const float* dx, float* dq, float* dk,
+                                      float* dv, int n_samples, int n_query, int n_key, int dim, int ldq, int ldk, int ldv,
+                                      int lddq, int lddk, int lddv, float scale, void* stream) {
+  if (!q || !k || !v || !dx || !dq || !dk || !dv) return FVQA_EINVAL;
+  if (n_samples <= 0 || n_query <= 0 || n_key <= 0 || n_key > 16 || dim <= 0 || dim % 4 || ldq < dim || ldk < dim ||
+      ldv < dim || lddq < dim || lddk < dim || lddv < dim)
+    return FVQA_ESHAPE;
+  if (ldq % 4 || ldk % 4 || ldv % 4 || lddq % 4 || lddk % 4 || lddv % 4 ||
+      (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dx | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15))
+    return FVQA_EALIGN;
+  hipLaunchKernelGGL(av_cross_attn_bwd_k, dim3(n_samples), dim3(256), 0, (hipStream_t)stream, q, k, v, dx, dq, dk, dv,
+                     n_query, n_key, dim, ldq, ldk, ldv, lddq, lddk, lddv, scale);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_proj_dx(const float* g0, const float* g1, const float* w, float* dx, int rows, int dim, int k,
+                               int ldg, int ldw, int lddx, void* stream) {
+  if (!g0 || !w || !dx) return FVQA_EINVAL;
+  if (rows <= 0 || dim <= 0 || dim % 64 || k <= 0 || k % 4 || ldg < dim || ldw < k || lddx < k) return FVQA_ESHAPE;
+  if (ldg % 4 || ldw % 4 || lddx % 4 || (((uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)w | (uintptr_t)dx) & 15))
+    return FVQA_EALIGN;
+  hipLaunchKernelGGL(av_proj_dx_k, dim3((k + 15) / 16, (rows + 15) / 16), dim3(256), 0, (hipStream_t)stream, g0, g1, w, dx,
+                     rows, dim, k, ldg, ldw, lddx);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" int fvqa_av_linear_bwd(const float* g, int ldg, const fvqa_proj_src* src, int n_src, float* dbias, int rows,
+                                  int dim, void* stream) {
+  if (!g) return FVQA_EINVAL;
+  if (rows <= 0 || dim <= 0 || ldg < dim) return FVQA_ESHAPE;
+  if (ldg % 4 || (((uintptr_t)g | (uintptr_t)dbias) & 15)) return FVQA_EALIGN;
+  AvSrcs S;
+  bool mfma_ok;
+  if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
+  bool narrow = true;
+  for (int s = 0; s < n_src; ++s) {
+    if (src[s].k > 2048) return FVQA_ESHAPE;
+    narrow = narrow && src[s].k <= 1024;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (narrow) {
+    hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, g, (const float*)nullptr, S,
+                       rows, dim, ldg, dbias);
+  } else {
+    for (int s = 0; s < n_src; ++s) {                         // (blockIdx.y == 0 in each: the bias rides on the first only)
+      AvSrcs one = S;
+      one.s[0] = S.s[s];
+      one.n = 1;
+      hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, g, (const float*)nullptr, one,
+                         rows, dim, ldg, s == 0 ? dbias : (float*)nullptr);
+    }
+  }
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

@@ -55,6 +55,9 @@ SIGNATURES = {
     "fvqa_av_proj_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fvqa_av_cross_attn_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "fvqa_av_proj_bwd": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _p]),
+    "fvqa_av_cross_attn_bwd": (_i, [_p] * 7 + [_i] * 10 + [_f, _p]),
+    "fvqa_av_proj_dx": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fvqa_av_linear_bwd": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
     "fvqa_embed_splice": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_splice_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_ce_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _p]),

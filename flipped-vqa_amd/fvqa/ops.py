@@ -722,6 +722,49 @@ def av_proj_bwd(d_tok, d_qav, srcs, dtemporal):
     _lib.check(rc, "fvqa_av_proj_bwd")
 
 
+def av_cross_attn_bwd(q, k, v, dx, dq, dk, dv, n_samples: int, n_query: int, n_key: int):
+    """dq, dk, dv (written) of x = softmax(q·k^T / sqrt(dim))·v from dx; k | v and dk | dv may be column ranges of one buffer
+    (include/fvqa.h fvqa_av_cross_attn_bwd)."""
+    _dev(q, k, v, dq, dk, dv, rows_strided=True)
+    _dev(dx)
+    dim = dx.shape[1]
+    _need(all(t.dtype == torch.float32 for t in (q, k, v, dx, dq, dk, dv)), "av_cross_attn_bwd: fp32")
+    _need(tuple(q.shape) == (n_samples * n_query, dim) == tuple(dx.shape) == tuple(dq.shape), "av_cross_attn_bwd: q / dx / dq shapes")
+    _need(tuple(k.shape) == (n_samples * n_key, dim) == tuple(v.shape) == tuple(dk.shape) == tuple(dv.shape),
+          "av_cross_attn_bwd: k / v / dk / dv shapes")
+    rc = _lib.load().fvqa_av_cross_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(dx), _ptr(dq), _ptr(dk), _ptr(dv), n_samples, n_query,
+                                            n_key, dim, q.stride(0), k.stride(0), v.stride(0), dq.stride(0), dk.stride(0),
+                                            dv.stride(0), 1.0 / math.sqrt(dim), _stream())
+    _lib.check(rc, "fvqa_av_cross_attn_bwd")
+
+
+def av_proj_dx(g0, g1, w, dx):
+    """dx (rows, k) = (g0 + g1)·w (written): g0, g1 (rows, dim) fp32 — g1 or None —, w (dim, k) a weight or a column range of
+    one (include/fvqa.h fvqa_av_proj_dx)."""
+    _dev(g0, g1, w, dx, rows_strided=True)
+    rows, dim = g0.shape
+    k = w.shape[1]
+    _need(all(t is None or t.dtype == torch.float32 for t in (g0, g1, w, dx)), "av_proj_dx: fp32")
+    _need(g1 is None or (tuple(g1.shape) == (rows, dim) and g1.stride(0) == g0.stride(0)), "av_proj_dx: g1")
+    _need(w.shape[0] == dim and tuple(dx.shape) == (rows, k), "av_proj_dx: shapes")
+    rc = _lib.load().fvqa_av_proj_dx(_ptr(g0), _ptr(g1), _ptr(w), _ptr(dx), rows, dim, k, g0.stride(0), w.stride(0), dx.stride(0),
+                                     _stream())
+    _lib.check(rc, "fvqa_av_proj_dx")
+
+
+def av_linear_bwd(g, srcs, dbias=None):
+    """dW += g^T·x for each (x, dW) of the 1..2 sources, g (rows, dim) fp32 — a column range of a wider matrix allowed —, and
+    dbias (dim) += sum_rows g (include/fvqa.h fvqa_av_linear_bwd)."""
+    _dev(g, rows_strided=True)
+    _dev(dbias)
+    rows, dim = g.shape
+    _need(g.dtype == torch.float32 and 1 <= len(srcs) <= 2, "av_linear_bwd: fp32 g, one or two sources")
+    _need(dbias is None or (dbias.dtype == torch.float32 and tuple(dbias.shape) == (dim,)), "av_linear_bwd: dbias")
+    arr = _proj_srcs(srcs, rows, dim, "av_linear_bwd")
+    rc = _lib.load().fvqa_av_linear_bwd(_ptr(g), g.stride(0), C.addressof(arr), len(srcs), _ptr(dbias), rows, dim, _stream())
+    _lib.check(rc, "fvqa_av_linear_bwd")
+
+
 def embed_splice(ids, emb, vf_tok, h, n_seq, S, F, *, vstart: int = 0, zero_labels=None, index=None, mode: int = 0):
     _dev(ids, emb, vf_tok, h, zero_labels, index)
     D = emb.shape[1]

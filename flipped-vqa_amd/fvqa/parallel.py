@@ -81,6 +81,8 @@ class DataParallel(torch.nn.Module):
         of the audio modes (audio_proj, the cross-attention): randomly initialised, outside every checkpoint and — seeded
         seed+rank — different on every rank until here. torch DDP's constructor broadcasts frozen parameters too."""
         self._bcast(self.module.flat_params().flat)
+        if getattr(self.module, "train_audio", False):         # --train_audio: they are segments of the flat buffer
+            return
         eng = getattr(self.module, "_engine", None)
         for name in ("w_audio", "w_qkv", "b_qkv"):
             t = getattr(eng, name, None)

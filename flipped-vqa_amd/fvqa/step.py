@@ -252,8 +252,19 @@ class StepEngine:
     def _pack_front(self, model):
         """The audio modes' frozen front-end weights as fp32 device tensors (they are fp32 parameters already unless someone cast
         the module); `attention`: query | key | value row-concatenated, so that K and V of the audio rows are one projection —
-        the parameters become views of the fused buffers, as the layers' wq / wk / wv are."""
+        the parameters become views of the fused buffers, as the layers' wq / wk / wv are. With --train_audio the parameters
+        live in the flat trainable buffer (Transformer.flat_trainable_names lays query | key | value out adjacent): the fused
+        operands are views of it, no copy — a copy would detach them from the optimizer."""
         self.w_audio = self.w_qkv = self.b_qkv = None
+        self.train_audio = bool(getattr(model, "train_audio", False))
+        if self.train_audio:
+            flat = model._flat
+            self.w_audio = flat.span(["audio_proj.weight"], flat.flat)
+            if self.audio == "attention":
+                parts = ("query", "key", "value")
+                self.w_qkv = flat.span([f"video_audio_cross_attn.{m}.weight" for m in parts], flat.flat)
+                self.b_qkv = flat.span([f"video_audio_cross_attn.{m}.bias" for m in parts], flat.flat)
+            return
         if self.audio in ("only", "sum", "attention"):
             p = model.audio_proj.weight
             p.data = p.data.to(self.device, torch.float32).contiguous()
@@ -276,7 +287,9 @@ class StepEngine:
           concat     [video | audio]·Wv^T               two sources against two column ranges of Wv (D, 1792)
           sum        audio·Wa^T + video·Wv^T            two sources, two weights; the audio branch is frozen
           attention  X·Wv^T, X = softmax(Q K^T / sqrt(768)) V with Q = video·Wq^T + bq, [K | V] = a·[Wk | Wv]^T + [bk | bv],
-                     a = audio·Wa^T: five launches; X is kept, nothing trainable lies before it."""
+                     a = audio·Wa^T: five launches; X is kept, nothing trainable lies before it.
+        With --train_audio the audio branch trains: the audio rows (and, in `attention`, the video rows, a, Q and K | V) are kept
+        in `_front_audio` for `_front_bwd`."""
         m, dev, F, D = self.model, self.device, self.F, self.D
         f32 = torch.float32
         mode = self.audio
@@ -296,6 +309,7 @@ class StepEngine:
                              (f" or ({B}, 1..{F}, K)" if mode == "attention" else ""))
         audio_d = audio.to(dev, dtype=f32, non_blocking=True).reshape(B * T, -1).contiguous()
         Kv = video_d.shape[1] if video_d is not None else 0
+        self._front_audio = dict(audio=audio_d) if self.train_audio else None      # what the audio half's backward reads
         if mode == "only":
             ops.av_proj_fwd([(audio_d, self.w_audio)], vf_raw, temporal=temporal, out_tok=vf_tok)
             return vf_raw, vf_tok, []
@@ -316,18 +330,45 @@ class StepEngine:
         ops.av_proj_fwd([(a, self.w_qkv[E:])], kv, bias=self.b_qkv[E:])
         ops.av_cross_attn_fwd(q, kv[:, :E], kv[:, E:], x, B, F, T)
         ops.av_proj_fwd([(x, W)], vf_raw, temporal=temporal, out_tok=vf_tok)
+        if self.train_audio:
+            self._front_audio.update(video=video_d, a=a, q=q, kv=kv, T=T)
         return vf_raw, vf_tok, [(x, 0, E)]
 
     def _front_bwd(self, sv: dict, ar: "Arena", grads: "FlatParams", has_qav: bool):
         """d visual_proj += G^T·(the trainable projection's sources), G = d_tok + d_qav; d temporal_emb += sum_b d_tok[b]. The
-        frozen audio branch (`sum`, `only`) and the cross-attention (`attention`) get no gradient (llama_vqa.py:72)."""
+        frozen audio branch (`sum`, `only`) and the cross-attention (`attention`) get no gradient (llama_vqa.py:72) — unless
+        --train_audio: then `only` / `sum` hand the audio source with audio_proj's gradient to the same launch, and `attention`
+        walks back through the cross-attention (six more launches), everything += into the flat gradient."""
         d_qav = ar.d_qav if has_qav else None
         dT = grads.grad_view("temporal_emb.weight")
         if self.audio == "none":
             ops.visual_proj_bwd(ar.d_tok, d_qav, sv["front"][0][0], grads.grad_view("visual_proj.weight"), dT)
             return
         gW = grads.grad_view("visual_proj.weight") if sv["front"] else None
-        ops.av_proj_bwd(ar.d_tok, d_qav, [(x, gW[:, c0:c0 + k]) for x, c0, k in sv["front"]], dT)
+        srcs = [(x, gW[:, c0:c0 + k]) for x, c0, k in sv["front"]]
+        fa = sv.get("front_audio")
+        if fa is not None and self.audio in ("only", "sum"):
+            srcs.append((fa["audio"], grads.grad_view("audio_proj.weight")))
+        ops.av_proj_bwd(ar.d_tok, d_qav, srcs, dT)
+        if fa is None or self.audio != "attention":
+            return
+        # X = softmax(Q K^T) V fed visual_proj: dX = G·W_visual, then the cross-attention, its three linear layers, audio_proj
+        x, q, kv, a, T = sv["front"][0][0], fa["q"], fa["kv"], fa["a"], fa["T"]
+        E = x.shape[1]
+        B = x.shape[0] // self.F
+        parts = ("query", "key", "value")
+        gw_qkv = grads.span([f"video_audio_cross_attn.{m}.weight" for m in parts], grads.flat_grad)
+        gb_qkv = grads.span([f"video_audio_cross_attn.{m}.bias" for m in parts], grads.flat_grad)
+        dxa = torch.empty_like(x)
+        dq = torch.empty_like(q)
+        dkv = torch.empty_like(kv)
+        da = torch.empty_like(a)
+        ops.av_proj_dx(ar.d_tok, d_qav, self.model.visual_proj.weight.data, dxa)
+        ops.av_cross_attn_bwd(q, kv[:, :E], kv[:, E:], dxa, dq, dkv[:, :E], dkv[:, E:], B, self.F, T)
+        ops.av_linear_bwd(dq, [(fa["video"], gw_qkv[:E])], gb_qkv[:E])
+        ops.av_linear_bwd(dkv, [(a, gw_qkv[E:])], gb_qkv[E:])
+        ops.av_proj_dx(dkv, None, self.w_qkv[E:], da)
+        ops.av_linear_bwd(da, [(fa["audio"], grads.grad_view("audio_proj.weight"))])
 
     # ------------------------------------------------------------------ native layer schedule
     def layer_plan(self, ar: "Arena", grads: "FlatParams", vstart: torch.Tensor):
@@ -482,7 +523,7 @@ class StepEngine:
             elif tl is None:
                 ops.ce_fwd(ar.logits[rows], labels[t], ar.lse[rows], ar.rowloss[rows], ar.loss_sum[k], B, S, V, 0)
         self.saved = dict(ar=ar, B=B, S=S, vs=vs, labels=labels, qidx=qidx, front=front, vf_raw=vf_raw,
-                          vstart=vstart, tail=tl)
+                          vstart=vstart, tail=tl, front_audio=getattr(self, "_front_audio", None))
         self.last_scored = tl                                   # (tests: which rows the compact results belong to)
         losses = ar.loss_sum[:, 0] / ar.loss_sum[:, 1]        # mean over scored rows (NaN if none, as torch CE)
         return losses
@@ -681,7 +722,8 @@ class FlatParams:
     """All trainables of the model as views of ONE flat fp32 buffer (and one flat grad buffer).
 
     Layout: adapter_query | visual_proj | temporal_emb | gates (L_all, 2, H) — the model names the segments ahead of the gates
-    (the audio-only model has no visual_proj, `concat` a 1792-wide one). Parameter objects keep
+    (the audio-only model has no visual_proj, `concat` a 1792-wide one; with --train_audio, audio_proj | the cross-attention's
+    three weights | its three biases follow temporal_emb). Parameter objects keep
     their reference names/shapes (llama_vqa.py:71-76 freeze policy), only their storage moves."""
 
     def __init__(self, model):
@@ -731,6 +773,18 @@ class FlatParams:
     def grad_view(self, name):
         off, sz, shape = self.offsets[name]
         return self.flat_grad[off:off + sz].view(shape)
+
+    def span(self, names, buf):
+        """The adjacent segments `names` of `buf` (the flat parameter or gradient buffer) as ONE tensor, row-concatenated: the
+        fused query | key | value operands of the --train_audio front end."""
+        off0, _, shape = self.offsets[names[0]]
+        off = off0
+        for n in names:
+            o, sz, sh = self.offsets[n]
+            if o != off or sh != shape:
+                raise ValueError(f"flat segments {names} are not adjacent and alike")
+            off += sz
+        return buf[off0:off].view((len(names) * shape[0],) + tuple(shape[1:]))
 
     def gate_grad_views(self, i):
         li = self.model.engine_layer_ids()[i]

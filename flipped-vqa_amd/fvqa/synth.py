@@ -172,8 +172,13 @@ AUDIO_MODES = ("none", "only", "concat", "sum", "attention")
 TRAINABLE_MARKS = ("gate", "adapter", "temporal_emb", "visual_proj")   # reference llama_vqa.py:72
 
 
-def is_trainable(name: str) -> bool:
-    return any(m in name for m in TRAINABLE_MARKS)
+AUDIO_TRAIN_PREFIXES = ("audio_proj.", "video_audio_cross_attn.")    # what --train_audio adds: the filter above misses them
+
+
+def is_trainable(name: str, train_audio: bool = False) -> bool:
+    """The reference's freeze filter; with `train_audio` (--train_audio, a deviation from the reference) the audio half of the
+    front end trains as well."""
+    return any(m in name for m in TRAINABLE_MARKS) or (train_audio and name.startswith(AUDIO_TRAIN_PREFIXES))
 
 
 def make_tensor(cfg: SynthConfig, name: str, shape, kind: str, device="cpu") -> torch.Tensor:

@@ -133,6 +133,9 @@ class Transformer(nn.Module):
         self.n_layers = params.n_layers
         self.max_feats = args.max_feats
         self.audio_mode = audio_mode(args)         # none | only | concat | sum | attention (reference llama/model.py:209-227)
+        # --train_audio: audio_proj and the cross-attention train, ride in the flat buffer and travel with the checkpoint
+        # (`concat` and the video-only model have no frozen audio part: nothing changes there)
+        self.train_audio = bool(getattr(args, "train_audio", False)) and self.audio_mode in ("only", "sum", "attention")
 
         self.tokenizer = Tokenizer(model_path=f"{args.llama_model_path}./tokenizer.model", args=args)
         self.eos_id = self.tokenizer.eos_id
@@ -142,9 +145,9 @@ class Transformer(nn.Module):
         self.tok_embeddings = _Weight(params.vocab_size, params.dim)
         self.adapter_query = _Weight(params.adapter_len * params.adapter_layer, params.dim, init="normal")
         # The front end's projections, registered in the reference's order (llama/model.py:209-227). audio_proj and the
-        # cross-attention are outside the freeze policy's filter (llama_vqa.py:72): they stay at this initialisation — nn.Linear's
-        # own rule, drawn from torch's seeded generator — in every mode, and no checkpoint of trainables holds them. They are
-        # kept in fp32 whatever the storage type: the front end is fp32 arithmetic.
+        # cross-attention are outside the freeze policy's filter (llama_vqa.py:72): without --train_audio they stay at this
+        # initialisation — nn.Linear's own rule, drawn from torch's seeded generator — in every mode, and no checkpoint of
+        # trainables holds them. They are kept in fp32 whatever the storage type: the front end is fp32 arithmetic.
         f32 = dict(dtype=torch.float32)
         am = self.audio_mode
         if am in ("only", "sum"):
@@ -185,10 +188,22 @@ class Transformer(nn.Module):
         g = self._flat.gates
         return g[li, 0], g[li, 1]
 
+    def is_trainable(self, name: str) -> bool:
+        """The freeze policy of THIS model: the reference's name filter, widened by --train_audio."""
+        from fvqa import synth
+        return synth.is_trainable(name, self.train_audio)
+
     def flat_trainable_names(self):
-        """The trainables FlatParams lays out ahead of the gates, in buffer order (no visual_proj in the audio-only model)."""
-        return ["adapter_query.weight"] + (["visual_proj.weight"] if hasattr(self, "visual_proj") else []) + \
+        """The trainables FlatParams lays out ahead of the gates, in buffer order (no visual_proj in the audio-only model). With
+        --train_audio the audio front end follows temporal_emb: audio_proj, then the cross-attention's query | key | value weights
+        adjacent and its three biases adjacent — the fused operands of the step engine are then single ranges of the buffer."""
+        names = ["adapter_query.weight"] + (["visual_proj.weight"] if hasattr(self, "visual_proj") else []) + \
             ["temporal_emb.weight"]
+        if self.train_audio:
+            names.append("audio_proj.weight")
+            if self.audio_mode == "attention":
+                names += [f"video_audio_cross_attn.{m}.{w}" for w in ("weight", "bias") for m in ("query", "key", "value")]
+        return names
 
     def trainable_parameters(self):
         return [p for p in self.parameters() if p.requires_grad]

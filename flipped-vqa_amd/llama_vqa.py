@@ -88,7 +88,7 @@ def LLaMA_VQA(args, **kwargs):
     if shards:
         model.load_state_dict(merge_shards(shards, params["n_layers"]), strict=False)
     for name, p in model.named_parameters():     # freeze policy
-        p.requires_grad = synth.is_trainable(name)
+        p.requires_grad = model.is_trainable(name)   # (the name filter, widened by --train_audio)
         if p.requires_grad:
             p.data = p.data.float()
     if not shards:

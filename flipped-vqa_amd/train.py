@@ -65,6 +65,8 @@ _FLAGS = [
     ("--audio_only", dict(action="store_true")),
     ("--audio_merge", dict(type=str, choices=["sum", "concat", "attention", "none"], default="none")),
     # MI355X build additions
+    ("--train_audio", dict(action="store_true", help="train (and checkpoint) audio_proj and the audio-video cross-attention, "
+                                                     "which the reference's freeze filter leaves at their random initialisation")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
     ("--synthetic", dict(action="store_true", help="synthetic tokenizer constants + synthetic batches")),
@@ -91,6 +93,11 @@ def validate_args(args):
     if args.audio and not args.audio_only:
         assert args.audio_merge in ("sum", "concat", "attention"), \
             "An audio_merge method must be specified if audio is True and audio_only is False"
+    if getattr(args, "train_audio", False):
+        assert args.audio, "--train_audio needs --audio: without it the model has no audio front end"
+        if args.audio_merge == "concat":
+            print("--train_audio changes nothing with --audio_merge concat: that mode has no frozen audio part "
+                  "(the audio columns of visual_proj train already)")
 
 
 def build_loaders(args, model):

@@ -308,7 +308,8 @@ class NativeScalerWithGradNormCount:
 def trainable_state(model_without_ddp):
     """name -> tensor for the parameters the freeze policy trains (reference llama_vqa.py:72,
     util/misc.py:303-306) — detached copies, so a checkpoint never aliases the flat buffer."""
-    return {n: p.detach().clone() for n, p in model_without_ddp.named_parameters() if is_trainable(n)}
+    rule = getattr(model_without_ddp, "is_trainable", is_trainable)      # the model's rule: --train_audio widens the name filter
+    return {n: p.detach().clone() for n, p in model_without_ddp.named_parameters() if rule(n)}
 
 
 def save_model(args, epoch, model, model_without_ddp, optimizer, loss_scaler, name):

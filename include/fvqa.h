@@ -310,14 +310,32 @@ typedef struct fvqa_proj_src {
 int fvqa_av_proj_fwd(const fvqa_proj_src* src, int n_src, const float* bias, const float* temporal, float* out_raw,
                      void* out_tok, int rows, int max_feats, int dim, int dtype, void* stream);
 /* x (n_samples*n_query, dim) fp32 = softmax_t(q·k_t * scale)·v over the n_key <= 16 keys of the same sample, maximum
- * subtracted (llama/model.py:153-169); q (n_samples*n_query, dim | ldq), k, v (n_samples*n_key, dim | ldk, ldv). Forward only:
- * the module is frozen and nothing trainable lies before it. */
+ * subtracted (llama/model.py:153-169); q (n_samples*n_query, dim | ldq), k, v (n_samples*n_key, dim | ldk, ldv). Its backward
+ * (--train_audio) is fvqa_av_cross_attn_bwd. */
 int fvqa_av_cross_attn_fwd(const float* q, const float* k, const float* v, float* x, int n_samples, int n_query,
                            int n_key, int dim, int ldq, int ldk, int ldv, float scale, void* stream);
 /* dW_s (dim, k_s | ldw) += (d_tok + d_qav)^T·x_s for each of n_src = 0..2 TRAINABLE sources (src[s].w = where the source's
  * columns start in the weight gradient, k_s <= 2048), dtemporal (F, dim) += sum_b d_tok[b] as fvqa_visual_proj_bwd. */
 int fvqa_av_proj_bwd(const float* d_tok, const float* d_qav, const fvqa_proj_src* src, int n_src, float* dtemporal,
                      int rows, int max_feats, int dim, void* stream);
+/* --train_audio: the backward of the audio half of the front end. Same contract as the entries above: exact fp32, fixed
+ * summation order, no float atomics, bitwise repeatable, operands checked before any launch.
+ * Backward of fvqa_av_cross_attn_fwd with the forward's operands and pitches (k and v may lie side by side in one buffer) and
+ * dx (n_samples*n_query, dim): dq (.., dim | lddq), dk, dv (n_samples*n_key, dim | lddk, lddv) are WRITTEN (dk | dv may share
+ * one pitched buffer). The softmax is recomputed, maximum subtracted: dv_t = sum_f P_ft dx_f, dP_ft = dx_f·v_t,
+ * dS = P o (dP - sum_t P dP), dq_f = scale sum_t dS_ft k_t, dk_t = scale sum_f dS_ft q_f. n_key <= 16, any n_query; one
+ * workgroup per sample. With one key, dq and dk are exact zeros. */
+int fvqa_av_cross_attn_bwd(const float* q, const float* k, const float* v, const float* dx, float* dq, float* dk, float* dv,
+                           int n_samples, int n_query, int n_key, int dim, int ldq, int ldk, int ldv, int lddq, int lddk,
+                           int lddv, float scale, void* stream);
+/* Input gradient of a projection: dx (rows, k | lddx) = (g0 + g1)·w, g0 and g1 (rows, dim | ldg) fp32 (g1 or NULL), w (dim, k |
+ * ldw) — a weight or a column range of one. Written. dim % 64 == 0 (the exact-fp32 matrix cores, 16 rows x 16 columns per workgroup). */
+int fvqa_av_proj_dx(const float* g0, const float* g1, const float* w, float* dx, int rows, int dim, int k, int ldg, int ldw,
+                    int lddx, void* stream);
+/* Weight (+ bias) gradient of a linear layer: dW_s (dim, k_s | ldw) += g^T·x_s for each of n_src = 1..2 sources, g (rows, dim |
+ * ldg) — fvqa_av_proj_bwd's kernel for a general, pitched g; dbias (dim) += sum_rows g, or NULL. */
+int fvqa_av_linear_bwd(const float* g, int ldg, const fvqa_proj_src* src, int n_src, float* dbias, int rows, int dim,
+                       void* stream);
 
 /* ---- token embedding gather + frame splice (llama/model.py:286-294,326-336) -----------
  * h[n,s,:] = emb[ids[n,s]] (zeroed where zero_labels[n,s] >= 0; NULL = never) then

@@ -9,6 +9,10 @@ anywhere):
     python tools/audio_frontend_profile.py --mode none --dump out.npz                      # losses + flat gradient of two
                                                                                            # video-only cases, for a bitwise diff
     python tools/audio_frontend_profile.py --diff a.npz b.npz
+    python tools/audio_frontend_profile.py --mode attention --audio_len 10 --interleave 4  # profiles/audio_train.log: --train_audio
+                                                                                           # off against on, alternating blocks
+    rocprofv3 --kernel-trace --stats --output-format csv -d out -- \\
+        python tools/audio_frontend_profile.py --mode attention --audio_len 10 --train_audio --layers 2 --steps 5
 
 C2 is BASELINE configs[1]: 7B, B = 8, S = 128, bf16, VQA loss. `--layers 2` keeps width and batch and cuts the depth (the front end
 does not see the depth)."""
@@ -26,7 +30,7 @@ for p in (os.path.join(ROOT, "flipped-vqa_amd"), ROOT):
 os.environ.setdefault("FVQA_SYNTHETIC_TOKENIZER", "1")
 
 
-def build(cfg, dtype, mode):
+def build(cfg, dtype, mode, train_audio=False):
     import torch
     import llama
     from fvqa import synth
@@ -38,7 +42,8 @@ def build(cfg, dtype, mode):
         audio = dict(audio=True, audio_only=False, audio_merge=mode)
     args = types.SimpleNamespace(max_feats=cfg.max_feats, bias=cfg.bias, tau=cfg.tau, llama_model_path="/nonexistent/",
                                  vaq=cfg.vaq, qav=cfg.qav, synthetic=True, vocab_size=cfg.vocab_size, debug=False,
-                                 adapter_len=cfg.adapter_len, adapter_layer=cfg.adapter_layer, max_seq_len=cfg.max_seq_len, **audio)
+                                 adapter_len=cfg.adapter_len, adapter_layer=cfg.adapter_layer, max_seq_len=cfg.max_seq_len, train_audio=train_audio,
+                                 **audio)
     ma = llama.ModelArgs(max_seq_len=cfg.max_seq_len, max_batch_size=32, adapter_len=cfg.adapter_len,
                          adapter_layer=cfg.adapter_layer, **cfg.params_json())
     ma.vocab_size = cfg.vocab_size
@@ -50,7 +55,7 @@ def build(cfg, dtype, mode):
     finally:
         torch.set_default_dtype(prev)
     for n, p in model.named_parameters():
-        p.requires_grad = synth.is_trainable(n)
+        p.requires_grad = synth.is_trainable(n, getattr(model, "train_audio", False))
         if p.requires_grad:
             p.data = p.data.float()
     fill_closed_form(model, cfg)
@@ -72,6 +77,10 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--train_audio", action="store_true", help="the audio half of the front end trains (train.py --train_audio)")
+    ap.add_argument("--audio_len", type=int, default=1, help="audio rows per sample in mode attention (the dataset hands 1)")
+    ap.add_argument("--interleave", type=int, default=0, metavar="ROUNDS",
+                    help="flag off and flag on in ONE process: ROUNDS alternating blocks of --steps steps each")
     ap.add_argument("--dump")
     ap.add_argument("--diff", nargs=2)
     a = ap.parse_args()
@@ -85,7 +94,7 @@ def main():
     from fvqa import build as fb
     from fvqa import synth
     from fvqa.step import stage_batch
-    over = {} if a.mode == "none" else dict(audio=a.mode, audio_len=1 if a.mode == "attention" else 0)
+    over = {} if a.mode == "none" else dict(audio=a.mode, audio_len=a.audio_len if a.mode == "attention" else 0)
     if a.dump:
         out = {}
         for name, pname, kw in (("tiny_all", "tiny", dict(vaq=True, qav=True)),
@@ -103,8 +112,31 @@ def main():
         print(json.dumps({"dumped": a.dump, "sources": fb.source_hash()[:12], "arrays": len(out)}))
         return
     cfg = synth.preset("7b", n_layers=a.layers, adapter_layer=a.layers, batch_size=8, **over)
-    model = build(cfg, torch.bfloat16, a.mode)
     batch = stage_batch(synth.make_batch(cfg, seed=0), torch.device("cuda"))
+    if a.interleave:
+        models = {flag: build(cfg, torch.bfloat16, a.mode, train_audio=flag) for flag in (False, True)}
+        for m in models.values():
+            for _ in range(a.warmup):
+                step(m, batch)
+        torch.cuda.synchronize()
+        ms = {False: [], True: []}
+        for _ in range(a.interleave):
+            for flag, m in models.items():
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+                for e0, e1 in ev:
+                    e0.record()
+                    step(m, batch)
+                    e1.record()
+                torch.cuda.synchronize()
+                ms[flag] += [e0.elapsed_time(e1) for e0, e1 in ev]
+        med = {flag: sorted(v)[len(v) // 2] for flag, v in ms.items()}
+        print(json.dumps({"mode": a.mode, "audio_len": cfg.audio_rows if a.mode != "none" else 0, "layers": a.layers, "B": 8,
+                          "S": cfg.max_seq_len, "dtype": "bf16", "steps_each": a.steps * a.interleave,
+                          "off_ms_median": round(med[False], 3), "on_ms_median": round(med[True], 3),
+                          "off_ms_min": round(min(ms[False]), 3), "on_ms_min": round(min(ms[True]), 3),
+                          "on_minus_off_ms": round(med[True] - med[False], 3), "sources": fb.source_hash()[:12]}))
+        return
+    model = build(cfg, torch.bfloat16, a.mode, train_audio=a.train_audio)
     for _ in range(a.warmup):
         losses = step(model, batch)
     torch.cuda.synchronize()
@@ -115,7 +147,7 @@ def main():
         e1.record()
     torch.cuda.synchronize()
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
-    print(json.dumps({"mode": a.mode, "layers": a.layers, "B": 8, "S": cfg.max_seq_len, "dtype": "bf16", "steps": a.steps,
+    print(json.dumps({"mode": a.mode, "train_audio": bool(getattr(model, "train_audio", False)), "layers": a.layers, "B": 8, "S": cfg.max_seq_len, "dtype": "bf16", "steps": a.steps,
                       "step_ms_median": round(ms[len(ms) // 2], 3), "step_ms_min": round(ms[0], 3),
                       "loss_vqa": float(losses[0].detach()), "sources": fb.source_hash()[:12]}))
 
