@@ -149,3 +149,9 @@ static inline bool fvqa_attr_needed(std::atomic<unsigned long long>& done) {
 
 static inline int fvqa_dtype_ok(int dt) { return dt == FVQA_F32 || dt == FVQA_H16; }   // (this build's 16-bit code only)
 static inline size_t fvqa_dtype_size(int dt) { return dt == FVQA_F32 ? 4 : 2; }
+// Host-side operand check of the entry points: every pointer of the list lies on a `bytes` boundary (a power of two: the widest
+// access its kernel makes on it). A null pointer (an optional operand) passes.
+template <typename... P> static inline bool fvqa_aligned(size_t bytes, P... p) {
+  return ((... | (uintptr_t)p) & (uintptr_t)(bytes - 1)) == 0;
+}
+static inline size_t fvqa_vec4_bytes(int dt) { return 4 * fvqa_dtype_size(dt); }   // one Vec4<T> access

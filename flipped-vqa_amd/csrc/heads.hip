@@ -842,12 +842,15 @@ extern "C" int fvqa_visual_proj_fwd(const float* video, const float* W, const fl
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_frames_total <= 0 || max_feats <= 0 || in_dim <= 0 || in_dim % 4 || in_dim > 2048 || dim <= 0)
     return FVQA_ESHAPE;
+  // both kernels read video and W 16 bytes at a time; the outputs and the temporal table are element accesses
+  if (!fvqa_aligned(16, video, W) || !fvqa_aligned(4, temporal, vf_raw) || !fvqa_aligned(fvqa_dtype_size(dtype), vf_tok))
+    return FVQA_EALIGN;
   dim3 grid((dim + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   // The wave-per-feature kernel re-reads the whole frame matrix for every output feature (1 GB of L2 traffic at
   // D = 4096: 120 us). Shapes of the step (K % 64 == 0, at most 128 frame rows, 16-byte rows) run on the exact-fp32
   // matrix cores instead, temporal embedding and cast included.
-  if (in_dim % 64 == 0 && n_frames_total <= 128 && !(((uintptr_t)video | (uintptr_t)W) & 15)) {
+  if (in_dim % 64 == 0 && n_frames_total <= 128) {
     const dim3 g16((dim + 15) / 16);
     if (dtype == FVQA_H16)
       hipLaunchKernelGGL(visual_proj_fwd_mfma_k<bf16_t>, g16, block, 0, st, video, W, temporal, vf_raw, (bf16_t*)vf_tok,
@@ -875,6 +878,7 @@ extern "C" int fvqa_visual_proj_bwd(const float* d_tok, const float* d_qav, cons
   if (n_frames_total <= 0 || max_feats <= 0 || n_frames_total % max_feats || in_dim <= 0 || in_dim % 4 ||
       in_dim > 2048 || dim <= 0)
     return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, video, dW) || !fvqa_aligned(4, d_tok, d_qav, dtemporal)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (in_dim <= 1024)        // 4 features per wave (4 x 16 accumulators), 4 waves per CU at D = 4096
     hipLaunchKernelGGL((visual_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16), dim3(256), 0, st, d_tok, d_qav, video, dW,
@@ -1023,6 +1027,7 @@ extern "C" int fvqa_ce_fwd(const float* logits, const int64_t* labels, float* ls
                            int n_seq, int seq_len, int vocab, int64_t ignore_index, void* stream) {
   if (!logits || !labels || !lse || !rowloss || !loss_sum) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len < 2 || vocab <= 0 || vocab % 4) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, logits) || !fvqa_aligned(8, labels) || !fvqa_aligned(4, lse, rowloss, loss_sum)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int rows = n_seq * seq_len;
   hipLaunchKernelGGL(ce_fwd_k, dim3(rows), dim3(1024), 0, st, logits, labels, lse, rowloss, seq_len, vocab,
@@ -1039,6 +1044,9 @@ extern "C" int fvqa_ce_bwd(const float* logits, const int64_t* labels, const flo
   if (!logits || !labels || !lse || !loss_sum || !gscale || !dlogits) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len < 2 || vocab <= 0 || vocab % 4) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, logits) || !fvqa_aligned(fvqa_vec4_bytes(dtype), dlogits) || !fvqa_aligned(8, labels) ||
+      !fvqa_aligned(4, lse, loss_sum, gscale))
+    return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int rows = n_seq * seq_len;
   if (dtype == FVQA_H16)
@@ -1058,6 +1066,9 @@ extern "C" int fvqa_qav_head_fwd(const void* xn, const float* vf_raw, const int6
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len < 2 || dim <= 0 || dim % 4 || max_feats <= 0 || max_feats > 16 || tau == 0.f)
     return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), xn) || !fvqa_aligned(16, vf_raw) || !fvqa_aligned(8, labels) ||
+      !fvqa_aligned(4, probs, rowloss, loss_sum))
+    return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int rows = n_seq * seq_len;
   dim3 grid((rows + 3) / 4), block(256);
@@ -1080,6 +1091,9 @@ extern "C" int fvqa_qav_head_bwd(const void* xn, const float* vf_raw, const int6
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len < 2 || dim <= 0 || dim % 4 || max_feats <= 0 || max_feats > 16 || tau == 0.f)
     return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), xn, dxn) || !fvqa_aligned(16, vf_raw, d_raw) || !fvqa_aligned(8, labels) ||
+      !fvqa_aligned(4, probs, loss_sum, gscale))
+    return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int rows = n_seq * seq_len;
   dim3 grid((rows + 3) / 4), block(256);

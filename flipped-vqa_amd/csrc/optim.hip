@@ -142,6 +142,10 @@ extern "C" int fvqa_grad_unscale_norm(float* grad, const int64_t* seg_off, int n
   if (!(grad_div >= 1.f) || ((uintptr_t)gemm_err & 7)) return FVQA_EINVAL;
   if (n_seg <= 0 || n_seg > 65535) return FVQA_ESHAPE;
   if (workspace_bytes < fvqa_grad_norm_workspace(n_seg)) return FVQA_EALIGN;
+  // the 16-byte body of a segment is aligned by ELEMENT index (unscale_sq_k: a0, a1), so the base itself must be
+  if (!fvqa_aligned(16, grad) || !fvqa_aligned(8, seg_off) ||
+      !fvqa_aligned(4, scale, err_lane, seg_sq, found_inf, total_norm, workspace))
+    return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(unscale_sq_k, dim3(NB, n_seg), dim3(256), 0, st, grad, seg_off, scale, grad_div, (float*)workspace);
   hipLaunchKernelGGL(norm_finish_k, dim3(1), dim3(1024), 0, st, (const float*)workspace, n_seg, seg_sq, found_inf,
@@ -155,6 +159,7 @@ extern "C" int fvqa_adamw_step(float* param, const float* grad, float* exp_avg, 
                                const float* found_inf, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || !step) return FVQA_EINVAL;
   if (n <= 0) return FVQA_ESHAPE;
+  if (!fvqa_aligned(4, param, grad, exp_avg, exp_avg_sq, step, found_inf)) return FVQA_EALIGN;   // scalar accesses: any slice
   int64_t g = (n + 255) / 256;
   if (g > 2048) g = 2048;
   hipLaunchKernelGGL(adamw_k, dim3((int)g), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,

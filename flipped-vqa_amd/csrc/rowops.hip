@@ -309,6 +309,7 @@ extern "C" int fvqa_rmsnorm_fwd(const void* x, const void* w, void* y, float* rs
   if (!x || !w || !y) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (!norm_dims_ok(rows, dim)) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, x, w, y) || !fvqa_aligned(4, rstd)) return FVQA_EALIGN;      // load8 / store8: 16-byte accesses
   DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_fwd_k<T>), dim3(rows), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)x, (const T*)w, (T*)y, rstd, dim, eps));
   FVQA_CHECK_LAUNCH();
@@ -320,6 +321,7 @@ extern "C" int fvqa_rmsnorm_bwd(const void* g, const void* x, const void* w, con
   if (!g || !x || !w || !rstd || !dx) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (!norm_dims_ok(rows, dim)) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, g, x, w, resid, dx) || !fvqa_aligned(4, rstd)) return FVQA_EALIGN;
   DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_bwd_k<T>), dim3(rows), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)g, (const T*)x, (const T*)w, rstd, (const T*)resid, (T*)dx, dim));
   FVQA_CHECK_LAUNCH();
@@ -333,6 +335,7 @@ extern "C" int fvqa_rope_qk(void* qkv, const float* cos_t, const float* sin_t, i
   if (n_seq <= 0 || seq_len <= 0 || n_heads <= 0 || head_dim <= 0 || head_dim % 4) return FVQA_ESHAPE;
   const int rows = n_seq * seq_len, dim = n_heads * head_dim;
   if (head_dim % 8) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, qkv, cos_t, sin_t)) return FVQA_EALIGN;      // 8 elements of a row, 4 table entries per access
   const float sign = inverse ? -1.f : 1.f;
   DISPATCH_T(dtype, hipLaunchKernelGGL(rope_qk_k<T>, dim3(rows), dim3(256), 0, (hipStream_t)stream, (T*)qkv, cos_t,
                                        sin_t, seq_len, dim, head_dim, sign));
@@ -344,6 +347,7 @@ extern "C" int fvqa_swiglu_fwd(const void* ab, void* z, int rows, int hidden, in
   if (!ab || !z) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (rows <= 0 || hidden <= 0 || hidden % 16) return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), ab, z)) return FVQA_EALIGN;
   const size_t n4 = (size_t)rows * (hidden / 4);
   DISPATCH_T(dtype, hipLaunchKernelGGL(swiglu_fwd_k<T>, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)ab, (T*)z, n4, hidden));
@@ -356,6 +360,7 @@ extern "C" int fvqa_swiglu_bwd(const void* dz, const void* ab, void* dab, int ro
   if (!dz || !ab || !dab) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (rows <= 0 || hidden <= 0 || hidden % 16) return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), dz, ab, dab)) return FVQA_EALIGN;
   const size_t n4 = (size_t)rows * (hidden / 4);
   DISPATCH_T(dtype, hipLaunchKernelGGL(swiglu_bwd_k<T>, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)dz, (const T*)ab, (T*)dab, n4, hidden));
@@ -366,11 +371,12 @@ extern "C" int fvqa_swiglu_bwd(const void* dz, const void* ab, void* dab, int ro
 extern "C" int fvqa_embed_splice(const int64_t* ids, const void* emb, const void* vf_tok, const int64_t* zero_labels,
                                  const int64_t* index, void* h, int n_seq, int seq_len, int dim, int max_feats,
                                  int vstart, int mode, int dtype, void* stream) {
-  if (!ids || !emb || !vf_tok || !h) return FVQA_EINVAL;
+  if (!ids || !emb || !h || (!vf_tok && max_feats > 0)) return FVQA_EINVAL;      // no frames: nothing reads vf_tok (an empty tensor is a null pointer)
   if (!fvqa_dtype_ok(dtype) || (mode != 0 && mode != 1)) return FVQA_EINVAL;
   if (mode == 1 && !index) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len <= 0 || dim <= 0 || dim % 4 || max_feats < 0) return FVQA_ESHAPE;
   if (mode == 0 && (vstart < 0 || vstart + max_feats > seq_len)) return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), emb, vf_tok, h) || !fvqa_aligned(8, ids, zero_labels, index)) return FVQA_EALIGN;
   const int rows = n_seq * seq_len;
   dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
   DISPATCH_T(dtype, hipLaunchKernelGGL(embed_splice_k<T>, grid, block, 0, (hipStream_t)stream, ids, (const T*)emb,
@@ -387,6 +393,7 @@ extern "C" int fvqa_splice_bwd(const void* dh, const int64_t* index, float* d_to
   if (mode == 1 && !index) return FVQA_EINVAL;
   if (n_seq <= 0 || seq_len <= 0 || dim <= 0 || dim % 4 || max_feats <= 0) return FVQA_ESHAPE;
   if (mode == 0 && (vstart < 0 || vstart + max_feats > seq_len)) return FVQA_ESHAPE;
+  if (!fvqa_aligned(fvqa_vec4_bytes(dtype), dh) || !fvqa_aligned(16, d_tok) || !fvqa_aligned(8, index)) return FVQA_EALIGN;
   DISPATCH_T(dtype, hipLaunchKernelGGL(splice_bwd_k<T>, dim3(n_seq * max_feats), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)dh, index, d_tok, n_seq, seq_len, dim, max_feats, vstart, mode));
   FVQA_CHECK_LAUNCH();
@@ -435,6 +442,7 @@ extern "C" int fvqa_cast_rows(const float* src, void* dst, int n_rows, int dim, 
   if (!src || !dst) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_rows <= 0 || dim <= 0 || dim % 4) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, src) || !fvqa_aligned(fvqa_vec4_bytes(dtype), dst)) return FVQA_EALIGN;
   const size_t n4 = (size_t)n_rows * dim / 4;
   DISPATCH_T(dtype, hipLaunchKernelGGL(cast_rows_k<T>, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, src,
                                        (T*)dst, n4));
