@@ -1,0 +1,99 @@
+"""Ask a trained model one question about one clip and print its answer (the generation API: fvqa.generate.prompt_batch ->
+Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling, ended by EOS).
+
+    python answer.py --model 7B --llama_model_path ... --resume ckpt.pth --features clip.pth|.npy [--audio_features ...] \
+        --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0]
+
+The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
+without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
+printed as token ids (a synthetic tokenizer has no vocabulary to decode with).
+"""
+import argparse
+import copy
+import re
+import zlib
+
+import numpy as np
+import torch
+
+import train
+import util.misc as misc
+from fvqa import generate
+from llama_vqa import LLaMA_VQA
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser("Flipped-VQA: answer one question (MI355X)", parents=[train.get_args_parser()])
+    p.add_argument("--question", type=str, required=True)
+    p.add_argument("--options", type=str, nargs="*", default=None, help="answer options of a multiple-choice question")
+    p.add_argument("--features", type=str, default=None, help="frame features of the clip, (n, 768): .pth or .npy")
+    p.add_argument("--audio_features", type=str, default=None, help="audio features of the clip, (n, 1024): .pth or .npy")
+    p.add_argument("--max_new_tokens", type=int, default=generate.N_NEW)
+    p.add_argument("--temperature", type=float, default=0.0)
+    p.add_argument("--top_p", type=float, default=1.0)
+    p.set_defaults(max_seq_len=128, seed=None)
+    return p
+
+
+class WordHashVocabulary:
+    """The stand-in `sp_model` of a synthetic run: words and punctuation marks hashed into the vocabulary, the prompt markers the
+    layouts look for ("Video", "Question", "Answer", newline) at LLaMA's ids."""
+    FIXED = {"Video": 15167, "Question": 16492, "Answer": 22550, "\n": 13}
+
+    def __init__(self, n_words: int):
+        self.n_words = n_words
+
+    def encode(self, s: str):
+        out = []
+        for w in re.findall(r"\w+|[^\w\s]|\n", s):
+            t = self.FIXED.get(w)
+            if t is None or t >= self.n_words:
+                t = 3 + zlib.crc32(w.encode()) % (self.n_words - 3)
+                while t in self.FIXED.values():
+                    t = 3 + (t - 2) % (self.n_words - 3)
+            out.append(t)
+        return out
+
+
+def load_features(path, dim: int):
+    """(n, dim) fp32 from a .npy array or a torch file holding a tensor."""
+    if path is None:
+        return None
+    feats = torch.from_numpy(np.load(path)) if str(path).endswith(".npy") else torch.load(path, map_location="cpu")
+    feats = torch.as_tensor(feats).float()
+    if feats.dim() != 2 or feats.shape[1] != dim:
+        raise ValueError(f"{path}: expected (n, {dim}) features, got {tuple(feats.shape)}")
+    return feats
+
+
+def main(args):
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    model = LLaMA_VQA(args).to(dev).eval()
+    args.eval = True
+    misc.load_model(args=args, model_without_ddp=model, optimizer=None, loss_scaler=None)
+    tok = model.tokenizer
+    if tok.sp_model is None:                      # synthetic: no vocabulary — a stand-in makes the prompt, ids are printed
+        tok = copy.copy(tok)
+        tok.sp_model = WordHashVocabulary(tok.n_words)
+    video = load_features(args.features, 768)
+    audio = load_features(args.audio_features, 1024)
+    if args.audio and audio is None:
+        raise SystemExit("--audio needs --audio_features")
+    batch = generate.prompt_batch(tok, [args.question], video=None if video is None else [video],
+                                  audio=None if audio is None else [audio], options=[args.options] if args.options else None,
+                                  max_seq_len=args.max_seq_len, max_feats=args.max_feats)
+    if args.audio_only:
+        batch.pop("video", None)
+    answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
+                            seed=args.seed)[0]
+    g = model.last_generation
+    print(f"[{int(g['n_generated'][0])} tokens, {g['steps']} steps]")
+    print(answer if isinstance(answer, str) else " ".join(str(t) for t in answer))
+    return answer
+
+
+if __name__ == "__main__":
+    a = get_args_parser().parse_args()
+    train.validate_args(a)
+    main(a)

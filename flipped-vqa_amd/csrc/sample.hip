@@ -1,0 +1,280 @@
+// The token step of the generation API (fvqa/generate.py: generate): everything between the LM head and the next token's first
+// RMSNorm in ONE launch, one 256-thread workgroup per sequence — pick the token (greedy, or temperature + nucleus sampling with
+// the reference's rule, llama/generation.py:17-68), write it into the id matrix, advance the position, raise the row's `done`
+// flag (EOS, or the end of the sequence), gather the next input embedding, count the rows still running.
+//
+// Picking with temperature > 0, per row (fp32 throughout, no sort):
+//   pass 1   m = max logit
+//   pass 2   e_i = __expf((l_i - m) / T), kept in LDS in place of the logits when 4*V bytes fit (else recomputed from the
+//            logits, which sit in L2, by every later pass); Z = sum e_i
+//   cut      the reference keeps a token iff the mass IN FRONT of it, in the order (p descending, index ascending), is
+//            <= top_p. G(t) = sum of the e_i whose bit pattern is > t is a non-increasing step function of the integer t (the
+//            bits of a non-negative float order as the float does), so the value of the last kept token is the smallest t
+//            with G(t) <= top_p * Z: a bisection over [0, bits(1.0f)], 30 masked sums of the row. Every token above t is
+//            kept; of the tokens EQUAL to t (a tie group, ordered by index) the j-th has G(t) + j*t in front of it.
+//   walk     in INDEX order (the reference draws with torch.multinomial from the re-normalised kept set; the order of the
+//            walk is free): each thread owns a contiguous index range, the kept mass and the tie count of the ranges are
+//            scanned across the workgroup, M = the scan's total, and the first kept token whose running kept mass exceeds
+//            u * M is the block-wide minimum of the threads' candidates (none exceeds it — u * M rounded up to M —: the last
+//            kept token).
+// Every sum runs in a fixed order (a thread's strided or contiguous elements, then shuffles, then the four waves in order);
+// there are no atomics on floats: two launches on the same inputs give the same bits.
+//
+// n_active needs a count across workgroups: each adds (1 arrival | its row still running << 16) to one device-resident ticket
+// word with an INTEGER atomic; the workgroup that arrives last writes the count and puts the ticket back to zero. The ticket is
+// a module global: launches of this entry on one device must be ordered (one stream, or events), as the decode loop's are.
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr size_t ROW_LDS_MAX = 144 * 1024;       // beside ~100 bytes of reduction scratch, under the CU's 160 KiB
+
+__device__ unsigned g_ticket = 0;
+
+__device__ __forceinline__ int block_sum_int(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ int block_min_int(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  return min(min(red[0], red[1]), min(red[2], red[3]));
+}
+__device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
+
+// exclusive prefix of v over the 256 threads in thread order (fixed tree); *total = the sum over all of them
+__device__ __forceinline__ float block_scan_f(float v, float* wtot, float* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  __syncthreads();
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  float base = 0.f;
+  for (int k = 0; k < w; ++k) base += wtot[k];
+  *total = ((wtot[0] + wtot[1]) + wtot[2]) + wtot[3];
+  return base + (x - v);
+}
+__device__ __forceinline__ int block_scan_i(int v, int* wtot) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  __syncthreads();
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < w; ++k) base += wtot[k];
+  return base + x - v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
+                                                    const T* __restrict__ emb, float temperature, float top_p, int eos_id,
+                                                    int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
+                                                    int32_t* __restrict__ done, T* __restrict__ x_next,
+                                                    int32_t* __restrict__ token_out, int32_t* __restrict__ n_kept_out,
+                                                    int32_t* __restrict__ n_active, int64_t* __restrict__ pos64, int B, int V,
+                                                    int D, int S, int row_in_lds, int vec16) {
+  extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds)
+  __shared__ float redf[4], wtotf[4];
+  __shared__ int redi[4], wtoti[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* lg = logits + (size_t)b * V;
+  int p = pos[b];
+  // a finished row, and one with no room for another token (the reference would index past the end), pick nothing
+  const bool live = done[b] == 0 && p >= -1 && p + 1 < S;
+  int tok = -1, kept = 0;
+
+  if (live && temperature == 0.f) {
+    // ---- greedy: the largest logit, the lowest index on exact ties
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < V; i += NT) {
+      const float v = lg[i];
+      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    }
+    const float m = block_max_256(bv, redf);
+    tok = block_min_int(bv == m ? bi : 0x7fffffff, redi);
+    if (tok >= V) tok = 0;                                         // (a row of NaNs)
+    kept = 1;
+  } else if (live) {
+    // ---- pass 1, 2: max, e_i, Z
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += NT) mx = fmaxf(mx, lg[i]);
+    const float m = block_max_256(mx, redf);
+    float z = 0.f;
+    for (int i = tid; i < V; i += NT) {
+      const float e = __expf((lg[i] - m) / temperature);
+      if (row_in_lds) erow[i] = e;
+      z += e;
+    }
+    const float Z = block_sum_256(z, redf);                        // (its barriers also publish erow)
+    auto pe = [&](int i) -> float { return row_in_lds ? erow[i] : __expf((lg[i] - m) / temperature); };
+    // ---- the cut: the smallest t with G(t) <= top_p * Z
+    const float X = top_p * Z;
+    unsigned lo = 0u, hi = 0x3f800000u;                            // G(bits(1.0f)) = 0: no e_i exceeds exp(0)
+    while (lo < hi) {
+      const unsigned mid = lo + ((hi - lo) >> 1);
+      float g = 0.f;
+      for (int i = tid; i < V; i += NT) {
+        const float e = pe(i);
+        g += __float_as_uint(e) > mid ? e : 0.f;
+      }
+      g = block_sum_256(g, redf);
+      if (g <= X) hi = mid; else lo = mid + 1u;
+    }
+    const unsigned tb = lo;
+    const float tf = __uint_as_float(tb);
+    float g = 0.f;
+    int n_gt = 0, n_eq = 0;
+    for (int i = tid; i < V; i += NT) {
+      const float e = pe(i);
+      const unsigned eb = __float_as_uint(e);
+      g += eb > tb ? e : 0.f;
+      n_gt += eb > tb ? 1 : 0;
+      n_eq += eb == tb ? 1 : 0;
+    }
+    g = block_sum_256(g, redf);
+    n_gt = block_sum_int(n_gt, redi);
+    n_eq = block_sum_int(n_eq, redi);
+    int n_tie = n_eq;                                              // of the tie group, the j-th has g + j * t in front
+    if (tf > 0.f) {
+      const float q = (X - g) / tf;
+      if (q < (float)n_eq) n_tie = (int)q + 1;
+    }
+    kept = n_gt + n_tie;
+    // ---- the walk, in index order over contiguous ranges
+    const int chunk = (V + NT - 1) / NT;
+    const int i0 = min(V, tid * chunk), i1 = min(V, i0 + chunk);
+    int c_eq = 0;
+    for (int i = i0; i < i1; ++i) c_eq += __float_as_uint(pe(i)) == tb ? 1 : 0;
+    const int rank0 = block_scan_i(c_eq, wtoti);
+    float mass = 0.f;
+    int rank = rank0, last = -1;
+    for (int i = i0; i < i1; ++i) {
+      const float e = pe(i);
+      const unsigned eb = __float_as_uint(e);
+      const bool k = eb > tb || (eb == tb && rank++ < n_tie);
+      if (k) { mass += e; last = i; }
+    }
+    float M;
+    const float before = block_scan_f(mass, wtotf, &M);
+    const float target = u_p[b] * M;
+    float run = before;
+    int cand = 0x7fffffff;
+    rank = rank0;
+    for (int i = i0; i < i1; ++i) {
+      const float e = pe(i);
+      const unsigned eb = __float_as_uint(e);
+      const bool k = eb > tb || (eb == tb && rank++ < n_tie);
+      if (k) {
+        run += e;
+        if (run > target && cand == 0x7fffffff) cand = i;
+      }
+    }
+    cand = block_min_int(cand, redi);
+    last = block_max_int(last, redi);
+    tok = cand < V ? cand : (last >= 0 ? last : 0);
+  }
+
+  // ---- step the row
+  int now_done = done[b] != 0 ? 1 : 0;
+  int64_t* row_ids = ids + (size_t)b * S;
+  int src;
+  if (live) {
+    p += 1;
+    src = tok;
+    if (stop_at_eos && tok == eos_id) now_done = 1;
+  } else {
+    now_done = 1;
+    const int at = p < 0 ? 0 : (p >= S ? S - 1 : p);
+    const int64_t t = row_ids[at];
+    src = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);                   // any valid embedding row: the batch stays rectangular
+  }
+  __syncthreads();                                                 // (every read of done / pos / ids above is over)
+  if (tid == 0) {
+    if (live) {
+      row_ids[p] = tok;
+      pos[b] = p;
+    }
+    done[b] = now_done;
+    if (pos64) pos64[b] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
+    token_out[b] = tok;
+    n_kept_out[b] = kept;
+    const unsigned old = atomicAdd(&g_ticket, 1u + (now_done ? 0u : 0x10000u));
+    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
+      *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
+      atomicExch(&g_ticket, 0u);
+    }
+  }
+  // ---- the next input row
+  const T* erow_src = emb + (size_t)src * D;
+  T* dst = x_next + (size_t)b * D;
+  if (vec16) {
+    const int n16 = (int)((size_t)D * sizeof(T) / 16);
+    const uint4* s4 = reinterpret_cast<const uint4*>(erow_src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    for (int i = tid; i < n16; i += NT) d4[i] = s4[i];
+  } else {
+    for (int i = tid; i < D; i += NT) dst[i] = erow_src[i];
+  }
+}
+
+template <typename T>
+int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
+           int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
+           int64_t* pos64, int B, int V, int D, int S, hipStream_t st) {
+  const size_t row_bytes = (size_t)V * sizeof(float);
+  const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
+  const size_t lds = in_lds ? row_bytes : 0;
+  static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
+  if (fvqa_attr_needed(attr_done))
+    (void)hipFuncSetAttribute((const void*)decode_next_k<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROW_LDS_MAX);
+  const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
+  hipLaunchKernelGGL(decode_next_k<T>, dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p, eos_id,
+                     stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+}  // namespace
+
+extern "C" int fvqa_decode_next(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next,
+                                int32_t* token, int32_t* n_kept, int32_t* n_active, int64_t* pos64, int n_seq, int vocab,
+                                int dim, int seq_len, int dtype, void* stream) {
+  if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
+  if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
+  if (temperature > 0.f && !u) return FVQA_EINVAL;
+  if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
+  if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
+  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
+      !fvqa_aligned(8, ids, pos64))
+    return FVQA_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FVQA_H16)
+    return launch<bf16_t>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                          n_active, pos64, n_seq, vocab, dim, seq_len, st);
+  return launch<float>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                       n_active, pos64, n_seq, vocab, dim, seq_len, st);
+}

@@ -33,7 +33,10 @@ def load_data(args, tokenizer, split="train"):
     dataset = dataset_mapping[args.dataset](args=args, tokenizer=tokenizer, split=split)
     sampler = torch.utils.data.DistributedSampler(dataset, num_replicas=misc.get_world_size(),
                                                   rank=misc.get_rank(), shuffle=split == "train")
-    return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.batch_size,
+    batch_size = args.batch_size
+    if split != "train" and getattr(args, "val_batch_size", None):     # --val_batch_size: the decode's rows per token step
+        batch_size = args.val_batch_size
+    return torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=batch_size,
                                        num_workers=args.num_workers, collate_fn=batch_collate,
                                        pin_memory=args.pin_mem, drop_last=False,
                                        worker_init_fn=_worker_init if args.num_workers > 0 else None,

@@ -131,3 +131,160 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
     c = torch.nn.functional.normalize(torch.stack(choice_vec), p=2, dim=2)
     sims = torch.bmm(c, o.unsqueeze(-1)).squeeze(-1)
     return sims.argmax(1), sims, extracted
+
+
+# ---------------------------------------------------------------------------------------------- the generation API
+@torch.no_grad()
+def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
+             stop_at_eos: bool = True, seed=None) -> dict:
+    """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
+    (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
+    and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
+    the next embedding, count the running rows — is ONE launch (ops.decode_next, csrc/sample.hip).
+    -> {"ids" (B, S) int64, "n_generated" (B,) int64, "steps": token steps launched, "tokens" (B, steps) int32 (-1: no token)}.
+    Sampling draws its uniforms from one device generator seeded with `seed` once per call (None: the default generator).
+    The stop lags by one step so that the device never idles: after token step t the count of running rows goes to pinned host
+    memory behind an event, and token step t + 1 is only launched once the count of step t - 1 has arrived and is not zero —
+    the host never waits for the step it has just queued, and at most one superfluous step is computed."""
+    m, pk = eng.model, eng.pack
+    dev = eng.device
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+    if max_new_tokens < 1 or not temperature >= 0 or not 0 < top_p <= 1:
+        raise ValueError("generate: max_new_tokens >= 1, temperature >= 0, 0 < top_p <= 1")
+    ids_all = data["text_id"]["vqa"]
+    B, _, S = ids_all.shape
+    sub = {k: data[k] for k in ("video", "audio") if k in data}
+    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    with vqa_stream_only(eng, "_gen_arena", "all"):
+        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
+        ar = eng.arena(B, S)
+        vstart = eng.saved["vstart"]
+        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
+        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
+        ids = ids_all[:, 0].to(dev).clone()
+        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
+        start = prefix - 1                                  # the position the first token is predicted at
+        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+        xin, xn, hn, h, xb, o_row = e(B, D), e(B, D), e(B, D), e(B, D), e(B, D), e(B, D)
+        qkv_row, ab, z = e(B, 3 * D), e(B, 2 * Hf), e(B, Hf)
+        lg = e(B, V, dtype=torch.float32)
+        lg.copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
+        pos = start.to(torch.int32)
+        pos64 = start.clone()
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        tokens = torch.full((max_new_tokens, B), -1, dtype=torch.int32, device=dev)
+        n_kept = torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev)
+        n_active = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev)
+        u = None
+        if temperature > 0:
+            gen = None
+            if seed is not None:
+                gen = torch.Generator(device=dev)
+                gen.manual_seed(int(seed))
+            u = torch.rand(max_new_tokens, B, dtype=torch.float32, device=dev, generator=gen)
+        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
+        arrived = []
+        steps = 0
+        for t in range(max_new_tokens):
+            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
+                arrived[t - 2].synchronize()
+                if int(running[t - 2]) == 0:
+                    break
+            ops.decode_next(lg, pk.emb, ids, pos, done, xin, tokens[t], n_kept[t], n_active[t:t + 1],
+                            u=None if u is None else u[t], pos64=pos64, temperature=temperature,
+                            top_p=top_p, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos)
+            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            arrived.append(ev)
+            steps = t + 1
+            if steps == max_new_tokens:
+                break                                       # (the logits after the last token pick nothing)
+            # a finished row stays in the batch (it is rectangular): it goes through every layer on the embedding of its last
+            # token and attn_decode rewrites its K/V at its frozen position — the same values each time, read by nobody
+            x, x2 = xin, xb
+            for i in range(L):                              # the per-kernel sequence of a layer, as greedy_decode runs it
+                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=B)
+                ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
+                g1, g2 = m.gate_views(i)
+                ops.attn_decode(qkv_row, ar.qkv[i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), B, S, H, Dh, A, F,
+                                cache_rotated=not fused)
+                ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
+                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=B)
+                ops.gemm_nt(hn, pk.w13[i], ab)
+                ops.swiglu_fwd(ab, z, B, Hf)
+                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
+                x, x2 = x2, x
+            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=B)
+            ops.gemm_nt(xn, pk.wout, lg)
+        return {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
+                "tokens": tokens[:steps].t().contiguous()}
+
+
+_CHOICE = ("(A)", "(B)", "(C)", "(D)", "(E)")
+_PLACEHOLDER = "x"          # the answer the prompt is cut in front of
+
+
+def question_text(question: str, options=None) -> dict:
+    """The prompt text of one question as dataloader/nextqa.py writes it (q_text, and o_text when the task is not a generation
+    task): the question capitalised, stripped and closed by "?", the options lettered one per line under "Choices:"."""
+    q = str(question).capitalize().strip()
+    if not q.endswith("?"):
+        q += "?"
+    o = ""
+    if options:
+        if len(options) > len(_CHOICE):
+            raise ValueError(f"at most {len(_CHOICE)} options")
+        o = "Choices: \n" + "".join(f"{_CHOICE[i]} {opt}\n" for i, opt in enumerate(options))
+    return {"q_text": f"Question: {q}\n", "o_text": o, "a_text": "Answer: The answer is "}
+
+
+def _features(feats, B: int, max_feats: int, dim: int) -> torch.Tensor:
+    """None | (B, n, dim) | a list of B (n_b, dim) -> (B, max_feats, dim) fp32, sub-sampled / zero-padded as the readers do."""
+    from dataloader.nextqa import sample_frames
+    if feats is None:
+        return torch.zeros(B, max_feats, dim)
+    rows = [torch.as_tensor(f).float() for f in feats]
+    if len(rows) != B or any(r.dim() != 2 or r.shape[1] != dim for r in rows):
+        raise ValueError(f"features: one (n, {dim}) array per question")
+    return torch.stack([sample_frames(r, max_feats)[0] for r in rows])
+
+
+def prompt_batch(tokenizer, questions, video=None, audio=None, options=None, *, max_seq_len: int, max_feats: int) -> dict:
+    """questions (a list of strings) -> a batch dict `generate` accepts, with no gold answer anywhere. Per question: the sequence
+    Tokenizer.encode_vqa emits in generation mode for a placeholder answer, cut at the prefix index it returns — text_id['vqa']
+    (B, 1, max_seq_len) holds the prompt and 0 from prefix_index on; video_start / prefix_index are what the reader would give;
+    label['vqa'] marks the one position after the prompt (the prefill needs a scored row; its loss is not used).
+    video / audio: None (zero features), a (B, n, 768 / 1024) array or a list of per-question arrays; `options`: one list of
+    answer options per question (or one list for all), written into the question text as the multiple-choice reader does.
+    A prompt that does not leave room for one token inside max_seq_len is a ValueError."""
+    questions = list(questions)
+    B = len(questions)
+    if B == 0:
+        raise ValueError("prompt_batch: no question")
+    if options is not None and (len(options) == 0 or isinstance(options[0], str)):
+        options = [list(options)] * B
+    ids = torch.zeros(B, 1, max_seq_len, dtype=torch.int64)
+    label = torch.zeros(B, 1, max_seq_len, dtype=torch.int64)
+    vstart, prefix = [], []
+    for b, q in enumerate(questions):
+        t = question_text(q, None if options is None else options[b])
+        text = {"q_text": t["q_text"] + t["o_text"], "o_text": "", "a_text": t["a_text"]}
+        seqs, p, vs = tokenizer.encode_vqa(text=text, max_feats=max_feats, split="val", answer_mapping={0: _PLACEHOLDER},
+                                           answer=0, options=[_PLACEHOLDER])
+        if p > max_seq_len - 1:
+            raise ValueError(f"question {b}: the prompt takes {p} tokens, max_seq_len - 1 = {max_seq_len - 1} are available")
+        ids[b, 0, :p] = torch.tensor(seqs[0][:p], dtype=torch.int64).clamp_min(0)      # (frame placeholders -2 -> 0)
+        label[b, 0, p] = 1
+        vstart.append(vs)
+        prefix.append(p)
+    out = {"text_id": {"vqa": ids}, "label": {"vqa": label}, "video_start": {"vqa": vstart}, "prefix_index": {"vqa": prefix},
+           "text": questions, "vid": [None] * B}
+    if video is not None or audio is None:
+        out["video"] = _features(video, B, max_feats, 768)
+    if audio is not None:
+        out["audio"] = _features(audio, B, max_feats, 1024)
+    return out

@@ -603,6 +603,32 @@ def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: in
     return il, s, cnt, mean, pred
 
 
+def decode_next(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, *, u=None, pos64=None, temperature: float = 0.0,
+                top_p: float = 1.0, eos_id: int = 2, stop_at_eos: bool = True):
+    """The token step of the generation API (include/fvqa.h fvqa_decode_next): logits (B, V) fp32 -> the picked token written
+    into ids (B, S) int64 at pos + 1, pos (B,) int32 advanced, done (B,) int32 raised on EOS / at the end of the sequence,
+    x_next (B, D) = emb[token], token / n_kept (B,) int32, n_active (1,) int32 = rows still running, pos64 (B,) int64 = pos
+    after the step (what attn_decode reads). u (B,) fp32 in [0, 1) is needed when temperature > 0."""
+    _dev(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, u, pos64)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next: logits (B, V) fp32")
+    B, V = logits.shape
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B, D), "decode_next: x_next (B, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next: ids (B, S) int64")
+    for t, n in ((pos, B), (done, B), (token, B), (n_kept, B), (n_active, 1)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next: pos / done / token / n_kept (B,), n_active (1,) int32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next: pos64 (B,) int64")
+    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
+          "decode_next: sampling needs u (B,) fp32")
+    rc = _lib.load(emb.dtype).fvqa_decode_next(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(eos_id),
+                                               1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(x_next),
+                                               _ptr(token), _ptr(n_kept), _ptr(n_active), _ptr(pos64), B, V, D, ids.shape[1],
+                                               dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_decode_next")
+    return token
+
+
 def attn_bwd_workspace(n_seq, S, H, Dh, A) -> int:
     return int(_lib.load().fvqa_attn_bwd_workspace(n_seq, S, H, Dh, A))
 

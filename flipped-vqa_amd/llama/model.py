@@ -232,10 +232,32 @@ class Transformer(nn.Module):
         -> (most_similar_indices (B,), extracted_answers list of dicts). KV-cached, batched: fvqa/generate.py."""
         from fvqa import generate
         eng = self.ensure_engine()
-        ids = generate.greedy_decode(eng, data)
+        if getattr(self.args, "gen_stop_eos", False):       # --gen_stop_eos: the same tokens up to each row's EOS, which is
+            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True)
+            ids = out["ids"]                                # where both readers of the ids cut them (match_answers, engine)
+        else:
+            ids = generate.greedy_decode(eng, data)
         best, sims, extracted = generate.match_answers(self, data, ids)
         self.last_generation = {"ids": ids, "similarities": sims}
         return best, extracted
+
+    @torch.no_grad()
+    def generate(self, data, **kw):
+        """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
+        keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed) -> one answer per row, the generated tokens up to (not
+        including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
+        per-row counts and the number of token steps launched are left in `last_generation`."""
+        from fvqa import generate
+        out = generate.generate(self.ensure_engine(), data, **kw)
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps")}
+        ids, n = out["ids"].cpu(), out["n_generated"].cpu()
+        answers = []
+        for b, p in enumerate(data["prefix_index"]["vqa"]):
+            row = ids[b, int(p): int(p) + int(n[b])].tolist()
+            if self.tokenizer.eos_id in row:
+                row = row[: row.index(self.tokenizer.eos_id)]
+            answers.append(self.tokenizer.decode(row) if self.tokenizer.sp_model is not None else row)
+        return answers
 
     @torch.no_grad()
     def score_options(self, data):

@@ -67,6 +67,9 @@ _FLAGS = [
     # MI355X build additions
     ("--train_audio", dict(action="store_true", help="train (and checkpoint) audio_proj and the audio-video cross-attention, "
                                                      "which the reference's freeze filter leaves at their random initialisation")),
+    ("--gen_stop_eos", dict(action="store_true", help="generation-task validation decodes through fvqa.generate.generate: each "
+                                                      "sample stops at its EOS and the batch stops when every sample has")),
+    ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
     ("--synthetic", dict(action="store_true", help="synthetic tokenizer constants + synthetic batches")),

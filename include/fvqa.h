@@ -258,6 +258,32 @@ int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, co
 int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,
                      float* option_sum, int64_t* option_count, float* option_mean, int64_t* prediction, int n_seq,
                      int n_options, int seq_len, void* stream);
+/* The token step of the generation API (csrc/sample.hip; reference llama/generation.py:17-68 and llama/model.py:438-470): one
+ * launch per generated token, one workgroup per sequence, between the LM head and the next token's first RMSNorm.
+ * In: logits (n_seq, vocab) fp32, finite; u (n_seq) fp32 in [0, 1) (may be NULL when temperature == 0); emb (vocab, dim) in the
+ * storage type. In/out: ids (n_seq, seq_len) int64, pos (n_seq) int32 (the position the logits were computed at, >= -1),
+ * done (n_seq) int32. Out: x_next (n_seq, dim) storage type, token (n_seq) int32 (-1 where none was picked), n_kept (n_seq)
+ * int32, n_active (ONE int32: rows with done == 0 after this step), pos64 (n_seq) int64 or NULL: each row's position after the
+ * step, the form fvqa_attn_decode reads. Per row:
+ *   - done != 0, or pos + 1 >= seq_len (no room: the row becomes done): ids and pos are not written, n_kept = 0, token = -1,
+ *     x_next = the embedding of the row's current token (a valid row: the batch stays rectangular through the layers);
+ *   - temperature == 0: token = the index of the largest logit, the lowest index on exact ties; n_kept = 1;
+ *   - temperature > 0: p = softmax(logits / temperature) (maximum subtracted, fp32); order by p descending, ties by index
+ *     ascending; a token is kept iff the total p in front of it is <= top_p (n_kept of them, kept mass M); token = the first
+ *     kept token IN INDEX ORDER whose running kept mass exceeds u * M — the reference's distribution (it draws with
+ *     torch.multinomial from the re-normalised kept set);
+ *   - then ids[pos + 1] = token, pos += 1, x_next = emb[token]; done = 1 if stop_at_eos and token == eos_id (the EOS is written).
+ * Fixed summation orders, no float atomics: bitwise repeatable. n_active is counted through one device-resident ticket word of
+ * the library: calls on one device must be ordered against each other (one stream, or events) — nothing enforces it, and two
+ * unordered calls corrupt each other's count. Only the last workgroup of a call puts the ticket back to zero: a launch that
+ * does not complete (a fault, a reset queue) leaves it non-zero, and every later n_active of that process is wrong until the
+ * library is loaded afresh. n_seq <= 65535.
+ * FVQA_EINVAL: a null pointer (u only when temperature > 0), temperature < 0 or NaN, top_p outside (0, 1], a bad dtype code;
+ * FVQA_ESHAPE: a dimension <= 0. */
+int fvqa_decode_next(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
+                     int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token,
+                     int32_t* n_kept, int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
+                     int dtype, void* stream);
 /* workspace bytes fvqa_attn_bwd needs (fp32 partials for the batch-summed adapter k/v
  * gradients and the per-head gate sums). Its FIRST 1024 BYTES are integer arrival counters of the
  * fused bf16 backward: the caller zeroes them once after allocating the workspace; every call

@@ -2,7 +2,13 @@
 """Generation/eval path measurement on the MI355X box: greedy decode of 31 answer tokens for
 a batch of B samples with the KV-cached row-wise decode, against the same decode done the reference's way on
 the same kernels (one full forward of the batch per generated token; the reference additionally runs its
-forwards one sample at a time)."""
+forwards one sample at a time).
+
+The generation API (fvqa.generate.generate) is measured with --generate (full length, stop_at_eos=False) or --stop_eos
+(each row stops at its EOS, the batch when every row has); --val_batch_size N decodes N rows per token step; --eos_at K
+puts the first EOS of every row at generated token K: the weights are the `peakedperm` closed form (token t is followed
+by pi(t), fvqa.synth.vocab_permutation) and the prompt's last token is pi^{-K}(EOS) — the trajectory of
+tests/test_generate_gpu.py. The rows' generated counts and the token steps launched are printed with the timing."""
 import argparse
 import os
 import sys
@@ -22,7 +28,17 @@ def main():
     ap.add_argument("--model", default="7B")
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--n_layers", type=int, default=0)
+    ap.add_argument("--generate", action="store_true", help="decode through generate(stop_at_eos=False)")
+    ap.add_argument("--stop_eos", action="store_true", help="decode through generate(stop_at_eos=True)")
+    ap.add_argument("--val_batch_size", type=int, default=0, help="rows per token step (default: --batch_size)")
+    ap.add_argument("--eos_at", type=int, nargs="*", default=[],
+                    help="first EOS of every row at generated token K (peakedperm weights); several K: one line each, then the "
+                         "full-length decode of the same model")
+    ap.add_argument("--pairs", type=int, default=0, help="N interleaved pairs greedy_decode / generate(stop_at_eos=False)")
+    ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
+    if a.val_batch_size:
+        a.batch_size = a.val_batch_size
     dev = torch.device("cuda", 0)
     margs = types.SimpleNamespace(
         llama_model_path="/nonexistent/", model=a.model, max_seq_len=128, adapter_len=10, adapter_layer=32,
@@ -38,17 +54,63 @@ def main():
                             max_seq_len=128, batch_size=a.batch_size, vaq=False, qav=False)
     b = synth.make_batch(cfg, seed=5)
     B = a.batch_size
-    b["prefix_index"] = {"vqa": [60 + i for i in range(B)]}
+    b["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B)]}
+    if a.eos_at:
+        import dataclasses
+        from llama_vqa import fill_closed_form
+        fill_closed_form(model, dataclasses.replace(cfg, max_feats=margs.max_feats, bias=margs.bias, tau=margs.tau,
+                                                    adapter_len=p.adapter_len, adapter_layer=p.adapter_layer,
+                                                    multiple_of=p.multiple_of, norm_eps=p.norm_eps, peaked_perm=True))
     eng = model.ensure_engine()
-    for _ in range(2):
+    last = {}
+
+    def timed(decode, reps=a.reps, warm=2):
+        for _ in range(warm):
+            decode()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            decode()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+
+    def greedy():
         generate.greedy_decode(eng, b)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    n = 3
-    for _ in range(n):
-        generate.greedy_decode(eng, b)
-    torch.cuda.synchronize()
-    t_kv = (time.perf_counter() - t0) / n
+
+    def gen(stop):
+        return lambda: last.update(generate.generate(eng, b, stop_at_eos=stop))
+
+    def line(what, t):
+        ng = last["n_generated"].tolist() if last else None
+        print(f"{a.model} L={p.n_layers} B={B} S=128 {what}: {t * 1e3:7.1f} ms/batch ({B / t:6.1f} samples/s)"
+              + (f"; steps {last['steps']}, generated per row min {min(ng)} max {max(ng)}" if last else ""), flush=True)
+        last.clear()
+
+    if a.pairs:
+        timed(greedy, reps=1)
+        timed(gen(False), reps=1)
+        for k in range(a.pairs):
+            line(f"pair {k} greedy_decode", timed(greedy, warm=0))
+            line(f"pair {k} generate(stop_at_eos=False)", timed(gen(False), warm=0))
+        return
+    if a.eos_at:
+        V = model.vocab_size
+        pi = synth.vocab_permutation(V)
+        mul, add = int((pi[1] - pi[0]) % V), int(pi[0])
+        for K in a.eos_at:
+            t = model.tokenizer.eos_id
+            for _ in range(K):
+                t = ((t - add) * pow(mul, -1, V)) % V
+            for i, pre in enumerate(b["prefix_index"]["vqa"]):
+                b["text_id"]["vqa"][i, :, pre - 1] = t
+            line(f"eos_at {K} generate(stop_at_eos=True)", timed(gen(True)))
+        line("same model, generate(stop_at_eos=False)", timed(gen(False)))
+        line("same model, greedy_decode", timed(greedy))
+        return
+    if a.generate or a.stop_eos:
+        line(f"generate(stop_at_eos={a.stop_eos})", timed(gen(a.stop_eos)))
+        return
+    t_kv = timed(greedy)
     eng.lm_head_rows = "all"        # the reference's re-forward evaluates the head at every position (llama/model.py:439-447)
     with torch.no_grad():
         for _ in range(2):
