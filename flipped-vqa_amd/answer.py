@@ -2,7 +2,8 @@
 Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling, ended by EOS).
 
     python answer.py --model 7B --llama_model_path ... --resume ckpt.pth --features clip.pth|.npy [--audio_features ...] \
-        --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0]
+        --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
+        [--num_beams N --length_penalty A]
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -31,6 +32,8 @@ def get_args_parser():
     p.add_argument("--max_new_tokens", type=int, default=generate.N_NEW)
     p.add_argument("--temperature", type=float, default=0.0)
     p.add_argument("--top_p", type=float, default=1.0)
+    p.add_argument("--length_penalty", type=float, default=0.0,
+                   help="with --num_beams > 1: the final hypotheses are ranked by score / n_generated ** A (0: by score)")
     p.set_defaults(max_seq_len=128, seed=None)
     return p
 
@@ -86,9 +89,10 @@ def main(args):
     if args.audio_only:
         batch.pop("video", None)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
-                            seed=args.seed)[0]
+                            seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty)[0]
     g = model.last_generation
-    print(f"[{int(g['n_generated'][0])} tokens, {g['steps']} steps]")
+    print(f"[{int(g['n_generated'][0])} tokens, {g['steps']} steps" +
+          (f", log-probability {float(g['score'][0]):.4f}]" if "score" in g else "]"))
     print(answer if isinstance(answer, str) else " ".join(str(t) for t in answer))
     return answer
 

@@ -136,7 +136,7 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
 # ---------------------------------------------------------------------------------------------- the generation API
 @torch.no_grad()
 def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
-             stop_at_eos: bool = True, seed=None) -> dict:
+             stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -145,7 +145,16 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     Sampling draws its uniforms from one device generator seeded with `seed` once per call (None: the default generator).
     The stop lags by one step so that the device never idles: after token step t the count of running rows goes to pinned host
     memory behind an event, and token step t + 1 is only launched once the count of step t - 1 has arrived and is not zero —
-    the host never waits for the step it has just queued, and at most one superfluous step is computed."""
+    the host never waits for the step it has just queued, and at most one superfluous step is computed.
+    num_beams > 1 (with temperature == 0): beam search, `beam_search` below — the keys above for the best hypothesis plus
+    "score" and "beams". num_beams == 1 is the code below, unchanged."""
+    if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
+        raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
+    if num_beams > 1 and temperature > 0:
+        raise ValueError("generate: num_beams > 1 searches, it does not sample: temperature must be 0")
+    if num_beams > 1 or _BEAM_PATH_AT_ONE:
+        return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
+                           length_penalty=float(length_penalty))
     m, pk = eng.model, eng.pack
     dev = eng.device
     if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
@@ -222,6 +231,138 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
             ops.gemm_nt(xn, pk.wout, lg)
         return {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
                 "tokens": tokens[:steps].t().contiguous()}
+
+
+_BEAM_PATH_AT_ONE = False   # (tests) send num_beams == 1 through beam_search too: K = 1 must reproduce the greedy ids
+
+
+@torch.no_grad()
+def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bool = True, num_beams: int,
+                length_penalty: float = 0.0, early_stop: bool = True) -> dict:
+    """The most likely answers under the model: K = num_beams slots per sample, every token step ranks the K * V continuations
+    of a sample and keeps the K best (include/fvqa.h fvqa_beam_step states the rule; a slot's score is the fp32 sum of the
+    log-probabilities of its generated tokens, the EOS included; finished slots are carried and compete with their score).
+    The prompt is prefilled ONCE per sample, at B rows, as `generate` does it; its cache rows [0, prefix) and the adapter rows
+    are fanned out into a cache of B * K sequences (ops.kv_beam_move) and the token loop runs `generate`'s per-layer kernel
+    sequence on B * K rows. Between the LM head and the next RMSNorm: the beam step (one launch) and the move of the generated
+    cache rows from parent to child slot (two launches through a scratch window, all layers at once) — no torch index kernels.
+    The stop lags by one step like `generate`'s: the count that leaves the device is the number of samples whose slot 0 is not
+    finished (length_penalty == 0: scores only fall and ties go to the lower slot, nothing can overtake a finished slot 0) or
+    that have any unfinished slot (length_penalty != 0). The penalty only ranks the final slots: score / n_generated ** penalty,
+    the lowest slot on ties; it never enters the search. early_stop=False runs all max_new_tokens steps.
+    -> generate's keys for the best hypothesis, "score" (B,) fp32, "beams": {"ids" (B, K, S), "score" (B, K), "n_generated"
+    (B, K), "done" (B, K)} in slot order, and per step "parents" / "step_tokens" (steps, B, K) int32 (token -1: carried)."""
+    m, pk = eng.model, eng.pack
+    dev = eng.device
+    K = int(num_beams)
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+    if max_new_tokens < 1 or not 1 <= K <= ops.BEAMS_MAX:
+        raise ValueError(f"beam_search: max_new_tokens >= 1, 1 <= num_beams <= {ops.BEAMS_MAX}")
+    ids_all = data["text_id"]["vqa"]
+    B, _, S = ids_all.shape
+    N = B * K
+    sub = {k: data[k] for k in ("video", "audio") if k in data}
+    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    with vqa_stream_only(eng, "_gen_arena", "all"):
+        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
+        ar = eng.arena(B, S)
+        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
+        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
+        i32 = dict(dtype=torch.int32, device=dev)
+        rep = lambda t: t.repeat_interleave(K).contiguous()  # noqa: E731  per sample -> per slot
+        vstart = rep(eng.saved["vstart"])
+        prefix64 = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
+        start = rep(prefix64 - 1)                           # the position the first token is predicted at
+        prefix = rep(prefix64).to(torch.int32)
+        W = min(int(max_new_tokens), S)                     # the generated rows a slot can have: the move's window
+        cache = _beam_cache(eng, N, S, W)
+        # fan-out: rows [0, prefix) of sample b and the adapter rows -> the K slots of b, every layer, one launch
+        ops.kv_beam_move(cache["qkv"], ar.qkv, rep(torch.arange(B, **i32)), torch.zeros(N, **i32), prefix, S=S, A=A)
+        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+        xin, xn, hn, h, xb, o_row = e(N, D), e(N, D), e(N, D), e(N, D), e(N, D), e(N, D)
+        qkv_row, ab, z = e(N, 3 * D), e(N, 2 * Hf), e(N, Hf)
+        lg = e(N, V, dtype=torch.float32)
+        rows = torch.arange(B, device=dev)
+        lg.view(B, K, V).copy_(ar.logits.view(B, S, V)[rows, (prefix64 - 1).clamp(0, S - 1)].unsqueeze(1).expand(B, K, V))
+        ids2 = [ids_all[:, 0].to(dev).repeat_interleave(K, 0).contiguous(), torch.empty(N, S, dtype=torch.int64, device=dev)]
+        pos = start.to(torch.int32)
+        pos64 = start.clone()
+        score = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
+        score[:, 0] = 0.0                                   # slot 0 is the prompt, the others are empty
+        done, n_gen = torch.zeros(N, **i32), torch.zeros(N, **i32)
+        parents, tokens = torch.zeros(max_new_tokens, N, **i32), torch.full((max_new_tokens, N), -1, **i32)
+        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
+        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
+        arrived = []
+        steps, cur = 0, 0
+        for t in range(max_new_tokens):
+            if t >= 2 and early_stop:                       # the count of step t - 2 left the device a whole step ago
+                arrived[t - 2].synchronize()
+                if int(running[t - 2]) == 0:
+                    break
+            ops.beam_step(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t], tokens[t],
+                          xin, n_active[t:t + 1], counter, num_beams=K, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos,
+                          count_any_live=length_penalty != 0)
+            cur = 1 - cur
+            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            arrived.append(ev)
+            steps = t + 1
+            if steps == max_new_tokens:
+                break                                       # (the logits after the last token pick nothing)
+            # the generated rows [prefix, pos) of every slot that changed its parent follow it, in all layers (a child writes
+            # its own row `pos` in the layer pass below; a carried slot's frozen row is rewritten there and read by nobody)
+            if K > 1:
+                ops.kv_beam_move(cache["qkv"], cache["qkv"], parents[t], prefix, pos, S=S, A=A, scratch=cache["scratch"],
+                                 window_rows=W, group=K)
+            x, x2 = xin, xb
+            for i in range(L):                              # the per-kernel sequence of a layer, as `generate` runs it
+                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=N)
+                ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
+                g1, g2 = m.gate_views(i)
+                ops.attn_decode(qkv_row, cache["qkv"][i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), N, S, H, Dh, A, F,
+                                cache_rotated=not fused)
+                ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
+                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=N)
+                ops.gemm_nt(hn, pk.w13[i], ab)
+                ops.swiglu_fwd(ab, z, N, Hf)
+                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
+                x, x2 = x2, x
+            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=N)
+            ops.gemm_nt(xn, pk.wout, lg)
+        ids = ids2[cur].view(B, K, S)
+        n_gen = n_gen.view(B, K).to(torch.int64)
+        if length_penalty == 0:
+            best = torch.zeros(B, dtype=torch.int64, device=dev)
+        else:                                               # (argmax returns the first of equal maxima: the lowest slot)
+            best = (score / n_gen.clamp(min=1).to(torch.float32) ** float(length_penalty)).argmax(1)
+        n_best = n_gen[rows, best]
+        col = torch.arange(steps, device=dev).unsqueeze(0)
+        tok_best = ids[rows, best].gather(1, (prefix64.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
+        tok_best = torch.where(col < n_best.unsqueeze(1), tok_best, torch.full_like(tok_best, -1))
+        return {"ids": ids[rows, best].contiguous(), "n_generated": n_best, "steps": steps, "tokens": tok_best,
+                "score": score[rows, best].clone(),
+                "beams": {"ids": ids.clone(), "score": score.clone(), "n_generated": n_gen, "done": done.view(B, K).clone()},
+                "parents": parents[:steps].view(steps, B, K).clone(), "step_tokens": tokens[:steps].view(steps, B, K).clone()}
+
+
+def _beam_cache(eng, N: int, S: int, W: int) -> dict:
+    """The KV cache of N = B * K sequences in fvqa_attn_decode's layout (L, N * S + A, 3 * D) and the scratch window of the
+    per-token move — kept on the engine for the next call of the same geometry. Not a second training arena: no activations."""
+    key = (N, S, W, eng.dtype)
+    c = getattr(eng, "_beam_kv", None)
+    if c is None or c["key"] != key:
+        eng._beam_kv = None                                 # (the old buffers go before the new ones come)
+        c = {"key": key,
+             "qkv": torch.zeros(eng.L, N * S + eng.A, 3 * eng.D, dtype=eng.dtype, device=eng.device),
+             "scratch": torch.empty(ops.kv_beam_move_scratch(N, W, eng.D, eng.L, eng.dtype), dtype=torch.uint8,
+                                    device=eng.device)}
+        eng._beam_kv = c
+    return c
 
 
 _CHOICE = ("(A)", "(B)", "(C)", "(D)", "(E)")

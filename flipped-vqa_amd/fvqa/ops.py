@@ -629,6 +629,71 @@ def decode_next(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, *,
     return token
 
 
+BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
+
+
+def beam_step(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter, *,
+              num_beams: int, eos_id: int = 2, stop_at_eos: bool = True, count_any_live: bool = False):
+    """One step of beam search (include/fvqa.h fvqa_beam_step): logits (B*K, V) fp32 -> the K best continuations of each sample
+    re-seated into its K slots: ids_out (B*K, S) int64 (ids_in is only read), pos / done / n_generated (B*K,) int32 and score
+    (B*K,) fp32 in place, pos64 (B*K,) int64, parent / token (B*K,) int32, x_next (B*K, D), n_active (1,) int32. counter: one
+    int32 word the caller zeroed once."""
+    _dev(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "beam_step: logits (B*K, V) fp32")
+    N, V = logits.shape
+    K = int(num_beams)
+    _need(1 <= K <= BEAMS_MAX and K <= V and N % K == 0, f"beam_step: 1 <= num_beams <= {BEAMS_MAX}, <= V, rows a multiple of it")
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "beam_step: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (N, D), "beam_step: x_next (B*K, D)")
+    _need(ids_in.dim() == 2 and ids_in.shape[0] == N and ids_in.dtype == torch.int64 and ids_out.dtype == torch.int64
+          and ids_out.shape == ids_in.shape and ids_in.data_ptr() != ids_out.data_ptr(),
+          "beam_step: ids_in, ids_out (B*K, S) int64, two buffers")
+    for t, n in ((pos, N), (done, N), (n_generated, N), (parent, N), (token, N), (n_active, 1), (counter, 1)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "beam_step: pos / done / n_generated / parent / token (B*K,), "
+                                                         "n_active / counter (1,) int32")
+    _need(score.dtype == torch.float32 and score.numel() == N, "beam_step: score (B*K,) fp32")
+    _need(pos64.dtype == torch.int64 and pos64.numel() == N, "beam_step: pos64 (B*K,) int64")
+    rc = _lib.load(emb.dtype).fvqa_beam_step(_ptr(logits), _ptr(emb), int(eos_id), 1 if stop_at_eos else 0,
+                                             1 if count_any_live else 0, _ptr(ids_in), _ptr(ids_out), _ptr(pos), _ptr(score),
+                                             _ptr(done), _ptr(n_generated), _ptr(pos64), _ptr(parent), _ptr(token), _ptr(x_next),
+                                             _ptr(n_active), _ptr(counter), N // K, K, V, D, ids_in.shape[1], dt_code(emb.dtype),
+                                             _stream())
+    _lib.check(rc, "fvqa_beam_step")
+    return parent, token
+
+
+def kv_beam_move_scratch(n_seq: int, window_rows: int, D: int, L: int, dtype) -> int:
+    return int(_lib.load(dtype).fvqa_kv_beam_move_scratch(n_seq, window_rows, D, L, dt_code(dtype)))
+
+
+def kv_beam_move(dst, src, src_seq, lo, hi, *, S: int, A: int, scratch=None, window_rows: int = 0, group: int = 0):
+    """Cached k / v rows follow the beams (include/fvqa.h fvqa_kv_beam_move). dst (L, n_dst*S + A, 3*D), src (L, n_src*S + A, 3*D);
+    for destination sequence n the rows [lo[n], hi[n]) come from sequence src_seq[n] (+ the sample's first slot when group > 0).
+    scratch None: dst is another buffer than src, adapter rows go along (one launch). scratch (bytes of kv_beam_move_scratch):
+    the move inside one cache through the window of window_rows rows (two launches; slots that are their own source skipped)."""
+    _dev(dst, src, src_seq, lo, hi, scratch)
+    _need(dst.dim() == 3 and src.dim() == 3 and dst.dtype == src.dtype and dst.shape[0] == src.shape[0]
+          and dst.shape[2] == src.shape[2] and dst.shape[2] % 3 == 0, "kv_beam_move: caches (L, n*S + A, 3*D) of one dtype")
+    L, D = dst.shape[0], dst.shape[2] // 3
+    _need(S >= 1 and A >= 0 and dst.shape[1] > A and (dst.shape[1] - A) % S == 0 and src.shape[1] > A
+          and (src.shape[1] - A) % S == 0, "kv_beam_move: rows = n*S + A")
+    n_dst, n_src = (dst.shape[1] - A) // S, (src.shape[1] - A) // S
+    for t in (src_seq, lo, hi):
+        _need(t.dtype == torch.int32 and t.numel() == n_dst, "kv_beam_move: src_seq / lo / hi (n_dst,) int32")
+    _need((D * dst.element_size()) % 16 == 0, "kv_beam_move: rows of whole 16-byte words")
+    if scratch is None:
+        _need(dst.data_ptr() != src.data_ptr(), "kv_beam_move: inside one cache the move needs a scratch window")
+    else:
+        _need(n_dst == n_src and window_rows >= 1, "kv_beam_move: one geometry and a window of >= 1 rows with scratch")
+        _need(scratch.dtype == torch.uint8, "kv_beam_move: scratch is a byte buffer")
+    rc = _lib.load(dst.dtype).fvqa_kv_beam_move(_ptr(dst), _ptr(src), _ptr(scratch), 0 if scratch is None else scratch.numel(),
+                                                _ptr(src_seq), _ptr(lo), _ptr(hi), n_dst, n_src, int(group), S, D, L, A,
+                                                int(window_rows), dt_code(dst.dtype), _stream())
+    _lib.check(rc, "fvqa_kv_beam_move")
+    return dst
+
+
 def attn_bwd_workspace(n_seq, S, H, Dh, A) -> int:
     return int(_lib.load().fvqa_attn_bwd_workspace(n_seq, S, H, Dh, A))
 

@@ -232,7 +232,11 @@ class Transformer(nn.Module):
         -> (most_similar_indices (B,), extracted_answers list of dicts). KV-cached, batched: fvqa/generate.py."""
         from fvqa import generate
         eng = self.ensure_engine()
-        if getattr(self.args, "gen_stop_eos", False):       # --gen_stop_eos: the same tokens up to each row's EOS, which is
+        if int(getattr(self.args, "num_beams", 1) or 1) > 1:    # --num_beams N: the most likely answer under the model
+            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
+                                    num_beams=int(self.args.num_beams))
+            ids = out["ids"]
+        elif getattr(self.args, "gen_stop_eos", False):     # --gen_stop_eos: the same tokens up to each row's EOS, which is
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True)
             ids = out["ids"]                                # where both readers of the ids cut them (match_answers, engine)
         else:
@@ -244,12 +248,13 @@ class Transformer(nn.Module):
     @torch.no_grad()
     def generate(self, data, **kw):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
-        keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed) -> one answer per row, the generated tokens up to (not
-        including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
-        per-row counts and the number of token steps launched are left in `last_generation`."""
+        keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty) -> one answer per row, the
+        generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
+        per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
+        hypothesis' and, under "score", the sum of its tokens' log-probabilities)."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
-        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps")}
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score") if k in out}
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
         answers = []
         for b, p in enumerate(data["prefix_index"]["vqa"]):

@@ -69,6 +69,8 @@ _FLAGS = [
                                                      "which the reference's freeze filter leaves at their random initialisation")),
     ("--gen_stop_eos", dict(action="store_true", help="generation-task validation decodes through fvqa.generate.generate: each "
                                                       "sample stops at its EOS and the batch stops when every sample has")),
+    ("--num_beams", dict(type=int, default=1, help="generation-task validation: beam search with N slots per sample "
+                                                   "(fvqa.generate.beam_search; 1: the decode chosen by --gen_stop_eos)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),

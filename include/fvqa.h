@@ -284,6 +284,47 @@ int fvqa_decode_next(const float* logits, const float* u, const void* emb, float
                      int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token,
                      int32_t* n_kept, int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
                      int dtype, void* stream);
+/* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
+ * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
+ * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)
+ * int64. In/out, per slot: pos int32, score fp32 (the sum of the log-probabilities of the generated tokens; -inf: an empty slot),
+ * done int32, n_generated int32. Out: ids_out (same shape as ids_in and NOT the same buffer: the caller ping-pongs the two),
+ * pos64 int64 (pos after the step, clamped into the sequence: what fvqa_attn_decode reads), parent int32 (the slot of the SAME
+ * sample each new slot descends from), token int32 (-1: carried without a token), x_next (n_samples*K, dim), n_active (ONE int32).
+ * The rule, per sample: a slot with done != 0 — or with pos + 1 >= seq_len, which makes it done first — offers ONE candidate
+ * (j, none) of value score[j]; a live slot j offers (j, v) of value score[j] + (l[j,v] - lse[j]) for every token v, lse[j] =
+ * m + log(sum exp(l - m)) in fp32 with a fixed summation order. The new slots 0..K-1 are the K best candidates in the order
+ * (value descending, parent ascending, token ascending). A child copies its parent's id row, writes v at pos + 1, advances, takes
+ * the value as its score, counts one more generated token, and is done iff stop_at_eos and v == eos_id; a carried candidate is a
+ * copy of slot j. x_next = emb[v], for a carried slot the embedding of its current token. No sort, no float atomics: bitwise
+ * repeatable. n_active = the number of samples whose new slot 0 is not done (count_any_live == 0: with scores that only fall and
+ * ties going to the lower parent nothing can overtake a finished slot 0) or that have any slot not done (count_any_live != 0).
+ * It is counted through `counter`, ONE 32-bit word owned by the caller and zeroed by the caller before the first call; every
+ * completed call leaves it zero again. Calls that share a counter must be ordered against each other.
+ * Limits: 1 <= n_beams <= 8, n_beams <= vocab, n_beams * vocab < 2^31, n_samples <= 65535 (else FVQA_ESHAPE).
+ * FVQA_EINVAL: a null pointer, ids_in == ids_out, a bad dtype code. */
+int fvqa_beam_step(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
+                   const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done, int32_t* n_generated,
+                   int64_t* pos64, int32_t* parent, int32_t* token, void* x_next, int32_t* n_active, uint32_t* counter,
+                   int n_samples, int n_beams, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* Cached keys and values follow the beams (csrc/beam.hip). dst: (n_layers, n_dst_seq*seq_len + adapter_len, 3*dim), src:
+ * (n_layers, n_src_seq*seq_len + adapter_len, 3*dim) — the layout fvqa_attn_decode takes, every layer, uniform layer stride.
+ * For destination sequence n, the k and v thirds of rows [lo[n], hi[n]) (clamped to [0, seq_len)) are copied from source sequence
+ * s = src_seq[n] (group == 0) or (n / group) * group + src_seq[n] (group > 0: src_seq holds the slot within the sample, as
+ * fvqa_beam_step writes `parent`); an s outside [0, n_src_seq) moves nothing. src_seq, lo, hi: int32 device arrays (n_dst_seq) —
+ * read on the device, the host never waits for them. The q third and every row outside the ranges are not written.
+ *   scratch == NULL: dst != src (FVQA_EINVAL otherwise). One launch; the adapter_len adapter rows behind the sequence rows are
+ *     copied too (k and v thirds). The fan-out of a prefill at n_src_seq sequences into a cache of n_dst_seq.
+ *   scratch != NULL: the move inside one cache (dst == src allowed; n_dst_seq == n_src_seq). Sequences with s == n are skipped;
+ *     the others go through the window — launch 1 gathers every moved row into scratch, launch 2 scatters them —, so cycles among
+ *     the parents (a swap, a 3-cycle) come out right. hi[n] - lo[n] <= window_rows is the caller's contract (rows beyond the
+ *     window are not moved); scratch_bytes >= fvqa_kv_beam_move_scratch(n_dst_seq, window_rows, dim, n_layers, dtype), else
+ *     FVQA_EALIGN. Adapter rows are not touched.
+ * dim * element size must be a multiple of 16 and the buffers 16-byte aligned. n_dst_seq, n_layers <= 65535. */
+size_t fvqa_kv_beam_move_scratch(int n_seq, int window_rows, int dim, int n_layers, int dtype);
+int fvqa_kv_beam_move(void* dst, const void* src, void* scratch, size_t scratch_bytes, const int32_t* src_seq,
+                      const int32_t* lo, const int32_t* hi, int n_dst_seq, int n_src_seq, int group, int seq_len, int dim,
+                      int n_layers, int adapter_len, int window_rows, int dtype, void* stream);
 /* workspace bytes fvqa_attn_bwd needs (fp32 partials for the batch-summed adapter k/v
  * gradients and the per-head gate sums). Its FIRST 1024 BYTES are integer arrival counters of the
  * fused bf16 backward: the caller zeroes them once after allocating the workspace; every call

@@ -8,7 +8,11 @@ The generation API (fvqa.generate.generate) is measured with --generate (full le
 (each row stops at its EOS, the batch when every row has); --val_batch_size N decodes N rows per token step; --eos_at K
 puts the first EOS of every row at generated token K: the weights are the `peakedperm` closed form (token t is followed
 by pi(t), fvqa.synth.vocab_permutation) and the prompt's last token is pi^{-K}(EOS) — the trajectory of
-tests/test_generate_gpu.py. The rows' generated counts and the token steps launched are printed with the timing."""
+tests/test_generate_gpu.py. The rows' generated counts and the token steps launched are printed with the timing.
+--num_beams N [N ...] times beam search (generate(num_beams=N, stop_at_eos=False): all 31 steps) interleaved with the greedy
+`generate` of the same batch; for N > 1 also the greedy `generate` of a batch of B * N rows — the like-for-like figure, the
+layer pass is the same size — and, with device events, one fvqa_beam_step and one fvqa_kv_beam_move of the loop's shapes (every
+slot moving 15 generated rows: the worst case half way through an answer)."""
 import argparse
 import os
 import sys
@@ -35,6 +39,8 @@ def main():
                     help="first EOS of every row at generated token K (peakedperm weights); several K: one line each, then the "
                          "full-length decode of the same model")
     ap.add_argument("--pairs", type=int, default=0, help="N interleaved pairs greedy_decode / generate(stop_at_eos=False)")
+    ap.add_argument("--num_beams", type=int, nargs="*", default=[], help="beam search with N slots per sample; several N: a "
+                                                                         "line each, interleaved with greedy generate")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -86,6 +92,9 @@ def main():
               + (f"; steps {last['steps']}, generated per row min {min(ng)} max {max(ng)}" if last else ""), flush=True)
         last.clear()
 
+    if a.num_beams:
+        beam_lines(a, eng, b, cfg, timed)
+        return
     if a.pairs:
         timed(greedy, reps=1)
         timed(gen(False), reps=1)
@@ -124,6 +133,60 @@ def main():
     print(f"{a.model} B={B} S=128: 31 greedy tokens — KV-cached rows {t_kv * 1e3:7.1f} ms/batch "
           f"({B / t_kv:6.1f} samples/s); one full batched forward per token {t_full * 1e3:7.1f} ms/batch "
           f"({B / t_full:6.1f} samples/s); ratio {t_full / t_kv:.2f}x")
+
+
+def device_us(fn, reps=20):
+    for _ in range(3):
+        fn()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) * 1e3 / reps
+
+
+def beam_lines(a, eng, b, cfg, timed):
+    import dataclasses
+    from fvqa import ops
+    B, T, dev = a.batch_size, generate.N_NEW, eng.device
+    tag = f"{a.model} L={eng.L} B={B} S=128"
+    for K in a.num_beams:
+        t_g = timed(lambda: generate.generate(eng, b, stop_at_eos=False))
+        t_b = timed(lambda: generate.generate(eng, b, stop_at_eos=False, num_beams=K))
+        print(f"{tag} greedy generate: {t_g * 1e3:7.1f} ms/batch, {B * T / t_g:8.1f} tokens/s | num_beams={K}: "
+              f"{t_b * 1e3:7.1f} ms/batch, {B * T / t_b:8.1f} answer tokens/s ({B * K * T / t_b:8.1f} slot tokens/s)", flush=True)
+        if K == 1:
+            continue
+        wide = synth.make_batch(dataclasses.replace(cfg, batch_size=B * K), seed=5)
+        wide["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B * K)]}
+        t_w = timed(lambda: generate.generate(eng, wide, stop_at_eos=False))
+        N, S, V, D = B * K, 128, eng.V, eng.D
+        i32 = dict(dtype=torch.int32, device=dev)
+        lg = 4 * torch.randn(N, V, device=dev)
+        ids = [torch.randint(3, V, (N, S), device=dev), torch.zeros(N, S, dtype=torch.int64, device=dev)]
+        pos, done, ngen = torch.full((N,), 70, **i32), torch.zeros(N, **i32), torch.zeros(N, **i32)
+        score, pos64 = torch.zeros(N, device=dev), torch.zeros(N, dtype=torch.int64, device=dev)
+        par, tok, act, cnt = torch.zeros(N, **i32), torch.zeros(N, **i32), torch.zeros(1, **i32), torch.zeros(1, **i32)
+        x = torch.empty(N, D, dtype=eng.dtype, device=dev)
+
+        def step():
+            pos.fill_(70)
+            ops.beam_step(lg, eng.pack.emb, ids[0], ids[1], pos, score, done, ngen, pos64, par, tok, x, act, cnt, num_beams=K,
+                          stop_at_eos=False)
+
+        fill = device_us(lambda: pos.fill_(70))
+        c = eng._beam_kv
+        W = c["key"][2]
+        rot = ((torch.arange(N, device=dev) + 1) % K).to(torch.int32)             # every slot takes its neighbour's rows
+        lo, hi = torch.full((N,), 60, **i32), torch.full((N,), 75, **i32)
+        us_step = device_us(step) - fill
+        us_move = device_us(lambda: ops.kv_beam_move(c["qkv"], c["qkv"], rot, lo, hi, S=S, A=eng.A, scratch=c["scratch"],
+                                                     window_rows=W, group=K))
+        print(f"{tag} num_beams={K}: per token {t_b / T * 1e3:6.3f} ms against {t_w / T * 1e3:6.3f} ms of a greedy batch of "
+              f"{N} rows ({t_b / t_w:5.3f}x); fvqa_beam_step {us_step:7.1f} us, fvqa_kv_beam_move (every slot, 15 rows, "
+              f"{eng.L} layers, two launches) {us_move:7.1f} us", flush=True)
 
 
 if __name__ == "__main__":
