@@ -3,7 +3,7 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
 
     python answer.py --model 7B --llama_model_path ... --resume ckpt.pth --features clip.pth|.npy [--audio_features ...] \
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
-        [--num_beams N --length_penalty A]
+        [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs]
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -34,6 +34,14 @@ def get_args_parser():
     p.add_argument("--top_p", type=float, default=1.0)
     p.add_argument("--length_penalty", type=float, default=0.0,
                    help="with --num_beams > 1: the final hypotheses are ranked by score / n_generated ** A (0: by score)")
+    p.add_argument("--top_k", type=int, default=0, help="sample from the K most likely tokens only (0: off)")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help=">= 1: the logits of the tokens generated so far are divided (positive) or multiplied (negative) by it; "
+                        "the prompt's tokens are not penalised")
+    p.add_argument("--num_samples", type=int, default=1,
+                   help="answers drawn per question from one prefill (needs --temperature > 0)")
+    p.add_argument("--logprobs", action="store_true",
+                   help="print each answer's log-probability under the model and its per-token geometric mean probability")
     p.set_defaults(max_seq_len=128, seed=None)
     return p
 
@@ -89,11 +97,21 @@ def main(args):
     if args.audio_only:
         batch.pop("video", None)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
-                            seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty)[0]
+                            seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
+                            repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,
+                            num_return_sequences=args.num_samples)[0]
     g = model.last_generation
-    print(f"[{int(g['n_generated'][0])} tokens, {g['steps']} steps" +
-          (f", log-probability {float(g['score'][0]):.4f}]" if "score" in g else "]"))
-    print(answer if isinstance(answer, str) else " ".join(str(t) for t in answer))
+    many = args.num_samples > 1
+    for k, a in enumerate(answer if many else [answer]):
+        n = int(g["n_generated"][0, k] if many else g["n_generated"][0])
+        head = f"[{n} tokens, {g['steps']} steps"
+        if "score" in g:
+            head += f", log-probability {float(g['score'][0]):.4f}"
+        if "sum_logprob" in g:
+            lp = float(g["sum_logprob"][0, k] if many else g["sum_logprob"][0])
+            head += f", log-probability {lp:.4f}, per-token probability {np.exp(lp / max(n, 1)):.4f}"
+        print(head + "]")
+        print(a if isinstance(a, str) else " ".join(str(t) for t in a))
     return answer
 
 

@@ -23,6 +23,17 @@
 // n_active needs a count across workgroups: each adds (1 arrival | its row still running << 16) to one device-resident ticket
 // word with an INTEGER atomic; the workgroup that arrives last writes the count and puts the ticket back to zero. The ticket is
 // a module global: launches of this entry on one device must be ordered (one stream, or events), as the decode loop's are.
+//
+// fvqa_decode_next_ex is the same kernel template with EX = true (the old entry instantiates EX = false, in which none of the
+// following exists): a repetition penalty, top-k, the token's log-probability and a ticket word the caller owns.
+//   penalty  the distinct ids at positions gen_start .. pos of the row's id matrix are marked in a bitmap of V bits in LDS
+//            (behind the row of e_i); every read of a logit goes through l1(): l / r or l * r where the bit is set. The logits
+//            are not written.
+//   top-k    C(t) = the NUMBER of e_i whose bit pattern is > t is a non-increasing step function like G(t): the value of the
+//            token at rank k is the smallest t with C(t) <= k - 1, the same bisection counting instead of summing. Of its tie
+//            group the first k - C(t) by index are inside the k. Z_k = G(t) + (k - C(t)) * t replaces Z in the nucleus bound;
+//            kept sets are prefixes of one order, so the cut is the shorter of the two prefixes (top_p == 1: the top-k one).
+//   logprob  l_tok - (m + logf(sum expf(l - m))) on the RAW logits, two passes of their own whose order no parameter changes.
 #include "common.h"
 
 namespace {
@@ -85,15 +96,27 @@ __device__ __forceinline__ int block_scan_i(int v, int* wtot) {
   return base + x - v;
 }
 
-template <typename T>
+// m + log(sum exp(l - m)) of one raw row, as fvqa_beam_step takes it
+__device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, float* red) {
+  float mx = -INFINITY;
+  for (int i = threadIdx.x; i < V; i += NT) mx = fmaxf(mx, lg[i]);
+  const float m = block_max_256(mx, red);
+  float z = 0.f;
+  for (int i = threadIdx.x; i < V; i += NT) z += expf(lg[i] - m);
+  return m + logf(block_sum_256(z, red));
+}
+
+template <typename T, bool EX>
 __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
                                                     const T* __restrict__ emb, float temperature, float top_p, int eos_id,
                                                     int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
                                                     int32_t* __restrict__ done, T* __restrict__ x_next,
                                                     int32_t* __restrict__ token_out, int32_t* __restrict__ n_kept_out,
                                                     int32_t* __restrict__ n_active, int64_t* __restrict__ pos64, int B, int V,
-                                                    int D, int S, int row_in_lds, int vec16) {
-  extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds)
+                                                    int D, int S, int row_in_lds, int vec16, int top_k, float rep,
+                                                    const int32_t* __restrict__ gen_start,
+                                                    float* __restrict__ logprob_out, unsigned* __restrict__ counter) {
+  extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX)
   __shared__ float redf[4], wtotf[4];
   __shared__ int redi[4], wtoti[4];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -102,13 +125,39 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   // a finished row, and one with no room for another token (the reference would index past the end), pick nothing
   const bool live = done[b] == 0 && p >= -1 && p + 1 < S;
   int tok = -1, kept = 0;
+  int64_t* row_ids = ids + (size_t)b * S;
+
+  // ---- EX: the raw row's lse; the bitmap of the ids generated so far
+  float lse = 0.f;
+  const bool pen = EX && rep != 1.f;
+  unsigned* bm = reinterpret_cast<unsigned*>(erow) + (row_in_lds ? ((V + 3) & ~3) : 0);
+  if constexpr (EX) {
+    if (live) lse = row_lse(lg, V, redf);
+    if (live && pen) {
+      for (int i = tid; i < ((V + 31) >> 5); i += NT) bm[i] = 0u;
+      __syncthreads();
+      const int g0 = gen_start[b];
+      for (int j = (g0 < 0 ? 0 : g0) + tid; j <= p; j += NT) {     // (p <= S - 2)
+        const int64_t t = row_ids[j];
+        if (t >= 0 && t < V) atomicOr(&bm[t >> 5], 1u << (t & 31));
+      }
+      __syncthreads();
+    }
+  }
+  auto l1 = [&](int i) -> float {                                  // the logit the pick sees
+    float v = lg[i];
+    if constexpr (EX) {
+      if (pen && ((bm[i >> 5] >> (i & 31)) & 1u)) v = v > 0.f ? v / rep : v * rep;
+    }
+    return v;
+  };
 
   if (live && temperature == 0.f) {
     // ---- greedy: the largest logit, the lowest index on exact ties
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = tid; i < V; i += NT) {
-      const float v = lg[i];
+      const float v = l1(i);
       if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     }
     const float m = block_max_256(bv, redf);
@@ -118,19 +167,49 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   } else if (live) {
     // ---- pass 1, 2: max, e_i, Z
     float mx = -INFINITY;
-    for (int i = tid; i < V; i += NT) mx = fmaxf(mx, lg[i]);
+    for (int i = tid; i < V; i += NT) mx = fmaxf(mx, l1(i));
     const float m = block_max_256(mx, redf);
     float z = 0.f;
     for (int i = tid; i < V; i += NT) {
-      const float e = __expf((lg[i] - m) / temperature);
+      const float e = __expf((l1(i) - m) / temperature);
       if (row_in_lds) erow[i] = e;
       z += e;
     }
     const float Z = block_sum_256(z, redf);                        // (its barriers also publish erow)
-    auto pe = [&](int i) -> float { return row_in_lds ? erow[i] : __expf((lg[i] - m) / temperature); };
-    // ---- the cut: the smallest t with G(t) <= top_p * Z
-    const float X = top_p * Z;
+    auto pe = [&](int i) -> float { return row_in_lds ? erow[i] : __expf((l1(i) - m) / temperature); };
+    // ---- EX, top-k: the smallest t with C(t) <= k - 1 is the value at rank k
+    float Zk = Z;
+    unsigned tkb = 0u;
+    int tie_k = 0;
+    const bool cut_k = EX && top_k >= 1 && top_k < V;
+    if constexpr (EX) {
+      if (cut_k) {
+        unsigned lo = 0u, hi = 0x3f800000u;                        // C(bits(1.0f)) = 0
+        while (lo < hi) {
+          const unsigned mid = lo + ((hi - lo) >> 1);
+          int c = 0;
+          for (int i = tid; i < V; i += NT) c += __float_as_uint(pe(i)) > mid ? 1 : 0;
+          c = block_sum_int(c, redi);
+          if (c < top_k) hi = mid; else lo = mid + 1u;
+        }
+        tkb = lo;
+        float g = 0.f;
+        int c = 0;
+        for (int i = tid; i < V; i += NT) {
+          const float e = pe(i);
+          const bool over = __float_as_uint(e) > tkb;
+          g += over ? e : 0.f;
+          c += over ? 1 : 0;
+        }
+        g = block_sum_256(g, redf);
+        tie_k = top_k - block_sum_int(c, redi);                    // >= 1, and the tie group at tkb has at least as many
+        Zk = g + (float)tie_k * __uint_as_float(tkb);
+      }
+    }
+    // ---- the cut: the smallest t with G(t) <= top_p * Z (Z_k under top-k)
+    const float X = top_p * Zk;
     unsigned lo = 0u, hi = 0x3f800000u;                            // G(bits(1.0f)) = 0: no e_i exceeds exp(0)
+    if (cut_k && top_p >= 1.f) lo = hi = tkb;                      // every rank < k has at most Z_k in front: the top-k cut
     while (lo < hi) {
       const unsigned mid = lo + ((hi - lo) >> 1);
       float g = 0.f;
@@ -141,7 +220,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       g = block_sum_256(g, redf);
       if (g <= X) hi = mid; else lo = mid + 1u;
     }
-    const unsigned tb = lo;
+    unsigned tb = lo;
     const float tf = __uint_as_float(tb);
     float g = 0.f;
     int n_gt = 0, n_eq = 0;
@@ -161,6 +240,11 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       if (q < (float)n_eq) n_tie = (int)q + 1;
     }
     kept = n_gt + n_tie;
+    if (cut_k && (kept > top_k || top_p >= 1.f)) {                 // the shorter prefix of the one order
+      tb = tkb;
+      n_tie = tie_k;
+      kept = top_k;
+    }
     // ---- the walk, in index order over contiguous ranges
     const int chunk = (V + NT - 1) / NT;
     const int i0 = min(V, tid * chunk), i1 = min(V, i0 + chunk);
@@ -197,7 +281,6 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
 
   // ---- step the row
   int now_done = done[b] != 0 ? 1 : 0;
-  int64_t* row_ids = ids + (size_t)b * S;
   int src;
   if (live) {
     p += 1;
@@ -219,10 +302,12 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     if (pos64) pos64[b] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
     token_out[b] = tok;
     n_kept_out[b] = kept;
-    const unsigned old = atomicAdd(&g_ticket, 1u + (now_done ? 0u : 0x10000u));
+    if constexpr (EX) logprob_out[b] = live ? lg[tok] - lse : 0.f;
+    unsigned* ticket = EX ? counter : &g_ticket;
+    const unsigned old = atomicAdd(ticket, 1u + (now_done ? 0u : 0x10000u));
     if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
       *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
-      atomicExch(&g_ticket, 0u);
+      atomicExch(ticket, 0u);
     }
   }
   // ---- the next input row
@@ -238,21 +323,64 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   }
 }
 
-template <typename T>
+// the operands fvqa_decode_next_ex adds (the old entry passes none: EX = false)
+struct ExArgs {
+  int top_k;
+  float rep;
+  const int32_t* gen_start;
+  float* logprob;
+  unsigned* counter;
+};
+constexpr size_t BITMAP_LDS_MAX = ROW_LDS_MAX / 32;                // the bitmap of the largest row that lives in LDS
+
+template <typename T, bool EX>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
            int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
-           int64_t* pos64, int B, int V, int D, int S, hipStream_t st) {
+           int64_t* pos64, int B, int V, int D, int S, ExArgs ex, hipStream_t st) {
   const size_t row_bytes = (size_t)V * sizeof(float);
   const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
-  const size_t lds = in_lds ? row_bytes : 0;
+  size_t lds = in_lds ? row_bytes : 0;
+  if (EX && ex.rep != 1.f) {                                       // the bitmap: V bits behind the row (on a 16-byte boundary)
+    const size_t bitmap = (((size_t)V + 31) / 32) * 4;
+    lds = in_lds ? (((size_t)V + 3) & ~(size_t)3) * sizeof(float) + bitmap : bitmap;
+    if (lds > ROW_LDS_MAX + BITMAP_LDS_MAX) return FVQA_ESHAPE;    // (a vocabulary beyond 1.2 million ids under a penalty)
+  }
   static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
   if (fvqa_attr_needed(attr_done))
-    (void)hipFuncSetAttribute((const void*)decode_next_k<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROW_LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
   const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-  hipLaunchKernelGGL(decode_next_k<T>, dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p, eos_id,
-                     stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16);
+  hipLaunchKernelGGL((decode_next_k<T, EX>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p, eos_id,
+                     stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16,
+                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
+}
+
+// the operand checks both entries share; then the launch
+template <bool EX>
+int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
+                   int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
+                   int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
+                   void* stream) {
+  if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
+  if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
+  if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
+  if (EX && (!(ex.rep >= 1.f) || ex.top_k < 0)) return FVQA_EINVAL;
+  if (temperature > 0.f && !u) return FVQA_EINVAL;
+  if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
+  if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
+  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
+      !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter))
+    return FVQA_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FVQA_H16)
+    return launch<bf16_t, EX>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                              n_active, pos64, n_seq, vocab, dim, seq_len, ex, st);
+  return launch<float, EX>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                           n_active, pos64, n_seq, vocab, dim, seq_len, ex, st);
 }
 
 }  // namespace
@@ -261,20 +389,17 @@ extern "C" int fvqa_decode_next(const float* logits, const float* u, const void*
                                 int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next,
                                 int32_t* token, int32_t* n_kept, int32_t* n_active, int64_t* pos64, int n_seq, int vocab,
                                 int dim, int seq_len, int dtype, void* stream) {
-  if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
-  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
-  if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
-  if (temperature > 0.f && !u) return FVQA_EINVAL;
-  if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
-  if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
-  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
-      !fvqa_aligned(8, ids, pos64))
-    return FVQA_EALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == FVQA_H16)
-    return launch<bf16_t>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
-                          n_active, pos64, n_seq, vocab, dim, seq_len, st);
-  return launch<float>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
-                       n_active, pos64, n_seq, vocab, dim, seq_len, st);
+  return checked_launch<false>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                               n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ExArgs{0, 1.f, nullptr, nullptr, nullptr},
+                               stream);
+}
+
+extern "C" int fvqa_decode_next_ex(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                   int top_k, float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos,
+                                   int32_t* done, const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept,
+                                   float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int vocab,
+                                   int dim, int seq_len, int dtype, void* stream) {
+  return checked_launch<true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                              n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
+                              ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream);
 }

@@ -48,6 +48,7 @@ SIGNATURES = {
     "fvqa_attn_suffix": (_i, [_p] * 10 + [_i] * 10 + [_p]),
     "fvqa_option_pick": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fvqa_decode_next": (_i, [_p, _p, _p, _f, _f, _i, _i] + [_p] * 8 + [_i] * 5 + [_p]),
+    "fvqa_decode_next_ex": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p]),
     "fvqa_beam_step": (_i, [_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
     "fvqa_kv_beam_move_scratch": (_sz, [_i, _i, _i, _i, _i]),
     "fvqa_kv_beam_move": (_i, [_p, _p, _p, _sz, _p, _p, _p] + [_i] * 9 + [_p]),

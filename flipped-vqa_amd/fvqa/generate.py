@@ -136,7 +136,8 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
 # ---------------------------------------------------------------------------------------------- the generation API
 @torch.no_grad()
 def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
-             stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0) -> dict:
+             stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
+             repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -147,11 +148,38 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     memory behind an event, and token step t + 1 is only launched once the count of step t - 1 has arrived and is not zero —
     the host never waits for the step it has just queued, and at most one superfluous step is computed.
     num_beams > 1 (with temperature == 0): beam search, `beam_search` below — the keys above for the best hypothesis plus
-    "score" and "beams". num_beams == 1 is the code below, unchanged."""
+    "score" and "beams". num_beams == 1 is the code below.
+    top_k, repetition_penalty, return_logprobs, num_return_sequences: at their defaults (0, 1.0, False, 1) the call launches
+    exactly what it launched before they existed; any other value sends the token step through ops.decode_next_ex, still one
+    launch (include/fvqa.h fvqa_decode_next_ex states the rule).
+      top_k >= 1: only the k most likely tokens are sampled from; top_p then bounds the mass in front of a token by top_p times
+        the mass of those k. Ignored when temperature == 0.
+      repetition_penalty r >= 1 (CTRL): the logits of the tokens GENERATED so far in the row are divided (if positive) or
+        multiplied (if not) by r before the pick, each id once. The prompt's tokens are not penalised — it lists the answer
+        options and must not push the model away from them (Hugging Face's processor penalises the prompt too).
+      return_logprobs: adds "logprobs" (B, steps) fp32 — log_softmax of the RAW logits at each picked token (no penalty,
+        temperature 1, no cut: the model's own log-probability, what beam search sums into "score"), 0 where "tokens" is -1 —
+        and "sum_logprob" (B,).
+      num_return_sequences n > 1 (needs temperature > 0, num_beams == 1, B * n <= 65535): n samples per prompt from ONE prefill —
+        its cache rows and the adapter rows are fanned out to n rows per sample (ops.kv_beam_move into beam search's cache, one
+        launch; samples never change parent, so nothing moves per token) and the token loop runs on B * n rows; the uniforms
+        are one torch.rand(max_new_tokens, B * n). The results gain a sample axis: "ids" (B, n, S), "n_generated" (B, n),
+        "tokens" / "logprobs" (B, n, steps), "sum_logprob" (B, n)."""
     if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
     if num_beams > 1 and temperature > 0:
         raise ValueError("generate: num_beams > 1 searches, it does not sample: temperature must be 0")
+    if int(top_k) != top_k or top_k < 0 or not repetition_penalty >= 1:
+        raise ValueError("generate: top_k >= 0 (0: off), repetition_penalty >= 1")
+    if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+        raise ValueError("generate: num_return_sequences >= 1")
+    n = int(num_return_sequences)
+    if n > 1 and (num_beams > 1 or not temperature > 0):
+        raise ValueError("generate: num_return_sequences > 1 draws samples: temperature > 0 and num_beams == 1")
+    ex = top_k != 0 or repetition_penalty != 1 or bool(return_logprobs) or n > 1
+    if num_beams > 1 and ex:
+        raise ValueError("generate: top_k, repetition_penalty, return_logprobs and num_return_sequences belong to "
+                         "num_beams == 1 (beam search reports \"score\")")
     if num_beams > 1 or _BEAM_PATH_AT_ONE:
         return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
                            length_penalty=float(length_penalty))
@@ -163,30 +191,47 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if max_new_tokens < 1 or not temperature >= 0 or not 0 < top_p <= 1:
         raise ValueError("generate: max_new_tokens >= 1, temperature >= 0, 0 < top_p <= 1")
     ids_all = data["text_id"]["vqa"]
-    B, _, S = ids_all.shape
+    B0, _, S = ids_all.shape
+    B = B0 * n                                              # the rows of the token loop
+    if B > 65535:
+        raise ValueError("generate: at most 65535 rows (samples times num_return_sequences)")
     sub = {k: data[k] for k in ("video", "audio") if k in data}
     sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
                 "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
     with vqa_stream_only(eng, "_gen_arena", "all"):
         eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B, S)
+        ar = eng.arena(B0, S)
         vstart = eng.saved["vstart"]
         D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
         fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
         ids = ids_all[:, 0].to(dev).clone()
         prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
         start = prefix - 1                                  # the position the first token is predicted at
+        first = ar.logits.view(B0, S, V)[torch.arange(B0, device=dev), start.clamp(0, S - 1)]
+        kv = ar.qkv
+        if n > 1:                                           # one prefill, n rows per sample: beam search's fan-out, no re-seating
+            i32 = dict(dtype=torch.int32, device=dev)
+            rep = lambda t: t.repeat_interleave(n, 0).contiguous()  # noqa: E731  per sample -> per row
+            kv = _beam_cache(eng, B, S, min(int(max_new_tokens), S))["qkv"]
+            ops.kv_beam_move(kv, ar.qkv, rep(torch.arange(B0, **i32)), torch.zeros(B, **i32), rep(prefix).to(torch.int32),
+                             S=S, A=A)
+            vstart, ids, prefix, start = rep(vstart), rep(ids), rep(prefix), rep(start)
+            first = first.unsqueeze(1).expand(B0, n, V).reshape(B, V)
         e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
         xin, xn, hn, h, xb, o_row = e(B, D), e(B, D), e(B, D), e(B, D), e(B, D), e(B, D)
         qkv_row, ab, z = e(B, 3 * D), e(B, 2 * Hf), e(B, Hf)
         lg = e(B, V, dtype=torch.float32)
-        lg.copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
+        lg.copy_(first)
         pos = start.to(torch.int32)
         pos64 = start.clone()
         done = torch.zeros(B, dtype=torch.int32, device=dev)
         tokens = torch.full((max_new_tokens, B), -1, dtype=torch.int32, device=dev)
         n_kept = torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev)
         n_active = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev)
+        if ex:
+            gen_start = prefix.to(torch.int32)
+            logprobs = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
+            counter = torch.zeros(1, dtype=torch.int32, device=dev)
         u = None
         if temperature > 0:
             gen = None
@@ -202,9 +247,16 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                 arrived[t - 2].synchronize()
                 if int(running[t - 2]) == 0:
                     break
-            ops.decode_next(lg, pk.emb, ids, pos, done, xin, tokens[t], n_kept[t], n_active[t:t + 1],
-                            u=None if u is None else u[t], pos64=pos64, temperature=temperature,
-                            top_p=top_p, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos)
+            if ex:
+                ops.decode_next_ex(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
+                                   n_active[t:t + 1], counter, u=None if u is None else u[t], pos64=pos64,
+                                   temperature=temperature, top_p=top_p, top_k=int(top_k),
+                                   repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
+                                   stop_at_eos=stop_at_eos)
+            else:
+                ops.decode_next(lg, pk.emb, ids, pos, done, xin, tokens[t], n_kept[t], n_active[t:t + 1],
+                                u=None if u is None else u[t], pos64=pos64, temperature=temperature,
+                                top_p=top_p, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos)
             running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
@@ -219,7 +271,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                 ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=B)
                 ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
                 g1, g2 = m.gate_views(i)
-                ops.attn_decode(qkv_row, ar.qkv[i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), B, S, H, Dh, A, F,
+                ops.attn_decode(qkv_row, kv[i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), B, S, H, Dh, A, F,
                                 cache_rotated=not fused)
                 ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
                 ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=B)
@@ -229,8 +281,16 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                 x, x2 = x2, x
             ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=B)
             ops.gemm_nt(xn, pk.wout, lg)
-        return {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
-                "tokens": tokens[:steps].t().contiguous()}
+        out = {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
+               "tokens": tokens[:steps].t().contiguous()}
+        if return_logprobs:
+            out["logprobs"] = logprobs[:steps].t().contiguous()
+            out["sum_logprob"] = out["logprobs"].sum(1)
+        if n > 1:
+            for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob"):
+                if k in out:
+                    out[k] = out[k].view(B0, n, *out[k].shape[1:])
+        return out
 
 
 _BEAM_PATH_AT_ONE = False   # (tests) send num_beams == 1 through beam_search too: K = 1 must reproduce the greedy ids

@@ -629,6 +629,37 @@ def decode_next(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, *,
     return token
 
 
+def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, *, u=None,
+                   pos64=None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
+                   eos_id: int = 2, stop_at_eos: bool = True):
+    """decode_next with top-k, a repetition penalty and the token's log-probability (include/fvqa.h fvqa_decode_next_ex states
+    the rule). On top of decode_next's operands: gen_start (B,) int32 — the ids at positions gen_start .. pos of a row are the
+    tokens the penalty applies to —, logprob (B,) fp32 out (log_softmax of the RAW logits at the token; 0 where none was
+    picked), counter: one int32 word the caller zeroed once (the library keeps no ticket for this entry)."""
+    _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, u, pos64)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_ex: logits (B, V) fp32")
+    B, V = logits.shape
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_ex: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B, D), "decode_next_ex: x_next (B, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_ex: ids (B, S) int64")
+    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (n_active, 1), (counter, 1)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_ex: pos / done / gen_start / token / n_kept (B,), "
+                                                         "n_active / counter (1,) int32")
+    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_ex: logprob (B,) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_ex: pos64 (B,) int64")
+    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
+          "decode_next_ex: sampling needs u (B,) fp32")
+    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_ex: top_k >= 0, repetition_penalty >= 1")
+    rc = _lib.load(emb.dtype).fvqa_decode_next_ex(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(top_k),
+                                                  float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0, _ptr(ids),
+                                                  _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token),
+                                                  _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), B, V,
+                                                  D, ids.shape[1], dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_decode_next_ex")
+    return token
+
+
 BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
 
 

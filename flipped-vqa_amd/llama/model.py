@@ -248,20 +248,29 @@ class Transformer(nn.Module):
     @torch.no_grad()
     def generate(self, data, **kw):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
-        keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty) -> one answer per row, the
+        keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
+        return_logprobs, num_return_sequences) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
-        hypothesis' and, under "score", the sum of its tokens' log-probabilities)."""
+        hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
+        "sum_logprob"). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
-        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score") if k in out}
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob")
+                                if k in out}
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
-        answers = []
-        for b, p in enumerate(data["prefix_index"]["vqa"]):
-            row = ids[b, int(p): int(p) + int(n[b])].tolist()
+
+        def answer(row):
             if self.tokenizer.eos_id in row:
                 row = row[: row.index(self.tokenizer.eos_id)]
-            answers.append(self.tokenizer.decode(row) if self.tokenizer.sp_model is not None else row)
+            return self.tokenizer.decode(row) if self.tokenizer.sp_model is not None else row
+
+        answers = []
+        for b, p in enumerate(data["prefix_index"]["vqa"]):
+            if ids.dim() == 3:
+                answers.append([answer(ids[b, k, int(p): int(p) + int(n[b, k])].tolist()) for k in range(ids.shape[1])])
+            else:
+                answers.append(answer(ids[b, int(p): int(p) + int(n[b])].tolist()))
         return answers
 
     @torch.no_grad()

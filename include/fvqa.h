@@ -284,6 +284,32 @@ int fvqa_decode_next(const float* logits, const float* u, const void* emb, float
                      int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token,
                      int32_t* n_kept, int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
                      int dtype, void* stream);
+/* fvqa_decode_next with a repetition penalty, top-k, the picked token's log-probability and a caller-owned ticket word (the
+ * same kernel template in csrc/sample.hip; generate(top_k / repetition_penalty / return_logprobs / num_return_sequences)). The
+ * operands, the row stepping and the errors of fvqa_decode_next hold; in addition: top_k >= 0 (0, or >= vocab: off),
+ * repetition_penalty r >= 1, gen_start (n_seq) int32 in, logprob (n_seq) fp32 out, counter (ONE 32-bit word owned by the
+ * caller and zeroed by the caller before the first call, as fvqa_beam_step's: every completed call leaves it zero again; calls
+ * that share a counter must be ordered against each other; the library keeps no state for this entry). Per live row, fp32:
+ *   1. R = the distinct ids at positions max(gen_start, 0) .. pos of the row's id matrix — the tokens generated so far, NOT the
+ *      prompt; ids outside [0, vocab) are ignored; empty when pos < gen_start. l1_i = l_i / r if l_i > 0 else l_i * r for i in
+ *      R (once, however often i occurs), l1_i = l_i elsewhere (the CTRL rule). r == 1: l1 is l bit for bit. The logits are read
+ *      only.
+ *   2. temperature == 0: token = the largest l1_i, lowest index on ties; n_kept = 1; top_k and top_p are ignored.
+ *      temperature > 0: e_i = exp((l1_i - max l1) / temperature).
+ *   3. Order by e descending, index ascending. k = top_k if 1 <= top_k < vocab, else vocab; Z_k = the mass of the first k
+ *      tokens. The token at rank j is kept iff j < k and the mass in front of it is <= top_p * Z_k (n_kept of them: a prefix of
+ *      the order). With k == vocab this is fvqa_decode_next's rule, and with r == 1 as well its results bit for bit.
+ *   4. token = the first kept token IN INDEX ORDER whose running kept mass exceeds u * M, else the last kept token.
+ *   5. logprob = l_token - (m + log(sum exp(l - m))) on the RAW logits (no penalty, temperature 1, no cut; fixed summation
+ *      order, the same bits whatever the sampling parameters) — the quantity fvqa_beam_step sums into score. 0 for a row that
+ *      picks nothing (token == -1).
+ * FVQA_EINVAL also for a null gen_start / logprob / counter, repetition_penalty < 1 or NaN, top_k < 0; FVQA_ESHAPE also for a
+ * vocab beyond 1216512 when repetition_penalty != 1 (the bitmap of R lives in LDS). */
+int fvqa_decode_next_ex(const float* logits, const float* u, const void* emb, float temperature, float top_p, int top_k,
+                        float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done,
+                        const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
+                        int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
+                        int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)

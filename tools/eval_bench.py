@@ -12,7 +12,10 @@ tests/test_generate_gpu.py. The rows' generated counts and the token steps launc
 --num_beams N [N ...] times beam search (generate(num_beams=N, stop_at_eos=False): all 31 steps) interleaved with the greedy
 `generate` of the same batch; for N > 1 also the greedy `generate` of a batch of B * N rows — the like-for-like figure, the
 layer pass is the same size — and, with device events, one fvqa_beam_step and one fvqa_kv_beam_move of the loop's shapes (every
-slot moving 15 generated rows: the worst case half way through an answer)."""
+slot moving 15 generated rows: the worst case half way through an answer).
+--top_k K [K ...] / --samples N [N ...] time sampling `generate(temperature=0.8, stop_at_eos=False)` with a top-k cut (and the
+log-probabilities: the fvqa_decode_next_ex token step) / with N samples per prompt from one prefill, each interleaved with the
+plain sampling `generate` of the same batch — for N > 1 also N calls of it, which is what the fan-out replaces."""
 import argparse
 import os
 import sys
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=0, help="N interleaved pairs greedy_decode / generate(stop_at_eos=False)")
     ap.add_argument("--num_beams", type=int, nargs="*", default=[], help="beam search with N slots per sample; several N: a "
                                                                          "line each, interleaved with greedy generate")
+    ap.add_argument("--top_k", type=int, nargs="*", default=[], help="sampling with a top-k cut; several K: a line each")
+    ap.add_argument("--samples", type=int, nargs="*", default=[], help="N samples per prompt from one prefill; several N: a line "
+                                                                       "each")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -94,6 +100,19 @@ def main():
 
     if a.num_beams:
         beam_lines(a, eng, b, cfg, timed)
+        return
+    if a.top_k or a.samples:
+        T = generate.N_NEW
+        tag = f"{a.model} L={eng.L} B={B} S=128 temperature=0.8"
+        plain = lambda **kw: generate.generate(eng, b, temperature=0.8, stop_at_eos=False, seed=0, **kw)   # noqa: E731
+        for K in a.top_k:
+            t_p, t_k = timed(plain), timed(lambda: plain(top_k=K, return_logprobs=True))
+            print(f"{tag} sampling generate: {t_p * 1e3:7.1f} ms/batch, {B * T / t_p:8.1f} tokens/s | top_k={K} with "
+                  f"log-probabilities: {t_k * 1e3:7.1f} ms/batch, {B * T / t_k:8.1f} tokens/s", flush=True)
+        for N in a.samples:
+            t_p, t_n = timed(plain), timed(lambda: plain(num_return_sequences=N))
+            print(f"{tag} sampling generate: {t_p * 1e3:7.1f} ms/batch | {N} samples per prompt from one prefill: "
+                  f"{t_n * 1e3:7.1f} ms/batch, {B * N * T / t_n:8.1f} tokens/s ({N * t_p / t_n:5.2f}x {N} calls)", flush=True)
         return
     if a.pairs:
         timed(greedy, reps=1)
