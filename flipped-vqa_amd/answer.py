@@ -3,7 +3,11 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
 
     python answer.py --model 7B --llama_model_path ... --resume ckpt.pth --features clip.pth|.npy [--audio_features ...] \
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
-        [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs]
+        [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
+        [--constrain | --answer_vocab FILE]
+
+`--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
+line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -19,12 +23,12 @@ import torch
 
 import train
 import util.misc as misc
-from fvqa import generate
+from fvqa import constrain, generate
 from llama_vqa import LLaMA_VQA
 
 
 def get_args_parser():
-    p = argparse.ArgumentParser("Flipped-VQA: answer one question (MI355X)", parents=[train.get_args_parser()])
+    p = train.ArgumentParser("Flipped-VQA: answer one question (MI355X)", parents=[train.get_args_parser()])
     p.add_argument("--question", type=str, required=True)
     p.add_argument("--options", type=str, nargs="*", default=None, help="answer options of a multiple-choice question")
     p.add_argument("--features", type=str, default=None, help="frame features of the clip, (n, 768): .pth or .npy")
@@ -42,6 +46,8 @@ def get_args_parser():
                    help="answers drawn per question from one prefill (needs --temperature > 0)")
     p.add_argument("--logprobs", action="store_true",
                    help="print each answer's log-probability under the model and its per-token geometric mean probability")
+    p.add_argument("--constrain", action="store_true",
+                   help="with --options: the answer is one of the options (constrained decoding); its index is printed")
     p.set_defaults(max_seq_len=128, seed=None)
     return p
 
@@ -96,10 +102,18 @@ def main(args):
                                   max_seq_len=args.max_seq_len, max_feats=args.max_feats)
     if args.audio_only:
         batch.pop("video", None)
+    allowed = None                                # --constrain / --answer_vocab: the allowed answers, as text
+    if args.constrain:
+        if not args.options:
+            raise SystemExit("--constrain needs --options")
+        allowed = list(args.options)
+    elif args.answer_vocab:
+        allowed = constrain.read_answer_vocab(args.answer_vocab)
+    kw = {} if allowed is None else {"constraints": constrain.encode_answers(tok, allowed)}
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
                             seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
                             repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,
-                            num_return_sequences=args.num_samples)[0]
+                            num_return_sequences=args.num_samples, **kw)[0]
     g = model.last_generation
     many = args.num_samples > 1
     for k, a in enumerate(answer if many else [answer]):
@@ -112,6 +126,9 @@ def main(args):
             head += f", log-probability {lp:.4f}, per-token probability {np.exp(lp / max(n, 1)):.4f}"
         print(head + "]")
         print(a if isinstance(a, str) else " ".join(str(t) for t in a))
+        if allowed is not None:
+            c = int(g["choice"][0, k] if many else g["choice"][0])
+            print(f"choice {c}: {allowed[c]}" if c >= 0 else "choice -1: no allowed answer was completed")
     return answer
 
 

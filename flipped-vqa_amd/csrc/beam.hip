@@ -16,6 +16,16 @@
 //   count    one integer per launch crosses workgroups, through a CALLER-owned word that the caller zeroes once: each workgroup
 //            adds (1 | counts << 16) with an integer atomic, the last to arrive writes the count and puts the word back to zero.
 //
+// fvqa_beam_step_trie — the same template with TRIE = true (false in fvqa_beam_step, in which none of this exists): constrained
+// decoding over a trie in CSR form (fvqa/constrain.py). Every slot sits at a node; a live slot at a node >= 0 offers (j, v) only
+// for the tokens v on the node's edges — the candidate loop runs over the edge list, the numbering c = j * V + v and so the
+// order are unchanged, lse stays that of the whole raw row —, a live slot without a usable edge (or at a node outside the trie)
+// is finished first, a slot at node -1 offers every v. After the K winners are known the edge (j, v) of each child is looked up
+// again in its parent's list (a block-wide search, K of them) and the slot takes that edge's child; a carried slot keeps its
+// parent's node. All K old nodes are read into LDS before any is written. Every index read from the trie is clamped: the edge
+// range into [0, n_edges], tokens outside [0, V) are skipped, a child outside [0, n_nodes) becomes n_nodes (which finishes the
+// slot at its next step).
+//
 // fvqa_kv_beam_move — cached keys and values follow the beams: for destination sequence n the k and v thirds of cache rows
 // [lo[n], hi[n]) of every layer come from sequence src[n]. Direct (scratch == NULL, dst != src: the fan-out of a B-sequence
 // prefill into a B*K-sequence cache, adapter rows included) in one launch; through a scratch window (the per-token move inside
@@ -31,7 +41,16 @@ constexpr int NONE = 0x7fffffff;
 
 __device__ __forceinline__ bool better(float v1, int i1, float v2, int i2) { return v1 > v2 || (v1 == v2 && i1 < i2); }
 
-template <typename T>
+// the operands fvqa_beam_step_trie adds (TRIE = true)
+struct TrieArgs {
+  int32_t* node;
+  const int32_t* node_first;
+  const int32_t* edge_token;
+  const int32_t* edge_child;
+  int n_nodes, n_edges;
+};
+
+template <typename T, bool TRIE>
 __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logits, const T* __restrict__ emb, int eos_id,
                                                   int stop_at_eos, int count_any_live, const int64_t* __restrict__ ids_in,
                                                   int64_t* __restrict__ ids_out, int32_t* __restrict__ pos,
@@ -39,11 +58,13 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
                                                   int32_t* __restrict__ n_generated, int64_t* __restrict__ pos64,
                                                   int32_t* __restrict__ parent_out, int32_t* __restrict__ token_out,
                                                   T* __restrict__ x_next, int32_t* __restrict__ n_active,
-                                                  unsigned* __restrict__ counter, int B, int K, int V, int D, int S, int vec16) {
+                                                  unsigned* __restrict__ counter, int B, int K, int V, int D, int S, int vec16,
+                                                  TrieArgs tr) {
   __shared__ float s_score[KMAX], s_lse[KMAX], redf[4];
   __shared__ int s_done[KMAX], s_pos[KMAX], s_ngen[KMAX];
   __shared__ float w_val[2][4], win_val[KMAX];
   __shared__ int w_idx[2][4], win_idx[KMAX];
+  __shared__ int s_node[KMAX], s_e0[KMAX], s_ne[KMAX], s_find[4];   // (TRIE)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const size_t r0 = (size_t)b * K;                                // the sample's first slot
 
@@ -55,6 +76,33 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
     s_done[tid] = (done[r0 + tid] != 0 || p < -1 || p + 1 >= S) ? 1 : 0;      // no room: the slot is finished first
   }
   __syncthreads();
+
+  // ---- TRIE: every slot's node and (clamped) edge range; a live slot at a node without a usable edge is finished first
+  if constexpr (TRIE) {
+    if (tid < K) {
+      const int nd = tr.node[r0 + tid];
+      int e0 = 0, e1 = 0;
+      if (nd >= 0 && nd < tr.n_nodes) {
+        e0 = tr.node_first[nd];
+        e1 = tr.node_first[nd + 1];
+        e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
+        e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
+      }
+      s_node[tid] = nd;
+      s_e0[tid] = e0;
+      s_ne[tid] = e1 - e0;
+    }
+    __syncthreads();
+    for (int j = 0; j < K; ++j) {
+      if (s_done[j] || s_node[j] == -1) continue;                  // (uniform over the workgroup)
+      const int32_t* et = tr.edge_token + s_e0[j];
+      int any = 0;
+      for (int i = tid; i < s_ne[j]; i += NT) any |= (unsigned)et[i] < (unsigned)V ? 1 : 0;
+      any = __syncthreads_or(any);
+      if (!any && tid == 0) s_done[j] = 1;
+    }
+    __syncthreads();
+  }
 
   // ---- lse of the live slots
   for (int j = 0; j < K; ++j) {
@@ -94,6 +142,16 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
     }
     const float* lg = logits + (r0 + j) * V;
     const float lse = s_lse[j];
+    if constexpr (TRIE) {
+      if (s_node[j] != -1) {                                       // the node's edges, in list order = token order
+        const int32_t* et = tr.edge_token + s_e0[j];
+        for (int i = tid; i < s_ne[j]; i += NT) {
+          const int v = et[i];
+          if ((unsigned)v < (unsigned)V) consider(sj + (lg[v] - lse), j * V + v);
+        }
+        continue;
+      }
+    }
     for (int v = tid; v < V; v += NT) consider(sj + (lg[v] - lse), j * V + v);
   }
 
@@ -122,6 +180,35 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
     }
   }
   __syncthreads();
+
+  // ---- TRIE: the node of every new slot (its parent's, or the child of the edge it took), from the OLD nodes in LDS
+  if constexpr (TRIE) {
+    for (int i = 0; i < K; ++i) {
+      const int c = win_idx[i];
+      const bool none = c == NONE;
+      const int j = none ? i : c / V;
+      const int v = none ? 0 : c - j * V;
+      int nd = s_node[j];
+      if (!none && s_done[j] == 0 && nd != -1) {                   // (uniform) a child: find the edge (j, v) again
+        const int32_t* et = tr.edge_token + s_e0[j];
+        int at = NONE;
+        for (int e = tid; e < s_ne[j]; e += NT)
+          if (et[e] == v) at = min(at, e);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) at = min(at, __shfl_xor(at, o, 64));
+        if (lane == 0) s_find[w] = at;
+        __syncthreads();
+        at = min(min(s_find[0], s_find[1]), min(s_find[2], s_find[3]));
+        nd = tr.n_nodes;
+        if (at != NONE) {
+          const int ch = tr.edge_child[s_e0[j] + at];
+          if (ch >= 0 && ch < tr.n_nodes) nd = ch;
+        }
+        __syncthreads();                                           // (s_find is read before the next round writes it)
+      }
+      if (tid == 0) tr.node[r0 + i] = nd;                          // (the old nodes are all in s_node)
+    }
+  }
 
   // ---- re-seat the slots
   for (int i = 0; i < K; ++i) {
@@ -216,35 +303,62 @@ __global__ __launch_bounds__(NT) void kv_move_k(uint4* __restrict__ dst, const u
 
 }  // namespace
 
-extern "C" int fvqa_beam_step(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
-                              const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done,
-                              int32_t* n_generated, int64_t* pos64, int32_t* parent, int32_t* token, void* x_next,
-                              int32_t* n_active, uint32_t* counter, int n_samples, int n_beams, int vocab, int dim, int seq_len,
-                              int dtype, void* stream) {
+namespace {
+
+template <bool TRIE>
+int beam_step_checked(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
+                      const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done, int32_t* n_generated,
+                      int64_t* pos64, int32_t* parent, int32_t* token, void* x_next, int32_t* n_active, uint32_t* counter,
+                      int n_samples, int n_beams, int vocab, int dim, int seq_len, int dtype, void* stream, TrieArgs tr) {
   if (!logits || !emb || !ids_in || !ids_out || !pos || !score || !done || !n_generated || !pos64 || !parent || !token ||
       !x_next || !n_active || !counter)
     return FVQA_EINVAL;
+  if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
   if (ids_in == ids_out) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_samples <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_beams < 1 || n_beams > KMAX || n_beams > vocab) return FVQA_ESHAPE;
   if (n_samples > 65535 || (long long)n_beams * vocab > 0x7ffffffeLL) return FVQA_ESHAPE;   // 16-bit arrivals; c fits an int
+  if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) ||
       !fvqa_aligned(4, logits, pos, score, done, n_generated, parent, token, n_active, counter) ||
-      !fvqa_aligned(8, ids_in, ids_out, pos64))
+      !fvqa_aligned(8, ids_in, ids_out, pos64) || !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int vec16 = ((size_t)dim * fvqa_dtype_size(dtype)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
   if (dtype == FVQA_H16)
-    hipLaunchKernelGGL(beam_step_k<bf16_t>, dim3(n_samples), dim3(NT), 0, st, logits, (const bf16_t*)emb, eos_id, stop_at_eos,
-                       count_any_live, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, (bf16_t*)x_next,
-                       n_active, counter, n_samples, n_beams, vocab, dim, seq_len, vec16);
+    hipLaunchKernelGGL((beam_step_k<bf16_t, TRIE>), dim3(n_samples), dim3(NT), 0, st, logits, (const bf16_t*)emb, eos_id,
+                       stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token,
+                       (bf16_t*)x_next, n_active, counter, n_samples, n_beams, vocab, dim, seq_len, vec16, tr);
   else
-    hipLaunchKernelGGL(beam_step_k<float>, dim3(n_samples), dim3(NT), 0, st, logits, (const float*)emb, eos_id, stop_at_eos,
-                       count_any_live, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, (float*)x_next,
-                       n_active, counter, n_samples, n_beams, vocab, dim, seq_len, vec16);
+    hipLaunchKernelGGL((beam_step_k<float, TRIE>), dim3(n_samples), dim3(NT), 0, st, logits, (const float*)emb, eos_id,
+                       stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token,
+                       (float*)x_next, n_active, counter, n_samples, n_beams, vocab, dim, seq_len, vec16, tr);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
+}
+
+}  // namespace
+
+extern "C" int fvqa_beam_step(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
+                              const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done,
+                              int32_t* n_generated, int64_t* pos64, int32_t* parent, int32_t* token, void* x_next,
+                              int32_t* n_active, uint32_t* counter, int n_samples, int n_beams, int vocab, int dim, int seq_len,
+                              int dtype, void* stream) {
+  return beam_step_checked<false>(logits, emb, eos_id, stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done,
+                                  n_generated, pos64, parent, token, x_next, n_active, counter, n_samples, n_beams, vocab, dim,
+                                  seq_len, dtype, stream, TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0});
+}
+
+extern "C" int fvqa_beam_step_trie(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
+                                   const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done,
+                                   int32_t* n_generated, int64_t* pos64, int32_t* parent, int32_t* token, void* x_next,
+                                   int32_t* n_active, uint32_t* counter, int32_t* node, const int32_t* node_first,
+                                   const int32_t* edge_token, const int32_t* edge_child, int n_nodes, int n_edges,
+                                   int n_samples, int n_beams, int vocab, int dim, int seq_len, int dtype, void* stream) {
+  return beam_step_checked<true>(logits, emb, eos_id, stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done,
+                                 n_generated, pos64, parent, token, x_next, n_active, counter, n_samples, n_beams, vocab, dim,
+                                 seq_len, dtype, stream, TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges});
 }
 
 extern "C" size_t fvqa_kv_beam_move_scratch(int n_seq, int window_rows, int dim, int n_layers, int dtype) {

@@ -34,6 +34,17 @@
 //            group the first k - C(t) by index are inside the k. Z_k = G(t) + (k - C(t)) * t replaces Z in the nucleus bound;
 //            kept sets are prefixes of one order, so the cut is the shorter of the two prefixes (top_p == 1: the top-k one).
 //   logprob  l_tok - (m + logf(sum expf(l - m))) on the RAW logits, two passes of their own whose order no parameter changes.
+//
+// fvqa_decode_next_trie is the template with TRIE = true as well (false in the two entries above, in which none of the following
+// exists): constrained decoding over a trie of allowed answers in CSR form (fvqa/constrain.py). A row at node >= 0 picks among
+// the children of its node only. Its passes run over the node's EDGE LIST instead of over the vocabulary — element i of every
+// loop is edge i of the node, its logit the one at edge_token[i] —: the maximum, Z, the counts and the masked sums of both
+// bisections, the tie group and the walk all see the allowed tokens and nothing else, and since a node's edges are in ascending
+// token order the list order is the index order of the rule. An edge whose token lies outside [0, V) is skipped: it is left out
+// of every count by an explicit test (its e would otherwise tie with an allowed token whose e underflowed to 0), top-k is cut
+// against the NUMBER ALLOWED, and the walk falls back to the last kept (or, on a row of NaNs, the first allowed) edge. Every
+// index read from the trie is clamped before it is used: the edge range into [0, n_edges], the child into [0, n_nodes) (else
+// the row is sent to the node n_nodes, which ends it at the next step). A row at node == -1 runs the loops over V as before.
 #include "common.h"
 
 namespace {
@@ -106,7 +117,16 @@ __device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, fl
   return m + logf(block_sum_256(z, red));
 }
 
-template <typename T, bool EX>
+// the operands fvqa_decode_next_trie adds (TRIE = true)
+struct TrieArgs {
+  int32_t* node;
+  const int32_t* node_first;
+  const int32_t* edge_token;
+  const int32_t* edge_child;
+  int n_nodes, n_edges;
+};
+
+template <typename T, bool EX, bool TRIE>
 __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
                                                     const T* __restrict__ emb, float temperature, float top_p, int eos_id,
                                                     int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
@@ -115,7 +135,9 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
                                                     int32_t* __restrict__ n_active, int64_t* __restrict__ pos64, int B, int V,
                                                     int D, int S, int row_in_lds, int vec16, int top_k, float rep,
                                                     const int32_t* __restrict__ gen_start,
-                                                    float* __restrict__ logprob_out, unsigned* __restrict__ counter) {
+                                                    float* __restrict__ logprob_out, unsigned* __restrict__ counter,
+                                                    TrieArgs tr) {
+  static_assert(EX || !TRIE, "the trie entry extends the EX entry");
   extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX)
   __shared__ float redf[4], wtotf[4];
   __shared__ int redi[4], wtoti[4];
@@ -123,9 +145,49 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   const float* lg = logits + (size_t)b * V;
   int p = pos[b];
   // a finished row, and one with no room for another token (the reference would index past the end), pick nothing
-  const bool live = done[b] == 0 && p >= -1 && p + 1 < S;
+  bool live = done[b] == 0 && p >= -1 && p + 1 < S;
   int tok = -1, kept = 0;
   int64_t* row_ids = ids + (size_t)b * S;
+
+  // ---- TRIE: the row's node -> its edge list et[0 .. N), every index clamped; N = V and element i = token i without one
+  int N = V, n_ok = V, first_ok = 0, nd = -1;
+  bool cons = false;
+  const int32_t* et = nullptr;
+  const int32_t* ec = nullptr;
+  if constexpr (TRIE) {
+    nd = tr.node[b];
+    if (live && nd != -1) {
+      cons = true;
+      N = 0;
+      if (nd >= 0 && nd < tr.n_nodes) {
+        int e0 = tr.node_first[nd], e1 = tr.node_first[nd + 1];
+        e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
+        e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
+        et = tr.edge_token + e0;
+        ec = tr.edge_child + e0;
+        N = e1 - e0;
+      }
+      int c = 0, f = 0x7fffffff;
+      for (int i = tid; i < N; i += NT)
+        if ((unsigned)et[i] < (unsigned)V) { c += 1; f = min(f, i); }
+      n_ok = block_sum_int(c, redi);
+      first_ok = block_min_int(f, redi);
+      if (n_ok == 0) live = false;                                 // no children (or a node outside the trie): the row ends
+    }
+  }
+  auto ok = [&](int i) -> bool {                                   // element i takes part (always, without a trie)
+    if constexpr (TRIE) {
+      if (cons) return (unsigned)et[i] < (unsigned)V;
+    }
+    return true;
+  };
+  auto tk = [&](int i) -> int {                                    // the token of element i (ok(i) holds)
+    if constexpr (TRIE) {
+      if (cons) return et[i];
+    }
+    return i;
+  };
+  const bool use_lds = row_in_lds && (!TRIE || N <= V);            // (a list longer than V: recomputed, never past the row)
 
   // ---- EX: the raw row's lse; the bitmap of the ids generated so far
   float lse = 0.f;
@@ -152,50 +214,58 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     return v;
   };
 
+  // Every loop below runs over the N elements of the row: the vocabulary, or (TRIE, a row at a node) the node's edges, of which
+  // those with ok() take part. `sel` is the element picked.
+  int sel = -1;
   if (live && temperature == 0.f) {
     // ---- greedy: the largest logit, the lowest index on exact ties
     float bv = -INFINITY;
     int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += NT) {
-      const float v = l1(i);
+    for (int i = tid; i < N; i += NT) {
+      if (!ok(i)) continue;
+      const float v = l1(tk(i));
       if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     }
     const float m = block_max_256(bv, redf);
-    tok = block_min_int(bv == m ? bi : 0x7fffffff, redi);
-    if (tok >= V) tok = 0;                                         // (a row of NaNs)
+    sel = block_min_int(bv == m ? bi : 0x7fffffff, redi);
+    if (sel >= N) sel = first_ok;                                  // (a row of NaNs)
     kept = 1;
   } else if (live) {
     // ---- pass 1, 2: max, e_i, Z
     float mx = -INFINITY;
-    for (int i = tid; i < V; i += NT) mx = fmaxf(mx, l1(i));
+    for (int i = tid; i < N; i += NT)
+      if (ok(i)) mx = fmaxf(mx, l1(tk(i)));
     const float m = block_max_256(mx, redf);
     float z = 0.f;
-    for (int i = tid; i < V; i += NT) {
-      const float e = __expf((l1(i) - m) / temperature);
-      if (row_in_lds) erow[i] = e;
+    for (int i = tid; i < N; i += NT) {
+      const float e = ok(i) ? __expf((l1(tk(i)) - m) / temperature) : 0.f;
+      if (use_lds) erow[i] = e;
       z += e;
     }
     const float Z = block_sum_256(z, redf);                        // (its barriers also publish erow)
-    auto pe = [&](int i) -> float { return row_in_lds ? erow[i] : __expf((l1(i) - m) / temperature); };
+    // (an element without ok() has e = 0: no `> t` test below sees it, and every `== t` test asks ok() as well)
+    auto pe = [&](int i) -> float {
+      return use_lds ? erow[i] : (ok(i) ? __expf((l1(tk(i)) - m) / temperature) : 0.f);
+    };
     // ---- EX, top-k: the smallest t with C(t) <= k - 1 is the value at rank k
     float Zk = Z;
     unsigned tkb = 0u;
     int tie_k = 0;
-    const bool cut_k = EX && top_k >= 1 && top_k < V;
+    const bool cut_k = EX && top_k >= 1 && top_k < n_ok;
     if constexpr (EX) {
       if (cut_k) {
         unsigned lo = 0u, hi = 0x3f800000u;                        // C(bits(1.0f)) = 0
         while (lo < hi) {
           const unsigned mid = lo + ((hi - lo) >> 1);
           int c = 0;
-          for (int i = tid; i < V; i += NT) c += __float_as_uint(pe(i)) > mid ? 1 : 0;
+          for (int i = tid; i < N; i += NT) c += __float_as_uint(pe(i)) > mid ? 1 : 0;
           c = block_sum_int(c, redi);
           if (c < top_k) hi = mid; else lo = mid + 1u;
         }
         tkb = lo;
         float g = 0.f;
         int c = 0;
-        for (int i = tid; i < V; i += NT) {
+        for (int i = tid; i < N; i += NT) {
           const float e = pe(i);
           const bool over = __float_as_uint(e) > tkb;
           g += over ? e : 0.f;
@@ -213,7 +283,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     while (lo < hi) {
       const unsigned mid = lo + ((hi - lo) >> 1);
       float g = 0.f;
-      for (int i = tid; i < V; i += NT) {
+      for (int i = tid; i < N; i += NT) {
         const float e = pe(i);
         g += __float_as_uint(e) > mid ? e : 0.f;
       }
@@ -224,12 +294,12 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     const float tf = __uint_as_float(tb);
     float g = 0.f;
     int n_gt = 0, n_eq = 0;
-    for (int i = tid; i < V; i += NT) {
+    for (int i = tid; i < N; i += NT) {
       const float e = pe(i);
       const unsigned eb = __float_as_uint(e);
       g += eb > tb ? e : 0.f;
       n_gt += eb > tb ? 1 : 0;
-      n_eq += eb == tb ? 1 : 0;
+      n_eq += (eb == tb && ok(i)) ? 1 : 0;
     }
     g = block_sum_256(g, redf);
     n_gt = block_sum_int(n_gt, redi);
@@ -246,17 +316,17 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       kept = top_k;
     }
     // ---- the walk, in index order over contiguous ranges
-    const int chunk = (V + NT - 1) / NT;
-    const int i0 = min(V, tid * chunk), i1 = min(V, i0 + chunk);
+    const int chunk = (N + NT - 1) / NT;
+    const int i0 = min(N, tid * chunk), i1 = min(N, i0 + chunk);
     int c_eq = 0;
-    for (int i = i0; i < i1; ++i) c_eq += __float_as_uint(pe(i)) == tb ? 1 : 0;
+    for (int i = i0; i < i1; ++i) c_eq += (__float_as_uint(pe(i)) == tb && ok(i)) ? 1 : 0;
     const int rank0 = block_scan_i(c_eq, wtoti);
     float mass = 0.f;
     int rank = rank0, last = -1;
     for (int i = i0; i < i1; ++i) {
       const float e = pe(i);
       const unsigned eb = __float_as_uint(e);
-      const bool k = eb > tb || (eb == tb && rank++ < n_tie);
+      const bool k = eb > tb || (eb == tb && ok(i) && rank++ < n_tie);
       if (k) { mass += e; last = i; }
     }
     float M;
@@ -268,7 +338,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     for (int i = i0; i < i1; ++i) {
       const float e = pe(i);
       const unsigned eb = __float_as_uint(e);
-      const bool k = eb > tb || (eb == tb && rank++ < n_tie);
+      const bool k = eb > tb || (eb == tb && ok(i) && rank++ < n_tie);
       if (k) {
         run += e;
         if (run > target && cand == 0x7fffffff) cand = i;
@@ -276,7 +346,17 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     }
     cand = block_min_int(cand, redi);
     last = block_max_int(last, redi);
-    tok = cand < V ? cand : (last >= 0 ? last : 0);
+    sel = cand < N ? cand : (last >= 0 ? last : first_ok);         // (u * M rounded up to M: the last KEPT element)
+  }
+  int child = -1;
+  if (live) {
+    tok = tk(sel);
+    if constexpr (TRIE) {
+      if (cons) {
+        child = ec[sel];
+        if (child < 0 || child >= tr.n_nodes) child = tr.n_nodes;  // (a broken trie: the row ends at its next step)
+      }
+    }
   }
 
   // ---- step the row
@@ -302,6 +382,9 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     if (pos64) pos64[b] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
     token_out[b] = tok;
     n_kept_out[b] = kept;
+    if constexpr (TRIE) {
+      if (live && cons) tr.node[b] = child;
+    }
     if constexpr (EX) logprob_out[b] = live ? lg[tok] - lse : 0.f;
     unsigned* ticket = EX ? counter : &g_ticket;
     const unsigned old = atomicAdd(ticket, 1u + (now_done ? 0u : 0x10000u));
@@ -333,10 +416,10 @@ struct ExArgs {
 };
 constexpr size_t BITMAP_LDS_MAX = ROW_LDS_MAX / 32;                // the bitmap of the largest row that lives in LDS
 
-template <typename T, bool EX>
+template <typename T, bool EX, bool TRIE>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
            int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
-           int64_t* pos64, int B, int V, int D, int S, ExArgs ex, hipStream_t st) {
+           int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st) {
   const size_t row_bytes = (size_t)V * sizeof(float);
   const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
   size_t lds = in_lds ? row_bytes : 0;
@@ -347,24 +430,25 @@ int launch(const float* logits, const float* u, const void* emb, float temperatu
   }
   static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
   if (fvqa_attr_needed(attr_done))
-    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
   const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-  hipLaunchKernelGGL((decode_next_k<T, EX>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p, eos_id,
-                     stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16,
-                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter);
+  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p,
+                     eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16,
+                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
 
-// the operand checks both entries share; then the launch
-template <bool EX>
+// the operand checks the entries share; then the launch
+template <bool EX, bool TRIE = false>
 int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
                    int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
                    int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
-                   void* stream) {
+                   void* stream, TrieArgs tr = TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
   if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
   if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
+  if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
   if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
@@ -372,15 +456,17 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
   if (temperature > 0.f && !u) return FVQA_EINVAL;
   if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
+  if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
-      !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter))
+      !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter) ||
+      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FVQA_H16)
-    return launch<bf16_t, EX>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
-                              n_active, pos64, n_seq, vocab, dim, seq_len, ex, st);
-  return launch<float, EX>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
-                           n_active, pos64, n_seq, vocab, dim, seq_len, ex, st);
+    return launch<bf16_t, EX, TRIE>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
+                                    n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st);
+  return launch<float, EX, TRIE>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
+                                 n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st);
 }
 
 }  // namespace
@@ -402,4 +488,17 @@ extern "C" int fvqa_decode_next_ex(const float* logits, const float* u, const vo
   return checked_launch<true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
                               n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
                               ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream);
+}
+
+extern "C" int fvqa_decode_next_trie(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                     int top_k, float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids,
+                                     int32_t* pos, int32_t* done, const int32_t* gen_start, void* x_next, int32_t* token,
+                                     int32_t* n_kept, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
+                                     int32_t* node, const int32_t* node_first, const int32_t* edge_token,
+                                     const int32_t* edge_child, int n_nodes, int n_edges, int n_seq, int vocab, int dim,
+                                     int seq_len, int dtype, void* stream) {
+  return checked_launch<true, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
+                                    n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
+                                    ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream,
+                                    TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges});
 }

@@ -15,7 +15,7 @@ from typing import List, Tuple
 
 import torch
 
-from . import ops
+from . import constrain, ops
 
 N_NEW = 31          # reference llama/model.py:438: positions prefix-1 .. prefix+29
 
@@ -137,7 +137,8 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
 @torch.no_grad()
 def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
              stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
-             repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1) -> dict:
+             repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
+             constraints=None) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -164,7 +165,17 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         its cache rows and the adapter rows are fanned out to n rows per sample (ops.kv_beam_move into beam search's cache, one
         launch; samples never change parent, so nothing moves per token) and the token loop runs on B * n rows; the uniforms
         are one torch.rand(max_new_tokens, B * n). The results gain a sample axis: "ids" (B, n, S), "n_generated" (B, n),
-        "tokens" / "logprobs" (B, n, steps), "sum_logprob" (B, n)."""
+        "tokens" / "logprobs" (B, n, steps), "sum_logprob" (B, n).
+    constraints (None: every code path above runs untouched): the set of allowed answers — a fvqa.constrain.TokenTrie, or raw
+      token sequences (one list for the batch, or one list per sample) that are compiled here. Every token step may only continue
+      a prefix of an allowed answer, and only the EOS ends one: greedy and sampled rows are members of the set by construction,
+      and beam search with num_beams >= the number of members returns the most likely member under the model (length_penalty 1:
+      by the mean log-probability of its tokens, the multiple-choice criterion). The token step goes through
+      ops.decode_next_trie / ops.beam_step_trie, still one launch (include/fvqa.h states the rule); all other keywords keep
+      their meaning, with "every token" read as "every allowed token". The results gain "choice": the index of the generated
+      member in its sample's list, (B,) — (B, n) with num_return_sequences = n; under beam search the best hypothesis' and
+      "beams"["choice"] (B, K) —, -1 for a row that ended before a leaf. ValueError: stop_at_eos=False (a leaf is reached by
+      the EOS), a member (EOS included) longer than max_new_tokens, a member that does not fit behind its prompt inside S."""
     if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
     if num_beams > 1 and temperature > 0:
@@ -180,9 +191,11 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if num_beams > 1 and ex:
         raise ValueError("generate: top_k, repetition_penalty, return_logprobs and num_return_sequences belong to "
                          "num_beams == 1 (beam search reports \"score\")")
+    trie = None if constraints is None else _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
     if num_beams > 1 or _BEAM_PATH_AT_ONE:
+        kw = {} if trie is None else {"constraints": trie}
         return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
-                           length_penalty=float(length_penalty))
+                           length_penalty=float(length_penalty), **kw)
     m, pk = eng.model, eng.pack
     dev = eng.device
     if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
@@ -228,10 +241,13 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         tokens = torch.full((max_new_tokens, B), -1, dtype=torch.int32, device=dev)
         n_kept = torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev)
         n_active = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev)
-        if ex:
+        if ex or trie is not None:
             gen_start = prefix.to(torch.int32)
             logprobs = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
             counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        if trie is not None:                                # every row starts at its sample's root (n rows per sample: repeated)
+            dtrie = trie.to(dev)
+            node = torch.as_tensor(trie.roots(B0), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
         u = None
         if temperature > 0:
             gen = None
@@ -247,7 +263,13 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                 arrived[t - 2].synchronize()
                 if int(running[t - 2]) == 0:
                     break
-            if ex:
+            if trie is not None:
+                ops.decode_next_trie(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
+                                     n_active[t:t + 1], counter, node, dtrie, u=None if u is None else u[t], pos64=pos64,
+                                     temperature=temperature, top_p=top_p, top_k=int(top_k),
+                                     repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
+                                     stop_at_eos=stop_at_eos)
+            elif ex:
                 ops.decode_next_ex(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
                                    n_active[t:t + 1], counter, u=None if u is None else u[t], pos64=pos64,
                                    temperature=temperature, top_p=top_p, top_k=int(top_k),
@@ -290,7 +312,33 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
             for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob"):
                 if k in out:
                     out[k] = out[k].view(B0, n, *out[k].shape[1:])
+        if trie is not None:
+            out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
         return out
+
+
+def _compiled(eng, data: dict, constraints, stop_at_eos: bool, max_new_tokens: int):
+    """generate's `constraints` -> the host TokenTrie, after the three checks that need no device."""
+    if not stop_at_eos:
+        raise ValueError("generate: constraints end an answer by its EOS: stop_at_eos=False cannot be served")
+    if isinstance(constraints, constrain.TokenTrie):
+        trie = constraints.host()
+    else:
+        trie = constrain.TokenTrie.from_sequences(constraints, eng.model.tokenizer.eos_id, eng.V)
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+    prefix = [int(p) for p in data["prefix_index"]["vqa"]]
+    S = int(data["text_id"]["vqa"].shape[2])
+    trie.roots(len(prefix))                                 # (a per-sample set built for another batch size)
+    longest = trie.max_len * len(prefix) if trie.shared else trie.max_len
+    if max(longest) > max_new_tokens:
+        raise ValueError(f"generate: an allowed answer takes {max(longest)} tokens with its EOS, max_new_tokens = {max_new_tokens}")
+    for b, (p, n_tok) in enumerate(zip(prefix, longest)):
+        if p + n_tok > S:
+            raise ValueError(f"generate: sample {b}: an allowed answer of {n_tok} tokens (EOS included) does not fit behind "
+                             f"the prompt of {p} tokens inside max_seq_len = {S}")
+    return trie
 
 
 _BEAM_PATH_AT_ONE = False   # (tests) send num_beams == 1 through beam_search too: K = 1 must reproduce the greedy ids
@@ -298,7 +346,7 @@ _BEAM_PATH_AT_ONE = False   # (tests) send num_beams == 1 through beam_search to
 
 @torch.no_grad()
 def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bool = True, num_beams: int,
-                length_penalty: float = 0.0, early_stop: bool = True) -> dict:
+                length_penalty: float = 0.0, early_stop: bool = True, constraints=None) -> dict:
     """The most likely answers under the model: K = num_beams slots per sample, every token step ranks the K * V continuations
     of a sample and keeps the K best (include/fvqa.h fvqa_beam_step states the rule; a slot's score is the fp32 sum of the
     log-probabilities of its generated tokens, the EOS included; finished slots are carried and compete with their score).
@@ -311,7 +359,11 @@ def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bo
     that have any unfinished slot (length_penalty != 0). The penalty only ranks the final slots: score / n_generated ** penalty,
     the lowest slot on ties; it never enters the search. early_stop=False runs all max_new_tokens steps.
     -> generate's keys for the best hypothesis, "score" (B,) fp32, "beams": {"ids" (B, K, S), "score" (B, K), "n_generated"
-    (B, K), "done" (B, K)} in slot order, and per step "parents" / "step_tokens" (steps, B, K) int32 (token -1: carried)."""
+    (B, K), "done" (B, K)} in slot order, and per step "parents" / "step_tokens" (steps, B, K) int32 (token -1: carried).
+    constraints (generate's keyword; None: nothing changes): every slot carries its trie node through ops.beam_step_trie and
+    offers its allowed tokens only. The stop then always waits for every slot (as with length_penalty != 0): the slots are the
+    ranking of the allowed set, and with num_beams >= the number of members the finite final slots are exactly the members.
+    The results gain "choice" (B,) and "beams"["choice"] (B, K)."""
     m, pk = eng.model, eng.pack
     dev = eng.device
     K = int(num_beams)
@@ -320,6 +372,7 @@ def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bo
                          "reference llama/model.py:381)")
     if max_new_tokens < 1 or not 1 <= K <= ops.BEAMS_MAX:
         raise ValueError(f"beam_search: max_new_tokens >= 1, 1 <= num_beams <= {ops.BEAMS_MAX}")
+    trie = None if constraints is None else _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
     ids_all = data["text_id"]["vqa"]
     B, _, S = ids_all.shape
     N = B * K
@@ -358,14 +411,22 @@ def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bo
         running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
         arrived = []
         steps, cur = 0, 0
+        if trie is not None:                                # every slot starts at its sample's root
+            dtrie = trie.to(dev)
+            node = torch.as_tensor(trie.roots(B), dtype=torch.int32).repeat_interleave(K).to(dev).contiguous()
         for t in range(max_new_tokens):
             if t >= 2 and early_stop:                       # the count of step t - 2 left the device a whole step ago
                 arrived[t - 2].synchronize()
                 if int(running[t - 2]) == 0:
                     break
-            ops.beam_step(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t], tokens[t],
-                          xin, n_active[t:t + 1], counter, num_beams=K, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos,
-                          count_any_live=length_penalty != 0)
+            if trie is not None:
+                ops.beam_step_trie(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t],
+                                   tokens[t], xin, n_active[t:t + 1], counter, node, dtrie, num_beams=K,
+                                   eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos, count_any_live=True)
+            else:
+                ops.beam_step(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t],
+                              tokens[t], xin, n_active[t:t + 1], counter, num_beams=K, eos_id=m.tokenizer.eos_id,
+                              stop_at_eos=stop_at_eos, count_any_live=length_penalty != 0)
             cur = 1 - cur
             running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
             ev = torch.cuda.Event()
@@ -404,10 +465,17 @@ def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bo
         col = torch.arange(steps, device=dev).unsqueeze(0)
         tok_best = ids[rows, best].gather(1, (prefix64.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
         tok_best = torch.where(col < n_best.unsqueeze(1), tok_best, torch.full_like(tok_best, -1))
-        return {"ids": ids[rows, best].contiguous(), "n_generated": n_best, "steps": steps, "tokens": tok_best,
-                "score": score[rows, best].clone(),
-                "beams": {"ids": ids.clone(), "score": score.clone(), "n_generated": n_gen, "done": done.view(B, K).clone()},
-                "parents": parents[:steps].view(steps, B, K).clone(), "step_tokens": tokens[:steps].view(steps, B, K).clone()}
+        out = {"ids": ids[rows, best].contiguous(), "n_generated": n_best, "steps": steps, "tokens": tok_best,
+               "score": score[rows, best].clone(),
+               "beams": {"ids": ids.clone(), "score": score.clone(), "n_generated": n_gen, "done": done.view(B, K).clone()},
+               "parents": parents[:steps].view(steps, B, K).clone(), "step_tokens": tokens[:steps].view(steps, B, K).clone()}
+        if trie is not None:                                # each slot's tokens, read back from its id row
+            tok_all = ids.gather(2, (prefix64.view(B, 1, 1) + col.unsqueeze(0)).clamp(max=S - 1).expand(B, K, steps))
+            tok_all = torch.where(col.unsqueeze(0) < n_gen.unsqueeze(2), tok_all, torch.full_like(tok_all, -1))
+            choice = torch.as_tensor(constrain.choice_of(trie, tok_all), device=dev)
+            out["beams"]["choice"] = choice
+            out["choice"] = choice[rows, best]
+        return out
 
 
 def _beam_cache(eng, N: int, S: int, W: int) -> dict:

@@ -660,6 +660,49 @@ def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept
     return token
 
 
+def _trie_arrays(trie, what: str):
+    """The device arrays of a compiled constraint (fvqa.constrain.TokenTrie.to(device), or any object with node_first,
+    edge_token, edge_child int32 tensors) -> (node_first, edge_token, edge_child, n_nodes, n_edges)."""
+    nf, et, ec = trie.node_first, trie.edge_token, trie.edge_child
+    for t in (nf, et, ec):
+        _need(torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(),
+              f"{what}: node_first, edge_token, edge_child are contiguous int32 vectors")
+    _need(nf.numel() >= 2 and et.numel() == ec.numel(), f"{what}: node_first (n_nodes + 1,), edge_token / edge_child (n_edges,)")
+    return nf, et, ec, nf.numel() - 1, et.numel()
+
+
+def decode_next_trie(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, node, trie, *,
+                     u=None, pos64=None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
+                     repetition_penalty: float = 1.0, eos_id: int = 2, stop_at_eos: bool = True):
+    """decode_next_ex under a trie of allowed answers (include/fvqa.h fvqa_decode_next_trie states the rule). On top of
+    decode_next_ex's operands: node (B,) int32, in and out — the trie node of each row, -1: unconstrained —, and `trie`, a
+    fvqa.constrain.TokenTrie on the device (node_first / edge_token / edge_child int32)."""
+    nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_trie")
+    _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, u, pos64, node, nf, et, ec)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_trie: logits (B, V) fp32")
+    B, V = logits.shape
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_trie: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B, D), "decode_next_trie: x_next (B, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_trie: ids (B, S) int64")
+    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (node, B), (n_active, 1), (counter, 1)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_trie: pos / done / gen_start / token / n_kept / node (B,), "
+                                                         "n_active / counter (1,) int32")
+    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_trie: logprob (B,) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_trie: pos64 (B,) int64")
+    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
+          "decode_next_trie: sampling needs u (B,) fp32")
+    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_trie: top_k >= 0, repetition_penalty >= 1")
+    rc = _lib.load(emb.dtype).fvqa_decode_next_trie(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p),
+                                                    int(top_k), float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0,
+                                                    _ptr(ids), _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token),
+                                                    _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64),
+                                                    _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D,
+                                                    ids.shape[1], dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_decode_next_trie")
+    return token
+
+
 BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
 
 
@@ -691,6 +734,39 @@ def beam_step(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64
                                              _ptr(n_active), _ptr(counter), N // K, K, V, D, ids_in.shape[1], dt_code(emb.dtype),
                                              _stream())
     _lib.check(rc, "fvqa_beam_step")
+    return parent, token
+
+
+def beam_step_trie(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter,
+                   node, trie, *, num_beams: int, eos_id: int = 2, stop_at_eos: bool = True, count_any_live: bool = False):
+    """beam_step under a trie of allowed answers (include/fvqa.h fvqa_beam_step_trie): on top of beam_step's operands node
+    (B*K,) int32, in and out — each slot's trie node, -1: unconstrained —, and `trie` as decode_next_trie takes it."""
+    nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "beam_step_trie")
+    _dev(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter, node, nf, et,
+         ec)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "beam_step_trie: logits (B*K, V) fp32")
+    N, V = logits.shape
+    K = int(num_beams)
+    _need(1 <= K <= BEAMS_MAX and K <= V and N % K == 0,
+          f"beam_step_trie: 1 <= num_beams <= {BEAMS_MAX}, <= V, rows a multiple of it")
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "beam_step_trie: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (N, D), "beam_step_trie: x_next (B*K, D)")
+    _need(ids_in.dim() == 2 and ids_in.shape[0] == N and ids_in.dtype == torch.int64 and ids_out.dtype == torch.int64
+          and ids_out.shape == ids_in.shape and ids_in.data_ptr() != ids_out.data_ptr(),
+          "beam_step_trie: ids_in, ids_out (B*K, S) int64, two buffers")
+    for t, n in ((pos, N), (done, N), (n_generated, N), (parent, N), (token, N), (node, N), (n_active, 1), (counter, 1)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "beam_step_trie: pos / done / n_generated / parent / token / node "
+                                                         "(B*K,), n_active / counter (1,) int32")
+    _need(score.dtype == torch.float32 and score.numel() == N, "beam_step_trie: score (B*K,) fp32")
+    _need(pos64.dtype == torch.int64 and pos64.numel() == N, "beam_step_trie: pos64 (B*K,) int64")
+    rc = _lib.load(emb.dtype).fvqa_beam_step_trie(_ptr(logits), _ptr(emb), int(eos_id), 1 if stop_at_eos else 0,
+                                                  1 if count_any_live else 0, _ptr(ids_in), _ptr(ids_out), _ptr(pos),
+                                                  _ptr(score), _ptr(done), _ptr(n_generated), _ptr(pos64), _ptr(parent),
+                                                  _ptr(token), _ptr(x_next), _ptr(n_active), _ptr(counter), _ptr(node), _ptr(nf),
+                                                  _ptr(et), _ptr(ec), n_nodes, n_edges, N // K, K, V, D, ids_in.shape[1],
+                                                  dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_beam_step_trie")
     return parent, token
 
 

@@ -232,6 +232,9 @@ class Transformer(nn.Module):
         -> (most_similar_indices (B,), extracted_answers list of dicts). KV-cached, batched: fvqa/generate.py."""
         from fvqa import generate
         eng = self.ensure_engine()
+        mode = getattr(self.args, "gen_constrain", None)
+        if mode:                                            # --gen_constrain: decode under the allowed answers
+            return self._constrained_inference(data, mode)
         if int(getattr(self.args, "num_beams", 1) or 1) > 1:    # --num_beams N: the most likely answer under the model
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
                                     num_beams=int(self.args.num_beams))
@@ -245,18 +248,51 @@ class Transformer(nn.Module):
         self.last_generation = {"ids": ids, "similarities": sims}
         return best, extracted
 
+    def _constrained_inference(self, data, mode):
+        """--gen_constrain options | vocab: every sample decodes under its own answer options (-> best = the index of the option
+        generated; a row that completed none falls back to the cosine pick) or under the shared answers of --answer_vocab (the
+        cosine pick then ranks the options against an answer of that vocabulary). --num_beams applies as before; each row ends
+        at its EOS. `last_generation` gains "choice"."""
+        from fvqa import constrain, generate
+        eng = self.ensure_engine()
+        if mode == "options":
+            S = data["text_id"]["vqa"].shape[2]             # (an option cut off by the end of the row keeps room for its EOS)
+            cons = [[o[: max(S - int(p) - 1, 0)] for o in opts]
+                    for opts, p in zip(constrain.options_of(data, self.tokenizer), data["prefix_index"]["vqa"])]
+            trie = constrain.TokenTrie.from_sequences(cons, self.tokenizer.eos_id, eng.V)
+        elif mode == "vocab":
+            trie = getattr(self, "_answer_vocab_trie", None)
+            if trie is None:
+                path = getattr(self.args, "answer_vocab", None)
+                if not path:
+                    raise ValueError("--gen_constrain vocab needs --answer_vocab FILE")
+                answers = constrain.read_answer_vocab(path)
+                trie = constrain.TokenTrie.from_sequences(constrain.encode_answers(self.tokenizer, answers),
+                                                          self.tokenizer.eos_id, eng.V)
+                self._answer_vocab_trie = trie
+        else:
+            raise ValueError(f"gen_constrain: 'options' or 'vocab', not {mode!r}")
+        out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)), temperature=0.0,
+                                stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie)
+        ids, choice = out["ids"], out["choice"]
+        best, sims, extracted = generate.match_answers(self, data, ids)
+        if mode == "options":
+            best = torch.where(choice >= 0, choice.to(best.dtype), best)
+        self.last_generation = {"ids": ids, "similarities": sims, "choice": choice}
+        return best, extracted
+
     @torch.no_grad()
     def generate(self, data, **kw):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
-        return_logprobs, num_return_sequences) -> one answer per row, the
+        return_logprobs, num_return_sequences, constraints) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
-        "sum_logprob"). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        "sum_logprob"; with constraints "choice", the index of each answer in the allowed set). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
-        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob")
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice")
                                 if k in out}
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
 

@@ -71,6 +71,11 @@ _FLAGS = [
                                                       "sample stops at its EOS and the batch stops when every sample has")),
     ("--num_beams", dict(type=int, default=1, help="generation-task validation: beam search with N slots per sample "
                                                    "(fvqa.generate.beam_search; 1: the decode chosen by --gen_stop_eos)")),
+    ("--gen_constrain", dict(type=str, choices=["options", "vocab"], default=None,
+                             help="generation-task validation decodes under a set of allowed answers (fvqa.generate.generate("
+                                  "constraints=...)): 'options' — the sample's own answer options, the prediction is the option "
+                                  "generated; 'vocab' — the shared answers of --answer_vocab. --num_beams applies as before")),
+    ("--answer_vocab", dict(type=str, default=None, help="a file with one allowed answer per line (needed by --gen_constrain vocab)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -79,8 +84,18 @@ _FLAGS = [
 ]
 
 
+class ArgumentParser(argparse.ArgumentParser):
+    """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file (answer.py uses it too)."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if getattr(a, "gen_constrain", None) == "vocab" and not getattr(a, "answer_vocab", None):
+            self.error("--gen_constrain vocab needs --answer_vocab FILE (one answer per line)")
+        return a
+
+
 def get_args_parser():
-    parser = argparse.ArgumentParser("Flipped-VQA training (MI355X)", add_help=False)
+    parser = ArgumentParser("Flipped-VQA training (MI355X)", add_help=False)
     for flag, kw in _FLAGS:
         parser.add_argument(flag, **kw)
     parser.set_defaults(pin_mem=True)

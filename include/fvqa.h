@@ -310,6 +310,36 @@ int fvqa_decode_next_ex(const float* logits, const float* u, const void* emb, fl
                         const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
                         int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
                         int dtype, void* stream);
+/* fvqa_decode_next_ex under a trie of allowed answers (the same kernel template in csrc/sample.hip; generate(constraints=...);
+ * fvqa/constrain.py builds the arrays). The operands, the row stepping and the errors of fvqa_decode_next_ex hold; in addition:
+ * node (n_seq) int32, in and out — the trie node each row stands at, -1 for an unconstrained row —, and the trie in CSR form,
+ * int32 device arrays that are only read: node_first (n_nodes + 1) edge offsets, edge_token (n_edges), edge_child (n_edges);
+ * the edges of a node carry distinct tokens in ascending order, so that list order is the index order of rules 3 and 4.
+ * Per live row:
+ *   - node == -1: fvqa_decode_next_ex's rule, unchanged (every node -1: its results bit for bit).
+ *   - 0 <= node < n_nodes: the row's vocabulary is the tokens on the edges of its node; an edge whose token lies outside
+ *     [0, vocab) is skipped. Rules 1-4 hold with "every token" read as "every allowed token": the penalty applies to allowed
+ *     tokens in R, the maximum that is subtracted is the largest allowed l1, Z sums the allowed e, k = min(top_k, number
+ *     allowed) when top_k >= 1, Z_k is the mass of the first k allowed tokens in the order (e descending, token ascending), the
+ *     walk runs over the kept tokens in token order, n_kept <= the number allowed. A token that is not allowed is never kept and
+ *     never returned — not when it would tie at e == 0 with allowed tokens whose e underflowed, not when u * M rounds up to M
+ *     (the last KEPT token is returned), not when top_k exceeds the number allowed (the cut is then off).
+ *     Rule 5 is unchanged: logprob is taken on the raw WHOLE row — the model's own log-probability, what fvqa_beam_step sums.
+ *     After the pick node = the child of the edge taken.
+ *   - a live row whose node has no (usable) edge, or whose node lies outside [-1, n_nodes): picks nothing and becomes done, as
+ *     a row with no room does (token -1, n_kept 0, logprob 0; ids, pos and node are not written).
+ * A row that picks nothing keeps its node. No index read from the trie leads outside the arrays: an edge range is clamped into
+ * [0, n_edges], and a child outside [0, n_nodes) is stored as n_nodes, which ends the row at its next step.
+ * The method: the passes of a constrained row run over its node's edge list in place of the vocabulary, with the same fixed
+ * summation orders; one launch, no float atomics, the caller-owned ticket word.
+ * FVQA_EINVAL also for a null node / node_first / edge_token / edge_child; FVQA_ESHAPE also for n_nodes <= 0 or n_edges < 0;
+ * FVQA_EALIGN also for one of them off its 4-byte boundary. */
+int fvqa_decode_next_trie(const float* logits, const float* u, const void* emb, float temperature, float top_p, int top_k,
+                          float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done,
+                          const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
+                          int32_t* n_active, uint32_t* counter, int64_t* pos64, int32_t* node, const int32_t* node_first,
+                          const int32_t* edge_token, const int32_t* edge_child, int n_nodes, int n_edges, int n_seq, int vocab,
+                          int dim, int seq_len, int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)
@@ -333,6 +363,27 @@ int fvqa_beam_step(const float* logits, const void* emb, int eos_id, int stop_at
                    const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done, int32_t* n_generated,
                    int64_t* pos64, int32_t* parent, int32_t* token, void* x_next, int32_t* n_active, uint32_t* counter,
                    int n_samples, int n_beams, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* fvqa_beam_step under a trie of allowed answers (the same kernel template in csrc/beam.hip; generate(num_beams > 1,
+ * constraints=...)). The operands, limits and errors of fvqa_beam_step hold; in addition node (n_samples*K) int32, in and out,
+ * per slot, and the trie of fvqa_decode_next_trie. The rule of fvqa_beam_step with these changes:
+ *   - a live slot j at a node in [0, n_nodes) offers (j, v) only for the tokens v on the edges of its node (tokens outside
+ *     [0, vocab) skipped), of value score[j] + (l[j,v] - lse[j]); lse is over the whole raw row, unchanged;
+ *   - a slot with node == -1 offers every v;
+ *   - a done slot, a slot with no room, and a live slot whose node has no usable edge or lies outside [-1, n_nodes) — which
+ *     becomes done first — each offer their one carried candidate;
+ *   - slots with score -inf offer their allowed tokens at -inf, as they offer everything in fvqa_beam_step;
+ *   - a new slot takes the child of the edge (parent, token) it was made from, a carried slot keeps its parent's node; all K old
+ *     nodes are read before any is written. A child outside [0, n_nodes) is stored as n_nodes (the slot is done at its next step).
+ * The order (value descending, parent ascending, token ascending), the count and everything else are fvqa_beam_step's; with
+ * every node -1 its results bit for bit.
+ * FVQA_EINVAL also for a null node / node_first / edge_token / edge_child; FVQA_ESHAPE also for n_nodes <= 0 or n_edges < 0;
+ * FVQA_EALIGN also for one of them off its 4-byte boundary. */
+int fvqa_beam_step_trie(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
+                        const int64_t* ids_in, int64_t* ids_out, int32_t* pos, float* score, int32_t* done,
+                        int32_t* n_generated, int64_t* pos64, int32_t* parent, int32_t* token, void* x_next, int32_t* n_active,
+                        uint32_t* counter, int32_t* node, const int32_t* node_first, const int32_t* edge_token,
+                        const int32_t* edge_child, int n_nodes, int n_edges, int n_samples, int n_beams, int vocab, int dim,
+                        int seq_len, int dtype, void* stream);
 /* Cached keys and values follow the beams (csrc/beam.hip). dst: (n_layers, n_dst_seq*seq_len + adapter_len, 3*dim), src:
  * (n_layers, n_src_seq*seq_len + adapter_len, 3*dim) — the layout fvqa_attn_decode takes, every layer, uniform layer stride.
  * For destination sequence n, the k and v thirds of rows [lo[n], hi[n]) (clamped to [0, seq_len)) are copied from source sequence
