@@ -45,6 +45,19 @@
 // against the NUMBER ALLOWED, and the walk falls back to the last kept (or, on a row of NaNs, the first allowed) edge. Every
 // index read from the trie is clamped before it is used: the edge range into [0, n_edges], the child into [0, n_nodes) (else
 // the row is sent to the node n_nodes, which ends it at the next step). A row at node == -1 runs the loops over V as before.
+//
+// fvqa_decode_next_pair is the template with PAIR = true (false in the three entries above, in which none of the following
+// exists), with and without TRIE: contrastive decoding against a twin row. A workgroup owns a PAIR of rows — b, the positive
+// one (the prompt with its clip), and b + n_seq, the negative one (the same ids with the twin's features) — and n_seq counts
+// pairs. With lp = l - lse(l) over the whole raw row:
+//   P        the plausible set: the allowed tokens (the vocabulary, or the usable edges of the pair's node) whose l+ lies within
+//            logf(beta) of the largest allowed l+. ok() asks for it as well, so a token outside P takes no part anywhere, just
+//            as an edge outside [0, V) takes none; n_ok = |P| is what top-k is cut against.
+//   c        c_i = l+_i + alpha * (lp+_i - lp-_i), computed inside l1() wherever a logit is read: no row of c exists, LDS holds
+//            one row of e_i and the bitmap as before, and a row beyond LDS re-reads BOTH rows per pass. alpha == 0, or twin rows
+//            of the same bits (whose two lse then have the same bits too), give c_i = l+_i + 0 = l+_i bit for bit.
+//   step     pos and done are read from the positive row; the token, pos, done, pos64 and x_next are written to both rows, so
+//            the two caches stay in step. logprob stays lp+ of the token; the ticket counts pairs.
 #include "common.h"
 
 namespace {
@@ -126,7 +139,13 @@ struct TrieArgs {
   int n_nodes, n_edges;
 };
 
-template <typename T, bool EX, bool TRIE>
+// the operands fvqa_decode_next_pair adds (PAIR = true)
+struct PairArgs {
+  float alpha, beta;
+  int32_t* n_plausible;
+};
+
+template <typename T, bool EX, bool TRIE, bool PAIR>
 __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
                                                     const T* __restrict__ emb, float temperature, float top_p, int eos_id,
                                                     int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
@@ -136,13 +155,15 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
                                                     int D, int S, int row_in_lds, int vec16, int top_k, float rep,
                                                     const int32_t* __restrict__ gen_start,
                                                     float* __restrict__ logprob_out, unsigned* __restrict__ counter,
-                                                    TrieArgs tr) {
+                                                    TrieArgs tr, PairArgs pr) {
   static_assert(EX || !TRIE, "the trie entry extends the EX entry");
+  static_assert(EX || !PAIR, "the pair entry extends the EX entry");
   extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX)
   __shared__ float redf[4], wtotf[4];
   __shared__ int redi[4], wtoti[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* lg = logits + (size_t)b * V;
+  const float* lgn = PAIR ? logits + ((size_t)b + B) * V : nullptr;   // the twin's row (B pairs: rows b and b + B)
   int p = pos[b];
   // a finished row, and one with no room for another token (the reference would index past the end), pick nothing
   bool live = done[b] == 0 && p >= -1 && p + 1 < S;
@@ -175,26 +196,52 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       if (n_ok == 0) live = false;                                 // no children (or a node outside the trie): the row ends
     }
   }
-  auto ok = [&](int i) -> bool {                                   // element i takes part (always, without a trie)
+  auto ok0 = [&](int i) -> bool {                                  // element i is allowed (always, without a trie)
     if constexpr (TRIE) {
       if (cons) return (unsigned)et[i] < (unsigned)V;
     }
     return true;
   };
-  auto tk = [&](int i) -> int {                                    // the token of element i (ok(i) holds)
+  auto tk = [&](int i) -> int {                                    // the token of element i (ok0(i) holds)
     if constexpr (TRIE) {
       if (cons) return et[i];
     }
     return i;
   };
+  // ---- PAIR: the plausible set P — the allowed elements whose l+ lies within logf(beta) of the largest allowed l+
+  float mxa = 0.f, lbeta = 0.f;
+  int n_plaus = 0;
+  if constexpr (PAIR) {
+    if (live) {
+      lbeta = logf(pr.beta);                                       // (beta == 0: -inf, every finite logit passes)
+      float mx = -INFINITY;
+      for (int i = tid; i < N; i += NT)
+        if (ok0(i)) mx = fmaxf(mx, lg[tk(i)]);
+      mxa = block_max_256(mx, redf);
+      int c = 0, f = 0x7fffffff;
+      for (int i = tid; i < N; i += NT)
+        if (ok0(i) && lg[tk(i)] - mxa >= lbeta) { c += 1; f = min(f, i); }
+      n_ok = n_plaus = block_sum_int(c, redi);
+      first_ok = block_min_int(f, redi);
+      if (n_ok == 0) live = false;                                 // (a row of NaNs: the pair ends, as at a node without edges)
+    }
+  }
+  auto ok = [&](int i) -> bool {                                   // element i takes part: allowed, and (PAIR) inside P
+    if (!ok0(i)) return false;
+    if constexpr (PAIR) return lg[tk(i)] - mxa >= lbeta;
+    return true;
+  };
   const bool use_lds = row_in_lds && (!TRIE || N <= V);            // (a list longer than V: recomputed, never past the row)
 
   // ---- EX: the raw row's lse; the bitmap of the ids generated so far
-  float lse = 0.f;
+  float lse = 0.f, lse_n = 0.f;
   const bool pen = EX && rep != 1.f;
   unsigned* bm = reinterpret_cast<unsigned*>(erow) + (row_in_lds ? ((V + 3) & ~3) : 0);
   if constexpr (EX) {
     if (live) lse = row_lse(lg, V, redf);
+    if constexpr (PAIR) {
+      if (live) lse_n = row_lse(lgn, V, redf);
+    }
     if (live && pen) {
       for (int i = tid; i < ((V + 31) >> 5); i += NT) bm[i] = 0u;
       __syncthreads();
@@ -208,6 +255,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   }
   auto l1 = [&](int i) -> float {                                  // the logit the pick sees
     float v = lg[i];
+    if constexpr (PAIR) v = v + pr.alpha * ((v - lse) - (lgn[i] - lse_n));   // c_i in place of l_i
     if constexpr (EX) {
       if (pen && ((bm[i >> 5] >> (i & 31)) & 1u)) v = v > 0.f ? v / rep : v * rep;
     }
@@ -380,6 +428,13 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     }
     done[b] = now_done;
     if (pos64) pos64[b] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
+    if constexpr (PAIR) {                                          // the twin row is stepped, or left, like the positive one
+      if (live) ids[((size_t)b + B) * S + p] = tok;
+      pos[b + B] = p;
+      done[b + B] = now_done;
+      if (pos64) pos64[b + B] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
+      pr.n_plausible[b] = live ? n_plaus : 0;
+    }
     token_out[b] = tok;
     n_kept_out[b] = kept;
     if constexpr (TRIE) {
@@ -401,8 +456,15 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     const uint4* s4 = reinterpret_cast<const uint4*>(erow_src);
     uint4* d4 = reinterpret_cast<uint4*>(dst);
     for (int i = tid; i < n16; i += NT) d4[i] = s4[i];
+    if constexpr (PAIR) {
+      uint4* e4 = reinterpret_cast<uint4*>(dst + (size_t)B * D);
+      for (int i = tid; i < n16; i += NT) e4[i] = s4[i];
+    }
   } else {
     for (int i = tid; i < D; i += NT) dst[i] = erow_src[i];
+    if constexpr (PAIR) {
+      for (int i = tid; i < D; i += NT) dst[(size_t)B * D + i] = erow_src[i];
+    }
   }
 }
 
@@ -416,10 +478,11 @@ struct ExArgs {
 };
 constexpr size_t BITMAP_LDS_MAX = ROW_LDS_MAX / 32;                // the bitmap of the largest row that lives in LDS
 
-template <typename T, bool EX, bool TRIE>
+template <typename T, bool EX, bool TRIE, bool PAIR = false>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
            int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
-           int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st) {
+           int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st,
+           PairArgs pr = PairArgs{0.f, 0.f, nullptr}) {
   const size_t row_bytes = (size_t)V * sizeof(float);
   const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
   size_t lds = in_lds ? row_bytes : 0;
@@ -430,22 +493,24 @@ int launch(const float* logits, const float* u, const void* emb, float temperatu
   }
   static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
   if (fvqa_attr_needed(attr_done))
-    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
-  const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p,
+  const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);   // (PAIR: the twin half follows B * D
+                                                                                            //  elements on, whole 16-byte rows)
+  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p,
                      eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16,
-                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr);
+                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
 
 // the operand checks the entries share; then the launch
-template <bool EX, bool TRIE = false>
+template <bool EX, bool TRIE = false, bool PAIR = false>
 int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
                    int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
                    int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
-                   void* stream, TrieArgs tr = TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
+                   void* stream, TrieArgs tr = TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0},
+                   PairArgs pr = PairArgs{0.f, 0.f, nullptr}) {
   if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
   if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
   if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
@@ -453,20 +518,22 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
   if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
   if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
   if (EX && (!(ex.rep >= 1.f) || ex.top_k < 0)) return FVQA_EINVAL;
+  if (PAIR && (!pr.n_plausible || !(pr.alpha >= 0.f) || !(pr.beta >= 0.f && pr.beta <= 1.f))) return FVQA_EINVAL;
   if (temperature > 0.f && !u) return FVQA_EINVAL;
   if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
+  if (PAIR && 2 * (int64_t)n_seq > 65535) return FVQA_ESHAPE;      // (n_seq pairs are 2 * n_seq rows of the token loop)
   if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
       !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter) ||
-      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child))
+      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child) || !fvqa_aligned(4, pr.n_plausible))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FVQA_H16)
-    return launch<bf16_t, EX, TRIE>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
-                                    n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st);
-  return launch<float, EX, TRIE>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
-                                 n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st);
+    return launch<bf16_t, EX, TRIE, PAIR>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
+                                          token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr);
+  return launch<float, EX, TRIE, PAIR>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
+                                       n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr);
 }
 
 }  // namespace
@@ -501,4 +568,22 @@ extern "C" int fvqa_decode_next_trie(const float* logits, const float* u, const 
                                     n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
                                     ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream,
                                     TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges});
+}
+
+extern "C" int fvqa_decode_next_pair(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                     int top_k, float repetition_penalty, float alpha, float beta, int eos_id, int stop_at_eos,
+                                     int64_t* ids, int32_t* pos, int32_t* done, const int32_t* gen_start, void* x_next,
+                                     int32_t* token, int32_t* n_kept, int32_t* n_plausible, float* logprob, int32_t* n_active,
+                                     uint32_t* counter, int64_t* pos64, int32_t* node, const int32_t* node_first,
+                                     const int32_t* edge_token, const int32_t* edge_child, int n_nodes, int n_edges, int n_seq,
+                                     int vocab, int dim, int seq_len, int dtype, void* stream) {
+  const ExArgs ex{top_k, repetition_penalty, gen_start, logprob, counter};
+  const PairArgs pr{alpha, beta, n_plausible};
+  if (!node && !node_first && !edge_token && !edge_child)          // no trie at all: the pairs pick from the vocabulary
+    return checked_launch<true, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
+                                             token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
+                                             TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, pr);
+  return checked_launch<true, true, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
+                                          n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
+                                          TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges}, pr);
 }

@@ -100,7 +100,9 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     Otherwise the original multiple-choice protocol (engine.py:86-93,122-129): every option is scored by its mean
     cross-entropy over the answer tokens and the lowest wins — `model.score_options(data)` (llama/model.py; a model without it
     is rejected) returns the reference's `individual_losses` and leaves count / prediction, reduced on the device, in
-    `last_scoring`: one host read per batch. Accuracy overall and per question type either way."""
+    `last_scoring`: one host read per batch. Accuracy overall and per question type either way.
+    `--contrast blind` (multiple choice): the prediction is the contrastive one (fvqa/score.py) and `acc_blind` / `acc_plain` —
+    the accuracy of the blind twin's and of the plain prediction — are logged from the same single host read."""
     gen = bool(getattr(args, "is_generation_task", False))
     owner = None
     if not gen:
@@ -115,18 +117,31 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
         answer = data["answer"]
         bsz = answer.shape[0]
         if not gen:
+            contrast = getattr(args, "contrast", None)       # --contrast blind: the prediction discounts the blind twin's means
             with torch.no_grad():
-                individual_losses = owner.score_options(data)
+                if contrast:
+                    individual_losses = owner.score_options(data, contrast=contrast,
+                                                            contrast_alpha=float(getattr(args, "contrast_alpha", 1.0)))
+                else:
+                    individual_losses = owner.score_options(data)
             last = getattr(owner, "last_scoring", None)
             if last is not None:
                 prediction = last["prediction"]
             else:                                            # (a model that only returns the losses: engine.py:88-93)
                 count = (individual_losses != 0).sum(-1)
                 prediction = (individual_losses.sum(-1) / count).argmin(-1)
-            hit = answer.cpu() == prediction.cpu()           # the batch's one device->host read
+            extra = None
+            if contrast and last is not None and "prediction_blind" in last:
+                prediction = torch.stack([prediction, last["prediction_blind"], last["prediction_plain"]])
+                extra = True
+            pred_h = prediction.cpu()                        # the batch's one device->host read
+            hit = answer.cpu() == (pred_h[0] if extra else pred_h)
             misc.log_qtype(data, hit, log, args)
             log.update(lr=optimizer.param_groups[0]["lr"])
             log.update(n=bsz, acc=hit.sum().item() / bsz)
+            if extra:                                        # what the model answers without looking, and without the contrast
+                log.update(n=bsz, acc_blind=(answer.cpu() == pred_h[1]).sum().item() / bsz,
+                           acc_plain=(answer.cpu() == pred_h[2]).sum().item() / bsz)
             if getattr(args, "debug", False):
                 break
             continue

@@ -138,7 +138,7 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
 def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
              stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
-             constraints=None) -> dict:
+             constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -175,7 +175,25 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       their meaning, with "every token" read as "every allowed token". The results gain "choice": the index of the generated
       member in its sample's list, (B,) — (B, n) with num_return_sequences = n; under beam search the best hypothesis' and
       "beams"["choice"] (B, K) —, -1 for a row that ended before a leaf. ValueError: stop_at_eos=False (a leaf is reached by
-      the EOS), a member (EOS included) longer than max_new_tokens, a member that does not fit behind its prompt inside S."""
+      the EOS), a member (EOS included) longer than max_new_tokens, a member that does not fit behind its prompt inside S.
+    contrast (None: every code path above runs untouched): contrastive decoding against a TWIN of the prompt — the same text run
+      a second time with other features — so that every token is picked from the difference of the two predictions and the
+      language prior is discounted (visual contrastive decoding; classifier-free guidance for language models).
+      contrast="blind": the twin's "video" and / or "audio" (whichever the batch has) are zeros — visual_proj has no bias, so a
+      zero frame becomes temporal_emb alone, which is what every zero-padded frame slot of a short clip looks like in training.
+      contrast={"video": ..., "audio": ...}: replacement tensors of the batch's own shapes (another clip, shuffled frames).
+      The rule, per sample and token step in fp32 (include/fvqa.h fvqa_decode_next_pair states it), with lp = log_softmax(l) of
+      the raw row: P = {i allowed : l+_i - max_allowed l+ >= log(contrast_beta)} is the plausible set (beta 0: everything,
+      beta 1: the maxima), c_i = l+_i + contrast_alpha * (lp+_i - lp-_i) for i in P, and everything else — the repetition
+      penalty, the greedy pick, temperature, top_k, top_p, the trie of `constraints` — sees c over P where it saw l over the
+      allowed tokens. alpha == 0 (or a twin equal to the batch) picks from l+ itself. "logprobs" stay lp+ of the picked token.
+      The flow: ONE prefill of 2 * B sequences (the features concatenated, the ids repeated), the fan-out of
+      num_return_sequences over 2 * B parents (rows: B * n positives, then B * n negatives), the token loop unchanged on
+      2 * B * n rows with ops.decode_next_pair as its token step — still one launch, which steps both rows of a pair with one
+      token —, the lag-one stop on the count of pairs. The results have today's shapes, taken from the positive rows, and gain
+      "n_plausible" (B[, n], steps) int32: |P| at each step, 0 where "tokens" is -1.
+      ValueError: a key the batch lacks, a tensor of another shape, contrast_alpha < 0, contrast_beta outside [0, 1],
+      num_beams > 1, 2 * B * num_return_sequences > 65535. Not built: a contrastive beam step; negatives whose TEXT differs."""
     if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
     if num_beams > 1 and temperature > 0:
@@ -191,8 +209,9 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if num_beams > 1 and ex:
         raise ValueError("generate: top_k, repetition_penalty, return_logprobs and num_return_sequences belong to "
                          "num_beams == 1 (beam search reports \"score\")")
+    twin = None if contrast is None else _twin(data, contrast, contrast_alpha, contrast_beta, num_beams)
     trie = None if constraints is None else _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
-    if num_beams > 1 or _BEAM_PATH_AT_ONE:
+    if num_beams > 1 or (_BEAM_PATH_AT_ONE and twin is None):
         kw = {} if trie is None else {"constraints": trie}
         return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
                            length_penalty=float(length_penalty), **kw)
@@ -206,19 +225,30 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     ids_all = data["text_id"]["vqa"]
     B0, _, S = ids_all.shape
     B = B0 * n                                              # the rows of the token loop
+    NP = B                                                  # the token steps' results: one per row — per PAIR under `contrast`
+    if twin is not None:
+        B = 2 * NP
+        if B > 65535:
+            raise ValueError("generate: contrast runs two rows per sample: 2 * samples * num_return_sequences <= 65535")
     if B > 65535:
         raise ValueError("generate: at most 65535 rows (samples times num_return_sequences)")
     sub = {k: data[k] for k in ("video", "audio") if k in data}
     sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
                 "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    if twin is not None:                                    # the B0 prompts with their clips, then the same prompts with the twin's
+        for k, v in twin.items():
+            sub[k] = torch.cat([sub[k], v.to(device=sub[k].device, dtype=sub[k].dtype)], 0)
+        sub["text_id"] = {"vqa": sub["text_id"]["vqa"].repeat(2, 1, 1)}
+        sub["label"] = {"vqa": sub["label"]["vqa"].repeat(2, 1, 1)}
+        B0 = 2 * B0                                         # the prefill's rows, and the parents of the fan-out
     with vqa_stream_only(eng, "_gen_arena", "all"):
         eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
         ar = eng.arena(B0, S)
         vstart = eng.saved["vstart"]
         D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
         fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
-        ids = ids_all[:, 0].to(dev).clone()
-        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
+        ids = sub["text_id"]["vqa"][:, 0].to(dev).clone()
+        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]] * (1 if twin is None else 2), device=dev)
         start = prefix - 1                                  # the position the first token is predicted at
         first = ar.logits.view(B0, S, V)[torch.arange(B0, device=dev), start.clamp(0, S - 1)]
         kv = ar.qkv
@@ -238,23 +268,25 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         pos = start.to(torch.int32)
         pos64 = start.clone()
         done = torch.zeros(B, dtype=torch.int32, device=dev)
-        tokens = torch.full((max_new_tokens, B), -1, dtype=torch.int32, device=dev)
-        n_kept = torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev)
+        tokens = torch.full((max_new_tokens, NP), -1, dtype=torch.int32, device=dev)
+        n_kept = torch.zeros(max_new_tokens, NP, dtype=torch.int32, device=dev)
         n_active = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev)
-        if ex or trie is not None:
+        if ex or trie is not None or twin is not None:
             gen_start = prefix.to(torch.int32)
-            logprobs = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
+            logprobs = torch.zeros(max_new_tokens, NP, dtype=torch.float32, device=dev)
             counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        if twin is not None:
+            n_plausible = torch.zeros(max_new_tokens, NP, dtype=torch.int32, device=dev)
         if trie is not None:                                # every row starts at its sample's root (n rows per sample: repeated)
             dtrie = trie.to(dev)
-            node = torch.as_tensor(trie.roots(B0), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
+            node = torch.as_tensor(trie.roots(NP // n), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
         u = None
         if temperature > 0:
             gen = None
             if seed is not None:
                 gen = torch.Generator(device=dev)
                 gen.manual_seed(int(seed))
-            u = torch.rand(max_new_tokens, B, dtype=torch.float32, device=dev, generator=gen)
+            u = torch.rand(max_new_tokens, NP, dtype=torch.float32, device=dev, generator=gen)
         running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
         arrived = []
         steps = 0
@@ -263,7 +295,15 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                 arrived[t - 2].synchronize()
                 if int(running[t - 2]) == 0:
                     break
-            if trie is not None:
+            if twin is not None:                            # both rows of every pair, one token (a trie node per pair)
+                ops.decode_next_pair(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], n_plausible[t],
+                                     logprobs[t], n_active[t:t + 1], counter, alpha=float(contrast_alpha),
+                                     beta=float(contrast_beta), node=None if trie is None else node,
+                                     trie=None if trie is None else dtrie, u=None if u is None else u[t], pos64=pos64,
+                                     temperature=temperature, top_p=top_p, top_k=int(top_k),
+                                     repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
+                                     stop_at_eos=stop_at_eos)
+            elif trie is not None:
                 ops.decode_next_trie(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
                                      n_active[t:t + 1], counter, node, dtrie, u=None if u is None else u[t], pos64=pos64,
                                      temperature=temperature, top_p=top_p, top_k=int(top_k),
@@ -305,16 +345,45 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
             ops.gemm_nt(xn, pk.wout, lg)
         out = {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
                "tokens": tokens[:steps].t().contiguous()}
+        if twin is not None:                                # the positive rows; the twins hold the same tokens
+            out["ids"], out["n_generated"] = out["ids"][:NP].contiguous(), out["n_generated"][:NP]
+            out["n_plausible"] = n_plausible[:steps].t().contiguous()
+            B0 = B0 // 2
         if return_logprobs:
             out["logprobs"] = logprobs[:steps].t().contiguous()
             out["sum_logprob"] = out["logprobs"].sum(1)
         if n > 1:
-            for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob"):
+            for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible"):
                 if k in out:
                     out[k] = out[k].view(B0, n, *out[k].shape[1:])
         if trie is not None:
             out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
         return out
+
+
+def _twin(data: dict, contrast, alpha, beta, num_beams=1) -> dict:
+    """generate's `contrast` -> the twin's feature tensors {"video" and / or "audio": ...}, after the checks that need no device."""
+    if not alpha >= 0 or not 0 <= beta <= 1:
+        raise ValueError("generate: contrast_alpha >= 0, 0 <= contrast_beta <= 1")
+    if num_beams > 1:
+        raise ValueError("generate: contrast belongs to num_beams == 1 (a contrastive beam step is not built)")
+    have = [k for k in ("video", "audio") if k in data]
+    if isinstance(contrast, str):
+        if contrast != "blind":
+            raise ValueError("generate: contrast is None, \"blind\" or a dict of replacement features")
+        if not have:
+            raise ValueError("generate: contrast=\"blind\" needs a batch with \"video\" or \"audio\"")
+        return {k: torch.zeros_like(data[k]) for k in have}
+    if not isinstance(contrast, dict) or not contrast:
+        raise ValueError("generate: contrast is None, \"blind\" or a dict of replacement features")
+    twin = {}
+    for k, v in contrast.items():
+        if k not in have:
+            raise ValueError(f"generate: contrast[{k!r}]: the batch has no such features (it has {have})")
+        if not torch.is_tensor(v) or tuple(v.shape) != tuple(data[k].shape):
+            raise ValueError(f"generate: contrast[{k!r}] must be a tensor of the batch's own shape {tuple(data[k].shape)}")
+        twin[k] = v
+    return twin
 
 
 def _compiled(eng, data: dict, constraints, stop_at_eos: bool, max_new_tokens: int):

@@ -703,6 +703,52 @@ def decode_next_trie(logits, emb, ids, pos, done, gen_start, x_next, token, n_ke
     return token
 
 
+def decode_next_pair(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, n_plausible, logprob, n_active, counter, *,
+                     alpha: float, beta: float, node=None, trie=None, u=None, pos64=None, temperature: float = 0.0,
+                     top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0, eos_id: int = 2,
+                     stop_at_eos: bool = True):
+    """The token step of contrastive decoding (include/fvqa.h fvqa_decode_next_pair states the rule): decode_next_ex — with
+    `node` and `trie`, decode_next_trie — on B PAIRS of rows. logits (2B, V), ids (2B, S), pos / done / pos64 (2B,) and x_next
+    (2B, D) hold the B positive rows followed by their B twins; gen_start, token, n_kept, n_plausible, node (B,) int32, logprob
+    and u (B,) fp32 are per pair (gen_start and u may be longer: their first B entries are read). n_active counts pairs."""
+    have_trie = trie is not None
+    _need(have_trie == (node is not None), "decode_next_pair: node and trie come together")
+    nf = et = ec = None
+    n_nodes = n_edges = 0
+    if have_trie:
+        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_pair")
+    _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, n_plausible, logprob, n_active, counter, u, pos64, node,
+         nf, et, ec)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] % 2 == 0 and logits.shape[0] > 0,
+          "decode_next_pair: logits (2B, V) fp32")
+    B2, V = logits.shape
+    B = B2 // 2
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_pair: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B2, D), "decode_next_pair: x_next (2B, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B2 and ids.dtype == torch.int64, "decode_next_pair: ids (2B, S) int64")
+    for t, n in ((pos, B2), (done, B2), (token, B), (n_kept, B), (n_plausible, B), (n_active, 1), (counter, 1)) + \
+            (((node, B),) if have_trie else ()):
+        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_pair: pos / done (2B,), token / n_kept / n_plausible / "
+                                                         "node (B,), n_active / counter (1,) int32")
+    _need(gen_start.dtype == torch.int32 and gen_start.numel() >= B, "decode_next_pair: gen_start (B,) int32")
+    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_pair: logprob (B,) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B2), "decode_next_pair: pos64 (2B,) int64")
+    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() >= B),
+          "decode_next_pair: sampling needs u (B,) fp32")
+    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_pair: top_k >= 0, repetition_penalty >= 1")
+    _need(alpha >= 0 and 0 <= beta <= 1, "decode_next_pair: alpha >= 0, 0 <= beta <= 1")
+    rc = _lib.load(emb.dtype).fvqa_decode_next_pair(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p),
+                                                    int(top_k), float(repetition_penalty), float(alpha), float(beta),
+                                                    int(eos_id), 1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done),
+                                                    _ptr(gen_start), _ptr(x_next), _ptr(token), _ptr(n_kept), _ptr(n_plausible),
+                                                    _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), _ptr(node),
+                                                    _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D, ids.shape[1],
+                                                    dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_decode_next_pair")
+    return token
+
+
 BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
 
 

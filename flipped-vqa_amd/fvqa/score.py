@@ -17,6 +17,10 @@ The reference runs B * n_options full sequences that differ only in their last f
 
 Both end in the same tail: the scored rows' losses in a compact array (fvqa_ce_fwd, shifted-label convention of fvqa/scored.py)
 -> fvqa_option_pick -> individual_losses (B, n_options, S-1), per-option sum / count / mean, prediction.
+
+score_options(contrast=...) is the scoring sibling of generate(contrast=...): the batch and its twin (the same text, the twin's
+features) are scored with the same route, and the prediction is the argmin over the options with count > 0 of
+mean+ + alpha * (mean+ - mean-) — host composition and a (B, n_options)-sized reduction on the device, no new kernel.
 """
 from __future__ import annotations
 
@@ -109,11 +113,31 @@ def _pick(eng, rowloss, row_map_host, n_rows, B, O, S):
     return ops.option_pick(rowloss, row_map, n_rows, B, O, S)
 
 
+def contrast_pick(mean_pos: torch.Tensor, mean_neg: torch.Tensor, count: torch.Tensor, alpha: float) -> torch.Tensor:
+    """(B, O) means of the batch and of its twin, (B, O) counts -> (B,) int64: the argmin over the options with count > 0 of
+    mean+ + alpha * (mean+ - mean-), the lowest index on ties (0 when no option has a scored token). Any device."""
+    s = mean_pos + float(alpha) * (mean_pos - mean_neg)
+    s = torch.where(count > 0, s, torch.full_like(s, float("inf")))
+    O = s.shape[1]
+    idx = torch.arange(O, device=s.device).expand_as(s)
+    first = torch.where(s == s.min(1, keepdim=True).values, idx, torch.full_like(idx, O)).min(1).values
+    return first.clamp(max=O - 1).to(torch.int64)
+
+
 @torch.no_grad()
-def score_options(eng, data: dict, route: Optional[str] = None, events: Optional[list] = None):
+def score_options(eng, data: dict, route: Optional[str] = None, events: Optional[list] = None, *, contrast=None,
+                  contrast_alpha: float = 1.0):
     """-> dict(individual_losses (B, O, S-1) fp32, sum, count (int64), mean (B, O), prediction (B,) int64 — all on the device —,
     route, plan). route: None = route_of(plan). events: a list that receives (name, start, end) torch.cuda.Event triples of the
-    passes (tools/score_bench.py)."""
+    passes (tools/score_bench.py).
+    contrast (None: nothing changes; "blind" or a dict of replacement features, as generate's keyword): the twin batch is scored
+    as well, by the same route. "prediction" becomes contrast_pick(mean, mean_blind, count, contrast_alpha); the result gains
+    "mean_blind" (B, O), "prediction_blind" (the argmin of the twin's means: what the model answers without looking) and
+    "prediction_plain" (the argmin of the batch's own means: the prediction without `contrast`). individual_losses, sum, count
+    and mean stay the batch's own. Not built: negatives whose text differs."""
+    if contrast is not None:
+        from .generate import _twin
+        twin = _twin(data, contrast, contrast_alpha, 0.0)
     ids = data["text_id"]["vqa"]
     lab = data["label"]["vqa"]
     ids_h, lab_h = ids.cpu(), lab.cpu()
@@ -129,7 +153,14 @@ def score_options(eng, data: dict, route: Optional[str] = None, events: Optional
         raise ValueError(f"score_options: this batch cannot take the shared form ({plan.why_dense})")
     fn = _shared if route == "shared" else _dense
     il, s, cnt, mean, pred = fn(eng, data, ids_h, lab_h, vs_list, plan, events)
-    return dict(individual_losses=il, sum=s, count=cnt, mean=mean, prediction=pred, route=route, plan=plan)
+    out = dict(individual_losses=il, sum=s, count=cnt, mean=mean, prediction=pred, route=route, plan=plan)
+    if contrast is not None:
+        blind = dict(data)
+        blind.update(twin)
+        _, _, _, mean_b, pred_b = fn(eng, blind, ids_h, lab_h, vs_list, plan, events)
+        out.update(mean_blind=mean_b, prediction_blind=pred_b, prediction_plain=pred,
+                   prediction=contrast_pick(mean, mean_b, cnt, contrast_alpha))
+    return out
 
 
 def _mark(events, name):

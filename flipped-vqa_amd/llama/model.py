@@ -235,6 +235,13 @@ class Transformer(nn.Module):
         mode = getattr(self.args, "gen_constrain", None)
         if mode:                                            # --gen_constrain: decode under the allowed answers
             return self._constrained_inference(data, mode)
+        if getattr(self.args, "contrast", None):            # --contrast blind: each token from the difference to the blind twin
+            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
+                                    **self._contrast_kw())
+            ids = out["ids"]
+            best, sims, extracted = generate.match_answers(self, data, ids)
+            self.last_generation = {"ids": ids, "similarities": sims, "n_plausible": out["n_plausible"]}
+            return best, extracted
         if int(getattr(self.args, "num_beams", 1) or 1) > 1:    # --num_beams N: the most likely answer under the model
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
                                     num_beams=int(self.args.num_beams))
@@ -248,11 +255,19 @@ class Transformer(nn.Module):
         self.last_generation = {"ids": ids, "similarities": sims}
         return best, extracted
 
+    def _contrast_kw(self) -> dict:
+        """--contrast / --contrast_alpha / --contrast_beta as generate's keywords ({} without --contrast)."""
+        c = getattr(self.args, "contrast", None)
+        if not c:
+            return {}
+        return {"contrast": c, "contrast_alpha": float(getattr(self.args, "contrast_alpha", 1.0)),
+                "contrast_beta": float(getattr(self.args, "contrast_beta", 0.1))}
+
     def _constrained_inference(self, data, mode):
         """--gen_constrain options | vocab: every sample decodes under its own answer options (-> best = the index of the option
         generated; a row that completed none falls back to the cosine pick) or under the shared answers of --answer_vocab (the
         cosine pick then ranks the options against an answer of that vocabulary). --num_beams applies as before; each row ends
-        at its EOS. `last_generation` gains "choice"."""
+        at its EOS. `last_generation` gains "choice". With --contrast the constrained pick is the contrastive one."""
         from fvqa import constrain, generate
         eng = self.ensure_engine()
         if mode == "options":
@@ -273,7 +288,8 @@ class Transformer(nn.Module):
         else:
             raise ValueError(f"gen_constrain: 'options' or 'vocab', not {mode!r}")
         out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)), temperature=0.0,
-                                stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie)
+                                stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie,
+                                **self._contrast_kw())
         ids, choice = out["ids"], out["choice"]
         best, sims, extracted = generate.match_answers(self, data, ids)
         if mode == "options":
@@ -285,14 +301,16 @@ class Transformer(nn.Module):
     def generate(self, data, **kw):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
-        return_logprobs, num_return_sequences, constraints) -> one answer per row, the
+        return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
-        "sum_logprob"; with constraints "choice", the index of each answer in the allowed set). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
+        size of the plausible set at every token step). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
-        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice")
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",
+                                                     "n_plausible")
                                 if k in out}
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
 
@@ -310,15 +328,20 @@ class Transformer(nn.Module):
         return answers
 
     @torch.no_grad()
-    def score_options(self, data):
+    def score_options(self, data, contrast=None, contrast_alpha: float = 1.0):
         """The multiple-choice protocol's model half (reference llama/model_my_original_mod.py:332-377,506 with
         `inference=True`, not a generation task): -> individual_losses (B, n_options, S-1) fp32 on the device, the per-token
         cross-entropy (ignore_index 0) of every option, zero wherever a row is not scored. The reduction engine.py:86-93 makes of
         it is done on the device as well and left in `last_scoring`: prediction (B,), per-option mean and count, and the route
-        that ran ("shared": the prompt once + each option's last rows; "dense": every option in full — fvqa/score.py)."""
+        that ran ("shared": the prompt once + each option's last rows; "dense": every option in full — fvqa/score.py).
+        contrast ("blind", or a dict of replacement features; None: nothing changes), contrast_alpha: the batch's twin is scored
+        too and the prediction is the argmin of mean+ + alpha * (mean+ - mean-); `last_scoring` gains "mean_blind",
+        "prediction_blind" and "prediction_plain" (fvqa/score.py: score_options). The returned losses stay the batch's own."""
         from fvqa import score
-        r = score.score_options(self.ensure_engine(), data)
-        self.last_scoring = {k: r[k] for k in ("prediction", "mean", "count", "route")}
+        kw = {} if contrast is None else {"contrast": contrast, "contrast_alpha": contrast_alpha}
+        r = score.score_options(self.ensure_engine(), data, **kw)
+        self.last_scoring = {k: r[k] for k in ("prediction", "mean", "count", "route", "mean_blind", "prediction_blind",
+                                               "prediction_plain") if k in r}
         return r["individual_losses"]
 
     def forward(self, data, inference=False):

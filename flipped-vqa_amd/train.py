@@ -76,6 +76,14 @@ _FLAGS = [
                                   "constraints=...)): 'options' — the sample's own answer options, the prediction is the option "
                                   "generated; 'vocab' — the shared answers of --answer_vocab. --num_beams applies as before")),
     ("--answer_vocab", dict(type=str, default=None, help="a file with one allowed answer per line (needed by --gen_constrain vocab)")),
+    ("--contrast", dict(type=str, choices=["blind"], default=None,
+                        help="validation only: contrastive decoding / scoring against the video-blind twin of every prompt (the "
+                             "same text, zero features): generation-task validation decodes through fvqa.generate.generate("
+                             "contrast='blind'), alone or with --gen_constrain; multiple-choice validation predicts by "
+                             "mean + alpha * (mean - mean_blind) and logs acc_blind / acc_plain. Not with --num_beams > 1")),
+    ("--contrast_alpha", dict(type=float, default=1.0, help="--contrast: the weight of the difference to the twin (>= 0)")),
+    ("--contrast_beta", dict(type=float, default=0.1, help="--contrast: a token is plausible iff its probability with the clip "
+                                                           "is at least beta times the largest (0 .. 1; generation only)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -85,12 +93,18 @@ _FLAGS = [
 
 
 class ArgumentParser(argparse.ArgumentParser):
-    """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file (answer.py uses it too)."""
+    """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
+    --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range (answer.py uses it too)."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
         if getattr(a, "gen_constrain", None) == "vocab" and not getattr(a, "answer_vocab", None):
             self.error("--gen_constrain vocab needs --answer_vocab FILE (one answer per line)")
+        if getattr(a, "contrast", None):
+            if int(getattr(a, "num_beams", 1) or 1) > 1:
+                self.error("--contrast decodes with num_beams == 1: a contrastive beam search is not built")
+            if not a.contrast_alpha >= 0 or not 0 <= a.contrast_beta <= 1:
+                self.error("--contrast_alpha >= 0, 0 <= --contrast_beta <= 1")
         return a
 
 

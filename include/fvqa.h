@@ -340,6 +340,41 @@ int fvqa_decode_next_trie(const float* logits, const float* u, const void* emb, 
                           int32_t* n_active, uint32_t* counter, int64_t* pos64, int32_t* node, const int32_t* node_first,
                           const int32_t* edge_token, const int32_t* edge_child, int n_nodes, int n_edges, int n_seq, int vocab,
                           int dim, int seq_len, int dtype, void* stream);
+/* Contrastive decoding against a twin row (the same kernel template in csrc/sample.hip with one more compile-time switch;
+ * generate(contrast=...)): fvqa_decode_next_ex, or with a trie fvqa_decode_next_trie, on PAIRS of rows. n_seq is the number of
+ * pairs and the grid is one workgroup per pair. logits, ids, pos, done, pos64 and x_next hold 2 * n_seq rows, row b + n_seq the
+ * twin of row b: row b is the positive row (logits l+: the prompt with its clip), row b + n_seq the negative one (l-: the same
+ * ids and positions, the twin's features). u, gen_start, token, n_kept, n_plausible, logprob and node hold n_seq entries.
+ * node == node_first == edge_token == edge_child == NULL: no trie (n_nodes, n_edges ignored); else all four as in
+ * fvqa_decode_next_trie, one node per pair. alpha >= 0, 0 <= beta <= 1. The rule, per pair and token step, fp32, with
+ * lp = l - lse(l), lse = m + log(sum exp(l - m)) over the whole raw row as in rule 5:
+ *   - plausible set: P = { i allowed : l+_i - max_allowed l+ >= logf(beta) }. beta == 0 keeps everything (logf(0) = -inf),
+ *     beta == 1 the maxima only. "Allowed" is the whole vocabulary, or the usable edges of the pair's node.
+ *   - contrast: c_i = l+_i + alpha * (lp+_i - lp-_i) for i in P; a token outside P takes no part, as an edge outside [0, vocab)
+ *     takes none. This is (1 + alpha) * lp+ - alpha * lp- up to a constant per row, written so that alpha == 0, or twin rows of
+ *     the same bits, give c_i = l+_i bit for bit — then, with beta == 0, the positive half of every operand comes out as
+ *     fvqa_decode_next_ex / _trie leaves it on the positive rows alone.
+ *   - everything downstream sees c where it saw l and P where it saw the allowed tokens: the repetition penalty (rule 1 on c),
+ *     the greedy pick with the lowest index on ties, the maximum, e_i, Z, top-k (cut against |P|), the nucleus cut, the walk,
+ *     the trie child. n_kept <= n_plausible.
+ *   - logprob stays lp+ of the token: the model's own log-probability with the clip, comparable to every other mode.
+ *   - pair state: the pair is live iff the positive row is (done == 0 and room for a token): pos and done are READ from the
+ *     positive row only. The token, the new pos, done, pos64 and x_next are WRITTEN to both rows (a pair that picks nothing
+ *     leaves both id rows alone and gives both rows the positive row's pos, done = 1 and the embedding of the positive row's
+ *     current token). R of rule 1 is read from the positive id row. n_active counts pairs, through `counter` as in _ex.
+ *   - n_plausible (n_seq) int32 out: |P|, 0 for a pair that picks nothing. A pair whose P is empty (logits that are not
+ *     finite) picks nothing and becomes done.
+ * No logit is written, every sum keeps a fixed order (two launches give the same bits), LDS holds one row of e_i and the
+ * bitmap as before — c is computed where a logit is read —, and when 4 * vocab exceeds the LDS row both rows are re-read per
+ * pass. Not built: a contrastive beam step; negatives whose TEXT differs (the pair shares one id row position by position).
+ * Errors of fvqa_decode_next_ex (and, with a trie, of _trie) hold; FVQA_EINVAL also for a null n_plausible, alpha < 0 or NaN,
+ * beta outside [0, 1] or NaN, a trie given in part; FVQA_ESHAPE also for 2 * n_seq > 65535. */
+int fvqa_decode_next_pair(const float* logits, const float* u, const void* emb, float temperature, float top_p, int top_k,
+                          float repetition_penalty, float alpha, float beta, int eos_id, int stop_at_eos, int64_t* ids,
+                          int32_t* pos, int32_t* done, const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept,
+                          int32_t* n_plausible, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
+                          int32_t* node, const int32_t* node_first, const int32_t* edge_token, const int32_t* edge_child,
+                          int n_nodes, int n_edges, int n_seq, int vocab, int dim, int seq_len, int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)

@@ -15,7 +15,10 @@ layer pass is the same size — and, with device events, one fvqa_beam_step and 
 slot moving 15 generated rows: the worst case half way through an answer).
 --top_k K [K ...] / --samples N [N ...] time sampling `generate(temperature=0.8, stop_at_eos=False)` with a top-k cut (and the
 log-probabilities: the fvqa_decode_next_ex token step) / with N samples per prompt from one prefill, each interleaved with the
-plain sampling `generate` of the same batch — for N > 1 also N calls of it, which is what the fan-out replaces."""
+plain sampling `generate` of the same batch — for N > 1 also N calls of it, which is what the fan-out replaces.
+--contrast times greedy `generate(contrast="blind", stop_at_eos=False)` — contrastive decoding runs twice the rows — interleaved
+(--pairs N times, default 3) with its two comparison points: the plain greedy `generate` of the same batch (B rows) and of a
+batch of 2 * B rows (the same layer pass as the pairs)."""
 import argparse
 import os
 import sys
@@ -47,6 +50,8 @@ def main():
     ap.add_argument("--top_k", type=int, nargs="*", default=[], help="sampling with a top-k cut; several K: a line each")
     ap.add_argument("--samples", type=int, nargs="*", default=[], help="N samples per prompt from one prefill; several N: a line "
                                                                        "each")
+    ap.add_argument("--contrast", action="store_true", help="contrastive decoding against the blind twin, interleaved with greedy "
+                                                            "generate at B and at 2 * B rows (--pairs rounds, default 3)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -100,6 +105,23 @@ def main():
 
     if a.num_beams:
         beam_lines(a, eng, b, cfg, timed)
+        return
+    if a.contrast:
+        import dataclasses
+        T = generate.N_NEW
+        tag = f"{a.model} L={eng.L} B={B} S=128 greedy"
+        wide = synth.make_batch(dataclasses.replace(cfg, batch_size=2 * B), seed=5)
+        wide["prefix_index"] = {"vqa": [60 + i % 32 for i in range(2 * B)]}
+        runs = (("generate, B rows", lambda: generate.generate(eng, b, stop_at_eos=False)),
+                ("generate, 2B rows", lambda: generate.generate(eng, wide, stop_at_eos=False)),
+                ("generate(contrast='blind'), B pairs", lambda: generate.generate(eng, b, stop_at_eos=False, contrast="blind")))
+        for _, fn in runs:
+            timed(fn, reps=1)
+        for k in range(a.pairs or 3):
+            t = [timed(fn, warm=0) for _, fn in runs]
+            print(f"{tag} round {k}: " + " | ".join(f"{name}: {x * 1e3:7.1f} ms/batch" for (name, _), x in zip(runs, t))
+                  + f" | contrast: {B * T / t[2]:8.1f} answer tokens/s, {t[2] / t[0]:5.2f}x B rows, {t[2] / t[1]:5.2f}x 2B rows",
+                  flush=True)
         return
     if a.top_k or a.samples:
         T = generate.N_NEW
