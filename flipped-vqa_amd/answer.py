@@ -4,12 +4,15 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
     python answer.py --model 7B --llama_model_path ... --resume ckpt.pth --features clip.pth|.npy [--audio_features ...] \
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
         [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
-        [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B]
+        [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
+        [--lookahead T --lookup_ngram G]
 
 `--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
 line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
 `--contrast blind` (train.py's flag) picks every token from the difference to the prompt's video-blind twin — the same text with
 zero features — and prints how many tokens were plausible per step (fvqa.generate.generate(contrast="blind")).
+`--lookahead T` (train.py's flag; greedy only) verifies a prompt-lookup draft of up to T - 1 tokens per pass and prints how many
+tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -114,6 +117,8 @@ def main(args):
     kw = {} if allowed is None else {"constraints": constrain.encode_answers(tok, allowed)}
     if args.contrast:
         kw.update(contrast=args.contrast, contrast_alpha=args.contrast_alpha, contrast_beta=args.contrast_beta)
+    if args.lookahead > 1:
+        kw.update(lookahead=args.lookahead, lookup_ngram=args.lookup_ngram)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
                             seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
                             repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,
@@ -131,6 +136,8 @@ def main(args):
         if "n_plausible" in g:
             npl = (g["n_plausible"][0, k] if many else g["n_plausible"][0])[:n]
             head += f", plausible tokens per step {float(npl.float().mean()) if n else 0.0:.1f}"
+        if "n_committed" in g:
+            head += ", committed per step " + " ".join(str(int(c)) for c in g["n_committed"][0])
         print(head + "]")
         print(a if isinstance(a, str) else " ".join(str(t) for t in a))
         if allowed is not None:

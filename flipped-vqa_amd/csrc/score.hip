@@ -18,6 +18,13 @@
 //   is a few hundred kFLOP next to the weight streams of the projections around it.
 //   Rows j >= len[n] are padding: never loaded (a NaN there reaches nothing), their output rows are written as zeros.
 //
+// fvqa_attn_suffix_append — the same kernel template with APPEND = true (fvqa_attn_suffix instantiates APPEND = false, in which
+//   none of the following exists), for ONE continuation per sample (draft-and-verify decoding, fvqa/generate.py): the suffix
+//   rows join the cache. The (head, sample) workgroup already stages its head's slice of every suffix key and value once; the
+//   threads that stage row j < len[n] also store it to cache row n*S + start[n] + j — k rotated and rounded when the cache holds
+//   rotated keys (rope_pair_as_decode: the bits fvqa_attn_decode stores for that row and position), the raw bits otherwise;
+//   v as it is. Nothing reads those rows in this launch: a workgroup reads the cache rows [0, start[n]) only.
+//
 // fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
 //   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
 //   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
@@ -66,6 +73,33 @@ __device__ __forceinline__ void rope16(float (&v)[16], const float* cs, const fl
   }
 }
 
+// RoPE of one pair (a, b) of a key that goes into the cache, operation by operation what fvqa_attn_decode's store of the new
+// token's key evaluates (csrc/attn_decode_body.h: `a * c - b * s`, `a * s + b * c`, as hipcc contracts them there: the second
+// always into one fma on the rounded a * s; the first into an fma on the rounded b * s in the 16-bit kernels and not at all in
+// the fp32 kernel). Spelled out with contraction off so that the row fvqa_attn_suffix_append stores has the bits the one-row
+// kernel stores for the same raw row and position — in fp32 the last bit shows; tests/test_lookahead_gpu.py compares them.
+template <typename T> __device__ __forceinline__ void rope_pair_as_decode(float a, float b, float c, float s, float& ra, float& rb) {
+#pragma clang fp contract(off)
+  const float bs = b * s, as = a * s;
+  if constexpr (sizeof(T) == 4) ra = a * c - bs;
+  else ra = __builtin_fmaf(a, c, -bs);
+  rb = __builtin_fmaf(b, c, as);
+}
+// 16 values to 16 consecutive elements of a row, rounded to the storage type
+template <typename T> __device__ __forceinline__ void store16_as(T* dst, const float (&v)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const float q[4] = {v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]};
+    Vec4<T>::store(dst + 4 * u, q);
+  }
+}
+// 16 consecutive elements of a row, bit for bit
+template <typename T> __device__ __forceinline__ void copy16(T* dst, const T* src) {
+#pragma unroll
+  for (int u = 0; u < (int)(16 * sizeof(T) / 16); ++u)
+    reinterpret_cast<uint4*>(dst)[u] = reinterpret_cast<const uint4*>(src)[u];
+}
+
 __device__ __forceinline__ void store16(float* dst, const float (&v)[16]) {
 #pragma unroll
   for (int u = 0; u < 4; ++u)
@@ -83,7 +117,7 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
-template <typename T>
+template <typename T, bool APPEND = false>
 __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, const T* __restrict__ cache,
                                                      T* __restrict__ o_suf, const float* __restrict__ gate1,
                                                      const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
@@ -180,6 +214,22 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         if (row) {
           load16<T>(row + D + sd0, k);
           load16<T>(row + 2 * D + sd0, v);
+          if constexpr (APPEND) {                        // (O == 1: one tile, one suffix chunk — each row is staged once)
+            if (kind == 1) {
+              T* crow = const_cast<T*>(seq) + (size_t)pos * ld;      // pos = start + j < S: len <= S - start
+              if (cache_rot) {
+                float kr[16];
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                  rope_pair_as_decode<T>(k[2 * e], k[2 * e + 1], cs[(size_t)pos * HP + sd0 / 2 + e],
+                                         sn[(size_t)pos * HP + sd0 / 2 + e], kr[2 * e], kr[2 * e + 1]);
+                store16_as<T>(crow + D + sd0, kr);
+              } else {
+                copy16<T>(crow + D + sd0, row + D + sd0);
+              }
+              copy16<T>(crow + 2 * D + sd0, row + 2 * D + sd0);
+            }
+          }
           if (rot) rope16<T>(k, cs, sn, pos, sd0);
         } else {
 #pragma unroll
@@ -320,11 +370,12 @@ __global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ r
 
 }  // namespace
 
-extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
-                                const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
-                                const float* cos_t, const float* sin_t, int n_seq, int n_options, int suffix_len,
-                                int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
-                                int dtype, void* stream) {
+namespace {
+template <bool APPEND>
+int suffix_launch(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                  const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t, const float* sin_t,
+                  int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim, int adapter_len,
+                  int max_feats, int cache_rotated, int dtype, void* stream) {
   if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !len || !cos_t || !sin_t)
     return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
@@ -332,19 +383,39 @@ extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void
       head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
     return FVQA_ESHAPE;
   if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || n_options > 4096) return FVQA_ESHAPE;
+  if (APPEND && n_options != 1) return FVQA_ESHAPE;      // (options share one cache: only a single continuation may join it)
   if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
   dim3 grid(n_heads, n_seq), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FVQA_H16)
-    hipLaunchKernelGGL(attn_suffix_k<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
+    hipLaunchKernelGGL((attn_suffix_k<bf16_t, APPEND>), grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
                        (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
                        seq_len, n_heads, adapter_len, max_feats, cache_rotated);
   else
-    hipLaunchKernelGGL(attn_suffix_k<float>, grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
+    hipLaunchKernelGGL((attn_suffix_k<float, APPEND>), grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
                        (float*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
                        seq_len, n_heads, adapter_len, max_feats, cache_rotated);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
+}
+}  // namespace
+
+extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
+                                const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
+                                const float* cos_t, const float* sin_t, int n_seq, int n_options, int suffix_len,
+                                int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
+                                int dtype, void* stream) {
+  return suffix_launch<false>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options,
+                              suffix_len, seq_len, n_heads, head_dim, adapter_len, max_feats, cache_rotated, dtype, stream);
+}
+
+extern "C" int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, void* o_suf, const float* gate1,
+                                       const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
+                                       const float* cos_t, const float* sin_t, int n_seq, int suffix_len, int seq_len,
+                                       int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated, int dtype,
+                                       void* stream) {
+  return suffix_launch<true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, 1, suffix_len,
+                             seq_len, n_heads, head_dim, adapter_len, max_feats, cache_rotated, dtype, stream);
 }
 
 extern "C" int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,

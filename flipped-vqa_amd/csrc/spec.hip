@@ -1,0 +1,238 @@
+// The token step of draft-and-verify greedy decoding (fvqa/generate.py: generate(lookahead=T)): everything between the LM head
+// and the next pass's first RMSNorm in ONE launch, one 256-thread workgroup per sequence. A pass carries up to T rows per
+// sequence — the last committed token and a draft of what follows it — and this step keeps every draft token the model would
+// have picked itself, so that the ids are greedy's, token for token (include/fvqa.h fvqa_spec_step states the rule).
+//
+//   verify   row i of the sequence's logits is scanned only if the drafts 1..i were all accepted: the largest logit (lowest
+//            index on exact ties, fvqa_decode_next's loop), then the row's lse for the log-probability (fvqa_decode_next_ex's
+//            rule 5: maximum, sum of expf in strided order, shuffles, the four waves in order). The token committed at row i is
+//            argmax L_i whether it was drafted or not — a draft only decides whether row i + 1 may be used —, so there is one
+//            commit loop and no separate "fresh token" case.
+//   commit   thread 0 writes the id row; the committed tokens also stay in LDS, so that the draft below never reads back what
+//            this launch wrote to global memory.
+//   draft    given drafts: a slice of the caller's (n_seq, max_new_tokens) array at the row's n_generated. Prompt lookup: the
+//            longest suffix of the committed ids (g = G down to 1 tokens) that occurs earlier in the row, the most recent
+//            occurrence, found by all threads over the match ends e and one block-wide maximum; the draft is what followed it.
+//            Every index is clamped, every id that would be fed on is checked against [0, vocab).
+//   outputs  the rows of the next pass (embeddings; zeros behind the draft), start / len for fvqa_attn_suffix_append, the step's
+//            tokens and log-probabilities, the count of running rows through the caller's ticket word (an INTEGER atomic; the
+//            workgroup that arrives last writes the count and puts the word back to zero, as in csrc/sample.hip).
+// No float atomics, fixed summation orders: two launches on the same inputs give the same bits.
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int TMAX = 16;                 // rows of a sequence per pass (fvqa_attn_suffix's suffix_len limit)
+constexpr int GMAX = 4;                  // the longest n-gram the prompt lookup matches
+
+__device__ __forceinline__ int block_min_int(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  return min(min(red[0], red[1]), min(red[2], red[3]));
+}
+__device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
+
+template <typename T>
+__global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logits, const T* __restrict__ emb,
+                                                  const int32_t* __restrict__ draft_tokens, int G, int eos_id, int stop_at_eos,
+                                                  int max_new, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
+                                                  int32_t* __restrict__ done, int32_t* __restrict__ n_generated,
+                                                  int32_t* __restrict__ w, int32_t* __restrict__ len_p,
+                                                  int32_t* __restrict__ start_p, T* __restrict__ x_next,
+                                                  int32_t* __restrict__ token_out, float* __restrict__ logprob_out,
+                                                  int32_t* __restrict__ n_committed, int32_t* __restrict__ n_drafted,
+                                                  int32_t* __restrict__ n_active, unsigned* __restrict__ counter,
+                                                  int64_t* __restrict__ pos64, int B, int Tn, int V, int D, int S, int vec16) {
+  __shared__ float redf[4];
+  __shared__ int redi[4];
+  __shared__ int cm[TMAX];               // the tokens committed by this step, in order
+  __shared__ int wn[TMAX];               // the rows of the next pass: w'_0 .. w'_{m'-1}
+  __shared__ int s_len;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int64_t* row_ids = ids + (size_t)b * S;
+  const int32_t* wrow = w + (size_t)b * Tn;
+  const int p0 = pos[b];
+  int ngen = n_generated[b];
+  int m = len_p[b];
+  m = m < 1 ? 1 : (m > Tn ? Tn : m);
+  // a finished row, one with no room for another token and one whose budget is spent commit nothing
+  const bool live = done[b] == 0 && p0 >= -1 && p0 + 1 < S && ngen < max_new;
+  int now_done = live ? 0 : 1;
+  int p = p0, nc = 0;
+
+  // ---- verify and commit: row i is scanned only while the drafts keep being accepted
+  if (live) {
+    for (int i = 0; i < m; ++i) {
+      const float* lg = logits + ((size_t)b * Tn + i) * V;
+      float bv = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int v = tid; v < V; v += NT) {
+        const float x = lg[v];
+        if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
+      }
+      const float mx = block_max_256(bv, redf);
+      int g = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
+      if (g >= V) g = 0;                                           // (a row of NaNs)
+      float z = 0.f;
+      for (int v = tid; v < V; v += NT) z += expf(lg[v] - mx);
+      const float lse = mx + logf(block_sum_256(z, redf));
+      p += 1;
+      ngen += 1;
+      if (tid == 0) {
+        cm[nc] = g;
+        row_ids[p] = g;                                            // (p <= S - 1: checked before every commit)
+        token_out[(size_t)b * Tn + nc] = g;
+        logprob_out[(size_t)b * Tn + nc] = lg[g] - lse;
+      }
+      nc += 1;
+      if (stop_at_eos && g == eos_id) { now_done = 1; break; }
+      if (ngen >= max_new) { now_done = 1; break; }
+      if (p + 1 >= S || i + 1 >= m) break;
+      if (wrow[i + 1] != g) break;                                 // the draft of row i + 1 is not what the model picks
+    }
+  }
+  __syncthreads();                                                 // (cm is published; every read of pos / done / len is over)
+
+  // ---- the next pass: w'_0, the room m', the draft
+  const int P = p;                                                 // the row's position now (live: 0 <= P <= S - 1)
+  const int at = P < 0 ? 0 : (P >= S ? S - 1 : P);
+  int m2 = 0;
+  if (!now_done) {
+    m2 = min(Tn, min(max_new - ngen, S - 1 - P));
+    if (m2 < 0) m2 = 0;
+  }
+  // id j of the row, 0 <= j <= P: what this step committed comes from LDS
+  auto id_at = [&](int j) -> int64_t { return j > p0 ? (int64_t)cm[j - p0 - 1] : row_ids[j]; };
+  int e_best = -1;
+  if (m2 >= 2 && !draft_tokens) {
+    for (int g = min(G, P); g >= 1; --g) {                         // an occurrence ends at e with g - 1 <= e < P
+      int best = -1;
+      for (int e = g - 1 + tid; e < P; e += NT) {
+        bool same = true;
+        for (int k = 0; k < g; ++k) same = same && id_at(e - k) == id_at(P - k);
+        if (same) best = e;                                        // (ascending e: the thread's most recent match)
+      }
+      best = block_max_int(best, redi);
+      if (best >= 0) { e_best = best; break; }
+    }
+  }
+  if (tid == 0) {
+    int w0;
+    if (live) {
+      w0 = cm[nc - 1];
+    } else {
+      const int64_t t = row_ids[at];
+      w0 = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);                  // any valid embedding row: the batch stays rectangular
+    }
+    wn[0] = w0;
+    int nd = 0;
+    if (m2 >= 2) {
+      if (draft_tokens) {
+        for (int i = 1; i < m2; ++i) {
+          const int at_d = ngen + i - 1;
+          if (at_d < 0 || at_d >= max_new) break;
+          const int t = draft_tokens[(size_t)b * max_new + at_d];
+          if ((unsigned)t >= (unsigned)V) break;
+          wn[i] = t;
+          nd += 1;
+        }
+      } else if (e_best >= 0) {
+        const int lim = min(m2 - 1, P - e_best);
+        for (int i = 1; i <= lim; ++i) {
+          const int64_t t = id_at(e_best + i);
+          if (t < 0 || t >= V) break;
+          wn[i] = (int)t;
+          nd += 1;
+        }
+      }
+    }
+    const int mlen = m2 >= 1 ? 1 + nd : 0;
+    s_len = mlen;
+    // ---- the row's state (a row that committed nothing keeps its ids, pos, n_generated and w) and the step's results
+    if (live) {
+      pos[b] = p;
+      n_generated[b] = ngen;
+      for (int j = 0; j < Tn; ++j) w[(size_t)b * Tn + j] = j < mlen ? wn[j] : -1;
+    }
+    done[b] = now_done;
+    len_p[b] = mlen;
+    start_p[b] = at;
+    if (pos64) pos64[b] = at;
+    for (int j = nc; j < Tn; ++j) {
+      token_out[(size_t)b * Tn + j] = -1;
+      logprob_out[(size_t)b * Tn + j] = 0.f;
+    }
+    n_committed[b] = nc;
+    n_drafted[b] = live ? m - 1 : 0;
+    const unsigned old = atomicAdd(counter, 1u + (now_done ? 0u : 0x10000u));
+    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
+      *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
+      atomicExch(counter, 0u);
+    }
+  }
+  __syncthreads();
+  // ---- the next pass's input rows: emb[w'_j] for j < m' (row 0 always: a row that feeds nothing stays a valid row), zeros behind
+  int n_emb = s_len;
+  if (n_emb < 1) n_emb = 1;
+  for (int j = 0; j < Tn; ++j) {
+    T* dst = x_next + ((size_t)b * Tn + j) * D;
+    if (j < n_emb) {
+      const T* src = emb + (size_t)wn[j] * D;
+      if (vec16) {
+        const int n16 = (int)((size_t)D * sizeof(T) / 16);
+        for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+      } else {
+        for (int i = tid; i < D; i += NT) dst[i] = src[i];
+      }
+    } else if (vec16) {
+      const int n16 = (int)((size_t)D * sizeof(T) / 16);
+      for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+      for (int i = tid; i < D; i += NT) dst[i] = from_f32<T>(0.f);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int fvqa_spec_step(const float* logits, const void* emb, const int32_t* draft_tokens, int lookup_ngram, int eos_id,
+                              int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done,
+                              int32_t* n_generated, int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token,
+                              float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active, uint32_t* counter,
+                              int64_t* pos64, int n_seq, int lookahead, int vocab, int dim, int seq_len, int dtype,
+                              void* stream) {
+  if (!logits || !emb || !ids || !pos || !done || !n_generated || !w || !len || !start || !x_next || !token || !logprob ||
+      !n_committed || !n_drafted || !n_active || !counter)
+    return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (!draft_tokens && (lookup_ngram < 1 || lookup_ngram > GMAX)) return FVQA_EINVAL;
+  if (n_seq <= 0 || lookahead <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0) return FVQA_ESHAPE;
+  if (lookahead > TMAX || n_seq > 65535 || (int64_t)n_seq * lookahead > 65535) return FVQA_ESHAPE;   // (the ticket counts
+                                                                   // arrivals in 16 bits; the pass's rows are a grid dimension)
+  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) ||
+      !fvqa_aligned(4, logits, draft_tokens, pos, done, n_generated, w, len, start, token, logprob, n_committed, n_drafted,
+                    n_active, counter) ||
+      !fvqa_aligned(8, ids, pos64))
+    return FVQA_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FVQA_H16) {
+    const int vec16 = ((size_t)dim * sizeof(bf16_t)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
+    hipLaunchKernelGGL(spec_step_k<bf16_t>, dim3(n_seq), dim3(NT), 0, st, logits, (const bf16_t*)emb, draft_tokens,
+                       lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
+                       (bf16_t*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead,
+                       vocab, dim, seq_len, vec16);
+  } else {
+    const int vec16 = ((size_t)dim * sizeof(float)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
+    hipLaunchKernelGGL(spec_step_k<float>, dim3(n_seq), dim3(NT), 0, st, logits, (const float*)emb, draft_tokens,
+                       lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
+                       (float*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead,
+                       vocab, dim, seq_len, vec16);
+  }
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}

@@ -46,11 +46,13 @@ SIGNATURES = {
     "fvqa_attn_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_attn_decode": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_attn_suffix": (_i, [_p] * 10 + [_i] * 10 + [_p]),
+    "fvqa_attn_suffix_append": (_i, [_p] * 10 + [_i] * 9 + [_p]),
     "fvqa_option_pick": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fvqa_decode_next": (_i, [_p, _p, _p, _f, _f, _i, _i] + [_p] * 8 + [_i] * 5 + [_p]),
     "fvqa_decode_next_ex": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p]),
     "fvqa_decode_next_trie": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 7 + [_p]),
     "fvqa_decode_next_pair": (_i, [_p, _p, _p, _f, _f, _i, _f, _f, _f, _i, _i] + [_p] * 16 + [_i] * 7 + [_p]),
+    "fvqa_spec_step": (_i, [_p, _p, _p, _i, _i, _i, _i] + [_p] * 15 + [_i] * 6 + [_p]),
     "fvqa_beam_step": (_i, [_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
     "fvqa_beam_step_trie": (_i, [_p, _p, _i, _i, _i] + [_p] * 16 + [_i] * 8 + [_p]),
     "fvqa_kv_beam_move_scratch": (_sz, [_i, _i, _i, _i, _i]),

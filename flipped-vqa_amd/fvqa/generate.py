@@ -138,7 +138,8 @@ def match_answers(model, data: dict, ids: torch.Tensor) -> Tuple[torch.Tensor, t
 def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float = 0.0, top_p: float = 1.0,
              stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
-             constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1) -> dict:
+             constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1,
+             lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -193,7 +194,36 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       token —, the lag-one stop on the count of pairs. The results have today's shapes, taken from the positive rows, and gain
       "n_plausible" (B[, n], steps) int32: |P| at each step, 0 where "tokens" is -1.
       ValueError: a key the batch lacks, a tensor of another shape, contrast_alpha < 0, contrast_beta outside [0, 1],
-      num_beams > 1, 2 * B * num_return_sequences > 65535. Not built: a contrastive beam step; negatives whose TEXT differs."""
+      num_beams > 1, 2 * B * num_return_sequences > 65535. Not built: a contrastive beam step; negatives whose TEXT differs.
+    lookahead T (0 or 1: every code path above runs untouched): draft-and-verify greedy decoding, `_generate_lookahead` below —
+      several tokens per pass through the layers (prompt-lookup / assisted generation, restricted to greedy). A pass carries up
+      to T rows per sample: the last committed token and a draft of up to T - 1 tokens behind it; every draft token that equals
+      the greedy choice is committed, so "ids", "n_generated" and "tokens" are those of the plain greedy call, token for token
+      ("tokens" is (B, longest row), padded with -1). The draft: with draft_tokens (B, max_new_tokens) int32 the answer someone
+      else proposes, read at each row's n_generated (an entry outside [0, vocab) ends a draft); without, prompt lookup — the
+      longest suffix of up to lookup_ngram (1 .. 4) committed tokens that occurs earlier in the row, most recent occurrence, and
+      what followed it (a multiple-choice prompt lists its answers). include/fvqa.h fvqa_spec_step states the rule. "steps" counts
+      the token steps launched; the results gain "n_committed" and "n_drafted" (B, steps) int32: the tokens each step committed
+      and the draft tokens it was offered. return_logprobs is served as above ("logprobs" (B, longest row), "sum_logprob").
+      ValueError: temperature > 0, num_beams > 1, top_k, repetition_penalty != 1, num_return_sequences > 1, constraints,
+      contrast, lookahead > 16 (ops.SUFFIX_MAX) or < 0, draft_tokens of another shape or without lookahead >= 2, lookup_ngram
+      outside [1, 4], B * T > 65535. Not built: drafts under sampling (they need the rejection rule), under beam search, a trie
+      or a contrastive pick; a draft model."""
+    if int(lookahead) != lookahead or not 0 <= lookahead <= ops.SUFFIX_MAX:
+        raise ValueError(f"generate: 0 <= lookahead <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
+    if lookahead < 2 and draft_tokens is not None:
+        raise ValueError("generate: draft_tokens are verified by lookahead >= 2")
+    if lookahead >= 2:
+        if temperature > 0 or num_beams != 1:
+            raise ValueError("generate: lookahead verifies drafts against the GREEDY choice: temperature == 0, num_beams == 1")
+        if top_k != 0 or repetition_penalty != 1 or num_return_sequences != 1:
+            raise ValueError("generate: lookahead is not built for top_k, repetition_penalty or num_return_sequences")
+        if constraints is not None or contrast is not None:
+            raise ValueError("generate: lookahead is not built for constraints or contrast")
+        if draft_tokens is None and (int(lookup_ngram) != lookup_ngram or not 1 <= lookup_ngram <= ops.LOOKUP_NGRAM_MAX):
+            raise ValueError(f"generate: 1 <= lookup_ngram <= {ops.LOOKUP_NGRAM_MAX}")
+        return _generate_lookahead(eng, data, T=int(lookahead), G=int(lookup_ngram), draft_tokens=draft_tokens,
+                                   max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, return_logprobs=return_logprobs)
     if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
     if num_beams > 1 and temperature > 0:
@@ -358,6 +388,107 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                     out[k] = out[k].view(B0, n, *out[k].shape[1:])
         if trie is not None:
             out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
+        return out
+
+
+@torch.no_grad()
+def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_new_tokens: int, stop_at_eos: bool,
+                        return_logprobs: bool) -> dict:
+    """generate(lookahead=T >= 2): the plain loop — the same prefill, the same lag-one stop on the count of running rows, the
+    same buffers at B * T rows — with fvqa_spec_step as its token step (verify the pass's drafts, commit, draft the next pass:
+    one launch) and, per layer, the suffix attention whose rows join the cache (ops.attn_suffix_append) where the plain loop
+    runs the one-row attention. Rejected drafts leave k / v behind a row's position; the next pass overwrites them from its
+    `start` on and reads nothing behind it."""
+    m, pk = eng.model, eng.pack
+    dev = eng.device
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+    if max_new_tokens < 1:
+        raise ValueError("generate: max_new_tokens >= 1")
+    ids_all = data["text_id"]["vqa"]
+    B, _, S = ids_all.shape
+    if B * T > 65535:
+        raise ValueError("generate: at most 65535 rows per pass (samples times lookahead)")
+    if draft_tokens is not None:
+        draft_tokens = torch.as_tensor(draft_tokens)
+        if tuple(draft_tokens.shape) != (B, int(max_new_tokens)) or draft_tokens.is_floating_point():
+            raise ValueError(f"generate: draft_tokens must be integers of shape (B, max_new_tokens) = ({B}, {int(max_new_tokens)})")
+        draft_tokens = draft_tokens.to(device=dev, dtype=torch.int32).contiguous()
+    sub = {k: data[k] for k in ("video", "audio") if k in data}
+    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    with vqa_stream_only(eng, "_gen_arena", "all"):
+        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
+        ar = eng.arena(B, S)
+        vstart = eng.saved["vstart"]
+        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
+        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
+        ids = ids_all[:, 0].to(dev).clone()
+        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
+        start = prefix - 1                                  # the position the first token is predicted at
+        R = B * T                                           # the rows of a pass
+        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+        xin, xn, hn, h, xb, o_rows = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+        qkv_rows, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
+        lg = torch.zeros(R, V, dtype=torch.float32, device=dev)
+        lg.view(B, T, V)[:, 0].copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
+        i32 = dict(dtype=torch.int32, device=dev)
+        pos, pos64 = start.to(torch.int32), start.clone()
+        done, n_gen, at = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        w, length = torch.full((B, T), -1, **i32), torch.ones(B, **i32)      # the first step verifies nothing: one row, no draft
+        tokens = torch.full((max_new_tokens, B, T), -1, **i32)
+        logprobs = torch.zeros(max_new_tokens, B, T, dtype=torch.float32, device=dev)
+        n_committed, n_drafted = torch.zeros(max_new_tokens, B, **i32), torch.zeros(max_new_tokens, B, **i32)
+        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
+        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
+        arrived = []
+        steps = 0
+        for t in range(max_new_tokens):
+            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
+                arrived[t - 2].synchronize()
+                if int(running[t - 2]) == 0:
+                    break
+            ops.spec_step(lg, pk.emb, ids, pos, done, n_gen, w, length, at, xin, tokens[t], logprobs[t], n_committed[t],
+                          n_drafted[t], n_active[t:t + 1], counter, max_new_tokens=int(max_new_tokens),
+                          draft_tokens=draft_tokens, lookup_ngram=G, pos64=pos64, eos_id=m.tokenizer.eos_id,
+                          stop_at_eos=stop_at_eos)
+            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            arrived.append(ev)
+            steps = t + 1
+            if steps == max_new_tokens:
+                break                                       # (every row has committed at least one token per step)
+            x, x2 = xin, xb
+            for i in range(L):                              # the plain loop's layer, on the pass's rows
+                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
+                ops.gemm_nt(xn, pk.wqkv[i], qkv_rows)
+                g1, g2 = m.gate_views(i)
+                ops.attn_suffix_append(qkv_rows, ar.qkv[i], o_rows, g1, g2, vstart, at, length, (eng.cos, eng.sin), B, T, S, H,
+                                       Dh, A, F, cache_rotated=not fused)
+                ops.gemm_nt(o_rows, pk.wo[i], h, residual=x)
+                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
+                ops.gemm_nt(hn, pk.w13[i], ab)
+                ops.swiglu_fwd(ab, z, R, Hf)
+                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
+                x, x2 = x2, x
+            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=R)
+            ops.gemm_nt(xn, pk.wout, lg)
+        n_generated = n_gen.to(torch.int64)
+        longest = int(n_generated.max())
+        col = torch.arange(longest, device=dev).unsqueeze(0)
+        inside = col < n_generated.unsqueeze(1)
+        tok = ids.gather(1, (prefix.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
+        out = {"ids": ids, "n_generated": n_generated, "steps": steps,
+               "tokens": torch.where(inside, tok, torch.full_like(tok, -1)),
+               "n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()}
+        if return_logprobs:                                 # the steps' (B, T) results, in order, without their padding
+            flat = tokens[:steps].permute(1, 0, 2).reshape(B, steps * T)
+            order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :longest]
+            lp = logprobs[:steps].permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
+            out["logprobs"] = torch.where(inside, lp, torch.zeros_like(lp))
+            out["sum_logprob"] = out["logprobs"].sum(1)
         return out
 
 

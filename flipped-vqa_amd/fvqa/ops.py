@@ -583,6 +583,32 @@ def attn_suffix(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, 
     return o_suf
 
 
+def attn_suffix_append(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, T, S, H, Dh, A, F,
+                       cache_rotated: bool):
+    """attn_suffix for ONE continuation per sequence whose rows join the cache (include/fvqa.h fvqa_attn_suffix_append; the
+    draft-and-verify pass of generate(lookahead=T)): qkv_suf (n_seq*T, 3*D) RAW projections of row j of sequence n at position
+    start[n] + j. Writes o_suf (n_seq*T, D) as attn_suffix does, and the k (in the cache's convention) and v of the rows
+    j < length[n] into cache row n*S + start[n] + j — the bits attn_decode stores for the same raw row and position."""
+    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_suffix_append")
+    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
+    R = n_seq * T
+    _need(cos_t is not None, "attn_suffix_append: rope tables")
+    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, "attn_suffix_append: dtype")
+    _need(1 <= T <= SUFFIX_MAX, f"attn_suffix_append: 1 <= rows per sequence <= {SUFFIX_MAX}")
+    _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), "attn_suffix_append: row shapes")
+    for t in (vstart, start, length):
+        _need(t.dtype == torch.int32 and t.numel() == n_seq, "attn_suffix_append: vstart / start / len are int32 (n_seq)")
+    for t in (gate1, gate2):
+        _need(t.dtype == torch.float32 and t.numel() == H, "attn_suffix_append: gate shape")
+    rc = _lib.load(qkv_cache.dtype).fvqa_attn_suffix_append(_ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1),
+                                                            _ptr(gate2), _ptr(vstart), _ptr(start), _ptr(length), _ptr(cos_t),
+                                                            _ptr(sin_t), n_seq, T, S, H, Dh, A, F, 1 if cache_rotated else 0,
+                                                            dt_code(qkv_suf.dtype), _stream())
+    _lib.check(rc, "fvqa_attn_suffix_append")
+    return o_suf
+
+
 def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: int):
     """The per-option reduction (include/fvqa.h fvqa_option_pick): rowloss fp32 compact per-row losses, row_map int32 (entry of
     (n_seq, n_options, S-1) each of the first n_rows rows belongs to, < 0 none) ->
@@ -657,6 +683,51 @@ def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept
                                                   _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), B, V,
                                                   D, ids.shape[1], dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next_ex")
+    return token
+
+
+LOOKUP_NGRAM_MAX = 4     # the longest n-gram fvqa_spec_step's prompt lookup matches (csrc/spec.hip GMAX)
+
+
+def spec_step(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted,
+              n_active, counter, *, max_new_tokens: int, draft_tokens=None, lookup_ngram: int = 2, pos64=None, eos_id: int = 2,
+              stop_at_eos: bool = True):
+    """The token step of draft-and-verify greedy decoding (include/fvqa.h fvqa_spec_step states the rule). logits (B*T, V) fp32:
+    row n*T + j was computed at position pos[n] + j on the token w[n, j] (j = 0: the last committed token, ids[n, pos[n]]).
+    In/out: ids (B, S) int64, pos / done / n_generated / length (B,) int32, w (B, T) int32. Out: start (B,) int32, x_next (B*T, D),
+    token (B, T) int32 (-1 padded), logprob (B, T) fp32 (0 padded), n_committed / n_drafted (B,) int32, n_active (1,) int32,
+    pos64 (B,) int64 or None. counter: one int32 word the caller zeroed once. draft_tokens (B, max_new_tokens) int32: the drafts
+    are read from it at each row's n_generated; None: prompt lookup with n-grams of up to lookup_ngram tokens."""
+    _dev(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted, n_active,
+         counter, draft_tokens, pos64)
+    _need(w.dim() == 2 and w.dtype == torch.int32, "spec_step: w (B, T) int32")
+    B, T = w.shape
+    _need(1 <= T <= SUFFIX_MAX and 1 <= B <= 65535 and B * T <= 65535, f"spec_step: 1 <= T <= {SUFFIX_MAX}, B * T <= 65535")
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] == B * T, "spec_step: logits (B*T, V) fp32")
+    V = logits.shape[1]
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "spec_step: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B * T, D), "spec_step: x_next (B*T, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "spec_step: ids (B, S) int64")
+    for t, n in ((pos, B), (done, B), (n_generated, B), (length, B), (start, B), (n_committed, B), (n_drafted, B), (n_active, 1),
+                 (counter, 1), (token, B * T)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "spec_step: pos / done / n_generated / len / start / n_committed / "
+                                                         "n_drafted (B,), token (B, T), n_active / counter (1,) int32")
+    _need(logprob.dtype == torch.float32 and logprob.numel() == B * T, "spec_step: logprob (B, T) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "spec_step: pos64 (B,) int64")
+    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, "spec_step: max_new_tokens >= 1")
+    if draft_tokens is None:
+        _need(int(lookup_ngram) == lookup_ngram and 1 <= lookup_ngram <= LOOKUP_NGRAM_MAX,
+              f"spec_step: 1 <= lookup_ngram <= {LOOKUP_NGRAM_MAX}")
+    else:
+        _need(draft_tokens.dtype == torch.int32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
+              "spec_step: draft_tokens (B, max_new_tokens) int32")
+    rc = _lib.load(emb.dtype).fvqa_spec_step(_ptr(logits), _ptr(emb), _ptr(draft_tokens), int(lookup_ngram), int(eos_id),
+                                             1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done),
+                                             _ptr(n_generated), _ptr(w), _ptr(length), _ptr(start), _ptr(x_next), _ptr(token),
+                                             _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(counter),
+                                             _ptr(pos64), B, T, V, D, ids.shape[1], dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_spec_step")
     return token
 
 

@@ -233,6 +233,8 @@ class Transformer(nn.Module):
         from fvqa import generate
         eng = self.ensure_engine()
         mode = getattr(self.args, "gen_constrain", None)
+        if int(getattr(self.args, "lookahead", 0) or 0) > 1 and (mode or getattr(self.args, "contrast", None)):
+            raise ValueError("--lookahead verifies drafts against the greedy choice: not with --gen_constrain or --contrast")
         if mode:                                            # --gen_constrain: decode under the allowed answers
             return self._constrained_inference(data, mode)
         if getattr(self.args, "contrast", None):            # --contrast blind: each token from the difference to the blind twin
@@ -241,6 +243,15 @@ class Transformer(nn.Module):
             ids = out["ids"]
             best, sims, extracted = generate.match_answers(self, data, ids)
             self.last_generation = {"ids": ids, "similarities": sims, "n_plausible": out["n_plausible"]}
+            return best, extracted
+        if int(getattr(self.args, "lookahead", 0) or 0) > 1:    # --lookahead T: greedy's tokens, several per pass
+            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
+                                    num_beams=int(getattr(self.args, "num_beams", 1) or 1), lookahead=int(self.args.lookahead),
+                                    lookup_ngram=int(getattr(self.args, "lookup_ngram", 2) or 2))
+            ids = out["ids"]
+            best, sims, extracted = generate.match_answers(self, data, ids)
+            self.last_generation = {"ids": ids, "similarities": sims, "n_committed": out["n_committed"],
+                                    "n_drafted": out["n_drafted"]}
             return best, extracted
         if int(getattr(self.args, "num_beams", 1) or 1) > 1:    # --num_beams N: the most likely answer under the model
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
@@ -301,16 +312,17 @@ class Transformer(nn.Module):
     def generate(self, data, **kw):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
-        return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta) -> one answer per row, the
+        return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta, lookahead, lookup_ngram,
+        draft_tokens) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
         "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
-        size of the plausible set at every token step). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",
-                                                     "n_plausible")
+                                                     "n_plausible", "n_committed", "n_drafted")
                                 if k in out}
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
 

@@ -84,6 +84,13 @@ _FLAGS = [
     ("--contrast_alpha", dict(type=float, default=1.0, help="--contrast: the weight of the difference to the twin (>= 0)")),
     ("--contrast_beta", dict(type=float, default=0.1, help="--contrast: a token is plausible iff its probability with the clip "
                                                            "is at least beta times the largest (0 .. 1; generation only)")),
+    ("--lookahead", dict(type=int, default=0,
+                         help="generation-task validation: draft-and-verify greedy decoding with up to T rows per pass "
+                              "(fvqa.generate.generate(lookahead=T)): greedy's tokens, each row ended by its EOS, several tokens "
+                              "per pass where the prompt-lookup draft is right. 0, 1: off. Not with --num_beams > 1, "
+                              "--gen_constrain or --contrast")),
+    ("--lookup_ngram", dict(type=int, default=2, help="--lookahead: the longest n-gram of committed tokens the prompt lookup "
+                                                      "matches (1 .. 4)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -94,7 +101,8 @@ _FLAGS = [
 
 class ArgumentParser(argparse.ArgumentParser):
     """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
-    --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range (answer.py uses it too)."""
+    --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead out of range or
+    together with a decode it is not built for (answer.py uses it too)."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -105,6 +113,15 @@ class ArgumentParser(argparse.ArgumentParser):
                 self.error("--contrast decodes with num_beams == 1: a contrastive beam search is not built")
             if not a.contrast_alpha >= 0 or not 0 <= a.contrast_beta <= 1:
                 self.error("--contrast_alpha >= 0, 0 <= --contrast_beta <= 1")
+        la = int(getattr(a, "lookahead", 0) or 0)
+        if la < 0 or la > 16:
+            self.error("0 <= --lookahead <= 16")
+        if la > 1:
+            if int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "gen_constrain", None) or getattr(a, "contrast", None):
+                self.error("--lookahead verifies drafts against the greedy choice: not with --num_beams > 1, --gen_constrain "
+                           "or --contrast")
+            if not 1 <= int(getattr(a, "lookup_ngram", 2)) <= 4:
+                self.error("1 <= --lookup_ngram <= 4")
         return a
 
 

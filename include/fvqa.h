@@ -249,6 +249,20 @@ int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, co
                      const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
                      const float* sin_t, int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim,
                      int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
+/* fvqa_attn_suffix for ONE continuation per sequence whose rows JOIN the cache (the same kernel template in csrc/score.hip with one
+ * more compile-time switch; the draft-and-verify pass of generate(lookahead=T), fvqa_spec_step below). The operands, limits and
+ * errors of fvqa_attn_suffix hold with n_options == 1: qkv_suf (n_seq*suffix_len, 3*dim), row n*suffix_len + j at sequence
+ * position start[n] + j; o_suf comes out bit for bit as fvqa_attn_suffix writes it. In addition the (head, sample) workgroup
+ * stores its head's slice of the rows j < len[n] (len clamped to seq_len - start[n]) into cache row n*seq_len + start[n] + j: k in
+ * the cache's convention — rotated at position start[n] + j and rounded to the storage type when cache_rotated is set, the raw
+ * bits otherwise —, v as it is: the bits fvqa_attn_decode stores for the same raw row and position. The q third of the cache,
+ * the rows j >= len[n], every other row of the cache and the adapter rows are not written. A query never reads a row this launch
+ * writes (it reads the cache rows [0, start[n]) and the suffix rows themselves), so rows left behind start[n] by an earlier call —
+ * rejected drafts — are overwritten or ignored, never read. */
+int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                            const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
+                            const float* sin_t, int n_seq, int suffix_len, int seq_len, int n_heads, int head_dim,
+                            int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
 /* The per-option reduction of the multiple-choice protocol (reference engine.py:86-93). rowloss: n_rows compact per-row losses
  * (fvqa_ce_fwd); row_map[r] = (n*n_options + c)*(seq_len-1) + t, the entry of individual_losses row r belongs to (< 0: a pad
  * row; each entry listed at most once). Writes individual_losses (n_seq, n_options, seq_len-1) fp32 — zero wherever no row was
@@ -375,6 +389,52 @@ int fvqa_decode_next_pair(const float* logits, const float* u, const void* emb, 
                           int32_t* n_plausible, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
                           int32_t* node, const int32_t* node_first, const int32_t* edge_token, const int32_t* edge_child,
                           int n_nodes, int n_edges, int n_seq, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* The token step of draft-and-verify greedy decoding (csrc/spec.hip; generate(lookahead=T); prompt-lookup / assisted generation
+ * restricted to greedy): one launch between the LM head and the next pass's first RMSNorm, one 256-thread workgroup per sequence.
+ * A pass feeds every sequence up to T = lookahead rows: the last committed token and a DRAFT of the tokens behind it. Every draft
+ * token that equals the greedy choice is committed, so the ids are those of fvqa_decode_next at temperature 0, token for token.
+ * Per row n, the pass was fed m = len[n] tokens w_0 .. w_{m-1} (1 <= m <= T; len is clamped into that range) at positions
+ * q .. q + m - 1, q = pos[n]: w_0 is the last committed token — it is ids[n, q] and is not read from w —, w_1 .. are the drafts,
+ * w[n, 1 .. m-1], which are NOT in ids. logits (n_seq*T, vocab) fp32: row n*T + j is L_j, computed at position q + j. (The first
+ * step: len = 1 and L_0 = the prefill's row at prefix - 1, as for fvqa_decode_next.) A row is live iff done == 0, pos >= -1,
+ * pos + 1 < seq_len and n_generated < max_new_tokens. Per live row:
+ *   1. verify: a = the largest value in [0, m - 1] with w_i == argmax L_{i-1} for all 1 <= i <= a; argmax is the first index on
+ *      exact ties (fvqa_decode_next's rule). Row L_i is scanned only if the drafts 1 .. i were accepted.
+ *   2. commit: the candidates w_1 .. w_a, then the fresh token g = argmax L_a — candidate i is argmax L_{i-1} either way —, in order:
+ *      ids[q + i] = candidate_i, pos += 1, n_generated += 1. Committing stops after a committed EOS when stop_at_eos is set, and
+ *      when n_generated == max_new_tokens: the row is then done. It also stops when pos + 1 >= seq_len: the row then has m' = 0
+ *      and becomes done at its next step, exactly as a full row does under fvqa_decode_next. The log-probability of a committed
+ *      token is L[tok] - lse(L) on the raw row it was verified against, lse = max + log(sum exp(l - max)) with the fixed summation
+ *      order of rule 5 of fvqa_decode_next_ex (the same bits).
+ *   3. draft the next pass, P = pos after the commit: w'_0 = the last committed token; m' = min(T, max_new_tokens - n_generated,
+ *      seq_len - 1 - P), 0 for a done row. With m' >= 2:
+ *      - draft_tokens != NULL ((n_seq, max_new_tokens) int32, read only): w'_i = draft_tokens[n, n_generated + i - 1] for
+ *        i = 1 .. m' - 1; the draft ends in front of the first entry outside [0, vocab) (a -1 ends it).
+ *      - draft_tokens == NULL, prompt lookup with G = lookup_ngram, 1 <= G <= 4, over the committed ids[n, 0 .. P]: for g = G down
+ *        to 1, e = the largest value with g - 1 <= e < P and ids[e-g+1 .. e] == ids[P-g+1 .. P]; the first g with a match wins
+ *        and w'_i = ids[e + i] for i = 1 .. min(m' - 1, P - e); the draft ends in front of the first id outside [0, vocab).
+ *      m' becomes 1 + the length of the draft (no match, an empty draft: 1 — a plain token step).
+ *   4. outputs: x_next (n_seq*T, dim): row n*T + j = emb[w'_j] for j < m', zeros behind; start[n] = P, len[n] = m', w[n, j] = w'_j
+ *      (-1 behind); token / logprob (n_seq, T): the tokens committed by this step in order and their log-probabilities, padded
+ *      with -1 / 0; n_committed[n]; n_drafted[n] = m - 1; pos64[n] = P (may be NULL); done.
+ * A row that is not live commits nothing and is done afterwards: ids, pos, n_generated and w are not written, token = -1,
+ * logprob = 0, n_committed = n_drafted = 0, len = 0, start = pos64 = pos clamped into the sequence, and row n*T of x_next is the
+ * embedding of the row's current token (a valid row: the batch stays rectangular; the same holds for a live row with m' = 0).
+ * n_active = the rows with done == 0 after the step, counted through `counter` exactly as in fvqa_decode_next_ex (ONE 32-bit
+ * word owned and zeroed once by the caller; every completed call leaves it zero; calls that share it must be ordered).
+ * With T == 1 (and max_new_tokens never reached) token, ids, pos, pos64, done, x_next and n_active are those of fvqa_decode_next
+ * at temperature 0, bit for bit.
+ * Rejected drafts leave their k and v in cache rows behind pos; nothing may read them: the next pass reads [0, start) plus its
+ * own rows and overwrites from start on (fvqa_attn_suffix_append).
+ * No float atomics, fixed summation orders: bitwise repeatable. Every index read from ids or draft_tokens is clamped.
+ * Limits: 1 <= lookahead <= 16, n_seq <= 65535, n_seq * lookahead <= 65535 (else FVQA_ESHAPE, as for a dimension <= 0).
+ * FVQA_EINVAL: a null pointer (draft_tokens and pos64 may be NULL), a bad dtype code, lookup_ngram outside [1, 4] when
+ * draft_tokens is NULL; FVQA_EALIGN: an operand off its element's boundary. */
+int fvqa_spec_step(const float* logits, const void* emb, const int32_t* draft_tokens, int lookup_ngram, int eos_id,
+                   int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done, int32_t* n_generated,
+                   int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token, float* logprob, int32_t* n_committed,
+                   int32_t* n_drafted, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int lookahead, int vocab,
+                   int dim, int seq_len, int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)

@@ -18,7 +18,13 @@ log-probabilities: the fvqa_decode_next_ex token step) / with N samples per prom
 plain sampling `generate` of the same batch — for N > 1 also N calls of it, which is what the fan-out replaces.
 --contrast times greedy `generate(contrast="blind", stop_at_eos=False)` — contrastive decoding runs twice the rows — interleaved
 (--pairs N times, default 3) with its two comparison points: the plain greedy `generate` of the same batch (B rows) and of a
-batch of 2 * B rows (the same layer pass as the pairs)."""
+batch of 2 * B rows (the same layer pass as the pairs).
+--lookahead T [T ...] times draft-and-verify greedy decoding, generate(lookahead=T, stop_at_eos=False), each arm interleaved
+(--pairs N times, default 3) with the same call without the keyword: the run's own answer as draft (full acceptance: the upper
+bound), drafts that are all wrong (the price of the wasted rows) and prompt lookup (--lookup_ngram G) on the synthetic batch as it
+is and with the first 12 answer tokens listed in the prompt, as a multiple-choice prompt lists its options. The weights are the
+`peakedperm` closed form of --eos_at: the greedy tokens are decided, whatever the number of rows in a pass. Per line: ms per
+batch, ms per committed token of a row, committed tokens per pass, and whether the ids are the plain call's."""
 import argparse
 import os
 import sys
@@ -52,6 +58,9 @@ def main():
                                                                        "each")
     ap.add_argument("--contrast", action="store_true", help="contrastive decoding against the blind twin, interleaved with greedy "
                                                             "generate at B and at 2 * B rows (--pairs rounds, default 3)")
+    ap.add_argument("--lookahead", type=int, nargs="*", default=[], help="draft-and-verify decoding with up to T rows per pass; "
+                                                                         "several T: three arms each, interleaved with plain generate")
+    ap.add_argument("--lookup_ngram", type=int, default=2, help="--lookahead: the prompt-lookup arm's longest n-gram")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -72,7 +81,7 @@ def main():
     b = synth.make_batch(cfg, seed=5)
     B = a.batch_size
     b["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B)]}
-    if a.eos_at:
+    if a.eos_at or a.lookahead:                  # decided tokens: what a draft is verified against must not hang on a near tie
         import dataclasses
         from llama_vqa import fill_closed_form
         fill_closed_form(model, dataclasses.replace(cfg, max_feats=margs.max_feats, bias=margs.bias, tau=margs.tau,
@@ -105,6 +114,9 @@ def main():
 
     if a.num_beams:
         beam_lines(a, eng, b, cfg, timed)
+        return
+    if a.lookahead:
+        lookahead_lines(a, eng, b, timed)
         return
     if a.contrast:
         import dataclasses
@@ -186,6 +198,38 @@ def device_us(fn, reps=20):
     ev[1].record()
     torch.cuda.synchronize()
     return ev[0].elapsed_time(ev[1]) * 1e3 / reps
+
+
+def lookahead_lines(a, eng, b, timed):
+    B, N = a.batch_size, generate.N_NEW
+    tag = f"{a.model} L={eng.L} B={B} S=128 greedy"
+    ref = generate.generate(eng, b, stop_at_eos=False)
+    answer = ref["tokens"].to(torch.int32)
+    listed = dict(b, text_id={"vqa": b["text_id"]["vqa"].clone()})              # the prompt lists the answer: last token, 12 answer
+    for i, pre in enumerate(b["prefix_index"]["vqa"]):                          # tokens, one other token, then the prompt's end
+        listed["text_id"]["vqa"][i, :, pre - 15] = b["text_id"]["vqa"][i, 0, pre - 1]
+        listed["text_id"]["vqa"][i, :, pre - 14:pre - 2] = answer[i, :12].cpu().to(torch.int64)
+        listed["text_id"]["vqa"][i, :, pre - 2] = 5
+    arms = (("the answer as draft", b, dict(draft_tokens=answer)),
+            ("drafts all wrong", b, dict(draft_tokens=(answer + 1) % eng.V)),
+            (f"prompt lookup, n-grams up to {a.lookup_ngram}", b, dict(lookup_ngram=a.lookup_ngram)),
+            (f"prompt lookup, n-grams up to {a.lookup_ngram}, 12 answer tokens listed in the prompt", listed,
+             dict(lookup_ngram=a.lookup_ngram)))
+    for T in a.lookahead:
+        for name, data, kw in arms:
+            out, base = {}, {}
+            plain = lambda: base.update(generate.generate(eng, data, stop_at_eos=False))               # noqa: E731
+            fn = lambda: out.update(generate.generate(eng, data, stop_at_eos=False, lookahead=T, **kw))   # noqa: E731
+            timed(plain, reps=1)
+            timed(fn, reps=1)
+            same = bool(torch.equal(out["ids"], base["ids"]))
+            passes = int((out["n_committed"].sum(0) > 0).sum())                  # (the steps that committed something)
+            for k in range(a.pairs or 3):
+                t_p, t_l = timed(plain, warm=0), timed(fn, warm=0)
+                print(f"{tag} round {k}: generate: {t_p * 1e3:7.1f} ms/batch, {t_p / N * 1e3:6.3f} ms per committed token | "
+                      f"lookahead={T}, {name}: {t_l * 1e3:7.1f} ms/batch, {t_l / N * 1e3:6.3f} ms per committed token, "
+                      f"{N / passes:5.2f} tokens per pass ({passes} passes, {out['steps']} steps launched), {t_p / t_l:5.2f}x; "
+                      f"ids {'equal' if same else 'DIFFER from'} the plain call's", flush=True)
 
 
 def beam_lines(a, eng, b, cfg, timed):
