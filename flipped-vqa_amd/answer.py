@@ -5,7 +5,7 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
         [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
         [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
-        [--lookahead T --lookup_ngram G]
+        [--lookahead T --lookup_ngram G] [--jump_forward T]
 
 `--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
 line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
@@ -13,6 +13,8 @@ line) makes it one of the file's answers (fvqa.generate.generate(constraints=...
 zero features — and prints how many tokens were plausible per step (fvqa.generate.generate(contrast="blind")).
 `--lookahead T` (train.py's flag; greedy only) verifies a prompt-lookup draft of up to T - 1 tokens per pass and prints how many
 tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
+`--jump_forward T` (with --constrain or --answer_vocab; greedy only) commits the tokens the trie of allowed answers fixes without
+a pass of their own, up to T per step, and prints the tokens committed per step (fvqa.generate.generate(jump_forward=T)).
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -53,6 +55,9 @@ def get_args_parser():
                    help="print each answer's log-probability under the model and its per-token geometric mean probability")
     p.add_argument("--constrain", action="store_true",
                    help="with --options: the answer is one of the options (constrained decoding); its index is printed")
+    p.add_argument("--jump_forward", type=int, default=0,
+                   help="with --constrain / --answer_vocab: up to T tokens per pass where the allowed answers leave no choice "
+                        "(0, 1: off)")
     p.set_defaults(max_seq_len=128, seed=None)
     return p
 
@@ -119,6 +124,8 @@ def main(args):
         kw.update(contrast=args.contrast, contrast_alpha=args.contrast_alpha, contrast_beta=args.contrast_beta)
     if args.lookahead > 1:
         kw.update(lookahead=args.lookahead, lookup_ngram=args.lookup_ngram)
+    if args.jump_forward > 1:
+        kw.update(jump_forward=args.jump_forward)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
                             seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
                             repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,

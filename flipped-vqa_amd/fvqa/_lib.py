@@ -53,6 +53,7 @@ SIGNATURES = {
     "fvqa_decode_next_trie": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 7 + [_p]),
     "fvqa_decode_next_pair": (_i, [_p, _p, _p, _f, _f, _i, _f, _f, _f, _i, _i] + [_p] * 16 + [_i] * 7 + [_p]),
     "fvqa_spec_step": (_i, [_p, _p, _p, _i, _i, _i, _i] + [_p] * 15 + [_i] * 6 + [_p]),
+    "fvqa_trie_jump_step": (_i, [_p] * 5 + [_i] * 6 + [_p] * 16 + [_i] * 6 + [_p]),
     "fvqa_beam_step": (_i, [_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
     "fvqa_beam_step_trie": (_i, [_p, _p, _i, _i, _i] + [_p] * 16 + [_i] * 8 + [_p]),
     "fvqa_kv_beam_move_scratch": (_sz, [_i, _i, _i, _i, _i]),

@@ -139,7 +139,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
              stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
              constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1,
-             lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None) -> dict:
+             lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None, jump_forward: int = 0) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -208,9 +208,38 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       ValueError: temperature > 0, num_beams > 1, top_k, repetition_penalty != 1, num_return_sequences > 1, constraints,
       contrast, lookahead > 16 (ops.SUFFIX_MAX) or < 0, draft_tokens of another shape or without lookahead >= 2, lookup_ngram
       outside [1, 4], B * T > 65535. Not built: drafts under sampling (they need the rejection rule), under beam search, a trie
-      or a contrastive pick; a draft model."""
+      or a contrastive pick; a draft model.
+    jump_forward T (0 or 1: every code path above runs untouched; needs `constraints`): jump-forward constrained greedy decoding,
+      `_generate_jump` below. Once a row's trie node has a single child the next token is fixed whatever the logits say, so a
+      token step picks the one token that is a decision and commits the tokens the trie fixes behind it, up to T per step; the
+      next pass feeds all of them (T rows per sample, lookahead's layer loop), so that their K / V join the cache without a pass
+      of their own. Nothing is drafted and nothing rejected: "ids", "n_generated", "tokens" ((B, longest row), -1 padded) and
+      "choice" are those of the plain generate(temperature=0, constraints=C) call, in as many passes as the generated path has
+      real decisions, plus those that chains longer than T tokens are cut into. include/fvqa.h fvqa_trie_jump_step states the
+      rule. The results gain "n_committed" (B, steps) int32. return_logprobs is served as above: a picked token's from its own
+      step, a chained token's from the pass that fed it — the EOS is then always PICKED, never chained, so that a row is still
+      running when the pass that owes its log-probabilities comes back (one more pass for an answer that ends in a chain).
+      ValueError: no constraints, temperature > 0, num_beams > 1, top_k, repetition_penalty != 1, num_return_sequences > 1,
+      contrast, lookahead >= 2, T > 16 (ops.SUFFIX_MAX) or < 0, B * T > 65535, stop_at_eos=False. Not built: sampling at the
+      picks, beams, contrast; the LM head on each sample's last fed row only (the other rows' logits are computed and, without
+      return_logprobs, never read)."""
     if int(lookahead) != lookahead or not 0 <= lookahead <= ops.SUFFIX_MAX:
         raise ValueError(f"generate: 0 <= lookahead <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
+    if int(jump_forward) != jump_forward or not 0 <= jump_forward <= ops.SUFFIX_MAX:
+        raise ValueError(f"generate: 0 <= jump_forward <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
+    if jump_forward >= 2:
+        if constraints is None:
+            raise ValueError("generate: jump_forward commits the tokens a trie fixes: it needs constraints")
+        if lookahead >= 2 or draft_tokens is not None:
+            raise ValueError("generate: jump_forward and lookahead are two token steps: one of them")
+        if temperature > 0 or num_beams != 1:
+            raise ValueError("generate: jump_forward is built for the greedy pick: temperature == 0, num_beams == 1")
+        if top_k != 0 or repetition_penalty != 1 or num_return_sequences != 1:
+            raise ValueError("generate: jump_forward is not built for top_k, repetition_penalty or num_return_sequences")
+        if contrast is not None:
+            raise ValueError("generate: jump_forward is not built for contrast")
+        return _generate_jump(eng, data, T=int(jump_forward), constraints=constraints, max_new_tokens=max_new_tokens,
+                              stop_at_eos=stop_at_eos, return_logprobs=return_logprobs)
     if lookahead < 2 and draft_tokens is not None:
         raise ValueError("generate: draft_tokens are verified by lookahead >= 2")
     if lookahead >= 2:
@@ -489,6 +518,108 @@ def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_ne
             lp = logprobs[:steps].permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
             out["logprobs"] = torch.where(inside, lp, torch.zeros_like(lp))
             out["sum_logprob"] = out["logprobs"].sum(1)
+        return out
+
+
+@torch.no_grad()
+def _generate_jump(eng, data: dict, *, T: int, constraints, max_new_tokens: int, stop_at_eos: bool,
+                   return_logprobs: bool) -> dict:
+    """generate(constraints=C, jump_forward=T >= 2): `_generate_lookahead`'s loop — the same prefill, the same lag-one stop, the
+    same buffers at B * T rows, the suffix attention whose rows join the cache — with fvqa_trie_jump_step as its token step: pick
+    one token on each row's last fed logits row, commit the tokens the trie fixes behind it, feed them all. Every row a pass
+    feeds is a committed token at its own position, so nothing rejected ever enters the cache."""
+    m, pk = eng.model, eng.pack
+    dev = eng.device
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+    if max_new_tokens < 1:
+        raise ValueError("generate: max_new_tokens >= 1")
+    ids_all = data["text_id"]["vqa"]
+    B, _, S = ids_all.shape
+    if B * T > 65535:
+        raise ValueError("generate: at most 65535 rows per pass (samples times jump_forward)")
+    trie = _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
+    want_lp = bool(return_logprobs)
+    sub = {k: data[k] for k in ("video", "audio") if k in data}
+    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    with vqa_stream_only(eng, "_gen_arena", "all"):
+        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
+        ar = eng.arena(B, S)
+        vstart = eng.saved["vstart"]
+        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
+        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
+        ids = ids_all[:, 0].to(dev).clone()
+        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
+        start = prefix - 1                                  # the position the first token is predicted at
+        R = B * T                                           # the rows of a pass
+        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+        xin, xn, hn, h, xb, o_rows = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
+        qkv_rows, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
+        lg = torch.zeros(R, V, dtype=torch.float32, device=dev)
+        lg.view(B, T, V)[:, 0].copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
+        i32 = dict(dtype=torch.int32, device=dev)
+        pos, pos64 = start.to(torch.int32), start.clone()
+        done, n_gen, at = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        w, length = torch.full((B, T), -1, **i32), torch.ones(B, **i32)      # the first step: one row, the prefill's
+        dtrie = trie.to(dev)
+        node = torch.as_tensor(trie.roots(B), dtype=torch.int32).to(dev).contiguous()
+        tokens = torch.full((max_new_tokens, B, T), -1, **i32)
+        lp_pick = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
+        lp_fed = torch.zeros(max_new_tokens + 1, B, T, dtype=torch.float32, device=dev)
+        n_committed = torch.zeros(max_new_tokens, B, **i32)
+        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
+        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
+        arrived = []
+        steps = 0
+        for t in range(max_new_tokens):
+            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
+                arrived[t - 2].synchronize()
+                if int(running[t - 2]) == 0:
+                    break
+            # with log-probabilities the EOS is never chained: a row that owes some is still live when they are read
+            ops.trie_jump_step(lg, pk.emb, ids, pos, done, n_gen, node, w, length, at, xin, tokens[t], lp_pick[t], lp_fed[t],
+                               n_committed[t], n_active[t:t + 1], counter, dtrie, max_new_tokens=int(max_new_tokens),
+                               chain_eos=not want_lp, want_logprobs=want_lp, pos64=pos64, eos_id=m.tokenizer.eos_id)
+            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            arrived.append(ev)
+            steps = t + 1
+            if steps == max_new_tokens:
+                break                                       # (every row has committed at least one token per step)
+            x, x2 = xin, xb
+            for i in range(L):                              # the plain loop's layer, on the pass's rows
+                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
+                ops.gemm_nt(xn, pk.wqkv[i], qkv_rows)
+                g1, g2 = m.gate_views(i)
+                ops.attn_suffix_append(qkv_rows, ar.qkv[i], o_rows, g1, g2, vstart, at, length, (eng.cos, eng.sin), B, T, S, H,
+                                       Dh, A, F, cache_rotated=not fused)
+                ops.gemm_nt(o_rows, pk.wo[i], h, residual=x)
+                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
+                ops.gemm_nt(hn, pk.w13[i], ab)
+                ops.swiglu_fwd(ab, z, R, Hf)
+                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
+                x, x2 = x2, x
+            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=R)
+            ops.gemm_nt(xn, pk.wout, lg)
+        n_generated = n_gen.to(torch.int64)
+        longest = int(n_generated.max())
+        col = torch.arange(longest, device=dev).unsqueeze(0)
+        inside = col < n_generated.unsqueeze(1)
+        tok = ids.gather(1, (prefix.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
+        out = {"ids": ids, "n_generated": n_generated, "steps": steps,
+               "tokens": torch.where(inside, tok, torch.full_like(tok, -1)),
+               "n_committed": n_committed[:steps].t().contiguous()}
+        if return_logprobs:                                 # token order: a step's pick, then its chain as the NEXT step read it
+            lp = torch.cat([lp_pick[:steps].unsqueeze(2), lp_fed[1:steps + 1, :, 1:]], 2)
+            flat = tokens[:steps].permute(1, 0, 2).reshape(B, steps * T)
+            order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :longest]
+            lp = lp.permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
+            out["logprobs"] = torch.where(inside, lp, torch.zeros_like(lp))
+            out["sum_logprob"] = out["logprobs"].sum(1)
+        out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
         return out
 
 

@@ -742,6 +742,52 @@ def _trie_arrays(trie, what: str):
     return nf, et, ec, nf.numel() - 1, et.numel()
 
 
+def trie_jump_step(logits, emb, ids, pos, done, n_generated, node, w, length, start, x_next, token, logprob_pick, logprob_fed,
+                   n_committed, n_active, counter, trie, *, max_new_tokens: int, chain_eos: bool = True,
+                   want_logprobs: bool = False, pos64=None, eos_id: int = 2):
+    """The token step of jump-forward constrained greedy decoding (include/fvqa.h fvqa_trie_jump_step states the rule). logits
+    (B*T, V) fp32: row n*T + j was computed on the token w[n, j]; the pick is made on row length[n] - 1. In/out: ids (B, S) int64,
+    pos / done / n_generated / node / length (B,) int32, w (B, T) int32. Out: start (B,) int32, x_next (B*T, D), token (B, T) int32
+    (-1 padded), logprob_pick (B,) and logprob_fed (B, T) fp32, n_committed (B,) int32, n_active (1,) int32, pos64 (B,) int64 or
+    None. counter: one int32 word the caller zeroed once. `trie`: a fvqa.constrain.TokenTrie on the device; None (with node None):
+    every row is unconstrained."""
+    _need((trie is None) == (node is None), "trie_jump_step: node and trie come together")
+    nf = et = ec = None
+    n_nodes = n_edges = 0
+    if trie is not None:
+        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "trie_jump_step")
+    _dev(logits, emb, ids, pos, done, n_generated, node, w, length, start, x_next, token, logprob_pick, logprob_fed, n_committed,
+         n_active, counter, pos64, nf, et, ec)
+    _need(w.dim() == 2 and w.dtype == torch.int32, "trie_jump_step: w (B, T) int32")
+    B, T = w.shape
+    _need(1 <= T <= SUFFIX_MAX and 1 <= B <= 65535 and B * T <= 65535, f"trie_jump_step: 1 <= T <= {SUFFIX_MAX}, B * T <= 65535")
+    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] == B * T,
+          "trie_jump_step: logits (B*T, V) fp32")
+    V = logits.shape[1]
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype,
+          "trie_jump_step: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B * T, D), "trie_jump_step: x_next (B*T, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "trie_jump_step: ids (B, S) int64")
+    for t, n in ((pos, B), (done, B), (n_generated, B), (length, B), (start, B), (n_committed, B), (n_active, 1), (counter, 1),
+                 (token, B * T)) + (() if node is None else ((node, B),)):
+        _need(t.dtype == torch.int32 and t.numel() == n, "trie_jump_step: pos / done / n_generated / node / len / start / "
+                                                         "n_committed (B,), token (B, T), n_active / counter (1,) int32")
+    _need(logprob_pick.dtype == torch.float32 and logprob_pick.numel() == B, "trie_jump_step: logprob_pick (B,) fp32")
+    _need(logprob_fed.dtype == torch.float32 and logprob_fed.numel() == B * T, "trie_jump_step: logprob_fed (B, T) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "trie_jump_step: pos64 (B,) int64")
+    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, "trie_jump_step: max_new_tokens >= 1")
+    rc = _lib.load(emb.dtype).fvqa_trie_jump_step(_ptr(logits), _ptr(emb), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges,
+                                                  int(eos_id), int(max_new_tokens), 1 if chain_eos else 0,
+                                                  1 if want_logprobs else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated),
+                                                  _ptr(node), _ptr(w), _ptr(length), _ptr(start), _ptr(pos64), _ptr(x_next),
+                                                  _ptr(token), _ptr(logprob_pick), _ptr(logprob_fed), _ptr(n_committed),
+                                                  _ptr(n_active), _ptr(counter), B, T, V, D, ids.shape[1], dt_code(emb.dtype),
+                                                  _stream())
+    _lib.check(rc, "fvqa_trie_jump_step")
+    return token
+
+
 def decode_next_trie(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, node, trie, *,
                      u=None, pos64=None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
                      repetition_penalty: float = 1.0, eos_id: int = 2, stop_at_eos: bool = True):

@@ -298,14 +298,18 @@ class Transformer(nn.Module):
                 self._answer_vocab_trie = trie
         else:
             raise ValueError(f"gen_constrain: 'options' or 'vocab', not {mode!r}")
+        jump = int(getattr(self.args, "gen_jump_forward", 0) or 0)      # --gen_jump_forward T: forced tokens without a pass of
+        kw = {"jump_forward": jump} if jump > 1 else {}                 # their own (0, 1: the call made before the flag existed)
         out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)), temperature=0.0,
                                 stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie,
-                                **self._contrast_kw())
+                                **self._contrast_kw(), **kw)
         ids, choice = out["ids"], out["choice"]
         best, sims, extracted = generate.match_answers(self, data, ids)
         if mode == "options":
             best = torch.where(choice >= 0, choice.to(best.dtype), best)
         self.last_generation = {"ids": ids, "similarities": sims, "choice": choice}
+        if jump > 1:
+            self.last_generation["n_committed"] = out["n_committed"]
         return best, extracted
 
     @torch.no_grad()
@@ -313,12 +317,12 @@ class Transformer(nn.Module):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
         return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta, lookahead, lookup_ngram,
-        draft_tokens) -> one answer per row, the
+        draft_tokens, jump_forward) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
         "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
-        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step; with jump_forward >= 2 "n_committed"). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",

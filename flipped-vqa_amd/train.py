@@ -91,6 +91,11 @@ _FLAGS = [
                               "--gen_constrain or --contrast")),
     ("--lookup_ngram", dict(type=int, default=2, help="--lookahead: the longest n-gram of committed tokens the prompt lookup "
                                                       "matches (1 .. 4)")),
+    ("--gen_jump_forward", dict(type=int, default=0,
+                                help="--gen_constrain: jump-forward decoding with up to T rows per pass (fvqa.generate.generate("
+                                     "constraints=..., jump_forward=T)): the tokens the trie of allowed answers fixes are committed "
+                                     "without a pass of their own — the same answers in fewer passes. 0, 1: off. Not with "
+                                     "--num_beams > 1, --contrast or --lookahead > 1")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -101,8 +106,9 @@ _FLAGS = [
 
 class ArgumentParser(argparse.ArgumentParser):
     """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
-    --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead out of range or
-    together with a decode it is not built for (answer.py uses it too)."""
+    --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead or
+    --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for (answer.py uses
+    it too)."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -122,6 +128,17 @@ class ArgumentParser(argparse.ArgumentParser):
                            "or --contrast")
             if not 1 <= int(getattr(a, "lookup_ngram", 2)) <= 4:
                 self.error("1 <= --lookup_ngram <= 4")
+        for flag, constrained in (("gen_jump_forward", getattr(a, "gen_constrain", None)),
+                                  ("jump_forward", getattr(a, "constrain", False) or getattr(a, "answer_vocab", None))):
+            jf = int(getattr(a, flag, 0) or 0)
+            if jf < 0 or jf > 16:
+                self.error(f"0 <= --{flag} <= 16")
+            if jf > 1:
+                if not constrained:
+                    self.error(f"--{flag} commits the tokens a trie of allowed answers fixes: it needs "
+                               + ("--gen_constrain" if flag == "gen_jump_forward" else "--constrain or --answer_vocab"))
+                if int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "contrast", None) or la > 1:
+                    self.error(f"--{flag} is built for the greedy pick: not with --num_beams > 1, --contrast or --lookahead > 1")
         return a
 
 

@@ -435,6 +435,52 @@ int fvqa_spec_step(const float* logits, const void* emb, const int32_t* draft_to
                    int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token, float* logprob, int32_t* n_committed,
                    int32_t* n_drafted, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int lookahead, int vocab,
                    int dim, int seq_len, int dtype, void* stream);
+/* The token step of jump-forward constrained greedy decoding (csrc/jump.hip; generate(constraints=C, jump_forward=T)): one launch
+ * where fvqa_spec_step sits, one 256-thread workgroup per sequence. Under the trie of fvqa_decode_next_trie a row whose node has a
+ * single edge has nothing to decide, so a step picks ONE token from the logits and then commits the tokens the trie fixes behind
+ * it, up to T = jump_forward per step; the next pass feeds all of them, so that their k / v join the cache
+ * (fvqa_attn_suffix_append) without a pass of their own. Nothing is drafted and nothing is ever rejected.
+ * logits (n_seq*T, vocab) fp32, read only: row n*T + j was computed on the token w[n, j] the previous step committed, of which
+ * there were m = len[n] clamped into [1, T]. (The first step: len = 1 and row 0 = the prefill's row at prefix - 1.) The trie: node
+ * (n_seq) int32 in and out, node_first / edge_token / edge_child as in fvqa_decode_next_trie; all four NULL: no trie, every row
+ * is unconstrained. In/out: ids (n_seq, seq_len) int64, pos, done, n_generated, len (n_seq) int32, w (n_seq, T) int32. Per row n:
+ *   1. live iff done == 0, pos >= -1, pos + 1 < seq_len and n_generated < max_new_tokens. A row that is not live commits nothing
+ *      and is done afterwards: ids, pos, n_generated, node and w are not written, len = 0, start = pos64 = pos clamped into the
+ *      sequence, row n*T of x_next = the embedding of the id at that position clamped into [0, vocab) (a valid row: the batch stays
+ *      rectangular), zeros behind, token = -1, the log-probabilities 0, n_committed = 0.
+ *   2. pick, on the LAST fed row L = logits[n*T + m - 1]. node == -1: argmax L over the vocabulary, the first index on exact ties
+ *      (fvqa_decode_next's rule); no chain follows. node >= 0: the node's edge range clamped into [0, n_edges], edges whose token
+ *      lies outside [0, vocab) skipped — no usable edge, or a node outside [0, n_nodes): the row ends, committing nothing, as in 1
+ *      except that w becomes -1 —; else the largest logit among the usable edges, the lowest edge on ties, and node = the edge's
+ *      child, n_nodes if that lies outside [0, n_nodes): fvqa_decode_next_trie's greedy pick. The token is committed: ids[pos + 1],
+ *      pos += 1, n_generated += 1, token[n, 0]; logprob_pick[n] = L[token] - lse(L) over the whole raw row (rule 5 of
+ *      fvqa_decode_next_ex, the same bits). The row is done if the token is eos_id or n_generated == max_new_tokens.
+ *   3. chain, while the row is not done, fewer than T tokens were committed by this step, pos + 1 < seq_len, n_generated <
+ *      max_new_tokens, the node lies inside [0, n_nodes), its clamped edge range holds EXACTLY ONE edge and that edge's token lies
+ *      inside [0, vocab): if the token is eos_id and chain_eos == 0, stop in front of it; else commit it as in 2, move to the
+ *      (clamped) child, and stop, done, if it was eos_id or the budget is now spent. A node with several edges of which one is
+ *      usable is left to the next step's pick: the chain never scans a node.
+ *   4. want_logprobs != 0: logprob_fed[n, j] for 1 <= j < m = logits[n*T + j - 1][w[n, j]] - lse of that row, for the INCOMING w
+ *      of a row that is live by rule 1 (0 for a w outside [0, vocab)); entry 0 and every other entry 0. With want_logprobs == 0
+ *      the whole array is 0 and the rows 0 .. m - 2 of the logits are never read. A caller that wants every token's
+ *      log-probability passes chain_eos = 0: a row then ends by PICKING its EOS, at a step that reads what the row still owes.
+ *   5. the next pass, nc = the tokens committed by this step: a row that goes on feeds them ALL — w[n, 0 .. nc) (-1 behind),
+ *      len = nc, start = pos64 = the position of the first one, x_next rows n*T + j = their embeddings, zeros behind. A row that
+ *      is done feeds as in 1: len = 0, start = its position, row n*T = the embedding of its last token. token (n_seq, T) = the
+ *      committed tokens, -1 behind; n_committed = nc.
+ * n_active = the rows with done == 0 after the step, counted through `counter` exactly as in fvqa_spec_step. pos64 may be NULL.
+ * With T == 1 (and max_new_tokens never reached) ids, pos, done, node, token, x_next, pos64, n_active and logprob_pick are those of
+ * fvqa_decode_next_trie at temperature 0 and repetition_penalty 1, bit for bit. No float atomics, fixed summation orders: bitwise
+ * repeatable. No index read from the trie, ids or w leads outside an array.
+ * Limits: 1 <= jump_forward <= 16, n_seq * jump_forward <= 65535, every size > 0, n_nodes > 0 and n_edges >= 0 with a trie (else
+ * FVQA_ESHAPE). FVQA_EINVAL: a null pointer (pos64 may be NULL), a bad dtype code, a trie given in part; FVQA_EALIGN: an operand
+ * off its element's boundary. */
+int fvqa_trie_jump_step(const float* logits, const void* emb, const int32_t* node_first, const int32_t* edge_token,
+                        const int32_t* edge_child, int n_nodes, int n_edges, int eos_id, int max_new_tokens, int chain_eos,
+                        int want_logprobs, int64_t* ids, int32_t* pos, int32_t* done, int32_t* n_generated, int32_t* node,
+                        int32_t* w, int32_t* len, int32_t* start, int64_t* pos64, void* x_next, int32_t* token,
+                        float* logprob_pick, float* logprob_fed, int32_t* n_committed, int32_t* n_active, uint32_t* counter,
+                        int n_seq, int jump_forward, int vocab, int dim, int seq_len, int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)

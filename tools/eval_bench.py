@@ -24,7 +24,13 @@ batch of 2 * B rows (the same layer pass as the pairs).
 bound), drafts that are all wrong (the price of the wasted rows) and prompt lookup (--lookup_ngram G) on the synthetic batch as it
 is and with the first 12 answer tokens listed in the prompt, as a multiple-choice prompt lists its options. The weights are the
 `peakedperm` closed form of --eos_at: the greedy tokens are decided, whatever the number of rows in a pass. Per line: ms per
-batch, ms per committed token of a row, committed tokens per pass, and whether the ids are the plain call's."""
+batch, ms per committed token of a row, committed tokens per pass, and whether the ids are the plain call's.
+--jump_forward T [T ...] times jump-forward constrained decoding, generate(constraints=C, jump_forward=T), interleaved (--pairs N
+times, default 3) with the plain constrained call generate(constraints=C) on the same trie, for two kinds of C: five options per
+sample (8 to 12 tokens each, two of them sharing their first two tokens and two more their first token: the options part within
+their first tokens and are then fixed up to their EOS) and one shared vocabulary of 400 answers of one to three words from a
+list of 60 (a trie that branches at its first depths and nowhere else). Per line: ms per batch and passes (the token steps that
+committed something) of each arm, and whether the ids are the plain call's."""
 import argparse
 import os
 import sys
@@ -61,6 +67,8 @@ def main():
     ap.add_argument("--lookahead", type=int, nargs="*", default=[], help="draft-and-verify decoding with up to T rows per pass; "
                                                                          "several T: three arms each, interleaved with plain generate")
     ap.add_argument("--lookup_ngram", type=int, default=2, help="--lookahead: the prompt-lookup arm's longest n-gram")
+    ap.add_argument("--jump_forward", type=int, nargs="*", default=[], help="jump-forward constrained decoding with up to T rows "
+                    "per pass; several T: a line per round each, interleaved with the plain constrained call")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -81,7 +89,7 @@ def main():
     b = synth.make_batch(cfg, seed=5)
     B = a.batch_size
     b["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B)]}
-    if a.eos_at or a.lookahead:                  # decided tokens: what a draft is verified against must not hang on a near tie
+    if a.eos_at or a.lookahead or a.jump_forward:   # decided tokens: what a draft is verified against must not hang on a near tie
         import dataclasses
         from llama_vqa import fill_closed_form
         fill_closed_form(model, dataclasses.replace(cfg, max_feats=margs.max_feats, bias=margs.bias, tau=margs.tau,
@@ -117,6 +125,9 @@ def main():
         return
     if a.lookahead:
         lookahead_lines(a, eng, b, timed)
+        return
+    if a.jump_forward:
+        jump_lines(a, eng, b, timed)
         return
     if a.contrast:
         import dataclasses
@@ -230,6 +241,47 @@ def lookahead_lines(a, eng, b, timed):
                       f"lookahead={T}, {name}: {t_l * 1e3:7.1f} ms/batch, {t_l / N * 1e3:6.3f} ms per committed token, "
                       f"{N / passes:5.2f} tokens per pass ({passes} passes, {out['steps']} steps launched), {t_p / t_l:5.2f}x; "
                       f"ids {'equal' if same else 'DIFFER from'} the plain call's", flush=True)
+
+
+def jump_lines(a, eng, b, timed):
+    import numpy as np
+    from fvqa.constrain import TokenTrie
+    B = a.batch_size
+    tag = f"{a.model} L={eng.L} B={B} S=128 greedy"
+    eos = eng.model.tokenizer.eos_id
+    rng = np.random.default_rng(0)
+    tok = lambda n: [int(t) for t in rng.choice(np.arange(3, eng.V), size=n, replace=False)]   # noqa: E731
+    options = []
+    for _ in range(B):                                      # five options: 0 / 1 share two tokens, 2 / 3 one, 4 stands alone
+        t = [tok(int(rng.integers(8, 13))) for _ in range(5)]
+        t[1][:2], t[3][:1] = t[0][:2], t[2][:1]
+        options.append(t)
+    words = [tok(int(rng.integers(1, 3))) for _ in range(60)]                                   # a "word": one or two tokens
+    vocab = {tuple(sum((words[int(i)] for i in rng.integers(0, 60, int(rng.integers(1, 4)))), [])) for _ in range(400)}
+    tries = (("five options per sample", TokenTrie.from_sequences(options, eos, eng.V)),
+             (f"a shared vocabulary of {len(vocab)} answers", TokenTrie.from_sequences([list(v) for v in sorted(vocab)], eos, eng.V)))
+    for T in a.jump_forward:
+        runs, outs = [], []
+        for name, trie in tries:
+            base, out = {}, {}
+            runs.append((f"generate(constraints: {name})", lambda trie=trie, base=base: base.update(
+                generate.generate(eng, b, constraints=trie))))
+            runs.append((f"jump_forward={T}, {name}", lambda trie=trie, out=out: out.update(
+                generate.generate(eng, b, constraints=trie, jump_forward=T))))
+            outs.append((base, out))
+        for _, fn in runs:
+            timed(fn, reps=1)
+        for k in range(a.pairs or 3):
+            t = [timed(fn, warm=0) for _, fn in runs]
+            parts = []
+            for i, (base, out) in enumerate(outs):
+                same = bool(torch.equal(out["ids"], base["ids"]) and torch.equal(out["choice"], base["choice"]))
+                p_plain = int((base["tokens"] >= 0).any(0).sum())
+                p_jump = int((out["n_committed"].sum(0) > 0).sum())
+                parts.append(f"{runs[2 * i][0]}: {t[2 * i] * 1e3:7.1f} ms/batch, {p_plain} passes | {runs[2 * i + 1][0]}: "
+                             f"{t[2 * i + 1] * 1e3:7.1f} ms/batch, {p_jump} passes ({out['steps']} steps launched), "
+                             f"{t[2 * i] / t[2 * i + 1]:5.2f}x; ids and choice {'equal' if same else 'DIFFER from'} the plain call's")
+            print(f"{tag} round {k}: " + " || ".join(parts), flush=True)
 
 
 def beam_lines(a, eng, b, cfg, timed):
