@@ -11,11 +11,12 @@ reference's quirks kept (choices padded with id 0 before averaging, llama/model.
 from __future__ import annotations
 
 import contextlib
+import types
 from typing import List, Tuple
 
 import torch
 
-from . import constrain, ops
+from . import constrain, ops, rowpass
 
 N_NEW = 31          # reference llama/model.py:438: positions prefix-1 .. prefix+29
 
@@ -35,60 +36,108 @@ def vqa_stream_only(eng, arenas: str, lm_head_rows: str):
         eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows = saved
 
 
+def _need_prefix(data: dict) -> None:
+    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
+        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
+                         "reference llama/model.py:381)")
+
+
+def _option0(data: dict, twin=None) -> dict:
+    """The prefill's batch: option 0 of every sample with its features; under `contrast` the B prompts with their clips, then
+    the same prompts with the twin's."""
+    sub = {k: data[k] for k in ("video", "audio") if k in data}      # (the audio-only batch has no "video")
+    sub.update({"text_id": {"vqa": data["text_id"]["vqa"][:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
+                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
+    if twin is not None:
+        for k, v in twin.items():
+            sub[k] = torch.cat([sub[k], v.to(device=sub[k].device, dtype=sub[k].dtype)], 0)
+        sub["text_id"] = {"vqa": sub["text_id"]["vqa"].repeat(2, 1, 1)}
+        sub["label"] = {"vqa": sub["label"]["vqa"].repeat(2, 1, 1)}
+    return sub
+
+
+def _prefill(eng, data: dict, twin=None) -> types.SimpleNamespace:
+    """The prompt, once: the training forward on `_option0` — logits of every position, and every layer's k / v stay in the arena
+    = the KV cache. -> B (the prefill's rows: twice the samples under `contrast`), S, ar (the arena), vstart, ids (B, S) int64 (a
+    copy of the prompts), prefix (B,) int64, start = prefix - 1 (the position the first token is predicted at), first (B, V) (the
+    logits rows at `start`), rows = arange(B), rotated (rowpass.cache_rotated)."""
+    sub = _option0(data, twin)
+    dev = eng.device
+    B, _, S = sub["text_id"]["vqa"].shape
+    with vqa_stream_only(eng, "_gen_arena", "all"):         # the prefill's logits are read at the prefix positions: every row
+        eng.forward(sub)
+        ar, vstart = eng.arena(B, S), eng.saved["vstart"]
+    rotated = rowpass.cache_rotated(eng)
+    ids = sub["text_id"]["vqa"][:, 0].to(dev).clone()
+    prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]] * (1 if twin is None else 2), device=dev)
+    start = prefix - 1
+    rows = torch.arange(B, device=dev)
+    first = ar.logits.view(B, S, eng.V)[rows, start.clamp(0, S - 1)]
+    return types.SimpleNamespace(B=B, S=S, ar=ar, vstart=vstart, ids=ids, prefix=prefix, start=start, first=first, rows=rows,
+                                 rotated=rotated)
+
+
+def _one_row_attn(eng, p, kv, vstart, pos):
+    """rowpass.layers' attention for one new row per sequence: the row against the cached keys / values of `kv` (+ adapter
+    prefix); its k, v join the cache at `pos`."""
+    def attn(i, qkv, o):
+        ops.attn_decode(qkv, kv[i], o, *eng.model.gate_views(i), vstart, pos, (eng.cos, eng.sin), qkv.shape[0], p.S, eng.H,
+                        eng.Dh, eng.A, eng.F, cache_rotated=p.rotated)
+    return attn
+
+
+class _LagOneStop:
+    """The stop that lags by one step (generate's docstring): after token step t the count of running rows goes to pinned host
+    memory behind an event, and step t + 1 is only launched once the count of step t - 1 has arrived and is not zero.
+    early_stop=False: every step may be launched."""
+
+    def __init__(self, max_steps: int, early_stop: bool = True):
+        self.running = torch.empty(max_steps, dtype=torch.int32).pin_memory()
+        self.arrived = []
+        self.early_stop = early_stop
+
+    def may_launch(self, t: int) -> bool:
+        if t < 2 or not self.early_stop:
+            return True
+        self.arrived[t - 2].synchronize()                   # the count of step t - 2 left the device a whole step ago
+        return int(self.running[t - 2]) != 0
+
+    def queued(self, t: int, n_active: torch.Tensor) -> None:
+        """Step t is queued; n_active (1,) int32 on the device is where it leaves its count."""
+        self.running[t:t + 1].copy_(n_active, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.arrived.append(ev)
+
+
+def _read_back(ids, prefix, n_generated, col):
+    """ids (B, S) int64, prefix and n_generated (B,) int64, col = arange(width)[None] -> (tokens (B, width) int32: the generated
+    tokens of each row as its id row holds them, -1 from n_generated on; inside (B, width) bool: col < n_generated)."""
+    inside = col < n_generated.unsqueeze(1)
+    tok = ids.gather(1, (prefix.unsqueeze(1) + col).clamp(max=ids.shape[1] - 1)).to(torch.int32)
+    return torch.where(inside, tok, torch.full_like(tok, -1)), inside
+
+
 @torch.no_grad()
 def greedy_decode(eng, data: dict, n_new: int = N_NEW) -> torch.Tensor:
     """-> ids (B, S) int64 on the device: option 0's prompt with the generated tokens written from
     position prefix_index['vqa'][b] on (reference llama/model.py:428-470)."""
-    m, pk = eng.model, eng.pack
-    dev = eng.device
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
-    ids_all = data["text_id"]["vqa"]
-    B, _, S = ids_all.shape
-    sub = {k: data[k] for k in ("video", "audio") if k in data}      # (the audio-only batch has no "video")
-    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-           "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    with vqa_stream_only(eng, "_gen_arena", "all"):         # the prefill's logits are read at the prefix positions: every row
-        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B, S)
-        vstart = eng.saved["vstart"]
-        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
-        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)   # the prefill left RAW keys in the cache
-        ids = ids_all[:, 0].to(dev).clone()
-        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
-        pos = prefix - 1                                    # start_idx of the first iteration
-        logits = ar.logits.view(B, S, V)
-        pred = logits[torch.arange(B, device=dev), pos.clamp(0, S - 1)].argmax(-1)
-        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-        xn, hn, h, x2, o_row = e(B, D), e(B, D), e(B, D), e(B, D), e(B, D)
-        qkv_row, ab, z = e(B, 3 * D), e(B, 2 * Hf), e(B, Hf)
-        lg = e(B, V, dtype=torch.float32)
-        for _ in range(n_new):
-            ok = pos + 1 < S                                # the reference would index past the end here
-            tgt = (pos + 1).clamp(max=S - 1)
-            ids[torch.arange(B, device=dev), tgt] = torch.where(ok, pred, ids[torch.arange(B, device=dev), tgt])
-            pos = tgt
-            x = pk.emb[ids[torch.arange(B, device=dev), pos]].contiguous()
-            for i in range(L):                                # the per-kernel sequence of a layer
-                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=B)
-                ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
-                g1, g2 = m.gate_views(i)
-                # the new row against the cached keys / values (+ adapter prefix); its k, v join the cache. The cache holds
-                # ROTATED keys (fp32 build; bf16 build with RoPE in the QKV epilogue, the default) unless the bf16 build runs
-                # with FVQA_ROPE_IN_GEMM=0 (raw keys, rotated on the fly): cache_rotated = !attn_rope_fused || rope_in_gemm
-                ops.attn_decode(qkv_row, ar.qkv[i], o_row, g1, g2, vstart, pos, (eng.cos, eng.sin), B, S, H, Dh, A, F,
-                                cache_rotated=not fused)
-                ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
-                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=B)
-                ops.gemm_nt(hn, pk.w13[i], ab)
-                ops.swiglu_fwd(ab, z, B, Hf)
-                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-                x, x2 = x2, x
-            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=B)
-            ops.gemm_nt(xn, pk.wout, lg)
-            pred = lg.argmax(-1)
-        return ids
+    _need_prefix(data)
+    p = _prefill(eng, data)
+    pk, dev, B, S = eng.pack, eng.device, p.B, p.S
+    ids, pos = p.ids, p.start                               # start_idx of the first iteration
+    pred = p.first.argmax(-1)
+    b = rowpass.buffers(eng, B, xin=False)
+    for _ in range(n_new):
+        ok = pos + 1 < S                                    # the reference would index past the end here
+        tgt = (pos + 1).clamp(max=S - 1)
+        ids[torch.arange(B, device=dev), tgt] = torch.where(ok, pred, ids[torch.arange(B, device=dev), tgt])
+        pos = tgt
+        x = pk.emb[ids[torch.arange(B, device=dev), pos]].contiguous()
+        x = rowpass.layers(eng, b, _one_row_attn(eng, p, p.ar.qkv, p.vstart, pos), x)
+        rowpass.head(eng, x, b.xn, b.lg)
+        pred = b.lg.argmax(-1)
+    return ids
 
 
 @torch.no_grad()
@@ -274,353 +323,227 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         kw = {} if trie is None else {"constraints": trie}
         return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
                            length_penalty=float(length_penalty), **kw)
-    m, pk = eng.model, eng.pack
-    dev = eng.device
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
+    _need_prefix(data)
     if max_new_tokens < 1 or not temperature >= 0 or not 0 < top_p <= 1:
         raise ValueError("generate: max_new_tokens >= 1, temperature >= 0, 0 < top_p <= 1")
-    ids_all = data["text_id"]["vqa"]
-    B0, _, S = ids_all.shape
-    B = B0 * n                                              # the rows of the token loop
-    NP = B                                                  # the token steps' results: one per row — per PAIR under `contrast`
-    if twin is not None:
-        B = 2 * NP
-        if B > 65535:
-            raise ValueError("generate: contrast runs two rows per sample: 2 * samples * num_return_sequences <= 65535")
+    NP = data["text_id"]["vqa"].shape[0] * n                # the token steps' results: one per row — per PAIR under `contrast`
+    B = NP if twin is None else 2 * NP                      # the rows of the token loop
+    if twin is not None and B > 65535:
+        raise ValueError("generate: contrast runs two rows per sample: 2 * samples * num_return_sequences <= 65535")
     if B > 65535:
         raise ValueError("generate: at most 65535 rows (samples times num_return_sequences)")
-    sub = {k: data[k] for k in ("video", "audio") if k in data}
-    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    if twin is not None:                                    # the B0 prompts with their clips, then the same prompts with the twin's
-        for k, v in twin.items():
-            sub[k] = torch.cat([sub[k], v.to(device=sub[k].device, dtype=sub[k].dtype)], 0)
-        sub["text_id"] = {"vqa": sub["text_id"]["vqa"].repeat(2, 1, 1)}
-        sub["label"] = {"vqa": sub["label"]["vqa"].repeat(2, 1, 1)}
-        B0 = 2 * B0                                         # the prefill's rows, and the parents of the fan-out
-    with vqa_stream_only(eng, "_gen_arena", "all"):
-        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B0, S)
-        vstart = eng.saved["vstart"]
-        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
-        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
-        ids = sub["text_id"]["vqa"][:, 0].to(dev).clone()
-        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]] * (1 if twin is None else 2), device=dev)
-        start = prefix - 1                                  # the position the first token is predicted at
-        first = ar.logits.view(B0, S, V)[torch.arange(B0, device=dev), start.clamp(0, S - 1)]
-        kv = ar.qkv
-        if n > 1:                                           # one prefill, n rows per sample: beam search's fan-out, no re-seating
-            i32 = dict(dtype=torch.int32, device=dev)
-            rep = lambda t: t.repeat_interleave(n, 0).contiguous()  # noqa: E731  per sample -> per row
-            kv = _beam_cache(eng, B, S, min(int(max_new_tokens), S))["qkv"]
-            ops.kv_beam_move(kv, ar.qkv, rep(torch.arange(B0, **i32)), torch.zeros(B, **i32), rep(prefix).to(torch.int32),
-                             S=S, A=A)
-            vstart, ids, prefix, start = rep(vstart), rep(ids), rep(prefix), rep(start)
-            first = first.unsqueeze(1).expand(B0, n, V).reshape(B, V)
-        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-        xin, xn, hn, h, xb, o_row = e(B, D), e(B, D), e(B, D), e(B, D), e(B, D), e(B, D)
-        qkv_row, ab, z = e(B, 3 * D), e(B, 2 * Hf), e(B, Hf)
-        lg = e(B, V, dtype=torch.float32)
-        lg.copy_(first)
-        pos = start.to(torch.int32)
-        pos64 = start.clone()
-        done = torch.zeros(B, dtype=torch.int32, device=dev)
-        tokens = torch.full((max_new_tokens, NP), -1, dtype=torch.int32, device=dev)
-        n_kept = torch.zeros(max_new_tokens, NP, dtype=torch.int32, device=dev)
-        n_active = torch.zeros(max_new_tokens, dtype=torch.int32, device=dev)
-        if ex or trie is not None or twin is not None:
-            gen_start = prefix.to(torch.int32)
-            logprobs = torch.zeros(max_new_tokens, NP, dtype=torch.float32, device=dev)
-            counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        if twin is not None:
-            n_plausible = torch.zeros(max_new_tokens, NP, dtype=torch.int32, device=dev)
-        if trie is not None:                                # every row starts at its sample's root (n rows per sample: repeated)
-            dtrie = trie.to(dev)
-            node = torch.as_tensor(trie.roots(NP // n), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
-        u = None
-        if temperature > 0:
-            gen = None
-            if seed is not None:
-                gen = torch.Generator(device=dev)
-                gen.manual_seed(int(seed))
-            u = torch.rand(max_new_tokens, NP, dtype=torch.float32, device=dev, generator=gen)
-        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
-        arrived = []
-        steps = 0
-        for t in range(max_new_tokens):
-            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
-                arrived[t - 2].synchronize()
-                if int(running[t - 2]) == 0:
-                    break
-            if twin is not None:                            # both rows of every pair, one token (a trie node per pair)
-                ops.decode_next_pair(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], n_plausible[t],
-                                     logprobs[t], n_active[t:t + 1], counter, alpha=float(contrast_alpha),
-                                     beta=float(contrast_beta), node=None if trie is None else node,
-                                     trie=None if trie is None else dtrie, u=None if u is None else u[t], pos64=pos64,
-                                     temperature=temperature, top_p=top_p, top_k=int(top_k),
-                                     repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
-                                     stop_at_eos=stop_at_eos)
-            elif trie is not None:
-                ops.decode_next_trie(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
-                                     n_active[t:t + 1], counter, node, dtrie, u=None if u is None else u[t], pos64=pos64,
-                                     temperature=temperature, top_p=top_p, top_k=int(top_k),
-                                     repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
-                                     stop_at_eos=stop_at_eos)
-            elif ex:
-                ops.decode_next_ex(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t],
-                                   n_active[t:t + 1], counter, u=None if u is None else u[t], pos64=pos64,
-                                   temperature=temperature, top_p=top_p, top_k=int(top_k),
-                                   repetition_penalty=float(repetition_penalty), eos_id=m.tokenizer.eos_id,
-                                   stop_at_eos=stop_at_eos)
-            else:
-                ops.decode_next(lg, pk.emb, ids, pos, done, xin, tokens[t], n_kept[t], n_active[t:t + 1],
-                                u=None if u is None else u[t], pos64=pos64, temperature=temperature,
-                                top_p=top_p, eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos)
-            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            arrived.append(ev)
-            steps = t + 1
-            if steps == max_new_tokens:
-                break                                       # (the logits after the last token pick nothing)
-            # a finished row stays in the batch (it is rectangular): it goes through every layer on the embedding of its last
-            # token and attn_decode rewrites its K/V at its frozen position — the same values each time, read by nobody
-            x, x2 = xin, xb
-            for i in range(L):                              # the per-kernel sequence of a layer, as greedy_decode runs it
-                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=B)
-                ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
-                g1, g2 = m.gate_views(i)
-                ops.attn_decode(qkv_row, kv[i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), B, S, H, Dh, A, F,
-                                cache_rotated=not fused)
-                ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
-                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=B)
-                ops.gemm_nt(hn, pk.w13[i], ab)
-                ops.swiglu_fwd(ab, z, B, Hf)
-                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-                x, x2 = x2, x
-            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=B)
-            ops.gemm_nt(xn, pk.wout, lg)
-        out = {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
-               "tokens": tokens[:steps].t().contiguous()}
-        if twin is not None:                                # the positive rows; the twins hold the same tokens
-            out["ids"], out["n_generated"] = out["ids"][:NP].contiguous(), out["n_generated"][:NP]
-            out["n_plausible"] = n_plausible[:steps].t().contiguous()
-            B0 = B0 // 2
-        if return_logprobs:
-            out["logprobs"] = logprobs[:steps].t().contiguous()
-            out["sum_logprob"] = out["logprobs"].sum(1)
-        if n > 1:
-            for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible"):
-                if k in out:
-                    out[k] = out[k].view(B0, n, *out[k].shape[1:])
-        if trie is not None:
-            out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
-        return out
+    p = _prefill(eng, data, twin)
+    pk, dev, S, V = eng.pack, eng.device, p.S, eng.V
+    vstart, ids, prefix, start, first, kv = p.vstart, p.ids, p.prefix, p.start, p.first, p.ar.qkv
+    i32 = dict(dtype=torch.int32, device=dev)
+    if n > 1:                                               # one prefill, n rows per sample: beam search's fan-out, no re-seating
+        rep = lambda t: t.repeat_interleave(n, 0).contiguous()  # noqa: E731  per sample -> per row
+        kv = _beam_cache(eng, B, S, min(int(max_new_tokens), S))["qkv"]
+        ops.kv_beam_move(kv, p.ar.qkv, rep(torch.arange(p.B, **i32)), torch.zeros(B, **i32), rep(prefix).to(torch.int32),
+                         S=S, A=eng.A)
+        vstart, ids, prefix, start = rep(vstart), rep(ids), rep(prefix), rep(start)
+        first = first.unsqueeze(1).expand(p.B, n, V).reshape(B, V)
+    b = rowpass.buffers(eng, B)
+    lg, xin = b.lg, b.xin
+    lg.copy_(first)
+    pos = start.to(torch.int32)
+    pos64 = start.clone()
+    done = torch.zeros(B, **i32)
+    tokens = torch.full((max_new_tokens, NP), -1, **i32)
+    n_kept = torch.zeros(max_new_tokens, NP, **i32)
+    n_active = torch.zeros(max_new_tokens, **i32)
+    if ex or trie is not None or twin is not None:
+        gen_start = prefix.to(torch.int32)
+        logprobs = torch.zeros(max_new_tokens, NP, dtype=torch.float32, device=dev)
+        counter = torch.zeros(1, **i32)
+    if twin is not None:
+        n_plausible = torch.zeros(max_new_tokens, NP, **i32)
+    dtrie = node = None
+    if trie is not None:                                    # every row starts at its sample's root (n rows per sample: repeated)
+        dtrie = trie.to(dev)
+        node = torch.as_tensor(trie.roots(NP // n), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
+    u = None
+    if temperature > 0:
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        u = torch.rand(max_new_tokens, NP, dtype=torch.float32, device=dev, generator=gen)
+    kw = dict(pos64=pos64, temperature=temperature, top_p=top_p, eos_id=eng.model.tokenizer.eos_id, stop_at_eos=stop_at_eos)
+    kw_ex = dict(kw, top_k=int(top_k), repetition_penalty=float(repetition_penalty))
+    # a finished row stays in the batch (it is rectangular): it goes through every layer on the embedding of its last token
+    # and attn_decode rewrites its K/V at its frozen position — the same values each time, read by nobody
+    attn = _one_row_attn(eng, p, kv, vstart, pos64)
+    stop = _LagOneStop(max_new_tokens)
+    steps = 0
+    for t in range(max_new_tokens):
+        if not stop.may_launch(t):
+            break
+        act, ut = n_active[t:t + 1], None if u is None else u[t]
+        if twin is not None:                                # both rows of every pair, one token (a trie node per pair)
+            ops.decode_next_pair(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], n_plausible[t], logprobs[t],
+                                 act, counter, alpha=float(contrast_alpha), beta=float(contrast_beta), node=node, trie=dtrie,
+                                 u=ut, **kw_ex)
+        elif trie is not None:
+            ops.decode_next_trie(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t], act, counter,
+                                 node, dtrie, u=ut, **kw_ex)
+        elif ex:
+            ops.decode_next_ex(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t], act, counter,
+                               u=ut, **kw_ex)
+        else:
+            ops.decode_next(lg, pk.emb, ids, pos, done, xin, tokens[t], n_kept[t], act, u=ut, **kw)
+        stop.queued(t, act)
+        steps = t + 1
+        if steps == max_new_tokens:
+            break                                           # (the logits after the last token pick nothing)
+        rowpass.head(eng, rowpass.layers(eng, b, attn), b.xn, lg)
+    out = {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
+           "tokens": tokens[:steps].t().contiguous()}
+    B0 = NP // n                                            # the samples
+    if twin is not None:                                    # the positive rows; the twins hold the same tokens
+        out["ids"], out["n_generated"] = out["ids"][:NP].contiguous(), out["n_generated"][:NP]
+        out["n_plausible"] = n_plausible[:steps].t().contiguous()
+    if return_logprobs:
+        out["logprobs"] = logprobs[:steps].t().contiguous()
+        out["sum_logprob"] = out["logprobs"].sum(1)
+    if n > 1:
+        for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible"):
+            if k in out:
+                out[k] = out[k].view(B0, n, *out[k].shape[1:])
+    if trie is not None:
+        out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
+    return out
+
+
+# ------------------------------------------------------------------------------- several rows per sample and pass
+def _pass_checks(data: dict, T: int, max_new_tokens: int, keyword: str) -> int:
+    """What a loop of T rows per sample and pass refuses before it reads the batch -> B."""
+    _need_prefix(data)
+    if max_new_tokens < 1:
+        raise ValueError("generate: max_new_tokens >= 1")
+    B = data["text_id"]["vqa"].shape[0]
+    if B * T > 65535:
+        raise ValueError(f"generate: at most 65535 rows per pass (samples times {keyword})")
+    return B
+
+
+def _pass_state(eng, data: dict, T: int, max_new_tokens: int) -> types.SimpleNamespace:
+    """The prefill, the buffers at B * T rows and the operands every token step of T rows per sample keeps: the first step finds
+    one row per sample, the prefill's (w = -1, length = 1), in logits that are zero elsewhere."""
+    p = _prefill(eng, data)
+    B, dev = p.B, eng.device
+    b = rowpass.buffers(eng, B * T, lg=False)
+    b.lg = torch.zeros(B * T, eng.V, dtype=torch.float32, device=dev)
+    b.lg.view(B, T, eng.V)[:, 0].copy_(p.first)
+    i32 = dict(dtype=torch.int32, device=dev)
+    return types.SimpleNamespace(
+        p=p, b=b, B=B, T=T, ids=p.ids, pos=p.start.to(torch.int32), pos64=p.start.clone(), done=torch.zeros(B, **i32),
+        n_gen=torch.zeros(B, **i32), at=torch.zeros(B, **i32), w=torch.full((B, T), -1, **i32), length=torch.ones(B, **i32),
+        tokens=torch.full((max_new_tokens, B, T), -1, **i32), n_active=torch.zeros(max_new_tokens, **i32),
+        counter=torch.zeros(1, **i32))
+
+
+def _pass_loop(eng, st, max_new_tokens: int, token_step) -> dict:
+    """The loop of T rows per sample and pass: the lag-one stop, token_step(t, n_active[t:t + 1]) — one launch that commits
+    tokens into st.ids and writes the next pass's rows (st.b.xin), their positions (st.at) and number (st.length) —, then the
+    layers with the suffix attention whose rows join the cache (ops.attn_suffix_append) and the LM head on all B * T rows.
+    -> ids, n_generated, steps and tokens (B, longest row), read back from ids; st.inside marks them."""
+    p, b = st.p, st.b
+
+    def attn(i, qkv, o):
+        ops.attn_suffix_append(qkv, p.ar.qkv[i], o, *eng.model.gate_views(i), p.vstart, st.at, st.length, (eng.cos, eng.sin),
+                               st.B, st.T, p.S, eng.H, eng.Dh, eng.A, eng.F, cache_rotated=p.rotated)
+    stop = _LagOneStop(max_new_tokens)
+    steps = 0
+    for t in range(max_new_tokens):
+        if not stop.may_launch(t):
+            break
+        act = st.n_active[t:t + 1]
+        token_step(t, act)
+        stop.queued(t, act)
+        steps = t + 1
+        if steps == max_new_tokens:
+            break                                           # (every row has committed at least one token per step)
+        rowpass.head(eng, rowpass.layers(eng, b, attn), b.xn, b.lg)
+    n_generated = st.n_gen.to(torch.int64)
+    col = torch.arange(int(n_generated.max()), device=eng.device).unsqueeze(0)
+    tokens, st.inside = _read_back(st.ids, p.prefix, n_generated, col)
+    return {"ids": st.ids, "n_generated": n_generated, "steps": steps, "tokens": tokens}
+
+
+def _token_order(tokens, values, inside):
+    """tokens, values (steps, B, T), inside (B, longest) -> (B, longest): the values at the tokens >= 0 of each row, the steps in
+    order and without their padding; 0 outside."""
+    steps, B, T = tokens.shape
+    flat = tokens.permute(1, 0, 2).reshape(B, steps * T)
+    order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :inside.shape[1]]
+    v = values.permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
+    return torch.where(inside, v, torch.zeros_like(v))
 
 
 @torch.no_grad()
 def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_new_tokens: int, stop_at_eos: bool,
                         return_logprobs: bool) -> dict:
-    """generate(lookahead=T >= 2): the plain loop — the same prefill, the same lag-one stop on the count of running rows, the
-    same buffers at B * T rows — with fvqa_spec_step as its token step (verify the pass's drafts, commit, draft the next pass:
-    one launch) and, per layer, the suffix attention whose rows join the cache (ops.attn_suffix_append) where the plain loop
-    runs the one-row attention. Rejected drafts leave k / v behind a row's position; the next pass overwrites them from its
-    `start` on and reads nothing behind it."""
-    m, pk = eng.model, eng.pack
+    """generate(lookahead=T >= 2): `_pass_loop` with fvqa_spec_step as its token step (verify the pass's drafts, commit, draft the
+    next pass: one launch). Rejected drafts leave k / v behind a row's position; the next pass overwrites them from its `start`
+    on and reads nothing behind it."""
+    B = _pass_checks(data, T, max_new_tokens, "lookahead")
     dev = eng.device
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
-    if max_new_tokens < 1:
-        raise ValueError("generate: max_new_tokens >= 1")
-    ids_all = data["text_id"]["vqa"]
-    B, _, S = ids_all.shape
-    if B * T > 65535:
-        raise ValueError("generate: at most 65535 rows per pass (samples times lookahead)")
     if draft_tokens is not None:
         draft_tokens = torch.as_tensor(draft_tokens)
         if tuple(draft_tokens.shape) != (B, int(max_new_tokens)) or draft_tokens.is_floating_point():
             raise ValueError(f"generate: draft_tokens must be integers of shape (B, max_new_tokens) = ({B}, {int(max_new_tokens)})")
         draft_tokens = draft_tokens.to(device=dev, dtype=torch.int32).contiguous()
-    sub = {k: data[k] for k in ("video", "audio") if k in data}
-    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    with vqa_stream_only(eng, "_gen_arena", "all"):
-        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B, S)
-        vstart = eng.saved["vstart"]
-        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
-        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
-        ids = ids_all[:, 0].to(dev).clone()
-        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
-        start = prefix - 1                                  # the position the first token is predicted at
-        R = B * T                                           # the rows of a pass
-        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-        xin, xn, hn, h, xb, o_rows = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
-        qkv_rows, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
-        lg = torch.zeros(R, V, dtype=torch.float32, device=dev)
-        lg.view(B, T, V)[:, 0].copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
-        i32 = dict(dtype=torch.int32, device=dev)
-        pos, pos64 = start.to(torch.int32), start.clone()
-        done, n_gen, at = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
-        w, length = torch.full((B, T), -1, **i32), torch.ones(B, **i32)      # the first step verifies nothing: one row, no draft
-        tokens = torch.full((max_new_tokens, B, T), -1, **i32)
-        logprobs = torch.zeros(max_new_tokens, B, T, dtype=torch.float32, device=dev)
-        n_committed, n_drafted = torch.zeros(max_new_tokens, B, **i32), torch.zeros(max_new_tokens, B, **i32)
-        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
-        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
-        arrived = []
-        steps = 0
-        for t in range(max_new_tokens):
-            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
-                arrived[t - 2].synchronize()
-                if int(running[t - 2]) == 0:
-                    break
-            ops.spec_step(lg, pk.emb, ids, pos, done, n_gen, w, length, at, xin, tokens[t], logprobs[t], n_committed[t],
-                          n_drafted[t], n_active[t:t + 1], counter, max_new_tokens=int(max_new_tokens),
-                          draft_tokens=draft_tokens, lookup_ngram=G, pos64=pos64, eos_id=m.tokenizer.eos_id,
-                          stop_at_eos=stop_at_eos)
-            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            arrived.append(ev)
-            steps = t + 1
-            if steps == max_new_tokens:
-                break                                       # (every row has committed at least one token per step)
-            x, x2 = xin, xb
-            for i in range(L):                              # the plain loop's layer, on the pass's rows
-                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
-                ops.gemm_nt(xn, pk.wqkv[i], qkv_rows)
-                g1, g2 = m.gate_views(i)
-                ops.attn_suffix_append(qkv_rows, ar.qkv[i], o_rows, g1, g2, vstart, at, length, (eng.cos, eng.sin), B, T, S, H,
-                                       Dh, A, F, cache_rotated=not fused)
-                ops.gemm_nt(o_rows, pk.wo[i], h, residual=x)
-                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
-                ops.gemm_nt(hn, pk.w13[i], ab)
-                ops.swiglu_fwd(ab, z, R, Hf)
-                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-                x, x2 = x2, x
-            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=R)
-            ops.gemm_nt(xn, pk.wout, lg)
-        n_generated = n_gen.to(torch.int64)
-        longest = int(n_generated.max())
-        col = torch.arange(longest, device=dev).unsqueeze(0)
-        inside = col < n_generated.unsqueeze(1)
-        tok = ids.gather(1, (prefix.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
-        out = {"ids": ids, "n_generated": n_generated, "steps": steps,
-               "tokens": torch.where(inside, tok, torch.full_like(tok, -1)),
-               "n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()}
-        if return_logprobs:                                 # the steps' (B, T) results, in order, without their padding
-            flat = tokens[:steps].permute(1, 0, 2).reshape(B, steps * T)
-            order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :longest]
-            lp = logprobs[:steps].permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
-            out["logprobs"] = torch.where(inside, lp, torch.zeros_like(lp))
-            out["sum_logprob"] = out["logprobs"].sum(1)
-        return out
+    st = _pass_state(eng, data, T, max_new_tokens)
+    logprobs = torch.zeros(max_new_tokens, B, T, dtype=torch.float32, device=dev)
+    n_committed, n_drafted = (torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev) for _ in range(2))
+
+    def token_step(t, n_active):
+        ops.spec_step(st.b.lg, eng.pack.emb, st.ids, st.pos, st.done, st.n_gen, st.w, st.length, st.at, st.b.xin, st.tokens[t],
+                      logprobs[t], n_committed[t], n_drafted[t], n_active, st.counter, max_new_tokens=int(max_new_tokens),
+                      draft_tokens=draft_tokens, lookup_ngram=G, pos64=st.pos64, eos_id=eng.model.tokenizer.eos_id,
+                      stop_at_eos=stop_at_eos)
+    out = _pass_loop(eng, st, max_new_tokens, token_step)
+    steps = out["steps"]
+    out.update({"n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()})
+    if return_logprobs:
+        out["logprobs"] = _token_order(st.tokens[:steps], logprobs[:steps], st.inside)
+        out["sum_logprob"] = out["logprobs"].sum(1)
+    return out
 
 
 @torch.no_grad()
 def _generate_jump(eng, data: dict, *, T: int, constraints, max_new_tokens: int, stop_at_eos: bool,
                    return_logprobs: bool) -> dict:
-    """generate(constraints=C, jump_forward=T >= 2): `_generate_lookahead`'s loop — the same prefill, the same lag-one stop, the
-    same buffers at B * T rows, the suffix attention whose rows join the cache — with fvqa_trie_jump_step as its token step: pick
-    one token on each row's last fed logits row, commit the tokens the trie fixes behind it, feed them all. Every row a pass
-    feeds is a committed token at its own position, so nothing rejected ever enters the cache."""
-    m, pk = eng.model, eng.pack
-    dev = eng.device
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
-    if max_new_tokens < 1:
-        raise ValueError("generate: max_new_tokens >= 1")
-    ids_all = data["text_id"]["vqa"]
-    B, _, S = ids_all.shape
-    if B * T > 65535:
-        raise ValueError("generate: at most 65535 rows per pass (samples times jump_forward)")
+    """generate(constraints=C, jump_forward=T >= 2): `_pass_loop` with fvqa_trie_jump_step as its token step: pick one token on
+    each row's last fed logits row, commit the tokens the trie fixes behind it, feed them all. Every row a pass feeds is a
+    committed token at its own position, so nothing rejected ever enters the cache."""
+    B = _pass_checks(data, T, max_new_tokens, "jump_forward")
     trie = _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
     want_lp = bool(return_logprobs)
-    sub = {k: data[k] for k in ("video", "audio") if k in data}
-    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    with vqa_stream_only(eng, "_gen_arena", "all"):
-        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B, S)
-        vstart = eng.saved["vstart"]
-        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
-        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
-        ids = ids_all[:, 0].to(dev).clone()
-        prefix = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
-        start = prefix - 1                                  # the position the first token is predicted at
-        R = B * T                                           # the rows of a pass
-        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-        xin, xn, hn, h, xb, o_rows = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
-        qkv_rows, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
-        lg = torch.zeros(R, V, dtype=torch.float32, device=dev)
-        lg.view(B, T, V)[:, 0].copy_(ar.logits.view(B, S, V)[torch.arange(B, device=dev), start.clamp(0, S - 1)])
-        i32 = dict(dtype=torch.int32, device=dev)
-        pos, pos64 = start.to(torch.int32), start.clone()
-        done, n_gen, at = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
-        w, length = torch.full((B, T), -1, **i32), torch.ones(B, **i32)      # the first step: one row, the prefill's
-        dtrie = trie.to(dev)
-        node = torch.as_tensor(trie.roots(B), dtype=torch.int32).to(dev).contiguous()
-        tokens = torch.full((max_new_tokens, B, T), -1, **i32)
-        lp_pick = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
-        lp_fed = torch.zeros(max_new_tokens + 1, B, T, dtype=torch.float32, device=dev)
-        n_committed = torch.zeros(max_new_tokens, B, **i32)
-        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
-        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
-        arrived = []
-        steps = 0
-        for t in range(max_new_tokens):
-            if t >= 2:                                      # the count of step t - 2 left the device a whole step ago
-                arrived[t - 2].synchronize()
-                if int(running[t - 2]) == 0:
-                    break
-            # with log-probabilities the EOS is never chained: a row that owes some is still live when they are read
-            ops.trie_jump_step(lg, pk.emb, ids, pos, done, n_gen, node, w, length, at, xin, tokens[t], lp_pick[t], lp_fed[t],
-                               n_committed[t], n_active[t:t + 1], counter, dtrie, max_new_tokens=int(max_new_tokens),
-                               chain_eos=not want_lp, want_logprobs=want_lp, pos64=pos64, eos_id=m.tokenizer.eos_id)
-            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            arrived.append(ev)
-            steps = t + 1
-            if steps == max_new_tokens:
-                break                                       # (every row has committed at least one token per step)
-            x, x2 = xin, xb
-            for i in range(L):                              # the plain loop's layer, on the pass's rows
-                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
-                ops.gemm_nt(xn, pk.wqkv[i], qkv_rows)
-                g1, g2 = m.gate_views(i)
-                ops.attn_suffix_append(qkv_rows, ar.qkv[i], o_rows, g1, g2, vstart, at, length, (eng.cos, eng.sin), B, T, S, H,
-                                       Dh, A, F, cache_rotated=not fused)
-                ops.gemm_nt(o_rows, pk.wo[i], h, residual=x)
-                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
-                ops.gemm_nt(hn, pk.w13[i], ab)
-                ops.swiglu_fwd(ab, z, R, Hf)
-                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-                x, x2 = x2, x
-            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=R)
-            ops.gemm_nt(xn, pk.wout, lg)
-        n_generated = n_gen.to(torch.int64)
-        longest = int(n_generated.max())
-        col = torch.arange(longest, device=dev).unsqueeze(0)
-        inside = col < n_generated.unsqueeze(1)
-        tok = ids.gather(1, (prefix.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
-        out = {"ids": ids, "n_generated": n_generated, "steps": steps,
-               "tokens": torch.where(inside, tok, torch.full_like(tok, -1)),
-               "n_committed": n_committed[:steps].t().contiguous()}
-        if return_logprobs:                                 # token order: a step's pick, then its chain as the NEXT step read it
-            lp = torch.cat([lp_pick[:steps].unsqueeze(2), lp_fed[1:steps + 1, :, 1:]], 2)
-            flat = tokens[:steps].permute(1, 0, 2).reshape(B, steps * T)
-            order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :longest]
-            lp = lp.permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
-            out["logprobs"] = torch.where(inside, lp, torch.zeros_like(lp))
-            out["sum_logprob"] = out["logprobs"].sum(1)
-        out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
-        return out
+    st = _pass_state(eng, data, T, max_new_tokens)
+    dev = eng.device
+    dtrie = trie.to(dev)
+    node = torch.as_tensor(trie.roots(B), dtype=torch.int32).to(dev).contiguous()
+    lp_pick = torch.zeros(max_new_tokens, B, dtype=torch.float32, device=dev)
+    lp_fed = torch.zeros(max_new_tokens + 1, B, T, dtype=torch.float32, device=dev)
+    n_committed = torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev)
+
+    def token_step(t, n_active):
+        # with log-probabilities the EOS is never chained: a row that owes some is still live when they are read
+        ops.trie_jump_step(st.b.lg, eng.pack.emb, st.ids, st.pos, st.done, st.n_gen, node, st.w, st.length, st.at, st.b.xin,
+                           st.tokens[t], lp_pick[t], lp_fed[t], n_committed[t], n_active, st.counter, dtrie,
+                           max_new_tokens=int(max_new_tokens), chain_eos=not want_lp, want_logprobs=want_lp, pos64=st.pos64,
+                           eos_id=eng.model.tokenizer.eos_id)
+    out = _pass_loop(eng, st, max_new_tokens, token_step)
+    steps = out["steps"]
+    out["n_committed"] = n_committed[:steps].t().contiguous()
+    if return_logprobs:                                     # token order: a step's pick, then its chain as the NEXT step read it
+        lp = torch.cat([lp_pick[:steps].unsqueeze(2), lp_fed[1:steps + 1, :, 1:]], 2)
+        out["logprobs"] = _token_order(st.tokens[:steps], lp, st.inside)
+        out["sum_logprob"] = out["logprobs"].sum(1)
+    out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
+    return out
 
 
 def _twin(data: dict, contrast, alpha, beta, num_beams=1) -> dict:
@@ -656,9 +579,7 @@ def _compiled(eng, data: dict, constraints, stop_at_eos: bool, max_new_tokens: i
         trie = constraints.host()
     else:
         trie = constrain.TokenTrie.from_sequences(constraints, eng.model.tokenizer.eos_id, eng.V)
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
+    _need_prefix(data)
     prefix = [int(p) for p in data["prefix_index"]["vqa"]]
     S = int(data["text_id"]["vqa"].shape[2])
     trie.roots(len(prefix))                                 # (a per-sample set built for another batch size)
@@ -695,118 +616,83 @@ def beam_search(eng, data: dict, *, max_new_tokens: int = N_NEW, stop_at_eos: bo
     offers its allowed tokens only. The stop then always waits for every slot (as with length_penalty != 0): the slots are the
     ranking of the allowed set, and with num_beams >= the number of members the finite final slots are exactly the members.
     The results gain "choice" (B,) and "beams"["choice"] (B, K)."""
-    m, pk = eng.model, eng.pack
-    dev = eng.device
     K = int(num_beams)
-    if "prefix_index" not in data or "vqa" not in data["prefix_index"]:
-        raise ValueError("generation needs data['prefix_index']['vqa'] (where each answer starts; "
-                         "reference llama/model.py:381)")
+    _need_prefix(data)
     if max_new_tokens < 1 or not 1 <= K <= ops.BEAMS_MAX:
         raise ValueError(f"beam_search: max_new_tokens >= 1, 1 <= num_beams <= {ops.BEAMS_MAX}")
     trie = None if constraints is None else _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
-    ids_all = data["text_id"]["vqa"]
-    B, _, S = ids_all.shape
+    p = _prefill(eng, data)
+    pk, dev, B, S, V, rows, eos = eng.pack, eng.device, p.B, p.S, eng.V, p.rows, eng.model.tokenizer.eos_id
     N = B * K
-    sub = {k: data[k] for k in ("video", "audio") if k in data}
-    sub.update({"text_id": {"vqa": ids_all[:, 0:1]}, "label": {"vqa": data["label"]["vqa"][:, 0:1]},
-                "video_start": {"vqa": data["video_start"]["vqa"], "vaq": data["video_start"]["vqa"]}})
-    with vqa_stream_only(eng, "_gen_arena", "all"):
-        eng.forward(sub)                                    # prefill: logits of every position + KV of every layer
-        ar = eng.arena(B, S)
-        D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
-        fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)
-        i32 = dict(dtype=torch.int32, device=dev)
-        rep = lambda t: t.repeat_interleave(K).contiguous()  # noqa: E731  per sample -> per slot
-        vstart = rep(eng.saved["vstart"])
-        prefix64 = torch.as_tensor([int(p) for p in data["prefix_index"]["vqa"]], device=dev)
-        start = rep(prefix64 - 1)                           # the position the first token is predicted at
-        prefix = rep(prefix64).to(torch.int32)
-        W = min(int(max_new_tokens), S)                     # the generated rows a slot can have: the move's window
-        cache = _beam_cache(eng, N, S, W)
-        # fan-out: rows [0, prefix) of sample b and the adapter rows -> the K slots of b, every layer, one launch
-        ops.kv_beam_move(cache["qkv"], ar.qkv, rep(torch.arange(B, **i32)), torch.zeros(N, **i32), prefix, S=S, A=A)
-        e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-        xin, xn, hn, h, xb, o_row = e(N, D), e(N, D), e(N, D), e(N, D), e(N, D), e(N, D)
-        qkv_row, ab, z = e(N, 3 * D), e(N, 2 * Hf), e(N, Hf)
-        lg = e(N, V, dtype=torch.float32)
-        rows = torch.arange(B, device=dev)
-        lg.view(B, K, V).copy_(ar.logits.view(B, S, V)[rows, (prefix64 - 1).clamp(0, S - 1)].unsqueeze(1).expand(B, K, V))
-        ids2 = [ids_all[:, 0].to(dev).repeat_interleave(K, 0).contiguous(), torch.empty(N, S, dtype=torch.int64, device=dev)]
-        pos = start.to(torch.int32)
-        pos64 = start.clone()
-        score = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
-        score[:, 0] = 0.0                                   # slot 0 is the prompt, the others are empty
-        done, n_gen = torch.zeros(N, **i32), torch.zeros(N, **i32)
-        parents, tokens = torch.zeros(max_new_tokens, N, **i32), torch.full((max_new_tokens, N), -1, **i32)
-        n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
-        running = torch.empty(max_new_tokens, dtype=torch.int32).pin_memory()
-        arrived = []
-        steps, cur = 0, 0
-        if trie is not None:                                # every slot starts at its sample's root
-            dtrie = trie.to(dev)
-            node = torch.as_tensor(trie.roots(B), dtype=torch.int32).repeat_interleave(K).to(dev).contiguous()
-        for t in range(max_new_tokens):
-            if t >= 2 and early_stop:                       # the count of step t - 2 left the device a whole step ago
-                arrived[t - 2].synchronize()
-                if int(running[t - 2]) == 0:
-                    break
-            if trie is not None:
-                ops.beam_step_trie(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t],
-                                   tokens[t], xin, n_active[t:t + 1], counter, node, dtrie, num_beams=K,
-                                   eos_id=m.tokenizer.eos_id, stop_at_eos=stop_at_eos, count_any_live=True)
-            else:
-                ops.beam_step(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t],
-                              tokens[t], xin, n_active[t:t + 1], counter, num_beams=K, eos_id=m.tokenizer.eos_id,
-                              stop_at_eos=stop_at_eos, count_any_live=length_penalty != 0)
-            cur = 1 - cur
-            running[t:t + 1].copy_(n_active[t:t + 1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            arrived.append(ev)
-            steps = t + 1
-            if steps == max_new_tokens:
-                break                                       # (the logits after the last token pick nothing)
-            # the generated rows [prefix, pos) of every slot that changed its parent follow it, in all layers (a child writes
-            # its own row `pos` in the layer pass below; a carried slot's frozen row is rewritten there and read by nobody)
-            if K > 1:
-                ops.kv_beam_move(cache["qkv"], cache["qkv"], parents[t], prefix, pos, S=S, A=A, scratch=cache["scratch"],
-                                 window_rows=W, group=K)
-            x, x2 = xin, xb
-            for i in range(L):                              # the per-kernel sequence of a layer, as `generate` runs it
-                ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=N)
-                ops.gemm_nt(xn, pk.wqkv[i], qkv_row)
-                g1, g2 = m.gate_views(i)
-                ops.attn_decode(qkv_row, cache["qkv"][i], o_row, g1, g2, vstart, pos64, (eng.cos, eng.sin), N, S, H, Dh, A, F,
-                                cache_rotated=not fused)
-                ops.gemm_nt(o_row, pk.wo[i], h, residual=x)
-                ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=N)
-                ops.gemm_nt(hn, pk.w13[i], ab)
-                ops.swiglu_fwd(ab, z, N, Hf)
-                ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-                x, x2 = x2, x
-            ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=N)
-            ops.gemm_nt(xn, pk.wout, lg)
-        ids = ids2[cur].view(B, K, S)
-        n_gen = n_gen.view(B, K).to(torch.int64)
-        if length_penalty == 0:
-            best = torch.zeros(B, dtype=torch.int64, device=dev)
-        else:                                               # (argmax returns the first of equal maxima: the lowest slot)
-            best = (score / n_gen.clamp(min=1).to(torch.float32) ** float(length_penalty)).argmax(1)
-        n_best = n_gen[rows, best]
-        col = torch.arange(steps, device=dev).unsqueeze(0)
-        tok_best = ids[rows, best].gather(1, (prefix64.unsqueeze(1) + col).clamp(max=S - 1)).to(torch.int32)
-        tok_best = torch.where(col < n_best.unsqueeze(1), tok_best, torch.full_like(tok_best, -1))
-        out = {"ids": ids[rows, best].contiguous(), "n_generated": n_best, "steps": steps, "tokens": tok_best,
-               "score": score[rows, best].clone(),
-               "beams": {"ids": ids.clone(), "score": score.clone(), "n_generated": n_gen, "done": done.view(B, K).clone()},
-               "parents": parents[:steps].view(steps, B, K).clone(), "step_tokens": tokens[:steps].view(steps, B, K).clone()}
-        if trie is not None:                                # each slot's tokens, read back from its id row
-            tok_all = ids.gather(2, (prefix64.view(B, 1, 1) + col.unsqueeze(0)).clamp(max=S - 1).expand(B, K, steps))
-            tok_all = torch.where(col.unsqueeze(0) < n_gen.unsqueeze(2), tok_all, torch.full_like(tok_all, -1))
-            choice = torch.as_tensor(constrain.choice_of(trie, tok_all), device=dev)
-            out["beams"]["choice"] = choice
-            out["choice"] = choice[rows, best]
-        return out
+    i32 = dict(dtype=torch.int32, device=dev)
+    rep = lambda t: t.repeat_interleave(K).contiguous()  # noqa: E731  per sample -> per slot
+    vstart, start = rep(p.vstart), rep(p.start)
+    prefix = rep(p.prefix).to(torch.int32)
+    W = min(int(max_new_tokens), S)                         # the generated rows a slot can have: the move's window
+    cache = _beam_cache(eng, N, S, W)
+    # fan-out: rows [0, prefix) of sample b and the adapter rows -> the K slots of b, every layer, one launch
+    ops.kv_beam_move(cache["qkv"], p.ar.qkv, rep(torch.arange(B, **i32)), torch.zeros(N, **i32), prefix, S=S, A=eng.A)
+    b = rowpass.buffers(eng, N)
+    lg, xin = b.lg, b.xin
+    lg.view(B, K, V).copy_(p.first.unsqueeze(1).expand(B, K, V))
+    ids2 = [p.ids.repeat_interleave(K, 0).contiguous(), torch.empty(N, S, dtype=torch.int64, device=dev)]
+    pos = start.to(torch.int32)
+    pos64 = start.clone()
+    score = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
+    score[:, 0] = 0.0                                       # slot 0 is the prompt, the others are empty
+    done, n_gen = torch.zeros(N, **i32), torch.zeros(N, **i32)
+    parents, tokens = torch.zeros(max_new_tokens, N, **i32), torch.full((max_new_tokens, N), -1, **i32)
+    n_active, counter = torch.zeros(max_new_tokens, **i32), torch.zeros(1, **i32)
+    if trie is not None:                                    # every slot starts at its sample's root
+        dtrie = trie.to(dev)
+        node = torch.as_tensor(trie.roots(B), dtype=torch.int32).repeat_interleave(K).to(dev).contiguous()
+    attn = _one_row_attn(eng, p, cache["qkv"], vstart, pos64)
+    stop = _LagOneStop(max_new_tokens, early_stop)
+    steps, cur = 0, 0
+    for t in range(max_new_tokens):
+        if not stop.may_launch(t):
+            break
+        act = n_active[t:t + 1]
+        if trie is not None:
+            ops.beam_step_trie(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t],
+                               tokens[t], xin, act, counter, node, dtrie, num_beams=K, eos_id=eos, stop_at_eos=stop_at_eos,
+                               count_any_live=True)
+        else:
+            ops.beam_step(lg, pk.emb, ids2[cur], ids2[1 - cur], pos, score.view(N), done, n_gen, pos64, parents[t], tokens[t],
+                          xin, act, counter, num_beams=K, eos_id=eos, stop_at_eos=stop_at_eos,
+                          count_any_live=length_penalty != 0)
+        cur = 1 - cur
+        stop.queued(t, act)
+        steps = t + 1
+        if steps == max_new_tokens:
+            break                                           # (the logits after the last token pick nothing)
+        # the generated rows [prefix, pos) of every slot that changed its parent follow it, in all layers (a child writes
+        # its own row `pos` in the layer pass below; a carried slot's frozen row is rewritten there and read by nobody)
+        if K > 1:
+            ops.kv_beam_move(cache["qkv"], cache["qkv"], parents[t], prefix, pos, S=S, A=eng.A, scratch=cache["scratch"],
+                             window_rows=W, group=K)
+        rowpass.head(eng, rowpass.layers(eng, b, attn), b.xn, lg)
+    ids = ids2[cur].view(B, K, S)
+    n_gen = n_gen.view(B, K).to(torch.int64)
+    if length_penalty == 0:
+        best = torch.zeros(B, dtype=torch.int64, device=dev)
+    else:                                                   # (argmax returns the first of equal maxima: the lowest slot)
+        best = (score / n_gen.clamp(min=1).to(torch.float32) ** float(length_penalty)).argmax(1)
+    n_best = n_gen[rows, best]
+    col = torch.arange(steps, device=dev).unsqueeze(0)
+    tok_best, _ = _read_back(ids[rows, best], p.prefix, n_best, col)
+    out = {"ids": ids[rows, best].contiguous(), "n_generated": n_best, "steps": steps, "tokens": tok_best,
+           "score": score[rows, best].clone(),
+           "beams": {"ids": ids.clone(), "score": score.clone(), "n_generated": n_gen, "done": done.view(B, K).clone()},
+           "parents": parents[:steps].view(steps, B, K).clone(), "step_tokens": tokens[:steps].view(steps, B, K).clone()}
+    if trie is not None:                                    # each slot's tokens, read back from its id row
+        tok_all = ids.gather(2, (p.prefix.view(B, 1, 1) + col.unsqueeze(0)).clamp(max=S - 1).expand(B, K, steps))
+        tok_all = torch.where(col.unsqueeze(0) < n_gen.unsqueeze(2), tok_all, torch.full_like(tok_all, -1))
+        choice = torch.as_tensor(constrain.choice_of(trie, tok_all), device=dev)
+        out["beams"]["choice"] = choice
+        out["choice"] = choice[rows, best]
+    return out
+
 
 
 def _beam_cache(eng, N: int, S: int, W: int) -> dict:

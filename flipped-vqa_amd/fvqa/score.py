@@ -30,7 +30,7 @@ from typing import Optional
 
 import torch
 
-from . import ops, scored
+from . import ops, rowpass, scored
 from .generate import vqa_stream_only
 
 ROUTES = ("shared", "dense")
@@ -198,7 +198,6 @@ def _dense(eng, data, ids_h, lab_h, vs_list, plan, events):
 def _shared(eng, data, ids_h, lab_h, vs_list, plan, events):
     m_, pk, dev = eng.model, eng.pack, eng.device
     B, O, S = ids_h.shape
-    D, H, Dh, Hf, A, F, L, V = eng.D, eng.H, eng.Dh, eng.Hf, eng.A, eng.F, eng.L, eng.V
     T = plan.T
     # ---- the prompt pass: option 0, no scored row (its labels are all ignored: the head sees pad rows only)
     sub = _front_inputs(data)
@@ -230,31 +229,22 @@ def _shared(eng, data, ids_h, lab_h, vs_list, plan, events):
     start_d, len_d = mv(start.to(torch.int32)), mv(length.to(torch.int32))
     R = B * O * T
     x = pk.emb[mv(ids_suf.reshape(-1))].contiguous()       # token embeddings: the planner keeps frame slots out of a suffix
-    e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-    xn, hn, h, x2, o = e(R, D), e(R, D), e(R, D), e(R, D), e(R, D)
-    qkv, ab, z = e(R, 3 * D), e(R, 2 * Hf), e(R, Hf)
-    fused = ops.attn_rope_fused(eng.dtype) and not ops.rope_in_gemm(eng.dtype)    # the prefill left RAW keys in the cache
-    for i in range(L):
-        ops.rmsnorm_fwd(x, pk.an[i], xn, None, eng.eps, rows=R)
-        ops.gemm_nt(xn, pk.wqkv[i], qkv)
-        g1, g2 = m_.gate_views(i)
-        ops.attn_suffix(qkv, ar.qkv[i], o, g1, g2, vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, H, Dh, A, F,
-                        cache_rotated=not fused)
-        ops.gemm_nt(o, pk.wo[i], h, residual=x)
-        ops.rmsnorm_fwd(h, pk.fn[i], hn, None, eng.eps, rows=R)
-        ops.gemm_nt(hn, pk.w13[i], ab)
-        ops.swiglu_fwd(ab, z, R, Hf)
-        ops.gemm_nt(z, pk.w2[i], x2, residual=h)
-        x, x2 = x2, x
+    b = rowpass.buffers(eng, R, xin=False, lg=False)
+    rotated = rowpass.cache_rotated(eng)
+
+    def attn(i, qkv, o):                                   # several continuations read one cached prompt, nothing is written
+        ops.attn_suffix(qkv, ar.qkv[i], o, *m_.gate_views(i), vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H,
+                        eng.Dh, eng.A, eng.F, cache_rotated=rotated)
+    x = rowpass.layers(eng, b, attn, x)
     # ---- the scored rows: final norm, LM head, cross-entropy (one "sequence" of `rows` positions, fvqa/scored.py)
-    xg, xf = e(rows, D), e(rows, D)
-    lg = e(rows, V, dtype=torch.float32)
+    e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+    xg, xf = e(rows, eng.D), e(rows, eng.D)
+    lg = e(rows, eng.V, dtype=torch.float32)
     lse, rowloss = e(rows, dtype=torch.float32), e(rows, dtype=torch.float32)
     loss_sum = torch.zeros(2, dtype=torch.float32, device=dev)
     ops.gather_rows(x, xg, ops.row_segs([mv(gidx)], [0, rows], R))
-    ops.rmsnorm_fwd(xg, pk.norm, xf, None, eng.eps, rows=rows)
-    ops.gemm_nt(xf, pk.wout, lg)
-    ops.ce_fwd(lg, mv(lab_shift), lse, rowloss, loss_sum, 1, rows, V, 0)
+    rowpass.head(eng, xg, xf, lg)
+    ops.ce_fwd(lg, mv(lab_shift), lse, rowloss, loss_sum, 1, rows, eng.V, 0)
     out = _pick(eng, rowloss, row_map, rows, B, O, S)
     done()
     return out
