@@ -6,6 +6,7 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
         [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
         [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
         [--lookahead T --lookup_ngram G] [--jump_forward T]
+    python answer.py ... --features clip.pth --questions FILE --slots N [--admit M]
 
 `--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
 line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
@@ -15,6 +16,9 @@ zero features — and prints how many tokens were plausible per step (fvqa.gener
 tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
 `--jump_forward T` (with --constrain or --answer_vocab; greedy only) commits the tokens the trie of allowed answers fixes without
 a pass of their own, up to T per step, and prints the tokens committed per step (fvqa.generate.generate(jump_forward=T)).
+`--questions FILE --slots N [--admit M]`: one question per line about the given clip, one answer per line, through in-flight
+batching (fvqa.stream.generate_stream): a decode batch of N rows in which a finished answer hands its slot to the next question.
+The sampling flags and --constrain / --answer_vocab apply; beams, --contrast, --lookahead, --jump_forward and --num_samples do not.
 
 The model, audio and dtype flags are train.py's (`train.get_args_parser()`, `validate_args`). `--random_init --synthetic` runs
 without LLaMA assets: the weights are closed-form, the prompt is made with a word-hash stand-in vocabulary, and the answer is
@@ -36,7 +40,11 @@ from llama_vqa import LLaMA_VQA
 
 def get_args_parser():
     p = train.ArgumentParser("Flipped-VQA: answer one question (MI355X)", parents=[train.get_args_parser()])
-    p.add_argument("--question", type=str, required=True)
+    p.add_argument("--question", type=str, default=None)
+    p.add_argument("--questions", type=str, default=None, metavar="FILE",
+                   help="a file with one question per line about the given clip: answered through --slots, one answer per line")
+    p.add_argument("--slots", type=int, default=0, help="with --questions: the rows of the decode batch (in-flight batching)")
+    p.add_argument("--admit", type=int, default=None, help="with --slots: questions admitted per prefill, 1 .. SLOTS")
     p.add_argument("--options", type=str, nargs="*", default=None, help="answer options of a multiple-choice question")
     p.add_argument("--features", type=str, default=None, help="frame features of the clip, (n, 768): .pth or .npy")
     p.add_argument("--audio_features", type=str, default=None, help="audio features of the clip, (n, 1024): .pth or .npy")
@@ -107,8 +115,13 @@ def main(args):
     audio = load_features(args.audio_features, 1024)
     if args.audio and audio is None:
         raise SystemExit("--audio needs --audio_features")
-    batch = generate.prompt_batch(tok, [args.question], video=None if video is None else [video],
-                                  audio=None if audio is None else [audio], options=[args.options] if args.options else None,
+    questions = [args.question]
+    if args.questions:
+        questions = [q.strip() for q in open(args.questions) if q.strip()]
+    n_q = len(questions)
+    batch = generate.prompt_batch(tok, questions, video=None if video is None else [video] * n_q,
+                                  audio=None if audio is None else [audio] * n_q,
+                                  options=[args.options] * n_q if args.options else None,
                                   max_seq_len=args.max_seq_len, max_feats=args.max_feats)
     if args.audio_only:
         batch.pop("video", None)
@@ -122,6 +135,21 @@ def main(args):
     kw = {} if allowed is None else {"constraints": constrain.encode_answers(tok, allowed)}
     if args.contrast:
         kw.update(contrast=args.contrast, contrast_alpha=args.contrast_alpha, contrast_beta=args.contrast_beta)
+    if args.questions:                            # every question of the file through one stream of --slots rows
+        answers = model.generate_stream(batch, slots=args.slots, admit=args.admit, max_new_tokens=args.max_new_tokens,
+                                        temperature=args.temperature, top_p=args.top_p, seed=args.seed, top_k=args.top_k,
+                                        repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs, **kw)
+        g = model.last_generation
+        print(f"[{n_q} questions, {g['steps']} token steps, {g['n_prefills']} prefills, occupancy {g['occupancy']:.2f}]")
+        for r, a in enumerate(answers):
+            line = a if isinstance(a, str) else " ".join(str(t) for t in a)
+            if "sum_logprob" in g:
+                line += f"\t[log-probability {float(g['sum_logprob'][r]):.4f}]"
+            if allowed is not None:
+                c = int(g["choice"][r])
+                line += f"\t[choice {c}: {allowed[c]}]" if c >= 0 else "\t[choice -1]"
+            print(line)
+        return answers
     if args.lookahead > 1:
         kw.update(lookahead=args.lookahead, lookup_ngram=args.lookup_ngram)
     if args.jump_forward > 1:
@@ -154,6 +182,11 @@ def main(args):
 
 
 if __name__ == "__main__":
-    a = get_args_parser().parse_args()
+    parser = get_args_parser()
+    a = parser.parse_args()
+    if (a.question is None) == (a.questions is None):
+        parser.error("one of --question TEXT and --questions FILE")
+    if (a.questions is not None) != (a.slots >= 1):
+        parser.error("--questions FILE and --slots N come together")
     train.validate_args(a)
     main(a)

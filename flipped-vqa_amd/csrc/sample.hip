@@ -58,6 +58,13 @@
 //            of the same bits (whose two lse then have the same bits too), give c_i = l+_i + 0 = l+_i bit for bit.
 //   step     pos and done are read from the positive row; the token, pos, done, pos64 and x_next are written to both rows, so
 //            the two caches stay in step. logprob stays lp+ of the token; the ticket counts pairs.
+//
+// fvqa_decode_next_stream is the template with STREAM = true (false in the four entries above, in which none of the following
+// exists), with and without TRIE: the token step of in-flight batching (fvqa/stream.py). A row is a SLOT that holds request
+// r = req[b] at token index i = pos + 1 - gen_start[b]. A slot whose r lies outside [0, n_req), or whose i lies outside
+// [0, min(budget[r], width)), is not live: it becomes done and nothing of any request's results is written. A live slot picks by
+// the _ex / _trie rule with the draw at u[i * n_req + r] — the request's own, wherever and whenever it sits —, is stepped as
+// before, leaves its token, log-probability and count in the request's result rows, and is also done once i + 1 == budget[r].
 #include "common.h"
 
 namespace {
@@ -145,7 +152,17 @@ struct PairArgs {
   int32_t* n_plausible;
 };
 
-template <typename T, bool EX, bool TRIE, bool PAIR>
+// the operands fvqa_decode_next_stream adds (STREAM = true)
+struct StreamArgs {
+  const int32_t* req;
+  const int32_t* budget;
+  int n_req, width;
+  int32_t* out_tokens;
+  float* out_logprob;
+  int32_t* out_n_generated;
+};
+
+template <typename T, bool EX, bool TRIE, bool PAIR, bool STREAM>
 __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
                                                     const T* __restrict__ emb, float temperature, float top_p, int eos_id,
                                                     int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
@@ -155,9 +172,10 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
                                                     int D, int S, int row_in_lds, int vec16, int top_k, float rep,
                                                     const int32_t* __restrict__ gen_start,
                                                     float* __restrict__ logprob_out, unsigned* __restrict__ counter,
-                                                    TrieArgs tr, PairArgs pr) {
+                                                    TrieArgs tr, PairArgs pr, StreamArgs sa) {
   static_assert(EX || !TRIE, "the trie entry extends the EX entry");
   static_assert(EX || !PAIR, "the pair entry extends the EX entry");
+  static_assert((EX && !PAIR) || !STREAM, "the stream entry extends the EX entry, one row per slot");
   extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX)
   __shared__ float redf[4], wtotf[4];
   __shared__ int redi[4], wtoti[4];
@@ -169,6 +187,20 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   bool live = done[b] == 0 && p >= -1 && p + 1 < S;
   int tok = -1, kept = 0;
   int64_t* row_ids = ids + (size_t)b * S;
+  // ---- STREAM: the slot's request r and token index ti, every index checked before it is used
+  int r = -1, ti = 0, last_of_budget = 0;
+  if constexpr (STREAM) {
+    r = sa.req[b];
+    const long long i = (long long)p + 1 - (long long)gen_start[b];
+    bool seated = r >= 0 && r < sa.n_req;
+    if (seated) {
+      const int bud = sa.budget[r];
+      const int lim = bud < sa.width ? bud : sa.width;
+      seated = i >= 0 && i < (long long)lim;
+      last_of_budget = seated && i + 1 == (long long)bud;
+    }
+    if (seated) ti = (int)i; else live = false;
+  }
 
   // ---- TRIE: the row's node -> its edge list et[0 .. N), every index clamped; N = V and element i = token i without one
   int N = V, n_ok = V, first_ok = 0, nd = -1;
@@ -379,7 +411,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     }
     float M;
     const float before = block_scan_f(mass, wtotf, &M);
-    const float target = u_p[b] * M;
+    const float target = (STREAM ? u_p[(size_t)ti * sa.n_req + r] : u_p[b]) * M;
     float run = before;
     int cand = 0x7fffffff;
     rank = rank0;
@@ -414,6 +446,9 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     p += 1;
     src = tok;
     if (stop_at_eos && tok == eos_id) now_done = 1;
+    if constexpr (STREAM) {
+      if (last_of_budget) now_done = 1;                            // (the token is still written)
+    }
   } else {
     now_done = 1;
     const int at = p < 0 ? 0 : (p >= S ? S - 1 : p);
@@ -441,6 +476,13 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       if (live && cons) tr.node[b] = child;
     }
     if constexpr (EX) logprob_out[b] = live ? lg[tok] - lse : 0.f;
+    if constexpr (STREAM) {
+      if (live) {                                                  // the request's own result row, at its own token index
+        sa.out_tokens[(size_t)r * sa.width + ti] = tok;
+        if (sa.out_logprob) sa.out_logprob[(size_t)r * sa.width + ti] = lg[tok] - lse;
+        sa.out_n_generated[r] = ti + 1;
+      }
+    }
     unsigned* ticket = EX ? counter : &g_ticket;
     const unsigned old = atomicAdd(ticket, 1u + (now_done ? 0u : 0x10000u));
     if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
@@ -478,11 +520,12 @@ struct ExArgs {
 };
 constexpr size_t BITMAP_LDS_MAX = ROW_LDS_MAX / 32;                // the bitmap of the largest row that lives in LDS
 
-template <typename T, bool EX, bool TRIE, bool PAIR = false>
+template <typename T, bool EX, bool TRIE, bool PAIR = false, bool STREAM = false>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
            int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
            int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st,
-           PairArgs pr = PairArgs{0.f, 0.f, nullptr}) {
+           PairArgs pr = PairArgs{0.f, 0.f, nullptr},
+           StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
   const size_t row_bytes = (size_t)V * sizeof(float);
   const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
   size_t lds = in_lds ? row_bytes : 0;
@@ -493,24 +536,25 @@ int launch(const float* logits, const float* u, const void* emb, float temperatu
   }
   static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
   if (fvqa_attr_needed(attr_done))
-    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE, PAIR, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
   const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);   // (PAIR: the twin half follows B * D
                                                                                             //  elements on, whole 16-byte rows)
-  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature, top_p,
-                     eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds, vec16,
-                     ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr);
+  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR, STREAM>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature,
+                     top_p, eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds,
+                     vec16, ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr, sa);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
 
 // the operand checks the entries share; then the launch
-template <bool EX, bool TRIE = false, bool PAIR = false>
+template <bool EX, bool TRIE = false, bool PAIR = false, bool STREAM = false>
 int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
                    int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
                    int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
                    void* stream, TrieArgs tr = TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0},
-                   PairArgs pr = PairArgs{0.f, 0.f, nullptr}) {
+                   PairArgs pr = PairArgs{0.f, 0.f, nullptr},
+                   StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
   if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
   if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
   if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
@@ -520,20 +564,24 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
   if (EX && (!(ex.rep >= 1.f) || ex.top_k < 0)) return FVQA_EINVAL;
   if (PAIR && (!pr.n_plausible || !(pr.alpha >= 0.f) || !(pr.beta >= 0.f && pr.beta <= 1.f))) return FVQA_EINVAL;
   if (temperature > 0.f && !u) return FVQA_EINVAL;
+  if (STREAM && (!sa.req || !sa.budget || !sa.out_tokens || !sa.out_n_generated)) return FVQA_EINVAL;
+  if (STREAM && (sa.n_req <= 0 || sa.width <= 0)) return FVQA_ESHAPE;
   if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
   if (PAIR && 2 * (int64_t)n_seq > 65535) return FVQA_ESHAPE;      // (n_seq pairs are 2 * n_seq rows of the token loop)
   if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
       !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter) ||
-      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child) || !fvqa_aligned(4, pr.n_plausible))
+      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child) || !fvqa_aligned(4, pr.n_plausible) ||
+      !fvqa_aligned(4, sa.req, sa.budget, sa.out_tokens, sa.out_logprob, sa.out_n_generated))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FVQA_H16)
-    return launch<bf16_t, EX, TRIE, PAIR>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
-                                          token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr);
-  return launch<float, EX, TRIE, PAIR>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
-                                       n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr);
+    return launch<bf16_t, EX, TRIE, PAIR, STREAM>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
+                                                  x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr,
+                                                  st, pr, sa);
+  return launch<float, EX, TRIE, PAIR, STREAM>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
+                                               token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr, sa);
 }
 
 }  // namespace
@@ -586,4 +634,25 @@ extern "C" int fvqa_decode_next_pair(const float* logits, const float* u, const 
   return checked_launch<true, true, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
                                           n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
                                           TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges}, pr);
+}
+
+extern "C" int fvqa_decode_next_stream(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                       int top_k, float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids,
+                                       int32_t* pos, int32_t* done, const int32_t* gen_start, void* x_next, int32_t* token,
+                                       int32_t* n_kept, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
+                                       int32_t* node, const int32_t* node_first, const int32_t* edge_token,
+                                       const int32_t* edge_child, int n_nodes, int n_edges, const int32_t* req,
+                                       const int32_t* budget, int n_req, int width, int32_t* out_tokens, float* out_logprob,
+                                       int32_t* out_n_generated, int n_seq, int vocab, int dim, int seq_len, int dtype,
+                                       void* stream) {
+  const ExArgs ex{top_k, repetition_penalty, gen_start, logprob, counter};
+  const PairArgs pr{0.f, 0.f, nullptr};
+  const StreamArgs sa{req, budget, n_req, width, out_tokens, out_logprob, out_n_generated};
+  if (!node && !node_first && !edge_token && !edge_child)          // no trie at all: the slots pick from the vocabulary
+    return checked_launch<true, false, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
+                                                    x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex,
+                                                    stream, TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, pr, sa);
+  return checked_launch<true, true, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
+                                                 token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
+                                                 TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges}, pr, sa);
 }

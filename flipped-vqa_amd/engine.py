@@ -102,7 +102,10 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     is rejected) returns the reference's `individual_losses` and leaves count / prediction, reduced on the device, in
     `last_scoring`: one host read per batch. Accuracy overall and per question type either way.
     `--contrast blind` (multiple choice): the prediction is the contrastive one (fvqa/score.py) and `acc_blind` / `acc_plain` —
-    the accuracy of the blind twin's and of the plain prediction — are logged from the same single host read."""
+    the accuracy of the blind twin's and of the plain prediction — are logged from the same single host read.
+    `--gen_stream SLOTS` (generation task): the loader's batches are materialised and decoded through ONE stream of SLOTS rows
+    with in-flight batching (`model.inference_stream`, fvqa/stream.py) before the per-batch body below runs on each batch's rows;
+    without the flag every call launches what it did."""
     gen = bool(getattr(args, "is_generation_task", False))
     owner = None
     if not gen:
@@ -113,6 +116,15 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     model.eval()
     log = misc.MetricLogger(delimiter="  ")
     log.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
+    streamed = None
+    n_slots = int(getattr(args, "gen_stream", 0) or 0) if gen else 0
+    if n_slots >= 1:
+        owner = next((m for m in (model, getattr(model, "module", None)) if hasattr(m, "inference_stream")), None)
+        if owner is None:
+            raise NotImplementedError("--gen_stream needs a model with inference_stream (llama/model.py)")
+        data_loader = list(data_loader)[: 1 if getattr(args, "debug", False) else None]
+        with torch.no_grad():
+            streamed = iter(owner.inference_stream(data_loader, n_slots, getattr(args, "gen_stream_admit", None)))
     for data in log.log_every(data_loader, max(1, len(data_loader) // 4), f"Epoch: [{epoch}]"):
         answer = data["answer"]
         bsz = answer.shape[0]
@@ -146,7 +158,7 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
                 break
             continue
         with torch.no_grad():
-            best, extracted = model(data, inference=True)
+            best, extracted = next(streamed) if streamed is not None else model(data, inference=True)
         if getattr(args, "output_dir", None):
             import os
             os.makedirs(os.path.join(args.output_dir, "extracted_answers"), exist_ok=True)

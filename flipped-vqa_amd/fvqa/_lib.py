@@ -52,6 +52,9 @@ SIGNATURES = {
     "fvqa_decode_next_ex": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p]),
     "fvqa_decode_next_trie": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 7 + [_p]),
     "fvqa_decode_next_pair": (_i, [_p, _p, _p, _f, _f, _i, _f, _f, _f, _i, _i] + [_p] * 16 + [_i] * 7 + [_p]),
+    "fvqa_decode_next_stream": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 2 + [_p] * 2 + [_i] * 2 + [_p] * 3
+                                + [_i] * 5 + [_p]),
+    "fvqa_slot_seat": (_i, [_p] * 3 + [_i] + [_p] * 5 + [_i] + [_p] * 10 + [_i] * 3 + [_p]),
     "fvqa_spec_step": (_i, [_p, _p, _p, _i, _i, _i, _i] + [_p] * 15 + [_i] * 6 + [_p]),
     "fvqa_trie_jump_step": (_i, [_p] * 5 + [_i] * 6 + [_p] * 16 + [_i] * 6 + [_p]),
     "fvqa_beam_step": (_i, [_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),

@@ -866,6 +866,92 @@ def decode_next_pair(logits, emb, ids, pos, done, gen_start, x_next, token, n_ke
     return token
 
 
+def decode_next_stream(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, req, budget,
+                       out_tokens, out_n_generated, *, out_logprob=None, node=None, trie=None, u=None, pos64=None,
+                       temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
+                       eos_id: int = 2, stop_at_eos: bool = True):
+    """The token step of in-flight batching (include/fvqa.h fvqa_decode_next_stream states the rule): decode_next_ex — with `node`
+    and `trie`, decode_next_trie — on B slots that hold requests. On top of their operands: req (B,) int32 — the request in each
+    slot, -1: none —, budget (N,) int32, out_tokens (N, W) int32, out_n_generated (N,) int32, out_logprob (N, W) fp32 or None;
+    u is (W, N) fp32: a slot at token index i of request r reads u[i, r]."""
+    have_trie = trie is not None
+    _need(have_trie == (node is not None), "decode_next_stream: node and trie come together")
+    nf = et = ec = None
+    n_nodes = n_edges = 0
+    if have_trie:
+        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_stream")
+    _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, req, budget, out_tokens,
+         out_n_generated, out_logprob, u, pos64, node, nf, et, ec)
+    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_stream: logits (B, V) fp32")
+    B, V = logits.shape
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype,
+          "decode_next_stream: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (B, D), "decode_next_stream: x_next (B, D)")
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_stream: ids (B, S) int64")
+    _need(out_tokens.dim() == 2 and out_tokens.dtype == torch.int32 and out_tokens.shape[0] >= 1 and out_tokens.shape[1] >= 1,
+          "decode_next_stream: out_tokens (N, W) int32")
+    N, W = out_tokens.shape
+    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (req, B), (n_active, 1), (counter, 1), (budget, N),
+                 (out_n_generated, N)) + (((node, B),) if have_trie else ()):
+        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_stream: pos / done / gen_start / token / n_kept / req / node "
+                                                         "(B,), budget / out_n_generated (N,), n_active / counter (1,) int32")
+    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_stream: logprob (B,) fp32")
+    _need(out_logprob is None or (out_logprob.dtype == torch.float32 and tuple(out_logprob.shape) == (N, W)),
+          "decode_next_stream: out_logprob (N, W) fp32")
+    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_stream: pos64 (B,) int64")
+    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and tuple(u.shape) == (W, N)),
+          "decode_next_stream: sampling needs u (W, N) fp32")
+    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1,
+          "decode_next_stream: top_k >= 0, repetition_penalty >= 1")
+    rc = _lib.load(emb.dtype).fvqa_decode_next_stream(
+        _ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(top_k), float(repetition_penalty), int(eos_id),
+        1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token), _ptr(n_kept),
+        _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges,
+        _ptr(req), _ptr(budget), N, W, _ptr(out_tokens), _ptr(out_logprob), _ptr(out_n_generated), B, V, D, ids.shape[1],
+        dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_decode_next_stream")
+    return token
+
+
+def slot_seat(slot, src, request, prompt_ids, prefix, vstart_src, logits_src, ids, pos, pos64, done, gen_start, vstart, req, lg,
+              err, *, root=None, node=None):
+    """Prefilled prompts take freed slots (include/fvqa.h fvqa_slot_seat). slot, src, request: three host lists of one length —
+    entry j seats row src[j] of the prefill (prompt_ids (M, S) int64, prefix (M,) int64, vstart_src (M,) int32, logits_src
+    (M, S, V) fp32, root (M,) int32 or None) in slot slot[j] for request request[j]. In/out per slot: ids (n, S) int64, pos / done /
+    gen_start / vstart / req / node (n,) int32, pos64 (n,) int64, lg (n, V) fp32; err (1,) int32: bit 0 is raised when the device
+    refused an entry (a slot or source row outside the arrays, a slot that holds a running request). Duplicate slots and duplicate
+    requests are refused here."""
+    slot, src, request = [int(x) for x in slot], [int(x) for x in src], [int(x) for x in request]
+    _need(len(slot) == len(src) == len(request) >= 1, "slot_seat: slot, src, request of one length >= 1")
+    _need(len(set(slot)) == len(slot), "slot_seat: a slot is named twice")
+    _need(len(set(request)) == len(request), "slot_seat: a request is named twice")
+    _need((root is None) == (node is None), "slot_seat: root and node come together")
+    _dev(prompt_ids, prefix, vstart_src, logits_src, root, ids, pos, pos64, done, gen_start, vstart, req, node, lg, err)
+    _need(ids.dim() == 2 and ids.dtype == torch.int64, "slot_seat: ids (n_slots, S) int64")
+    n_slots, S = ids.shape
+    _need(prompt_ids.dim() == 2 and prompt_ids.dtype == torch.int64 and prompt_ids.shape[1] == S,
+          "slot_seat: prompt_ids (M, S) int64")
+    M = prompt_ids.shape[0]
+    _need(lg.dim() == 2 and lg.dtype == torch.float32 and lg.shape[0] == n_slots, "slot_seat: lg (n_slots, V) fp32")
+    V = lg.shape[1]
+    _need(logits_src.dtype == torch.float32 and logits_src.numel() == M * S * V, "slot_seat: logits_src (M, S, V) fp32")
+    _need(prefix.dtype == torch.int64 and prefix.numel() == M, "slot_seat: prefix (M,) int64")
+    for t, n in ((vstart_src, M), (pos, n_slots), (done, n_slots), (gen_start, n_slots), (vstart, n_slots), (req, n_slots),
+                 (err, 1)) + (() if root is None else ((root, M), (node, n_slots))):
+        _need(t.dtype == torch.int32 and t.numel() == n, "slot_seat: vstart_src / root (M,), pos / done / gen_start / vstart / req / "
+                                                         "node (n_slots,), err (1,) int32")
+    _need(pos64.dtype == torch.int64 and pos64.numel() == n_slots, "slot_seat: pos64 (n_slots,) int64")
+    _need(len(slot) <= n_slots <= 65535, "slot_seat: at most n_slots <= 65535 entries")
+    tri = torch.tensor([slot, src, request], dtype=torch.int32).to(ids.device, non_blocking=True)
+    rc = _lib.load().fvqa_slot_seat(_ptr(tri[0]), _ptr(tri[1]), _ptr(tri[2]), len(slot), _ptr(prompt_ids), _ptr(prefix),
+                                    _ptr(vstart_src), _ptr(logits_src), _ptr(root), M, _ptr(ids), _ptr(pos), _ptr(pos64),
+                                    _ptr(done), _ptr(gen_start), _ptr(vstart), _ptr(req), _ptr(node), _ptr(lg), _ptr(err), n_slots,
+                                    S, V, _stream())
+    _lib.check(rc, "fvqa_slot_seat")
+    return tri
+
+
 BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
 
 

@@ -266,6 +266,58 @@ class Transformer(nn.Module):
         self.last_generation = {"ids": ids, "similarities": sims}
         return best, extracted
 
+    @torch.no_grad()
+    def inference_stream(self, batches, slots, admit=None):
+        """`inference` over a list of validation batches with in-flight batching (--gen_stream SLOTS; fvqa/stream.py): every row of
+        every batch is a request of ONE stream of `slots` rows — plain greedy with EOS stop (--gen_stop_eos's tokens), or
+        --gen_constrain options | vocab with one trie over all requests —, then `match_answers` per batch.
+        -> [(most_similar_indices, extracted_answers)] per batch. `last_generation`: the last batch's, plus "steps", "n_prefills"
+        and "occupancy" of the stream."""
+        from fvqa import constrain, generate, stream
+        eng = self.ensure_engine()
+        batches = list(batches)
+        for k, what in (("num_beams", 1), ("lookahead", 1), ("gen_jump_forward", 1)):
+            if int(getattr(self.args, k, 0) or 0) > what:
+                raise ValueError(f"--gen_stream decodes one token per row and pass: not with --{k} > {what}")
+        if getattr(self.args, "contrast", None):
+            raise ValueError("--gen_stream is not built for --contrast")
+        mode = getattr(self.args, "gen_constrain", None)
+        trie, n_new = None, generate.N_NEW
+        if mode == "options":
+            cons = []
+            for data in batches:
+                S = data["text_id"]["vqa"].shape[2]
+                cons += [[o[: max(S - int(p) - 1, 0)] for o in opts]
+                         for opts, p in zip(constrain.options_of(data, self.tokenizer), data["prefix_index"]["vqa"])]
+            trie = constrain.TokenTrie.from_sequences(cons, self.tokenizer.eos_id, eng.V)
+        elif mode == "vocab":
+            path = getattr(self.args, "answer_vocab", None)
+            if not path:
+                raise ValueError("--gen_constrain vocab needs --answer_vocab FILE")
+            trie = constrain.TokenTrie.from_sequences(constrain.encode_answers(self.tokenizer, constrain.read_answer_vocab(path)),
+                                                      self.tokenizer.eos_id, eng.V)
+        elif mode:
+            raise ValueError(f"gen_constrain: 'options' or 'vocab', not {mode!r}")
+        if trie is not None:
+            n_new = max(n_new, max(trie.max_len))
+        out = stream.generate_stream(eng, batches, slots=slots, admit=admit, max_new_tokens=n_new, temperature=0.0,
+                                     stop_at_eos=True, constraints=trie)
+        results, lo = [], 0
+        for data in batches:
+            hi = lo + data["text_id"]["vqa"].shape[0]
+            ids = out["ids"][lo:hi].contiguous()
+            best, sims, extracted = generate.match_answers(self, data, ids)
+            self.last_generation = {"ids": ids, "similarities": sims}
+            if trie is not None:
+                choice = out["choice"][lo:hi]
+                if mode == "options":
+                    best = torch.where(choice >= 0, choice.to(best.dtype), best)
+                self.last_generation["choice"] = choice
+            results.append((best, extracted))
+            lo = hi
+        self.last_generation.update(steps=out["steps"], n_prefills=out["n_prefills"], occupancy=out["occupancy"])
+        return results
+
     def _contrast_kw(self) -> dict:
         """--contrast / --contrast_alpha / --contrast_beta as generate's keywords ({} without --contrast)."""
         c = getattr(self.args, "contrast", None)
@@ -341,6 +393,32 @@ class Transformer(nn.Module):
                 answers.append([answer(ids[b, k, int(p): int(p) + int(n[b, k])].tolist()) for k in range(ids.shape[1])])
             else:
                 answers.append(answer(ids[b, int(p): int(p) + int(n[b])].tolist()))
+        return answers
+
+    @torch.no_grad()
+    def generate_stream(self, batches, **kw):
+        """`generate` over many requests with in-flight batching (fvqa.stream.generate_stream's keywords: slots, admit,
+        max_new_tokens — an int or one per request —, temperature, top_p, top_k, repetition_penalty, return_logprobs, constraints,
+        stop_at_eos, seed): `batches` is one batch of `prompt_batch` / a validation batch or a list of them, their rows are the
+        requests, and a finished row hands its slot of the decode batch to the next request. -> one answer per request, formed as
+        `generate` forms them. `last_generation`: "ids", "n_generated", "tokens", "steps", "n_prefills", "occupancy", "seated"
+        (and "logprobs", "sum_logprob", "choice" where asked). ValueError: num_beams, contrast, lookahead, jump_forward and
+        num_return_sequences are not built into the stream."""
+        from fvqa import stream
+        for k in ("num_beams", "contrast", "lookahead", "jump_forward", "num_return_sequences"):
+            if k in kw:
+                raise ValueError(f"generate_stream: {k} is not built into the stream (beams, contrast, lookahead, jump-forward "
+                                 "and several samples per prompt run through generate())")
+        out = stream.generate_stream(self.ensure_engine(), batches, **kw)
+        self.last_generation = {k: out[k] for k in ("ids", "n_generated", "tokens", "steps", "n_prefills", "occupancy", "seated",
+                                                     "logprobs", "sum_logprob", "choice") if k in out}
+        tokens, n = out["tokens"].cpu(), out["n_generated"].cpu()
+        answers = []
+        for r in range(tokens.shape[0]):
+            row = tokens[r, : int(n[r])].tolist()
+            if self.tokenizer.eos_id in row:
+                row = row[: row.index(self.tokenizer.eos_id)]
+            answers.append(self.tokenizer.decode(row) if self.tokenizer.sp_model is not None else row)
         return answers
 
     @torch.no_grad()

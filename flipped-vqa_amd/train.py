@@ -96,6 +96,14 @@ _FLAGS = [
                                      "constraints=..., jump_forward=T)): the tokens the trie of allowed answers fixes are committed "
                                      "without a pass of their own — the same answers in fewer passes. 0, 1: off. Not with "
                                      "--num_beams > 1, --contrast or --lookahead > 1")),
+    ("--gen_stream", dict(type=int, default=0, metavar="SLOTS",
+                          help="generation-task validation with in-flight batching (fvqa.stream.generate_stream): the split's "
+                               "questions go through one decode batch of SLOTS rows in which a finished row hands its slot to "
+                               "the next question; greedy with EOS stop (--gen_stop_eos's answers), or --gen_constrain. 0: off. "
+                               "Not with --num_beams > 1, --contrast, --lookahead > 1 or --gen_jump_forward > 1")),
+    ("--gen_stream_admit", dict(type=int, default=None, metavar="M",
+                                help="--gen_stream (answer.py: --slots / --admit): questions admitted per prefill, 1 .. SLOTS "
+                                     "(default: SLOTS // 2)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -107,8 +115,8 @@ _FLAGS = [
 class ArgumentParser(argparse.ArgumentParser):
     """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
     --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead or
-    --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for (answer.py uses
-    it too)."""
+    --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for, and
+    --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too)."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -139,6 +147,18 @@ class ArgumentParser(argparse.ArgumentParser):
                                + ("--gen_constrain" if flag == "gen_jump_forward" else "--constrain or --answer_vocab"))
                 if int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "contrast", None) or la > 1:
                     self.error(f"--{flag} is built for the greedy pick: not with --num_beams > 1, --contrast or --lookahead > 1")
+        for flag, admit in (("gen_stream", "gen_stream_admit"), ("slots", "admit")):
+            n = int(getattr(a, flag, 0) or 0)
+            if n < 0 or n > 65535:
+                self.error(f"0 <= --{flag} <= 65535")
+            m = getattr(a, admit, None)
+            if m is not None and not (n >= 1 and 1 <= int(m) <= n):
+                self.error(f"--{admit} lies in [1, --{flag}]")
+            if n >= 1 and (int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "contrast", None) or la > 1
+                           or int(getattr(a, "gen_jump_forward", 0) or 0) > 1 or int(getattr(a, "jump_forward", 0) or 0) > 1
+                           or int(getattr(a, "num_samples", 1) or 1) > 1):
+                self.error(f"--{flag} decodes one token per row and pass: not with --num_beams > 1, --contrast, --lookahead > 1, "
+                           "jump-forward or several samples per prompt")
         return a
 
 

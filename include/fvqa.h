@@ -389,6 +389,49 @@ int fvqa_decode_next_pair(const float* logits, const float* u, const void* emb, 
                           int32_t* n_plausible, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
                           int32_t* node, const int32_t* node_first, const int32_t* edge_token, const int32_t* edge_child,
                           int n_nodes, int n_edges, int n_seq, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* The token step of in-flight batching (the same kernel template in csrc/sample.hip with one more compile-time switch;
+ * fvqa/stream.py generate_stream): fvqa_decode_next_ex, or with a trie fvqa_decode_next_trie, on SLOTS that hold requests. The
+ * n_seq rows are the slots of the decode batch; the operands, the row stepping, n_active, the caller-owned ticket word and the
+ * errors of fvqa_decode_next_ex hold. node == node_first == edge_token == edge_child == NULL: no trie (n_nodes, n_edges
+ * ignored); else all four as in fvqa_decode_next_trie, one node per slot. In addition, int32 device arrays: req (n_seq) in — the
+ * request each slot holds, -1: none —, budget (n_req) in — the tokens each request may generate —, out_tokens (n_req, width)
+ * out, out_logprob (n_req, width) fp32 out or NULL, out_n_generated (n_req) out; u is (width, n_req) fp32: the draws of a
+ * request are its own, wherever and whenever it is seated. Per slot b, with r = req[b] and i = pos + 1 - gen_start[b]:
+ *   - r outside [0, n_req), or i outside [0, min(budget[r], width)): the slot is not live. It becomes done as a row with no
+ *     room does (token -1, n_kept 0, logprob 0, x_next = the embedding of its current token), and nothing of any request's
+ *     results is written. An empty slot is done = 1, req = -1, pos = 0 over an all-zero id row: a valid row for the layers.
+ *   - otherwise the rule of fvqa_decode_next_ex / _trie picks the token, reading the draw at u[i * n_req + r]; the slot is
+ *     stepped as there (token, n_kept and logprob are written per slot as well), and out_tokens[r, i] = token,
+ *     out_logprob[r, i] = logprob, out_n_generated[r] = i + 1.
+ *   - done = 1 also when i + 1 == budget[r]: the token is still written.
+ * Every index read from req, budget and gen_start is range-checked before it is used. With req = 0 .. n_seq - 1, budgets out of
+ * reach and width == 1 every operand fvqa_decode_next_ex / _trie writes comes out bit for bit. Two slots must not hold one
+ * request. FVQA_EINVAL also for a null req / budget / out_tokens / out_n_generated, a trie given in part; FVQA_ESHAPE also for
+ * n_req <= 0 or width <= 0. */
+int fvqa_decode_next_stream(const float* logits, const float* u, const void* emb, float temperature, float top_p, int top_k,
+                            float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done,
+                            const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
+                            int32_t* n_active, uint32_t* counter, int64_t* pos64, int32_t* node, const int32_t* node_first,
+                            const int32_t* edge_token, const int32_t* edge_child, int n_nodes, int n_edges, const int32_t* req,
+                            const int32_t* budget, int n_req, int width, int32_t* out_tokens, float* out_logprob,
+                            int32_t* out_n_generated, int n_seq, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* Seats prefilled prompts in freed slots of the decode batch (csrc/stream.hip; fvqa/stream.py), one launch per admission, one
+ * workgroup per entry. In: slot, src, request (n_admit) int32 — entry j puts row src[j] of the prefill into slot slot[j] for
+ * request request[j]; the slots of one call are distinct —; the prefill's prompt_ids (n_src, seq_len) int64, prefix (n_src)
+ * int64 (where each answer starts), vstart_src (n_src) int32, logits_src (n_src, seq_len, vocab) fp32, root (n_src) int32 (the
+ * trie root of each row) or NULL together with node. In/out, per slot: ids (n_slots, seq_len) int64, pos / done / gen_start /
+ * vstart / req / node (n_slots) int32, pos64 (n_slots) int64, lg (n_slots, vocab) fp32. For entry j: ids[slot] =
+ * prompt_ids[src], pos = pos64 = prefix - 1, gen_start = prefix, vstart = vstart_src[src], req = request, node = root[src],
+ * lg[slot] = logits_src[src, prefix - 1] (the row the first token is picked from), done = 0. prefix < 1 or > seq_len: done = 1,
+ * pos = pos64 = gen_start = 0 and lg is left alone — the request ends with zero tokens, as a row with no room.
+ * Refused — nothing of the entry is written, bit 0 of err (ONE 32-bit word owned by the caller) is raised —: slot outside
+ * [0, n_slots), src outside [0, n_src), a slot that holds a running request (done == 0 and req >= 0). The cached k / v of the
+ * prompt are moved by fvqa_kv_beam_move. FVQA_EINVAL: a null pointer (root and node: both or neither); FVQA_ESHAPE: a dimension
+ * <= 0, n_admit > n_slots, n_slots > 65535; FVQA_EALIGN: an int64 array off its 8-byte, another off its 4-byte boundary. */
+int fvqa_slot_seat(const int32_t* slot, const int32_t* src, const int32_t* request, int n_admit, const int64_t* prompt_ids,
+                   const int64_t* prefix, const int32_t* vstart_src, const float* logits_src, const int32_t* root, int n_src,
+                   int64_t* ids, int32_t* pos, int64_t* pos64, int32_t* done, int32_t* gen_start, int32_t* vstart, int32_t* req,
+                   int32_t* node, float* lg, uint32_t* err, int n_slots, int seq_len, int vocab, void* stream);
 /* The token step of draft-and-verify greedy decoding (csrc/spec.hip; generate(lookahead=T); prompt-lookup / assisted generation
  * restricted to greedy): one launch between the LM head and the next pass's first RMSNorm, one 256-thread workgroup per sequence.
  * A pass feeds every sequence up to T = lookahead rows: the last committed token and a DRAFT of the tokens behind it. Every draft

@@ -30,7 +30,12 @@ times, default 3) with the plain constrained call generate(constraints=C) on the
 sample (8 to 12 tokens each, two of them sharing their first two tokens and two more their first token: the options part within
 their first tokens and are then fixed up to their EOS) and one shared vocabulary of 400 answers of one to three words from a
 list of 60 (a trie that branches at its first depths and nowhere else). Per line: ms per batch and passes (the token steps that
-committed something) of each arm, and whether the ids are the plain call's."""
+committed something) of each arm, and whether the ids are the plain call's.
+--stream SLOTS --admit M [M ...] times in-flight batching, fvqa.stream.generate_stream(slots=SLOTS, admit=M), on --requests N
+requests (default 64) with stop_at_eos=False and per-request budgets cycling 3, 6, 12, 24 tokens, each arm interleaved (--pairs N
+times, default 3) with the plain arm: generate() over the same requests in batches of SLOTS, each at its batch's largest budget —
+what a rectangular batch must run. Prefills are included on both sides. Per line: ms per request, token steps, prefills and
+occupancy of each arm, beside what fvqa.stream.simulate predicts, and whether every request's tokens are the plain call's."""
 import argparse
 import os
 import sys
@@ -69,10 +74,16 @@ def main():
     ap.add_argument("--lookup_ngram", type=int, default=2, help="--lookahead: the prompt-lookup arm's longest n-gram")
     ap.add_argument("--jump_forward", type=int, nargs="*", default=[], help="jump-forward constrained decoding with up to T rows "
                     "per pass; several T: a line per round each, interleaved with the plain constrained call")
+    ap.add_argument("--stream", type=int, default=0, metavar="SLOTS", help="in-flight batching through SLOTS rows, interleaved "
+                    "with generate() over batches of SLOTS")
+    ap.add_argument("--admit", type=int, nargs="*", default=[], help="--stream: requests admitted per prefill; several M: an arm each")
+    ap.add_argument("--requests", type=int, default=64, help="--stream: the number of requests")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
         a.batch_size = a.val_batch_size
+    if a.stream:
+        a.batch_size = a.stream
     dev = torch.device("cuda", 0)
     margs = types.SimpleNamespace(
         llama_model_path="/nonexistent/", model=a.model, max_seq_len=128, adapter_len=10, adapter_layer=32,
@@ -89,7 +100,7 @@ def main():
     b = synth.make_batch(cfg, seed=5)
     B = a.batch_size
     b["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B)]}
-    if a.eos_at or a.lookahead or a.jump_forward:   # decided tokens: what a draft is verified against must not hang on a near tie
+    if a.eos_at or a.lookahead or a.jump_forward or a.stream:   # decided tokens: what a draft is verified against must not hang on a near tie
         import dataclasses
         from llama_vqa import fill_closed_form
         fill_closed_form(model, dataclasses.replace(cfg, max_feats=margs.max_feats, bias=margs.bias, tau=margs.tau,
@@ -128,6 +139,9 @@ def main():
         return
     if a.jump_forward:
         jump_lines(a, eng, b, timed)
+        return
+    if a.stream:
+        stream_lines(a, eng, cfg, timed)
         return
     if a.contrast:
         import dataclasses
@@ -241,6 +255,43 @@ def lookahead_lines(a, eng, b, timed):
                       f"lookahead={T}, {name}: {t_l * 1e3:7.1f} ms/batch, {t_l / N * 1e3:6.3f} ms per committed token, "
                       f"{N / passes:5.2f} tokens per pass ({passes} passes, {out['steps']} steps launched), {t_p / t_l:5.2f}x; "
                       f"ids {'equal' if same else 'DIFFER from'} the plain call's", flush=True)
+
+
+def stream_lines(a, eng, cfg, timed):
+    import dataclasses
+    from fvqa import stream
+    slots, N = a.stream, a.requests
+    tag = f"{a.model} L={eng.L} S=128 greedy, {N} requests, budgets 3/6/12/24"
+    budgets = [(3, 6, 12, 24)[r % 4] for r in range(N)]
+    batches = []
+    for k in range(0, N, slots):
+        n = min(slots, N - k)
+        d = synth.make_batch(dataclasses.replace(cfg, batch_size=n), seed=5 + k)
+        d["prefix_index"] = {"vqa": [60 + (k + i) % 32 for i in range(n)]}
+        batches.append(d)
+    ref, out = [], {}
+
+    def plain():
+        ref.clear()
+        for k, d in enumerate(batches):
+            ref.append(generate.generate(eng, d, stop_at_eos=False, max_new_tokens=max(budgets[k * slots:(k + 1) * slots])))
+
+    timed(plain, reps=1)
+    tok_plain = [row[:budgets[r]] for r, row in enumerate(sum((o["tokens"].tolist() for o in ref), []))]
+    steps_plain = sum(o["steps"] for o in ref)
+    for M in a.admit or [max(1, slots // 2)]:
+        fn = lambda: out.update(stream.generate_stream(eng, batches, slots=slots, admit=M, max_new_tokens=budgets,   # noqa: E731
+                                                       stop_at_eos=False))
+        timed(fn, reps=1)
+        same = [row[:budgets[r]] for r, row in enumerate(out["tokens"].tolist())] == tok_plain
+        sim = stream.simulate(budgets, slots, M)
+        for k in range(a.pairs or 3):
+            t_p, t_s = timed(plain, warm=0), timed(fn, warm=0)
+            print(f"{tag} round {k}: generate in batches of {slots}: {t_p / N * 1e3:7.2f} ms/request, {steps_plain} token steps, "
+                  f"{len(batches)} prefills of {slots}, occupancy {sum(budgets) / (slots * steps_plain):.3f} | stream slots={slots} "
+                  f"admit={M}: {t_s / N * 1e3:7.2f} ms/request, {out['steps']} token steps, {out['n_prefills']} prefills of {M}, "
+                  f"occupancy {out['occupancy']:.3f} (simulate: {sim[0]} steps, {sim[1]} prefills), {t_p / t_s:5.2f}x; tokens "
+                  f"{'equal' if same else 'DIFFER from'} the plain call's", flush=True)
 
 
 def jump_lines(a, eng, b, timed):
