@@ -14,7 +14,8 @@
 //            host ping-pongs them), the token at pos + 1, pos, score, done, n_generated; x_next = emb[token] (a carried slot:
 //            the embedding of its current token, so that the layer pass stays well-defined).
 //   count    one integer per launch crosses workgroups, through a CALLER-owned word that the caller zeroes once: each workgroup
-//            adds (1 | counts << 16) with an integer atomic, the last to arrive writes the count and puts the word back to zero.
+//            adds (1 | counts << 16) with an integer atomic, the last to arrive writes the count and puts the word back to zero
+//            (csrc/token_step.h).
 //
 // fvqa_beam_step_trie — the same template with TRIE = true (false in fvqa_beam_step, in which none of this exists): constrained
 // decoding over a trie in CSR form (fvqa/constrain.py). Every slot sits at a node; a live slot at a node >= 0 offers (j, v) only
@@ -22,33 +23,23 @@
 // order are unchanged, lse stays that of the whole raw row —, a live slot without a usable edge (or at a node outside the trie)
 // is finished first, a slot at node -1 offers every v. After the K winners are known the edge (j, v) of each child is looked up
 // again in its parent's list (a block-wide search, K of them) and the slot takes that edge's child; a carried slot keeps its
-// parent's node. All K old nodes are read into LDS before any is written. Every index read from the trie is clamped: the edge
-// range into [0, n_edges], tokens outside [0, V) are skipped, a child outside [0, n_nodes) becomes n_nodes (which finishes the
-// slot at its next step).
+// parent's node. All K old nodes are read into LDS before any is written. Every index read from the trie is clamped
+// (csrc/token_step.h): the edge range into [0, n_edges], tokens outside [0, V) are skipped, a child outside [0, n_nodes) becomes
+// n_nodes (which finishes the slot at its next step).
 //
 // fvqa_kv_beam_move — cached keys and values follow the beams: for destination sequence n the k and v thirds of cache rows
 // [lo[n], hi[n]) of every layer come from sequence src[n]. Direct (scratch == NULL, dst != src: the fan-out of a B-sequence
 // prefill into a B*K-sequence cache, adapter rows included) in one launch; through a scratch window (the per-token move inside
 // one cache, where the parents of a sample may form cycles) in two: gather every moved row, then scatter. A slot that is its own
 // parent launches blocks that return at once. The q third and every row outside the ranges are never written.
-#include "common.h"
+#include "token_step.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int KMAX = 8;
 constexpr int NONE = 0x7fffffff;
 
 __device__ __forceinline__ bool better(float v1, int i1, float v2, int i2) { return v1 > v2 || (v1 == v2 && i1 < i2); }
-
-// the operands fvqa_beam_step_trie adds (TRIE = true)
-struct TrieArgs {
-  int32_t* node;
-  const int32_t* node_first;
-  const int32_t* edge_token;
-  const int32_t* edge_child;
-  int n_nodes, n_edges;
-};
 
 template <typename T, bool TRIE>
 __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logits, const T* __restrict__ emb, int eos_id,
@@ -59,7 +50,8 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
                                                   int32_t* __restrict__ parent_out, int32_t* __restrict__ token_out,
                                                   T* __restrict__ x_next, int32_t* __restrict__ n_active,
                                                   unsigned* __restrict__ counter, int B, int K, int V, int D, int S, int vec16,
-                                                  TrieArgs tr) {
+                                                  TrieArgs ta) {
+  const Trie& tr = ta.trie;
   __shared__ float s_score[KMAX], s_lse[KMAX], redf[4];
   __shared__ int s_done[KMAX], s_pos[KMAX], s_ngen[KMAX];
   __shared__ float w_val[2][4], win_val[KMAX];
@@ -80,14 +72,9 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
   // ---- TRIE: every slot's node and (clamped) edge range; a live slot at a node without a usable edge is finished first
   if constexpr (TRIE) {
     if (tid < K) {
-      const int nd = tr.node[r0 + tid];
+      const int nd = ta.node[r0 + tid];
       int e0 = 0, e1 = 0;
-      if (nd >= 0 && nd < tr.n_nodes) {
-        e0 = tr.node_first[nd];
-        e1 = tr.node_first[nd + 1];
-        e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
-        e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
-      }
+      if (nd >= 0 && nd < tr.n_nodes) tr.edges(nd, e0, e1);
       s_node[tid] = nd;
       s_e0[tid] = e0;
       s_ne[tid] = e1 - e0;
@@ -107,8 +94,8 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
   // ---- lse of the live slots
   for (int j = 0; j < K; ++j) {
     if (s_done[j]) continue;                                       // (uniform over the workgroup)
-    const float* lg = logits + (r0 + j) * V;
-    float mx = -INFINITY;
+    const float* lg = logits + (r0 + j) * V;                       // row_lse of csrc/token_step.h, thread 0 alone taking the
+    float mx = -INFINITY;                                          // logarithm (as a call this launch measured slower)
     for (int i = tid; i < V; i += NT) mx = fmaxf(mx, lg[i]);
     const float m = block_max_256(mx, redf);
     float z = 0.f;
@@ -199,14 +186,10 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
         if (lane == 0) s_find[w] = at;
         __syncthreads();
         at = min(min(s_find[0], s_find[1]), min(s_find[2], s_find[3]));
-        nd = tr.n_nodes;
-        if (at != NONE) {
-          const int ch = tr.edge_child[s_e0[j] + at];
-          if (ch >= 0 && ch < tr.n_nodes) nd = ch;
-        }
+        nd = at != NONE ? tr.child(tr.edge_child[s_e0[j] + at]) : tr.n_nodes;
         __syncthreads();                                           // (s_find is read before the next round writes it)
       }
-      if (tid == 0) tr.node[r0 + i] = nd;                          // (the old nodes are all in s_node)
+      if (tid == 0) ta.node[r0 + i] = nd;                          // (the old nodes are all in s_node)
     }
   }
 
@@ -222,32 +205,19 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
     int64_t* dst_row = ids_out + (r0 + i) * S;
     for (int s = tid; s < S; s += NT) dst_row[s] = (!carried && s == pj + 1) ? (int64_t)v : src_row[s];
     int src_tok = v;
-    if (carried) {
-      const int at = pj < 0 ? 0 : (pj >= S ? S - 1 : pj);
-      const int64_t t = src_row[at];
-      src_tok = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);             // any valid embedding row: the batch stays rectangular
-    }
+    if (carried) src_tok = valid_token(src_row[valid_pos(pj, S)], V);
     if (tid == 0) {
       const size_t n = r0 + i;
       const int np = carried ? pj : pj + 1;
       pos[n] = np;
-      pos64[n] = np < 0 ? 0 : (np >= S ? S - 1 : np);
+      pos64[n] = valid_pos(np, S);
       score[n] = none ? s_score[j] : win_val[i];
       done[n] = (carried || (stop_at_eos && v == eos_id)) ? 1 : 0;
       n_generated[n] = s_ngen[j] + (carried ? 0 : 1);
       parent_out[n] = j;
       token_out[n] = carried ? -1 : v;
     }
-    const T* erow = emb + (size_t)src_tok * D;
-    T* xrow = x_next + (r0 + i) * D;
-    if (vec16) {
-      const int n16 = (int)((size_t)D * sizeof(T) / 16);
-      const uint4* s4 = reinterpret_cast<const uint4*>(erow);
-      uint4* d4 = reinterpret_cast<uint4*>(xrow);
-      for (int k = tid; k < n16; k += NT) d4[k] = s4[k];
-    } else {
-      for (int k = tid; k < D; k += NT) xrow[k] = erow[k];
-    }
+    copy_row(x_next + (r0 + i) * D, emb + (size_t)src_tok * D, D, vec16, tid);
   }
 
   // ---- the count: samples whose slot 0 is not finished, or samples with any unfinished slot
@@ -261,11 +231,7 @@ __global__ __launch_bounds__(NT) void beam_step_k(const float* __restrict__ logi
       const bool fin = none || s_done[j] != 0 || (stop_at_eos && v == eos_id);
       running |= fin ? 0 : 1;
     }
-    const unsigned old = atomicAdd(counter, 1u + (running ? 0x10000u : 0u));
-    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
-      *n_active = (int)(old >> 16) + running;
-      atomicExch(counter, 0u);
-    }
+    ticket_arrive(counter, n_active, B, running);
   }
 }
 
@@ -313,19 +279,19 @@ int beam_step_checked(const float* logits, const void* emb, int eos_id, int stop
   if (!logits || !emb || !ids_in || !ids_out || !pos || !score || !done || !n_generated || !pos64 || !parent || !token ||
       !x_next || !n_active || !counter)
     return FVQA_EINVAL;
-  if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
+  if (TRIE && fvqa_trie_given(tr.node, tr.trie.node_first, tr.trie.edge_token, tr.trie.edge_child) != 1) return FVQA_EINVAL;
   if (ids_in == ids_out) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_samples <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_beams < 1 || n_beams > KMAX || n_beams > vocab) return FVQA_ESHAPE;
   if (n_samples > 65535 || (long long)n_beams * vocab > 0x7ffffffeLL) return FVQA_ESHAPE;   // 16-bit arrivals; c fits an int
-  if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
+  if (TRIE && (tr.trie.n_nodes <= 0 || tr.trie.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) ||
       !fvqa_aligned(4, logits, pos, score, done, n_generated, parent, token, n_active, counter) ||
-      !fvqa_aligned(8, ids_in, ids_out, pos64) || !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child))
+      !fvqa_aligned(8, ids_in, ids_out, pos64) || !fvqa_aligned(4, tr.node, tr.trie.node_first, tr.trie.edge_token, tr.trie.edge_child))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  const int vec16 = ((size_t)dim * fvqa_dtype_size(dtype)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
+  const int vec16 = fvqa_vec16((size_t)dim * fvqa_dtype_size(dtype), emb, x_next);
   if (dtype == FVQA_H16)
     hipLaunchKernelGGL((beam_step_k<bf16_t, TRIE>), dim3(n_samples), dim3(NT), 0, st, logits, (const bf16_t*)emb, eos_id,
                        stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token,
@@ -347,7 +313,7 @@ extern "C" int fvqa_beam_step(const float* logits, const void* emb, int eos_id, 
                               int dtype, void* stream) {
   return beam_step_checked<false>(logits, emb, eos_id, stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done,
                                   n_generated, pos64, parent, token, x_next, n_active, counter, n_samples, n_beams, vocab, dim,
-                                  seq_len, dtype, stream, TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0});
+                                  seq_len, dtype, stream, TrieArgs{});
 }
 
 extern "C" int fvqa_beam_step_trie(const float* logits, const void* emb, int eos_id, int stop_at_eos, int count_any_live,
@@ -358,7 +324,7 @@ extern "C" int fvqa_beam_step_trie(const float* logits, const void* emb, int eos
                                    int n_samples, int n_beams, int vocab, int dim, int seq_len, int dtype, void* stream) {
   return beam_step_checked<true>(logits, emb, eos_id, stop_at_eos, count_any_live, ids_in, ids_out, pos, score, done,
                                  n_generated, pos64, parent, token, x_next, n_active, counter, n_samples, n_beams, vocab, dim,
-                                 seq_len, dtype, stream, TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges});
+                                 seq_len, dtype, stream, TrieArgs{node, {node_first, edge_token, edge_child, n_nodes, n_edges}});
 }
 
 extern "C" size_t fvqa_kv_beam_move_scratch(int n_seq, int window_rows, int dim, int n_layers, int dtype) {

@@ -16,50 +16,13 @@
 //            inside the vocabulary". The committed tokens stay in LDS for the embedding gather.
 //   outputs  the rows of the next pass (embeddings of the committed tokens; zeros behind), start / len for the suffix attention,
 //            the step's tokens and log-probabilities, the count of running rows through the caller's ticket word (an INTEGER
-//            atomic; the workgroup that arrives last writes the count and puts the word back to zero, as in csrc/sample.hip).
+//            atomic; the workgroup that arrives last writes the count and puts the word back to zero: csrc/token_step.h).
 // No float atomics, fixed summation orders: two launches on the same inputs give the same bits.
-#include "common.h"
+#include "token_step.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int TMAX = 16;                 // rows of a sequence per pass (fvqa_attn_suffix's suffix_len limit)
-
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ int block_min_int(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return min(min(red[0], red[1]), min(red[2], red[3]));
-}
-
-// m + log(sum exp(l - m)) of one raw row, as csrc/sample.hip takes it (the same bits)
-__device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, float* red) {
-  float mx = -INFINITY;
-  for (int i = threadIdx.x; i < V; i += NT) mx = fmaxf(mx, lg[i]);
-  const float m = block_max_256(mx, red);
-  float z = 0.f;
-  for (int i = threadIdx.x; i < V; i += NT) z += expf(lg[i] - m);
-  return m + logf(block_sum_256(z, red));
-}
-
-struct Trie {
-  const int32_t* node_first;
-  const int32_t* edge_token;
-  const int32_t* edge_child;
-  int n_nodes, n_edges;
-};
 
 template <typename T>
 __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__ logits, const T* __restrict__ emb, Trie tr,
@@ -113,9 +76,8 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
     cons = true;
     N = 0;
     if (tr.node_first && nd >= 0 && nd < tr.n_nodes) {
-      int e0 = tr.node_first[nd], e1 = tr.node_first[nd + 1];
-      e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
-      e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
+      int e0, e1;
+      tr.edges(nd, e0, e1);
       et = tr.edge_token + e0;
       ec = tr.edge_child + e0;
       N = e1 - e0;
@@ -142,10 +104,7 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
     int sel = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
     if (sel >= N) sel = first_ok;                                  // (a row of NaNs)
     tok = cons ? et[sel] : sel;
-    if (cons) {
-      child = ec[sel];
-      if (child < 0 || child >= tr.n_nodes) child = tr.n_nodes;    // (a broken trie: the row ends at its next step)
-    }
+    if (cons) child = tr.child(ec[sel]);
   }
   __syncthreads();                                                 // (every read of pos / done / len / w / node above is over)
 
@@ -161,9 +120,8 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
       if (cons) cur = child;
       if (tok == eos_id || ngen >= max_new) now_done = 1;
       while (cons && !now_done && nc < Tn && p + 1 < S && ngen < max_new && cur >= 0 && cur < tr.n_nodes) {
-        int e0 = tr.node_first[cur], e1 = tr.node_first[cur + 1];
-        e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
-        e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
+        int e0, e1;
+        tr.edges(cur, e0, e1);
         if (e1 - e0 != 1) break;                                   // a decision (or a dead end): the next step's pick
         const int t = tr.edge_token[e0];
         if ((unsigned)t >= (unsigned)V) break;
@@ -172,9 +130,7 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
         ngen += 1;
         row_ids[p] = t;
         cm[nc++] = t;
-        int ch = tr.edge_child[e0];
-        if (ch < 0 || ch >= tr.n_nodes) ch = tr.n_nodes;
-        cur = ch;
+        cur = tr.child(tr.edge_child[e0]);
         if (t == eos_id || ngen >= max_new) now_done = 1;
       }
       pos[b] = p;
@@ -188,46 +144,26 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
     n_committed[b] = nc;
     done[b] = now_done;
     // what the next pass feeds: a running row all it committed, from the first one's position on; a done row one valid row
-    const int at = p < 0 ? 0 : (p >= S ? S - 1 : p);
+    const int at = valid_pos(p, S);
     const int feed = now_done ? 0 : nc;
     const int st = now_done ? at : p0 + 1;
     len_p[b] = feed;
     start_p[b] = st;
     if (pos64) pos64[b] = st;
     int src = 0;
-    if (now_done) {
-      const int64_t t = nc > 0 ? (int64_t)cm[nc - 1] : row_ids[at];     // (the id at `at`: a commit of this step is in LDS)
-      src = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);                 // any valid embedding row: the batch stays rectangular
-    }
+    if (now_done) src = valid_token(nc > 0 ? (int64_t)cm[nc - 1] : row_ids[at], V);   // (a commit of this step is in LDS)
     s_nc = feed;
     s_done = now_done;
     s_src = src;
-    const unsigned old = atomicAdd(counter, 1u + (now_done ? 0u : 0x10000u));
-    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
-      *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
-      atomicExch(counter, 0u);
-    }
+    ticket_arrive(counter, n_active, B, !now_done);
   }
   __syncthreads();
   // ---- the next pass's input rows: emb of the committed tokens (a done row: of its current token, one row), zeros behind
-  const int n_emb = s_done ? 1 : s_nc;
+  const int n_emb = s_done ? 1 : s_nc;                             // (next_pass_rows costs this kernel two SGPRs and a wave of occupancy)
   for (int j = 0; j < Tn; ++j) {
     T* dst = x_next + ((size_t)b * Tn + j) * D;
-    if (j < n_emb) {
-      const int t = s_done ? s_src : cm[j];
-      const T* src = emb + (size_t)t * D;
-      if (vec16) {
-        const int n16 = (int)((size_t)D * sizeof(T) / 16);
-        for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
-      } else {
-        for (int i = tid; i < D; i += NT) dst[i] = src[i];
-      }
-    } else if (vec16) {
-      const int n16 = (int)((size_t)D * sizeof(T) / 16);
-      for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = make_uint4(0u, 0u, 0u, 0u);
-    } else {
-      for (int i = tid; i < D; i += NT) dst[i] = from_f32<T>(0.f);
-    }
+    if (j < n_emb) copy_row(dst, emb + (size_t)(s_done ? s_src : cm[j]) * D, D, vec16, tid);
+    else zero_row(dst, D, vec16, tid);
   }
 }
 
@@ -244,8 +180,9 @@ extern "C" int fvqa_trie_jump_step(const float* logits, const void* emb, const i
       !logprob_fed || !n_committed || !n_active || !counter)
     return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  const bool no_trie = !node && !node_first && !edge_token && !edge_child;   // every row unconstrained
-  if (!no_trie && (!node || !node_first || !edge_token || !edge_child)) return FVQA_EINVAL;   // a trie given in part
+  const int given = fvqa_trie_given(node, node_first, edge_token, edge_child);
+  if (given < 0) return FVQA_EINVAL;
+  const bool no_trie = given == 0;                                 // every row unconstrained
   if (n_seq <= 0 || jump_forward <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0) return FVQA_ESHAPE;
   if (jump_forward > TMAX || n_seq > 65535 || (int64_t)n_seq * jump_forward > 65535) return FVQA_ESHAPE;   // (the ticket counts
                                                                    // arrivals in 16 bits; the pass's rows are a grid dimension)
@@ -257,19 +194,13 @@ extern "C" int fvqa_trie_jump_step(const float* logits, const void* emb, const i
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   const Trie tr{node_first, edge_token, edge_child, no_trie ? 0 : n_nodes, no_trie ? 0 : n_edges};
-  if (dtype == FVQA_H16) {
-    const int vec16 = ((size_t)dim * sizeof(bf16_t)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-    hipLaunchKernelGGL(trie_jump_step_k<bf16_t>, dim3(n_seq), dim3(NT), 0, st, logits, (const bf16_t*)emb, tr, eos_id,
-                       max_new_tokens, chain_eos, want_logprobs, ids, pos, done, n_generated, node, w, len, start, pos64,
-                       (bf16_t*)x_next, token, logprob_pick, logprob_fed, n_committed, n_active, counter, n_seq, jump_forward,
-                       vocab, dim, seq_len, vec16);
-  } else {
-    const int vec16 = ((size_t)dim * sizeof(float)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-    hipLaunchKernelGGL(trie_jump_step_k<float>, dim3(n_seq), dim3(NT), 0, st, logits, (const float*)emb, tr, eos_id,
-                       max_new_tokens, chain_eos, want_logprobs, ids, pos, done, n_generated, node, w, len, start, pos64,
-                       (float*)x_next, token, logprob_pick, logprob_fed, n_committed, n_active, counter, n_seq, jump_forward,
-                       vocab, dim, seq_len, vec16);
-  }
+  fvqa_by_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(trie_jump_step_k<T>, dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, tr, eos_id, max_new_tokens,
+                       chain_eos, want_logprobs, ids, pos, done, n_generated, node, w, len, start, pos64, (T*)x_next, token,
+                       logprob_pick, logprob_fed, n_committed, n_active, counter, n_seq, jump_forward, vocab, dim, seq_len,
+                       fvqa_vec16(dim * sizeof(T), emb, x_next));
+  });
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

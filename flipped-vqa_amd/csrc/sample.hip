@@ -20,9 +20,8 @@
 // Every sum runs in a fixed order (a thread's strided or contiguous elements, then shuffles, then the four waves in order);
 // there are no atomics on floats: two launches on the same inputs give the same bits.
 //
-// n_active needs a count across workgroups: each adds (1 arrival | its row still running << 16) to one device-resident ticket
-// word with an INTEGER atomic; the workgroup that arrives last writes the count and puts the ticket back to zero. The ticket is
-// a module global: launches of this entry on one device must be ordered (one stream, or events), as the decode loop's are.
+// n_active needs a count across workgroups: the ticket word of csrc/token_step.h. The ticket of fvqa_decode_next is a module
+// global: launches of this entry on one device must be ordered (one stream, or events), as the decode loop's are.
 //
 // fvqa_decode_next_ex is the same kernel template with EX = true (the old entry instantiates EX = false, in which none of the
 // following exists): a repetition penalty, top-k, the token's log-probability and a ticket word the caller owns.
@@ -43,8 +42,9 @@
 // token order the list order is the index order of the rule. An edge whose token lies outside [0, V) is skipped: it is left out
 // of every count by an explicit test (its e would otherwise tie with an allowed token whose e underflowed to 0), top-k is cut
 // against the NUMBER ALLOWED, and the walk falls back to the last kept (or, on a row of NaNs, the first allowed) edge. Every
-// index read from the trie is clamped before it is used: the edge range into [0, n_edges], the child into [0, n_nodes) (else
-// the row is sent to the node n_nodes, which ends it at the next step). A row at node == -1 runs the loops over V as before.
+// index read from the trie is clamped before it is used (csrc/token_step.h): the edge range into [0, n_edges], the child into
+// [0, n_nodes) (else the row is sent to the node n_nodes, which ends it at the next step). A row at node == -1 runs the loops
+// over V as before.
 //
 // fvqa_decode_next_pair is the template with PAIR = true (false in the three entries above, in which none of the following
 // exists), with and without TRIE: contrastive decoding against a twin row. A workgroup owns a PAIR of rows — b, the positive
@@ -65,34 +65,13 @@
 // [0, min(budget[r], width)), is not live: it becomes done and nothing of any request's results is written. A live slot picks by
 // the _ex / _trie rule with the draw at u[i * n_req + r] — the request's own, wherever and whenever it sits —, is stepped as
 // before, leaves its token, log-probability and count in the request's result rows, and is also done once i + 1 == budget[r].
-#include "common.h"
+#include "token_step.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr size_t ROW_LDS_MAX = 144 * 1024;       // beside ~100 bytes of reduction scratch, under the CU's 160 KiB
 
 __device__ unsigned g_ticket = 0;
-
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ int block_min_int(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return min(min(red[0], red[1]), min(red[2], red[3]));
-}
-__device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
 
 // exclusive prefix of v over the 256 threads in thread order (fixed tree); *total = the sum over all of them
 __device__ __forceinline__ float block_scan_f(float v, float* wtot, float* total) {
@@ -127,25 +106,6 @@ __device__ __forceinline__ int block_scan_i(int v, int* wtot) {
   return base + x - v;
 }
 
-// m + log(sum exp(l - m)) of one raw row, as fvqa_beam_step takes it
-__device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, float* red) {
-  float mx = -INFINITY;
-  for (int i = threadIdx.x; i < V; i += NT) mx = fmaxf(mx, lg[i]);
-  const float m = block_max_256(mx, red);
-  float z = 0.f;
-  for (int i = threadIdx.x; i < V; i += NT) z += expf(lg[i] - m);
-  return m + logf(block_sum_256(z, red));
-}
-
-// the operands fvqa_decode_next_trie adds (TRIE = true)
-struct TrieArgs {
-  int32_t* node;
-  const int32_t* node_first;
-  const int32_t* edge_token;
-  const int32_t* edge_child;
-  int n_nodes, n_edges;
-};
-
 // the operands fvqa_decode_next_pair adds (PAIR = true)
 struct PairArgs {
   float alpha, beta;
@@ -172,7 +132,8 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
                                                     int D, int S, int row_in_lds, int vec16, int top_k, float rep,
                                                     const int32_t* __restrict__ gen_start,
                                                     float* __restrict__ logprob_out, unsigned* __restrict__ counter,
-                                                    TrieArgs tr, PairArgs pr, StreamArgs sa) {
+                                                    TrieArgs ta, PairArgs pr, StreamArgs sa) {
+  const Trie& tr = ta.trie;
   static_assert(EX || !TRIE, "the trie entry extends the EX entry");
   static_assert(EX || !PAIR, "the pair entry extends the EX entry");
   static_assert((EX && !PAIR) || !STREAM, "the stream entry extends the EX entry, one row per slot");
@@ -208,14 +169,13 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   const int32_t* et = nullptr;
   const int32_t* ec = nullptr;
   if constexpr (TRIE) {
-    nd = tr.node[b];
+    nd = ta.node[b];
     if (live && nd != -1) {
       cons = true;
       N = 0;
       if (nd >= 0 && nd < tr.n_nodes) {
-        int e0 = tr.node_first[nd], e1 = tr.node_first[nd + 1];
-        e0 = e0 < 0 ? 0 : (e0 > tr.n_edges ? tr.n_edges : e0);
-        e1 = e1 < e0 ? e0 : (e1 > tr.n_edges ? tr.n_edges : e1);
+        int e0, e1;
+        tr.edges(nd, e0, e1);
         et = tr.edge_token + e0;
         ec = tr.edge_child + e0;
         N = e1 - e0;
@@ -432,10 +392,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
   if (live) {
     tok = tk(sel);
     if constexpr (TRIE) {
-      if (cons) {
-        child = ec[sel];
-        if (child < 0 || child >= tr.n_nodes) child = tr.n_nodes;  // (a broken trie: the row ends at its next step)
-      }
+      if (cons) child = tr.child(ec[sel]);
     }
   }
 
@@ -451,9 +408,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     }
   } else {
     now_done = 1;
-    const int at = p < 0 ? 0 : (p >= S ? S - 1 : p);
-    const int64_t t = row_ids[at];
-    src = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);                   // any valid embedding row: the batch stays rectangular
+    src = valid_token(row_ids[valid_pos(p, S)], V);
   }
   __syncthreads();                                                 // (every read of done / pos / ids above is over)
   if (tid == 0) {
@@ -462,18 +417,18 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       pos[b] = p;
     }
     done[b] = now_done;
-    if (pos64) pos64[b] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
+    if (pos64) pos64[b] = live ? p : valid_pos(p, S);
     if constexpr (PAIR) {                                          // the twin row is stepped, or left, like the positive one
       if (live) ids[((size_t)b + B) * S + p] = tok;
       pos[b + B] = p;
       done[b + B] = now_done;
-      if (pos64) pos64[b + B] = live ? p : (p < 0 ? 0 : (p >= S ? S - 1 : p));
+      if (pos64) pos64[b + B] = live ? p : valid_pos(p, S);
       pr.n_plausible[b] = live ? n_plaus : 0;
     }
     token_out[b] = tok;
     n_kept_out[b] = kept;
     if constexpr (TRIE) {
-      if (live && cons) tr.node[b] = child;
+      if (live && cons) ta.node[b] = child;
     }
     if constexpr (EX) logprob_out[b] = live ? lg[tok] - lse : 0.f;
     if constexpr (STREAM) {
@@ -483,31 +438,13 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
         sa.out_n_generated[r] = ti + 1;
       }
     }
-    unsigned* ticket = EX ? counter : &g_ticket;
-    const unsigned old = atomicAdd(ticket, 1u + (now_done ? 0u : 0x10000u));
-    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
-      *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
-      atomicExch(ticket, 0u);
-    }
+    ticket_arrive(EX ? counter : &g_ticket, n_active, B, !now_done);
   }
   // ---- the next input row
   const T* erow_src = emb + (size_t)src * D;
   T* dst = x_next + (size_t)b * D;
-  if (vec16) {
-    const int n16 = (int)((size_t)D * sizeof(T) / 16);
-    const uint4* s4 = reinterpret_cast<const uint4*>(erow_src);
-    uint4* d4 = reinterpret_cast<uint4*>(dst);
-    for (int i = tid; i < n16; i += NT) d4[i] = s4[i];
-    if constexpr (PAIR) {
-      uint4* e4 = reinterpret_cast<uint4*>(dst + (size_t)B * D);
-      for (int i = tid; i < n16; i += NT) e4[i] = s4[i];
-    }
-  } else {
-    for (int i = tid; i < D; i += NT) dst[i] = erow_src[i];
-    if constexpr (PAIR) {
-      for (int i = tid; i < D; i += NT) dst[(size_t)B * D + i] = erow_src[i];
-    }
-  }
+  copy_row(dst, erow_src, D, vec16, tid);
+  if constexpr (PAIR) copy_row(dst + (size_t)B * D, erow_src, D, vec16, tid);   // the twin's row
 }
 
 // the operands fvqa_decode_next_ex adds (the old entry passes none: EX = false)
@@ -538,8 +475,7 @@ int launch(const float* logits, const float* u, const void* emb, float temperatu
   if (fvqa_attr_needed(attr_done))
     (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE, PAIR, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
-  const int vec16 = ((size_t)D * sizeof(T)) % 16 == 0 && fvqa_aligned(16, emb, x_next);   // (PAIR: the twin half follows B * D
-                                                                                            //  elements on, whole 16-byte rows)
+  const int vec16 = fvqa_vec16((size_t)D * sizeof(T), emb, x_next);   // (PAIR: the twin half follows B * D elements on, whole rows)
   hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR, STREAM>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature,
                      top_p, eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds,
                      vec16, ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr, sa);
@@ -552,12 +488,12 @@ template <bool EX, bool TRIE = false, bool PAIR = false, bool STREAM = false>
 int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
                    int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
                    int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
-                   void* stream, TrieArgs tr = TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0},
+                   void* stream, TrieArgs tr = TrieArgs{},
                    PairArgs pr = PairArgs{0.f, 0.f, nullptr},
                    StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
   if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
   if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
-  if (TRIE && (!tr.node || !tr.node_first || !tr.edge_token || !tr.edge_child)) return FVQA_EINVAL;
+  if (TRIE && fvqa_trie_given(tr.node, tr.trie.node_first, tr.trie.edge_token, tr.trie.edge_child) != 1) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (!(temperature >= 0.f)) return FVQA_EINVAL;                   // (a NaN fails the comparison)
   if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
@@ -569,10 +505,10 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
   if (n_seq <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0) return FVQA_ESHAPE;
   if (n_seq > 65535) return FVQA_ESHAPE;                           // (the ticket word counts arrivals in 16 bits)
   if (PAIR && 2 * (int64_t)n_seq > 65535) return FVQA_ESHAPE;      // (n_seq pairs are 2 * n_seq rows of the token loop)
-  if (TRIE && (tr.n_nodes <= 0 || tr.n_edges < 0)) return FVQA_ESHAPE;
+  if (TRIE && (tr.trie.n_nodes <= 0 || tr.trie.n_edges < 0)) return FVQA_ESHAPE;
   if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) || !fvqa_aligned(4, logits, u, pos, done, token, n_kept, n_active) ||
       !fvqa_aligned(8, ids, pos64) || !fvqa_aligned(4, ex.gen_start, ex.logprob, ex.counter) ||
-      !fvqa_aligned(4, tr.node, tr.node_first, tr.edge_token, tr.edge_child) || !fvqa_aligned(4, pr.n_plausible) ||
+      !fvqa_aligned(4, tr.node, tr.trie.node_first, tr.trie.edge_token, tr.trie.edge_child) || !fvqa_aligned(4, pr.n_plausible) ||
       !fvqa_aligned(4, sa.req, sa.budget, sa.out_tokens, sa.out_logprob, sa.out_n_generated))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
@@ -615,7 +551,7 @@ extern "C" int fvqa_decode_next_trie(const float* logits, const float* u, const 
   return checked_launch<true, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
                                     n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
                                     ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream,
-                                    TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges});
+                                    TrieArgs{node, {node_first, edge_token, edge_child, n_nodes, n_edges}});
 }
 
 extern "C" int fvqa_decode_next_pair(const float* logits, const float* u, const void* emb, float temperature, float top_p,
@@ -627,13 +563,13 @@ extern "C" int fvqa_decode_next_pair(const float* logits, const float* u, const 
                                      int vocab, int dim, int seq_len, int dtype, void* stream) {
   const ExArgs ex{top_k, repetition_penalty, gen_start, logprob, counter};
   const PairArgs pr{alpha, beta, n_plausible};
-  if (!node && !node_first && !edge_token && !edge_child)          // no trie at all: the pairs pick from the vocabulary
+  if (fvqa_trie_given(node, node_first, edge_token, edge_child) == 0)   // no trie at all: the pairs pick from the vocabulary
     return checked_launch<true, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
                                              token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
-                                             TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, pr);
+                                             TrieArgs{}, pr);
   return checked_launch<true, true, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token,
                                           n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
-                                          TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges}, pr);
+                                          TrieArgs{node, {node_first, edge_token, edge_child, n_nodes, n_edges}}, pr);
 }
 
 extern "C" int fvqa_decode_next_stream(const float* logits, const float* u, const void* emb, float temperature, float top_p,
@@ -648,11 +584,11 @@ extern "C" int fvqa_decode_next_stream(const float* logits, const float* u, cons
   const ExArgs ex{top_k, repetition_penalty, gen_start, logprob, counter};
   const PairArgs pr{0.f, 0.f, nullptr};
   const StreamArgs sa{req, budget, n_req, width, out_tokens, out_logprob, out_n_generated};
-  if (!node && !node_first && !edge_token && !edge_child)          // no trie at all: the slots pick from the vocabulary
+  if (fvqa_trie_given(node, node_first, edge_token, edge_child) == 0)   // no trie at all: the slots pick from the vocabulary
     return checked_launch<true, false, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
                                                     x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex,
-                                                    stream, TrieArgs{nullptr, nullptr, nullptr, nullptr, 0, 0}, pr, sa);
+                                                    stream, TrieArgs{}, pr, sa);
   return checked_launch<true, true, false, true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
                                                  token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, dtype, ex, stream,
-                                                 TrieArgs{node, node_first, edge_token, edge_child, n_nodes, n_edges}, pr, sa);
+                                                 TrieArgs{node, {node_first, edge_token, edge_child, n_nodes, n_edges}}, pr, sa);
 }

@@ -16,26 +16,14 @@
 //            Every index is clamped, every id that would be fed on is checked against [0, vocab).
 //   outputs  the rows of the next pass (embeddings; zeros behind the draft), start / len for fvqa_attn_suffix_append, the step's
 //            tokens and log-probabilities, the count of running rows through the caller's ticket word (an INTEGER atomic; the
-//            workgroup that arrives last writes the count and puts the word back to zero, as in csrc/sample.hip).
+//            workgroup that arrives last writes the count and puts the word back to zero: csrc/token_step.h).
 // No float atomics, fixed summation orders: two launches on the same inputs give the same bits.
-#include "common.h"
+#include "token_step.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int TMAX = 16;                 // rows of a sequence per pass (fvqa_attn_suffix's suffix_len limit)
 constexpr int GMAX = 4;                  // the longest n-gram the prompt lookup matches
-
-__device__ __forceinline__ int block_min_int(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return min(min(red[0], red[1]), min(red[2], red[3]));
-}
-__device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
 
 template <typename T>
 __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logits, const T* __restrict__ emb,
@@ -78,8 +66,8 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
       const float mx = block_max_256(bv, redf);
       int g = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
       if (g >= V) g = 0;                                           // (a row of NaNs)
-      float z = 0.f;
-      for (int v = tid; v < V; v += NT) z += expf(lg[v] - mx);
+      float z = 0.f;                                               // row_lse's second half on the arg-max's maximum: a call
+      for (int v = tid; v < V; v += NT) z += expf(lg[v] - mx);     // would add a pass over the row (the same operations and bits)
       const float lse = mx + logf(block_sum_256(z, redf));
       p += 1;
       ngen += 1;
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
 
   // ---- the next pass: w'_0, the room m', the draft
   const int P = p;                                                 // the row's position now (live: 0 <= P <= S - 1)
-  const int at = P < 0 ? 0 : (P >= S ? S - 1 : P);
+  const int at = valid_pos(P, S);
   int m2 = 0;
   if (!now_done) {
     m2 = min(Tn, min(max_new - ngen, S - 1 - P));
@@ -122,14 +110,7 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
     }
   }
   if (tid == 0) {
-    int w0;
-    if (live) {
-      w0 = cm[nc - 1];
-    } else {
-      const int64_t t = row_ids[at];
-      w0 = t < 0 ? 0 : (t >= V ? V - 1 : (int)t);                  // any valid embedding row: the batch stays rectangular
-    }
-    wn[0] = w0;
+    wn[0] = live ? cm[nc - 1] : valid_token(row_ids[at], V);
     int nd = 0;
     if (m2 >= 2) {
       if (draft_tokens) {
@@ -169,33 +150,11 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
     }
     n_committed[b] = nc;
     n_drafted[b] = live ? m - 1 : 0;
-    const unsigned old = atomicAdd(counter, 1u + (now_done ? 0u : 0x10000u));
-    if ((int)(old & 0xffffu) == B - 1) {                           // the last workgroup to arrive
-      *n_active = (int)(old >> 16) + (now_done ? 0 : 1);
-      atomicExch(counter, 0u);
-    }
+    ticket_arrive(counter, n_active, B, !now_done);
   }
   __syncthreads();
   // ---- the next pass's input rows: emb[w'_j] for j < m' (row 0 always: a row that feeds nothing stays a valid row), zeros behind
-  int n_emb = s_len;
-  if (n_emb < 1) n_emb = 1;
-  for (int j = 0; j < Tn; ++j) {
-    T* dst = x_next + ((size_t)b * Tn + j) * D;
-    if (j < n_emb) {
-      const T* src = emb + (size_t)wn[j] * D;
-      if (vec16) {
-        const int n16 = (int)((size_t)D * sizeof(T) / 16);
-        for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
-      } else {
-        for (int i = tid; i < D; i += NT) dst[i] = src[i];
-      }
-    } else if (vec16) {
-      const int n16 = (int)((size_t)D * sizeof(T) / 16);
-      for (int i = tid; i < n16; i += NT) reinterpret_cast<uint4*>(dst)[i] = make_uint4(0u, 0u, 0u, 0u);
-    } else {
-      for (int i = tid; i < D; i += NT) dst[i] = from_f32<T>(0.f);
-    }
-  }
+  next_pass_rows(x_next, emb, b, Tn, D, vec16, tid, s_len < 1 ? 1 : s_len, [&](int j) { return wn[j]; });
 }
 
 }  // namespace
@@ -220,19 +179,13 @@ extern "C" int fvqa_spec_step(const float* logits, const void* emb, const int32_
       !fvqa_aligned(8, ids, pos64))
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FVQA_H16) {
-    const int vec16 = ((size_t)dim * sizeof(bf16_t)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-    hipLaunchKernelGGL(spec_step_k<bf16_t>, dim3(n_seq), dim3(NT), 0, st, logits, (const bf16_t*)emb, draft_tokens,
-                       lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
-                       (bf16_t*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead,
-                       vocab, dim, seq_len, vec16);
-  } else {
-    const int vec16 = ((size_t)dim * sizeof(float)) % 16 == 0 && fvqa_aligned(16, emb, x_next);
-    hipLaunchKernelGGL(spec_step_k<float>, dim3(n_seq), dim3(NT), 0, st, logits, (const float*)emb, draft_tokens,
-                       lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
-                       (float*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead,
-                       vocab, dim, seq_len, vec16);
-  }
+  fvqa_by_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(spec_step_k<T>, dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, draft_tokens, lookup_ngram, eos_id,
+                       stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start, (T*)x_next, token, logprob,
+                       n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab, dim, seq_len,
+                       fvqa_vec16(dim * sizeof(T), emb, x_next));
+  });
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

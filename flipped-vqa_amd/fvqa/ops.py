@@ -56,6 +56,17 @@ def _need(cond: bool, msg: str):
         raise ValueError(msg)
 
 
+def _rider(what: str, rider_a, rider_b, rider_out, accumulate: bool = False):
+    """The small product a GEMM launch carries: rider_out (M2 <= 16, N2) = rider_a (M2, K2) @ rider_b (N2, K2)^T, unit inner
+    strides -> the SkRider the library takes. The dtype rule is the caller's."""
+    M2, K2 = rider_a.shape
+    N2 = rider_b.shape[0]
+    _need(rider_b.shape[1] == K2 and tuple(rider_out.shape) == (M2, N2) and M2 <= 16 and
+          rider_a.stride(1) == rider_b.stride(1) == rider_out.stride(1) == 1, f"{what}: rider shapes")
+    return _lib.SkRider(rider_a.data_ptr(), rider_b.data_ptr(), rider_out.data_ptr(), M2, N2, K2, rider_a.stride(0),
+                        rider_b.stride(0), rider_out.stride(0), 1 if accumulate else 0)
+
+
 # ------------------------------------------------------------------------------------ GEMM
 _GEMM_WS = {}
 
@@ -131,7 +142,6 @@ def gemm4w_choose(M: int, N: int, K: int, *, out_f32: bool = False, epilogue: in
                   n_cu: int = 256) -> int:
     """Tile width (in 16-column blocks) the cost model picks for a bf16 projection on n_cu CUs; 0 = not the whole-tile kernel's
     problem. rider_nk: (N2, K2) of a <= 16-row rider product carried by the launch. Host only (no GPU touched)."""
-    import ctypes as C
     rd = None
     if rider_nk is not None:
         rd = _lib.SkRider(1, 1, 1, 10, int(rider_nk[0]), int(rider_nk[1]), int(rider_nk[1]), int(rider_nk[1]), int(rider_nk[0]), 0)
@@ -196,7 +206,6 @@ def gemm_nt_rider(a, b, out, *, rider_a, rider_b, rider_out, accumulate: bool = 
     """out = a @ b^T (+ residual | SwiGLU' epilogue with swiglu_ab) and, on the CUs that launch leaves idle (or right
     after it), the small product rider_out (<= 16 rows) = rider_a @ rider_b^T (accumulate: fp32 rider_out += product).
     Operands may be column-block views of wider matrices (rows 16-byte aligned)."""
-    import ctypes as C
     for t in (a, b, out, residual, swiglu_ab, rider_a, rider_b, rider_out):
         if t is not None and (not t.is_cuda or t.dim() != 2 or t.stride(1) != 1):
             raise ValueError("gemm_nt_rider: 2-D device tensors with unit inner stride")
@@ -213,17 +222,12 @@ def gemm_nt_rider(a, b, out, *, rider_a, rider_b, rider_out, accumulate: bool = 
         if residual is not None:
             _need(residual.shape == out.shape and residual.stride(0) == ldc, "gemm_nt_rider: residual")
             epi, R = EPI_RESIDUAL, residual
-    M2, K2 = rider_a.shape
-    N2 = rider_b.shape[0]
-    _need(rider_b.shape[1] == K2 and tuple(rider_out.shape) == (M2, N2) and M2 <= 16, "gemm_nt_rider: rider shapes")
-    acc = bool(accumulate)
-    if acc:
-        _need(rider_out.dtype == torch.float32 and rider_out.stride(0) == N2,
+    rd = _rider("gemm_nt_rider", rider_a, rider_b, rider_out, bool(accumulate))
+    if accumulate:
+        _need(rider_out.dtype == torch.float32 and rider_out.stride(0) == rider_out.shape[1],
               "gemm_nt_rider: an accumulated rider_out is contiguous fp32")
     else:
         _need(rider_out.dtype == a.dtype, "gemm_nt_rider: rider_out dtype")
-    rd = _lib.SkRider(rider_a.data_ptr(), rider_b.data_ptr(), rider_out.data_ptr(), M2, N2, K2, rider_a.stride(0),
-                      rider_b.stride(0), rider_out.stride(0), 1 if acc else 0)
     lib = _lib.load(a.dtype)
     ws = gemm_workspace(a.device, int(lib.fvqa_gemm_sk_workspace()))
     rc = lib.fvqa_gemm_nt_rider(_ptr(a), _ptr(b), _ptr(out), _ptr(R), M, N, K, a.stride(0), b.stride(0), ldc,
@@ -245,7 +249,6 @@ def gemm_timing_enable(on, stride: int = 1) -> None:
 
 def gemm_timing_read():
     """-> list of (microseconds, flops, kind) per recorded launch (all loaded libraries, one after the other); clears the record."""
-    import ctypes as C
     out = []
     for lib in list(_lib._LIBS.values()):
         n = int(lib.fvqa_gemm_timing_read(0, None, None, None))
@@ -274,14 +277,8 @@ def gemm_nt_swiglu_fwd(x: torch.Tensor, w13: torch.Tensor, ab: torch.Tensor, z: 
     ws = gemm_workspace(x.device, int(lib.fvqa_gemm_sk_workspace()))
     if rider_a is not None:
         _need(st, "gemm_nt_swiglu_fwd: a rider needs st=True")
-        M2, K2 = rider_a.shape
-        N2 = rider_b.shape[0]
-        _need(rider_b.shape[1] == K2 and tuple(rider_out.shape) == (M2, N2) and M2 <= 16 and
-              rider_a.dtype == rider_b.dtype == rider_out.dtype == x.dtype and
-              rider_a.stride(1) == rider_b.stride(1) == rider_out.stride(1) == 1, "gemm_nt_swiglu_fwd: rider")
-        rd = _lib.SkRider(rider_a.data_ptr(), rider_b.data_ptr(), rider_out.data_ptr(), M2, N2, K2, rider_a.stride(0),
-                          rider_b.stride(0), rider_out.stride(0), 0)
-        import ctypes as C
+        rd = _rider("gemm_nt_swiglu_fwd", rider_a, rider_b, rider_out)
+        _need(rider_a.dtype == rider_b.dtype == rider_out.dtype == x.dtype, "gemm_nt_swiglu_fwd: rider dtype")
         rc = lib.fvqa_gemm_nt_swiglu_fwd_st_rider(_ptr(x), _ptr(w13), _ptr(ab), _ptr(z), M, N // 2, K, K, K, dt_code(x.dtype),
                                                   C.byref(rd), _ptr(ws), ws.numel(), _stream())
         _lib.check(rc, "fvqa_gemm_nt_swiglu_fwd_st_rider")
@@ -411,7 +408,6 @@ def row_segs(maps, offs, stream_rows: int):
 
 def gather_rows(src, dst, segs):
     """dst (M, dim) compact <- rows of src ((n * stream_rows), dim) dense, by segs (row_segs of idx maps)."""
-    import ctypes as C
     _dev(src, dst)
     _need(src.dim() == 2 and dst.dim() == 2 and src.dtype == dst.dtype and src.shape[1] == dst.shape[1], "gather_rows: shape")
     _need(src.shape[0] >= segs.n * segs.stream_rows and dst.shape[0] >= segs.off[segs.n], "gather_rows: rows")
@@ -422,7 +418,6 @@ def gather_rows(src, dst, segs):
 
 def scatter_rows(src, dst, segs):
     """dst ((n * stream_rows), dim) dense <- rows of src (M, dim) compact by segs (row_segs of inv maps), zeros where the map is < 0."""
-    import ctypes as C
     _dev(src, dst)
     _need(src.dim() == 2 and dst.dim() == 2 and src.dtype == dst.dtype and src.shape[1] == dst.shape[1], "scatter_rows: shape")
     _need(dst.shape[0] >= segs.n * segs.stream_rows and src.shape[0] >= segs.off[segs.n], "scatter_rows: rows")
@@ -483,16 +478,11 @@ def gemm_nt_rope(a, b, out, rope, seq_len, head_dim, n_heads, *, rider_a=None, r
     rp = _lib.SkRope(cos_t.data_ptr(), sin_t.data_ptr(), seq_len, head_dim, 2 * D)
     rd = None
     if rider_a is not None:
-        M2, K2 = rider_a.shape
-        N2 = rider_b.shape[0]
-        _need(rider_b.shape[1] == K2 and tuple(rider_out.shape) == (M2, N2) and M2 <= 16 and rider_out.dtype == a.dtype and
-              rider_a.stride(1) == rider_b.stride(1) == rider_out.stride(1) == 1, "gemm_nt_rope: rider")
-        rd = _lib.SkRider(rider_a.data_ptr(), rider_b.data_ptr(), rider_out.data_ptr(), M2, N2, K2, rider_a.stride(0),
-                          rider_b.stride(0), rider_out.stride(0), 0)
+        rd = _rider("gemm_nt_rope", rider_a, rider_b, rider_out)
+        _need(rider_out.dtype == a.dtype, "gemm_nt_rope: rider dtype")
     ws = gemm_workspace(a.device)
-    import ctypes
     rc = _lib.load(a.dtype).fvqa_gemm_nt_rope(_ptr(a), _ptr(b), _ptr(out), M, N, K, a.stride(0), b.stride(0), out.stride(0),
-                                       ctypes.byref(rp), ctypes.byref(rd) if rd is not None else None, _ptr(ws), ws.numel(),
+                                       C.byref(rp), C.byref(rd) if rd is not None else None, _ptr(ws), ws.numel(),
                                        _stream())
     _lib.check(rc, "fvqa_gemm_nt_rope")
     return out
@@ -552,10 +542,31 @@ def attn_decode(qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_se
     return o_row
 
 
-DECODE_PTRS = 9
-
-
 SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)
+
+
+def _attn_suffix(what, qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
+                 cache_rotated):
+    """attn_suffix (n_options >= 1 continuations per sequence, the cache only read) and attn_suffix_append (n_options None: one,
+    whose rows join the cache): the same operands but for the options."""
+    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, what)
+    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
+    R = n_seq * (n_options or 1) * T
+    _need(cos_t is not None, f"{what}: rope tables")
+    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, f"{what}: dtype")
+    _need(1 <= T <= SUFFIX_MAX and (n_options is None or n_options >= 1), f"{what}: 1 <= {'rows per sequence' if n_options is None else 'suffix rows'} <= {SUFFIX_MAX}")
+    _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), f"{what}: row shapes")
+    for t in (vstart, start, length):
+        _need(t.dtype == torch.int32 and t.numel() == n_seq, f"{what}: vstart / start / len are int32 (n_seq)")
+    for t in (gate1, gate2):
+        _need(t.dtype == torch.float32 and t.numel() == H, f"{what}: gate shape")
+    rc = getattr(_lib.load(qkv_cache.dtype), "fvqa_" + what)(
+        _ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1), _ptr(gate2), _ptr(vstart), _ptr(start), _ptr(length),
+        _ptr(cos_t), _ptr(sin_t), n_seq, *(() if n_options is None else (n_options,)), T, S, H, Dh, A, F,
+        1 if cache_rotated else 0, dt_code(qkv_suf.dtype), _stream())
+    _lib.check(rc, "fvqa_" + what)
+    return o_suf
 
 
 def attn_suffix(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
@@ -563,24 +574,8 @@ def attn_suffix(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, 
     """The option-scoring path's attention at the suffix rows (include/fvqa.h fvqa_attn_suffix): qkv_suf (n_seq*n_options*T,
     3*D) RAW projections of suffix row j of option c of sample n at position start[n] + j; qkv_cache the layer's prefill buffer
     (read only). Writes o_suf (n_seq*n_options*T, D); rows j >= length[n] are padding (zeros)."""
-    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
-    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_suffix")
-    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
-    R = n_seq * n_options * T
-    _need(cos_t is not None, "attn_suffix: rope tables")
-    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, "attn_suffix: dtype")
-    _need(1 <= T <= SUFFIX_MAX and n_options >= 1, f"attn_suffix: 1 <= suffix rows <= {SUFFIX_MAX}")
-    _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), "attn_suffix: row shapes")
-    for t in (vstart, start, length):
-        _need(t.dtype == torch.int32 and t.numel() == n_seq, "attn_suffix: vstart / start / len are int32 (n_seq)")
-    for t in (gate1, gate2):
-        _need(t.dtype == torch.float32 and t.numel() == H, "attn_suffix: gate shape")
-    rc = _lib.load(qkv_cache.dtype).fvqa_attn_suffix(_ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1), _ptr(gate2),
-                                                     _ptr(vstart), _ptr(start), _ptr(length), _ptr(cos_t), _ptr(sin_t), n_seq,
-                                                     n_options, T, S, H, Dh, A, F, 1 if cache_rotated else 0,
-                                                     dt_code(qkv_suf.dtype), _stream())
-    _lib.check(rc, "fvqa_attn_suffix")
-    return o_suf
+    return _attn_suffix("attn_suffix", qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq,
+                        int(n_options), T, S, H, Dh, A, F, cache_rotated)
 
 
 def attn_suffix_append(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, T, S, H, Dh, A, F,
@@ -589,24 +584,8 @@ def attn_suffix_append(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, l
     draft-and-verify pass of generate(lookahead=T)): qkv_suf (n_seq*T, 3*D) RAW projections of row j of sequence n at position
     start[n] + j. Writes o_suf (n_seq*T, D) as attn_suffix does, and the k (in the cache's convention) and v of the rows
     j < length[n] into cache row n*S + start[n] + j — the bits attn_decode stores for the same raw row and position."""
-    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
-    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_suffix_append")
-    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
-    R = n_seq * T
-    _need(cos_t is not None, "attn_suffix_append: rope tables")
-    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, "attn_suffix_append: dtype")
-    _need(1 <= T <= SUFFIX_MAX, f"attn_suffix_append: 1 <= rows per sequence <= {SUFFIX_MAX}")
-    _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), "attn_suffix_append: row shapes")
-    for t in (vstart, start, length):
-        _need(t.dtype == torch.int32 and t.numel() == n_seq, "attn_suffix_append: vstart / start / len are int32 (n_seq)")
-    for t in (gate1, gate2):
-        _need(t.dtype == torch.float32 and t.numel() == H, "attn_suffix_append: gate shape")
-    rc = _lib.load(qkv_cache.dtype).fvqa_attn_suffix_append(_ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1),
-                                                            _ptr(gate2), _ptr(vstart), _ptr(start), _ptr(length), _ptr(cos_t),
-                                                            _ptr(sin_t), n_seq, T, S, H, Dh, A, F, 1 if cache_rotated else 0,
-                                                            dt_code(qkv_suf.dtype), _stream())
-    _lib.check(rc, "fvqa_attn_suffix_append")
-    return o_suf
+    return _attn_suffix("attn_suffix_append", qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, None,
+                        T, S, H, Dh, A, F, cache_rotated)
 
 
 def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: int):
@@ -629,6 +608,59 @@ def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: in
     return il, s, cnt, mean, pred
 
 
+_I32, _I64, _F32 = torch.int32, torch.int64, torch.float32
+_DTYPE_NAME = {_I32: "int32", _I64: "int64", _F32: "fp32"}
+
+
+def _lead(t) -> int:
+    """Rows of a 2-D operand; -1, which no check accepts, of anything else."""
+    return t.shape[0] if t.dim() == 2 else -1
+
+
+def _of(dtype, numel, **tensors):
+    """Rows of _token_step's table: the named operands are `dtype` tensors of `numel` elements."""
+    return [(name, t, dtype, numel) for name, t in tensors.items()]
+
+
+def _token_step(what, logits, n_logits, emb, x_next, ids, n_ids, table, *, pos64=None, n_pos64=0, ids_name="ids",
+                temperature=0.0, u=None, u_shape=(), u_longer=False, top_k=0, repetition_penalty=1.0):
+    """The operand checks of the token-step family (decode_next*, spec_step, trie_jump_step, beam_step*), under the entry's name
+    `what`: logits (n_logits, V) fp32, emb of V rows and x_next's dtype, x_next (n_logits, D), ids of n_ids rows, int64; `table` rows
+    (name, tensor, dtype, numel) for the entry's other operands; pos64 None or (n_pos64,) int64; the sampling keywords: under
+    temperature > 0, u fp32 of u_shape (one dimension: that many elements, more with u_longer), top_k >= 0 and
+    repetition_penalty >= 1. -> (V, D, S). Nothing is launched here."""
+    _need(logits.dim() == 2 and logits.dtype == _F32 and logits.shape[0] == n_logits, f"{what}: logits ({n_logits}, V) fp32")
+    V = logits.shape[1]
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, f"{what}: emb (V, D) and x_next of one dtype")
+    D = emb.shape[1]
+    _need(tuple(x_next.shape) == (n_logits, D), f"{what}: x_next ({n_logits}, D), a row per row of logits")
+    _need(ids.dim() == 2 and ids.shape[0] == n_ids and ids.dtype == _I64, f"{what}: {ids_name} (B, S) int64, B = {n_ids} rows")
+    for name, t, dtype, numel in table:
+        _need(t.dtype == dtype and t.numel() == numel, f"{what}: {name} is {_DTYPE_NAME[dtype]}, {numel} elements")
+    _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == n_pos64), f"{what}: pos64 ({n_pos64},) int64")
+    if temperature != 0:
+        _need(u is not None and u.dtype == _F32 and
+              (tuple(u.shape) == u_shape if len(u_shape) > 1 else u.numel() == u_shape[0] or (u_longer and u.numel() > u_shape[0])),
+              f"{what}: sampling needs u {u_shape} fp32")
+    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, f"{what}: top_k >= 0, repetition_penalty >= 1")
+    return V, D, ids.shape[1]
+
+
+def _trie_args(what: str, node, trie):
+    """(node, trie) -> the five trie arguments of an entry (node_first, edge_token, edge_child, n_nodes, n_edges); without a trie
+    (and without node: the two come together) three None and two 0. `trie`: a compiled constraint (fvqa.constrain.TokenTrie
+    .to(device), or any object with node_first, edge_token, edge_child int32 tensors)."""
+    _need((trie is None) == (node is None), f"{what}: node and trie come together")
+    if trie is None:
+        return None, None, None, 0, 0
+    nf, et, ec = trie.node_first, trie.edge_token, trie.edge_child
+    for t in (nf, et, ec):
+        _need(torch.is_tensor(t) and t.dtype == _I32 and t.dim() == 1 and t.is_contiguous(),
+              f"{what}: node_first, edge_token, edge_child are contiguous int32 vectors")
+    _need(nf.numel() >= 2 and et.numel() == ec.numel(), f"{what}: node_first (n_nodes + 1,), edge_token / edge_child (n_edges,)")
+    return nf, et, ec, nf.numel() - 1, et.numel()
+
+
 def decode_next(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, *, u=None, pos64=None, temperature: float = 0.0,
                 top_p: float = 1.0, eos_id: int = 2, stop_at_eos: bool = True):
     """The token step of the generation API (include/fvqa.h fvqa_decode_next): logits (B, V) fp32 -> the picked token written
@@ -636,23 +668,22 @@ def decode_next(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, *,
     x_next (B, D) = emb[token], token / n_kept (B,) int32, n_active (1,) int32 = rows still running, pos64 (B,) int64 = pos
     after the step (what attn_decode reads). u (B,) fp32 in [0, 1) is needed when temperature > 0."""
     _dev(logits, emb, ids, pos, done, x_next, token, n_kept, n_active, u, pos64)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next: logits (B, V) fp32")
-    B, V = logits.shape
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B, D), "decode_next: x_next (B, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next: ids (B, S) int64")
-    for t, n in ((pos, B), (done, B), (token, B), (n_kept, B), (n_active, 1)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next: pos / done / token / n_kept (B,), n_active (1,) int32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next: pos64 (B,) int64")
-    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
-          "decode_next: sampling needs u (B,) fp32")
+    B = _lead(logits)
+    V, D, S = _token_step("decode_next", logits, B, emb, x_next, ids, B,
+                          _of(_I32, B, pos=pos, done=done, token=token, n_kept=n_kept) + _of(_I32, 1, n_active=n_active),
+                          pos64=pos64, n_pos64=B, temperature=temperature, u=u, u_shape=(B,))
     rc = _lib.load(emb.dtype).fvqa_decode_next(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(eos_id),
                                                1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(x_next),
-                                               _ptr(token), _ptr(n_kept), _ptr(n_active), _ptr(pos64), B, V, D, ids.shape[1],
+                                               _ptr(token), _ptr(n_kept), _ptr(n_active), _ptr(pos64), B, V, D, S,
                                                dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next")
     return token
+
+
+def _ex_table(B, pos, done, gen_start, token, n_kept, logprob, n_active, counter):
+    """The operands decode_next_ex, _trie and _stream share, one per row or one per launch."""
+    return (_of(_I32, B, pos=pos, done=done, gen_start=gen_start, token=token, n_kept=n_kept) + _of(_F32, B, logprob=logprob) +
+            _of(_I32, 1, n_active=n_active, counter=counter))
 
 
 def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, *, u=None,
@@ -663,30 +694,28 @@ def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept
     tokens the penalty applies to —, logprob (B,) fp32 out (log_softmax of the RAW logits at the token; 0 where none was
     picked), counter: one int32 word the caller zeroed once (the library keeps no ticket for this entry)."""
     _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, u, pos64)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_ex: logits (B, V) fp32")
-    B, V = logits.shape
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_ex: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B, D), "decode_next_ex: x_next (B, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_ex: ids (B, S) int64")
-    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (n_active, 1), (counter, 1)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_ex: pos / done / gen_start / token / n_kept (B,), "
-                                                         "n_active / counter (1,) int32")
-    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_ex: logprob (B,) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_ex: pos64 (B,) int64")
-    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
-          "decode_next_ex: sampling needs u (B,) fp32")
-    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_ex: top_k >= 0, repetition_penalty >= 1")
+    B = _lead(logits)
+    V, D, S = _token_step("decode_next_ex", logits, B, emb, x_next, ids, B,
+                          _ex_table(B, pos, done, gen_start, token, n_kept, logprob, n_active, counter), pos64=pos64, n_pos64=B,
+                          temperature=temperature, u=u, u_shape=(B,), top_k=top_k, repetition_penalty=repetition_penalty)
     rc = _lib.load(emb.dtype).fvqa_decode_next_ex(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(top_k),
                                                   float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0, _ptr(ids),
                                                   _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token),
                                                   _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), B, V,
-                                                  D, ids.shape[1], dt_code(emb.dtype), _stream())
+                                                  D, S, dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next_ex")
     return token
 
 
 LOOKUP_NGRAM_MAX = 4     # the longest n-gram fvqa_spec_step's prompt lookup matches (csrc/spec.hip GMAX)
+
+
+def _pass_rows(what: str, w):
+    """w (B, T) int32, the tokens a pass of up to T rows per sequence was fed -> (B, T)."""
+    _need(w.dim() == 2 and w.dtype == _I32, f"{what}: w (B, T) int32")
+    B, T = w.shape
+    _need(1 <= T <= SUFFIX_MAX and 1 <= B <= 65535 and B * T <= 65535, f"{what}: 1 <= T <= {SUFFIX_MAX}, B * T <= 65535")
+    return B, T
 
 
 def spec_step(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted,
@@ -700,46 +729,25 @@ def spec_step(logits, emb, ids, pos, done, n_generated, w, length, start, x_next
     are read from it at each row's n_generated; None: prompt lookup with n-grams of up to lookup_ngram tokens."""
     _dev(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted, n_active,
          counter, draft_tokens, pos64)
-    _need(w.dim() == 2 and w.dtype == torch.int32, "spec_step: w (B, T) int32")
-    B, T = w.shape
-    _need(1 <= T <= SUFFIX_MAX and 1 <= B <= 65535 and B * T <= 65535, f"spec_step: 1 <= T <= {SUFFIX_MAX}, B * T <= 65535")
-    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] == B * T, "spec_step: logits (B*T, V) fp32")
-    V = logits.shape[1]
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "spec_step: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B * T, D), "spec_step: x_next (B*T, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "spec_step: ids (B, S) int64")
-    for t, n in ((pos, B), (done, B), (n_generated, B), (length, B), (start, B), (n_committed, B), (n_drafted, B), (n_active, 1),
-                 (counter, 1), (token, B * T)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "spec_step: pos / done / n_generated / len / start / n_committed / "
-                                                         "n_drafted (B,), token (B, T), n_active / counter (1,) int32")
-    _need(logprob.dtype == torch.float32 and logprob.numel() == B * T, "spec_step: logprob (B, T) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "spec_step: pos64 (B,) int64")
+    B, T = _pass_rows("spec_step", w)
+    V, D, S = _token_step("spec_step", logits, B * T, emb, x_next, ids, B,
+                          _of(_I32, B, pos=pos, done=done, n_generated=n_generated, len=length, start=start,
+                              n_committed=n_committed, n_drafted=n_drafted) + _of(_I32, 1, n_active=n_active, counter=counter) +
+                          _of(_I32, B * T, token=token) + _of(_F32, B * T, logprob=logprob), pos64=pos64, n_pos64=B)
     _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, "spec_step: max_new_tokens >= 1")
     if draft_tokens is None:
         _need(int(lookup_ngram) == lookup_ngram and 1 <= lookup_ngram <= LOOKUP_NGRAM_MAX,
               f"spec_step: 1 <= lookup_ngram <= {LOOKUP_NGRAM_MAX}")
     else:
-        _need(draft_tokens.dtype == torch.int32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
+        _need(draft_tokens.dtype == _I32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
               "spec_step: draft_tokens (B, max_new_tokens) int32")
     rc = _lib.load(emb.dtype).fvqa_spec_step(_ptr(logits), _ptr(emb), _ptr(draft_tokens), int(lookup_ngram), int(eos_id),
                                              1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done),
                                              _ptr(n_generated), _ptr(w), _ptr(length), _ptr(start), _ptr(x_next), _ptr(token),
                                              _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(counter),
-                                             _ptr(pos64), B, T, V, D, ids.shape[1], dt_code(emb.dtype), _stream())
+                                             _ptr(pos64), B, T, V, D, S, dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_spec_step")
     return token
-
-
-def _trie_arrays(trie, what: str):
-    """The device arrays of a compiled constraint (fvqa.constrain.TokenTrie.to(device), or any object with node_first,
-    edge_token, edge_child int32 tensors) -> (node_first, edge_token, edge_child, n_nodes, n_edges)."""
-    nf, et, ec = trie.node_first, trie.edge_token, trie.edge_child
-    for t in (nf, et, ec):
-        _need(torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(),
-              f"{what}: node_first, edge_token, edge_child are contiguous int32 vectors")
-    _need(nf.numel() >= 2 and et.numel() == ec.numel(), f"{what}: node_first (n_nodes + 1,), edge_token / edge_child (n_edges,)")
-    return nf, et, ec, nf.numel() - 1, et.numel()
 
 
 def trie_jump_step(logits, emb, ids, pos, done, n_generated, node, w, length, start, x_next, token, logprob_pick, logprob_fed,
@@ -751,39 +759,23 @@ def trie_jump_step(logits, emb, ids, pos, done, n_generated, node, w, length, st
     (-1 padded), logprob_pick (B,) and logprob_fed (B, T) fp32, n_committed (B,) int32, n_active (1,) int32, pos64 (B,) int64 or
     None. counter: one int32 word the caller zeroed once. `trie`: a fvqa.constrain.TokenTrie on the device; None (with node None):
     every row is unconstrained."""
-    _need((trie is None) == (node is None), "trie_jump_step: node and trie come together")
-    nf = et = ec = None
-    n_nodes = n_edges = 0
-    if trie is not None:
-        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "trie_jump_step")
+    nf, et, ec, n_nodes, n_edges = _trie_args("trie_jump_step", node, trie)
     _dev(logits, emb, ids, pos, done, n_generated, node, w, length, start, x_next, token, logprob_pick, logprob_fed, n_committed,
          n_active, counter, pos64, nf, et, ec)
-    _need(w.dim() == 2 and w.dtype == torch.int32, "trie_jump_step: w (B, T) int32")
-    B, T = w.shape
-    _need(1 <= T <= SUFFIX_MAX and 1 <= B <= 65535 and B * T <= 65535, f"trie_jump_step: 1 <= T <= {SUFFIX_MAX}, B * T <= 65535")
-    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] == B * T,
-          "trie_jump_step: logits (B*T, V) fp32")
-    V = logits.shape[1]
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype,
-          "trie_jump_step: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B * T, D), "trie_jump_step: x_next (B*T, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "trie_jump_step: ids (B, S) int64")
-    for t, n in ((pos, B), (done, B), (n_generated, B), (length, B), (start, B), (n_committed, B), (n_active, 1), (counter, 1),
-                 (token, B * T)) + (() if node is None else ((node, B),)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "trie_jump_step: pos / done / n_generated / node / len / start / "
-                                                         "n_committed (B,), token (B, T), n_active / counter (1,) int32")
-    _need(logprob_pick.dtype == torch.float32 and logprob_pick.numel() == B, "trie_jump_step: logprob_pick (B,) fp32")
-    _need(logprob_fed.dtype == torch.float32 and logprob_fed.numel() == B * T, "trie_jump_step: logprob_fed (B, T) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "trie_jump_step: pos64 (B,) int64")
+    B, T = _pass_rows("trie_jump_step", w)
+    V, D, S = _token_step("trie_jump_step", logits, B * T, emb, x_next, ids, B,
+                          _of(_I32, B, pos=pos, done=done, n_generated=n_generated, len=length, start=start,
+                              n_committed=n_committed, **({} if node is None else {"node": node})) +
+                          _of(_I32, 1, n_active=n_active, counter=counter) + _of(_I32, B * T, token=token) +
+                          _of(_F32, B, logprob_pick=logprob_pick) + _of(_F32, B * T, logprob_fed=logprob_fed),
+                          pos64=pos64, n_pos64=B)
     _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, "trie_jump_step: max_new_tokens >= 1")
     rc = _lib.load(emb.dtype).fvqa_trie_jump_step(_ptr(logits), _ptr(emb), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges,
                                                   int(eos_id), int(max_new_tokens), 1 if chain_eos else 0,
                                                   1 if want_logprobs else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated),
                                                   _ptr(node), _ptr(w), _ptr(length), _ptr(start), _ptr(pos64), _ptr(x_next),
                                                   _ptr(token), _ptr(logprob_pick), _ptr(logprob_fed), _ptr(n_committed),
-                                                  _ptr(n_active), _ptr(counter), B, T, V, D, ids.shape[1], dt_code(emb.dtype),
-                                                  _stream())
+                                                  _ptr(n_active), _ptr(counter), B, T, V, D, S, dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_trie_jump_step")
     return token
 
@@ -794,28 +786,19 @@ def decode_next_trie(logits, emb, ids, pos, done, gen_start, x_next, token, n_ke
     """decode_next_ex under a trie of allowed answers (include/fvqa.h fvqa_decode_next_trie states the rule). On top of
     decode_next_ex's operands: node (B,) int32, in and out — the trie node of each row, -1: unconstrained —, and `trie`, a
     fvqa.constrain.TokenTrie on the device (node_first / edge_token / edge_child int32)."""
-    nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_trie")
+    nf, et, ec, n_nodes, n_edges = _trie_args("decode_next_trie", node, trie)
     _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, u, pos64, node, nf, et, ec)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_trie: logits (B, V) fp32")
-    B, V = logits.shape
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_trie: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B, D), "decode_next_trie: x_next (B, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_trie: ids (B, S) int64")
-    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (node, B), (n_active, 1), (counter, 1)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_trie: pos / done / gen_start / token / n_kept / node (B,), "
-                                                         "n_active / counter (1,) int32")
-    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_trie: logprob (B,) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_trie: pos64 (B,) int64")
-    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() == B),
-          "decode_next_trie: sampling needs u (B,) fp32")
-    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_trie: top_k >= 0, repetition_penalty >= 1")
+    B = _lead(logits)
+    V, D, S = _token_step("decode_next_trie", logits, B, emb, x_next, ids, B,
+                          _ex_table(B, pos, done, gen_start, token, n_kept, logprob, n_active, counter) + _of(_I32, B, node=node),
+                          pos64=pos64, n_pos64=B, temperature=temperature, u=u, u_shape=(B,), top_k=top_k,
+                          repetition_penalty=repetition_penalty)
     rc = _lib.load(emb.dtype).fvqa_decode_next_trie(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p),
                                                     int(top_k), float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0,
                                                     _ptr(ids), _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token),
                                                     _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64),
-                                                    _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D,
-                                                    ids.shape[1], dt_code(emb.dtype), _stream())
+                                                    _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D, S,
+                                                    dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next_trie")
     return token
 
@@ -828,39 +811,26 @@ def decode_next_pair(logits, emb, ids, pos, done, gen_start, x_next, token, n_ke
     `node` and `trie`, decode_next_trie — on B PAIRS of rows. logits (2B, V), ids (2B, S), pos / done / pos64 (2B,) and x_next
     (2B, D) hold the B positive rows followed by their B twins; gen_start, token, n_kept, n_plausible, node (B,) int32, logprob
     and u (B,) fp32 are per pair (gen_start and u may be longer: their first B entries are read). n_active counts pairs."""
-    have_trie = trie is not None
-    _need(have_trie == (node is not None), "decode_next_pair: node and trie come together")
-    nf = et = ec = None
-    n_nodes = n_edges = 0
-    if have_trie:
-        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_pair")
+    nf, et, ec, n_nodes, n_edges = _trie_args("decode_next_pair", node, trie)
     _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, n_plausible, logprob, n_active, counter, u, pos64, node,
          nf, et, ec)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32 and logits.shape[0] % 2 == 0 and logits.shape[0] > 0,
-          "decode_next_pair: logits (2B, V) fp32")
-    B2, V = logits.shape
+    B2 = _lead(logits)
+    _need(B2 > 0 and B2 % 2 == 0, "decode_next_pair: logits (2B, V) fp32")
     B = B2 // 2
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "decode_next_pair: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B2, D), "decode_next_pair: x_next (2B, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B2 and ids.dtype == torch.int64, "decode_next_pair: ids (2B, S) int64")
-    for t, n in ((pos, B2), (done, B2), (token, B), (n_kept, B), (n_plausible, B), (n_active, 1), (counter, 1)) + \
-            (((node, B),) if have_trie else ()):
-        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_pair: pos / done (2B,), token / n_kept / n_plausible / "
-                                                         "node (B,), n_active / counter (1,) int32")
-    _need(gen_start.dtype == torch.int32 and gen_start.numel() >= B, "decode_next_pair: gen_start (B,) int32")
-    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_pair: logprob (B,) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B2), "decode_next_pair: pos64 (2B,) int64")
-    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and u.numel() >= B),
-          "decode_next_pair: sampling needs u (B,) fp32")
-    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1, "decode_next_pair: top_k >= 0, repetition_penalty >= 1")
+    V, D, S = _token_step("decode_next_pair", logits, B2, emb, x_next, ids, B2,
+                          _of(_I32, B2, pos=pos, done=done) + _of(_F32, B, logprob=logprob) +
+                          _of(_I32, B, token=token, n_kept=n_kept, n_plausible=n_plausible, **({} if node is None else {"node": node})) +
+                          _of(_I32, 1, n_active=n_active, counter=counter), pos64=pos64, n_pos64=B2,
+                          temperature=temperature, u=u, u_shape=(B,), u_longer=True, top_k=top_k,
+                          repetition_penalty=repetition_penalty)
+    _need(gen_start.dtype == _I32 and gen_start.numel() >= B, "decode_next_pair: gen_start (B,) int32")
     _need(alpha >= 0 and 0 <= beta <= 1, "decode_next_pair: alpha >= 0, 0 <= beta <= 1")
     rc = _lib.load(emb.dtype).fvqa_decode_next_pair(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p),
                                                     int(top_k), float(repetition_penalty), float(alpha), float(beta),
                                                     int(eos_id), 1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done),
                                                     _ptr(gen_start), _ptr(x_next), _ptr(token), _ptr(n_kept), _ptr(n_plausible),
                                                     _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), _ptr(node),
-                                                    _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D, ids.shape[1],
+                                                    _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, B, V, D, S,
                                                     dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next_pair")
     return token
@@ -874,41 +844,25 @@ def decode_next_stream(logits, emb, ids, pos, done, gen_start, x_next, token, n_
     and `trie`, decode_next_trie — on B slots that hold requests. On top of their operands: req (B,) int32 — the request in each
     slot, -1: none —, budget (N,) int32, out_tokens (N, W) int32, out_n_generated (N,) int32, out_logprob (N, W) fp32 or None;
     u is (W, N) fp32: a slot at token index i of request r reads u[i, r]."""
-    have_trie = trie is not None
-    _need(have_trie == (node is not None), "decode_next_stream: node and trie come together")
-    nf = et = ec = None
-    n_nodes = n_edges = 0
-    if have_trie:
-        nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "decode_next_stream")
+    nf, et, ec, n_nodes, n_edges = _trie_args("decode_next_stream", node, trie)
     _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, req, budget, out_tokens,
          out_n_generated, out_logprob, u, pos64, node, nf, et, ec)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "decode_next_stream: logits (B, V) fp32")
-    B, V = logits.shape
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype,
-          "decode_next_stream: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (B, D), "decode_next_stream: x_next (B, D)")
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == torch.int64, "decode_next_stream: ids (B, S) int64")
-    _need(out_tokens.dim() == 2 and out_tokens.dtype == torch.int32 and out_tokens.shape[0] >= 1 and out_tokens.shape[1] >= 1,
+    _need(out_tokens.dim() == 2 and out_tokens.dtype == _I32 and out_tokens.shape[0] >= 1 and out_tokens.shape[1] >= 1,
           "decode_next_stream: out_tokens (N, W) int32")
     N, W = out_tokens.shape
-    for t, n in ((pos, B), (done, B), (gen_start, B), (token, B), (n_kept, B), (req, B), (n_active, 1), (counter, 1), (budget, N),
-                 (out_n_generated, N)) + (((node, B),) if have_trie else ()):
-        _need(t.dtype == torch.int32 and t.numel() == n, "decode_next_stream: pos / done / gen_start / token / n_kept / req / node "
-                                                         "(B,), budget / out_n_generated (N,), n_active / counter (1,) int32")
-    _need(logprob.dtype == torch.float32 and logprob.numel() == B, "decode_next_stream: logprob (B,) fp32")
-    _need(out_logprob is None or (out_logprob.dtype == torch.float32 and tuple(out_logprob.shape) == (N, W)),
+    B = _lead(logits)
+    V, D, S = _token_step("decode_next_stream", logits, B, emb, x_next, ids, B,
+                          _ex_table(B, pos, done, gen_start, token, n_kept, logprob, n_active, counter) +
+                          _of(_I32, B, req=req, **({} if node is None else {"node": node})) +
+                          _of(_I32, N, budget=budget, out_n_generated=out_n_generated), pos64=pos64, n_pos64=B,
+                          temperature=temperature, u=u, u_shape=(W, N), top_k=top_k, repetition_penalty=repetition_penalty)
+    _need(out_logprob is None or (out_logprob.dtype == _F32 and tuple(out_logprob.shape) == (N, W)),
           "decode_next_stream: out_logprob (N, W) fp32")
-    _need(pos64 is None or (pos64.dtype == torch.int64 and pos64.numel() == B), "decode_next_stream: pos64 (B,) int64")
-    _need(temperature == 0 or (u is not None and u.dtype == torch.float32 and tuple(u.shape) == (W, N)),
-          "decode_next_stream: sampling needs u (W, N) fp32")
-    _need(int(top_k) == top_k and top_k >= 0 and repetition_penalty >= 1,
-          "decode_next_stream: top_k >= 0, repetition_penalty >= 1")
     rc = _lib.load(emb.dtype).fvqa_decode_next_stream(
         _ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p), int(top_k), float(repetition_penalty), int(eos_id),
         1 if stop_at_eos else 0, _ptr(ids), _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token), _ptr(n_kept),
         _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges,
-        _ptr(req), _ptr(budget), N, W, _ptr(out_tokens), _ptr(out_logprob), _ptr(out_n_generated), B, V, D, ids.shape[1],
+        _ptr(req), _ptr(budget), N, W, _ptr(out_tokens), _ptr(out_logprob), _ptr(out_n_generated), B, V, D, S,
         dt_code(emb.dtype), _stream())
     _lib.check(rc, "fvqa_decode_next_stream")
     return token
@@ -955,6 +909,32 @@ def slot_seat(slot, src, request, prompt_ids, prefix, vstart_src, logits_src, id
 BEAMS_MAX = 8            # slots per sample fvqa_beam_step takes (csrc/beam.hip KMAX)
 
 
+def _beam_step(what, trie_args, logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active,
+               counter, node, num_beams, eos_id, stop_at_eos, count_any_live):
+    """beam_step (trie_args None) and beam_step_trie: the same operands but for node and the trie."""
+    N, K = _lead(logits), int(num_beams)
+    _need(N >= 0, f"{what}: logits (B*K, V) fp32")
+    _need(1 <= K <= BEAMS_MAX and K <= logits.shape[1] and N % K == 0,
+          f"{what}: 1 <= num_beams <= {BEAMS_MAX}, <= V, rows a multiple of it")
+    V, D, S = _token_step(what, logits, N, emb, x_next, ids_in, N,
+                          _of(_I32, N, pos=pos, done=done, n_generated=n_generated, parent=parent, token=token,
+                              **({} if trie_args is None else {"node": node})) + _of(_I32, 1, n_active=n_active, counter=counter) +
+                          _of(_F32, N, score=score) + _of(_I64, N, pos64=pos64), ids_name="ids_in")
+    _need(ids_out.dtype == _I64 and ids_out.shape == ids_in.shape and ids_in.data_ptr() != ids_out.data_ptr(),
+          f"{what}: ids_in, ids_out (B*K, S) int64, two buffers")
+    head = (_ptr(logits), _ptr(emb), int(eos_id), 1 if stop_at_eos else 0, 1 if count_any_live else 0, _ptr(ids_in), _ptr(ids_out),
+            _ptr(pos), _ptr(score), _ptr(done), _ptr(n_generated), _ptr(pos64), _ptr(parent), _ptr(token), _ptr(x_next),
+            _ptr(n_active), _ptr(counter))
+    tail = (N // K, K, V, D, S, dt_code(emb.dtype), _stream())
+    if trie_args is None:
+        rc = _lib.load(emb.dtype).fvqa_beam_step(*head, *tail)
+    else:
+        nf, et, ec, n_nodes, n_edges = trie_args
+        rc = _lib.load(emb.dtype).fvqa_beam_step_trie(*head, _ptr(node), _ptr(nf), _ptr(et), _ptr(ec), n_nodes, n_edges, *tail)
+    _lib.check(rc, "fvqa_" + what)
+    return parent, token
+
+
 def beam_step(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter, *,
               num_beams: int, eos_id: int = 2, stop_at_eos: bool = True, count_any_live: bool = False):
     """One step of beam search (include/fvqa.h fvqa_beam_step): logits (B*K, V) fp32 -> the K best continuations of each sample
@@ -962,61 +942,19 @@ def beam_step(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64
     (B*K,) fp32 in place, pos64 (B*K,) int64, parent / token (B*K,) int32, x_next (B*K, D), n_active (1,) int32. counter: one
     int32 word the caller zeroed once."""
     _dev(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "beam_step: logits (B*K, V) fp32")
-    N, V = logits.shape
-    K = int(num_beams)
-    _need(1 <= K <= BEAMS_MAX and K <= V and N % K == 0, f"beam_step: 1 <= num_beams <= {BEAMS_MAX}, <= V, rows a multiple of it")
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "beam_step: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (N, D), "beam_step: x_next (B*K, D)")
-    _need(ids_in.dim() == 2 and ids_in.shape[0] == N and ids_in.dtype == torch.int64 and ids_out.dtype == torch.int64
-          and ids_out.shape == ids_in.shape and ids_in.data_ptr() != ids_out.data_ptr(),
-          "beam_step: ids_in, ids_out (B*K, S) int64, two buffers")
-    for t, n in ((pos, N), (done, N), (n_generated, N), (parent, N), (token, N), (n_active, 1), (counter, 1)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "beam_step: pos / done / n_generated / parent / token (B*K,), "
-                                                         "n_active / counter (1,) int32")
-    _need(score.dtype == torch.float32 and score.numel() == N, "beam_step: score (B*K,) fp32")
-    _need(pos64.dtype == torch.int64 and pos64.numel() == N, "beam_step: pos64 (B*K,) int64")
-    rc = _lib.load(emb.dtype).fvqa_beam_step(_ptr(logits), _ptr(emb), int(eos_id), 1 if stop_at_eos else 0,
-                                             1 if count_any_live else 0, _ptr(ids_in), _ptr(ids_out), _ptr(pos), _ptr(score),
-                                             _ptr(done), _ptr(n_generated), _ptr(pos64), _ptr(parent), _ptr(token), _ptr(x_next),
-                                             _ptr(n_active), _ptr(counter), N // K, K, V, D, ids_in.shape[1], dt_code(emb.dtype),
-                                             _stream())
-    _lib.check(rc, "fvqa_beam_step")
-    return parent, token
+    return _beam_step("beam_step", None, logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next,
+                      n_active, counter, None, num_beams, eos_id, stop_at_eos, count_any_live)
 
 
 def beam_step_trie(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter,
                    node, trie, *, num_beams: int, eos_id: int = 2, stop_at_eos: bool = True, count_any_live: bool = False):
     """beam_step under a trie of allowed answers (include/fvqa.h fvqa_beam_step_trie): on top of beam_step's operands node
     (B*K,) int32, in and out — each slot's trie node, -1: unconstrained —, and `trie` as decode_next_trie takes it."""
-    nf, et, ec, n_nodes, n_edges = _trie_arrays(trie, "beam_step_trie")
-    _dev(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter, node, nf, et,
-         ec)
-    _need(logits.dim() == 2 and logits.dtype == torch.float32, "beam_step_trie: logits (B*K, V) fp32")
-    N, V = logits.shape
-    K = int(num_beams)
-    _need(1 <= K <= BEAMS_MAX and K <= V and N % K == 0,
-          f"beam_step_trie: 1 <= num_beams <= {BEAMS_MAX}, <= V, rows a multiple of it")
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype, "beam_step_trie: emb (V, D) and x_next of one dtype")
-    D = emb.shape[1]
-    _need(tuple(x_next.shape) == (N, D), "beam_step_trie: x_next (B*K, D)")
-    _need(ids_in.dim() == 2 and ids_in.shape[0] == N and ids_in.dtype == torch.int64 and ids_out.dtype == torch.int64
-          and ids_out.shape == ids_in.shape and ids_in.data_ptr() != ids_out.data_ptr(),
-          "beam_step_trie: ids_in, ids_out (B*K, S) int64, two buffers")
-    for t, n in ((pos, N), (done, N), (n_generated, N), (parent, N), (token, N), (node, N), (n_active, 1), (counter, 1)):
-        _need(t.dtype == torch.int32 and t.numel() == n, "beam_step_trie: pos / done / n_generated / parent / token / node "
-                                                         "(B*K,), n_active / counter (1,) int32")
-    _need(score.dtype == torch.float32 and score.numel() == N, "beam_step_trie: score (B*K,) fp32")
-    _need(pos64.dtype == torch.int64 and pos64.numel() == N, "beam_step_trie: pos64 (B*K,) int64")
-    rc = _lib.load(emb.dtype).fvqa_beam_step_trie(_ptr(logits), _ptr(emb), int(eos_id), 1 if stop_at_eos else 0,
-                                                  1 if count_any_live else 0, _ptr(ids_in), _ptr(ids_out), _ptr(pos),
-                                                  _ptr(score), _ptr(done), _ptr(n_generated), _ptr(pos64), _ptr(parent),
-                                                  _ptr(token), _ptr(x_next), _ptr(n_active), _ptr(counter), _ptr(node), _ptr(nf),
-                                                  _ptr(et), _ptr(ec), n_nodes, n_edges, N // K, K, V, D, ids_in.shape[1],
-                                                  dt_code(emb.dtype), _stream())
-    _lib.check(rc, "fvqa_beam_step_trie")
-    return parent, token
+    trie_args = _trie_args("beam_step_trie", node, trie)
+    _dev(logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent, token, x_next, n_active, counter, node,
+         *trie_args[:3])
+    return _beam_step("beam_step_trie", trie_args, logits, emb, ids_in, ids_out, pos, score, done, n_generated, pos64, parent,
+                      token, x_next, n_active, counter, node, num_beams, eos_id, stop_at_eos, count_any_live)
 
 
 def kv_beam_move_scratch(n_seq: int, window_rows: int, D: int, L: int, dtype) -> int:
