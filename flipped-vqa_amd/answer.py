@@ -5,7 +5,7 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
         [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
         [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
-        [--lookahead T --lookup_ngram G] [--jump_forward T]
+        [--lookahead T --lookup_ngram G] [--jump_forward T] [--frame_attention] [--json FILE]
     python answer.py ... --features clip.pth --questions FILE --slots N [--admit M]
 
 `--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
@@ -16,6 +16,10 @@ zero features — and prints how many tokens were plausible per step (fvqa.gener
 tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
 `--jump_forward T` (with --constrain or --answer_vocab; greedy only) commits the tokens the trie of allowed answers fixes without
 a pass of their own, up to T per step, and prints the tokens committed per step (fvqa.generate.generate(jump_forward=T)).
+`--frame_attention` prints, under each answer, the weight its tokens' text softmax put on each of the clip's frame keys and their
+sum, the video mass (fvqa.generate.generate(frame_attention=True), fvqa.attribution.summarize: mean over the answer's tokens, the
+layers and the heads); `--json FILE` writes the answers — and those numbers — as a JSON list. Not with beams, --contrast,
+--lookahead, --jump_forward or --slots.
 `--questions FILE --slots N [--admit M]`: one question per line about the given clip, one answer per line, through in-flight
 batching (fvqa.stream.generate_stream): a decode batch of N rows in which a finished answer hands its slot to the next question.
 The sampling flags and --constrain / --answer_vocab apply; beams, --contrast, --lookahead, --jump_forward and --num_samples do not.
@@ -66,6 +70,10 @@ def get_args_parser():
     p.add_argument("--jump_forward", type=int, default=0,
                    help="with --constrain / --answer_vocab: up to T tokens per pass where the allowed answers leave no choice "
                         "(0, 1: off)")
+    p.add_argument("--frame_attention", action="store_true",
+                   help="print the share of attention each frame of the clip received from the answer's tokens, and their sum")
+    p.add_argument("--json", type=str, default=None, metavar="FILE",
+                   help="write the answers (with --frame_attention: frame_share and video_mass too) as a JSON list")
     p.set_defaults(max_seq_len=128, seed=None)
     return p
 
@@ -154,12 +162,20 @@ def main(args):
         kw.update(lookahead=args.lookahead, lookup_ngram=args.lookup_ngram)
     if args.jump_forward > 1:
         kw.update(jump_forward=args.jump_forward)
+    if args.frame_attention:
+        kw.update(frame_attention=True)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
                             seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
                             repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,
                             num_return_sequences=args.num_samples, **kw)[0]
     g = model.last_generation
     many = args.num_samples > 1
+    share = None
+    if args.frame_attention:                      # (1[, n], F) and (1[, n]): the one question's answers
+        from fvqa import attribution
+        s = attribution.summarize(g)
+        share, mass = s["frame_share"][0].cpu().reshape(-1, s["frame_share"].shape[-1]), s["video_mass"][0].cpu().reshape(-1)
+    records = []
     for k, a in enumerate(answer if many else [answer]):
         n = int(g["n_generated"][0, k] if many else g["n_generated"][0])
         head = f"[{n} tokens, {g['steps']} steps"
@@ -178,6 +194,14 @@ def main(args):
         if allowed is not None:
             c = int(g["choice"][0, k] if many else g["choice"][0])
             print(f"choice {c}: {allowed[c]}" if c >= 0 else "choice -1: no allowed answer was completed")
+        records.append({"answer": a})
+        if share is not None:
+            print("frame shares " + " ".join(f"{float(x):.4f}" for x in share[k]) + f" | video mass {float(mass[k]):.4f}")
+            records[-1].update(frame_share=[float(x) for x in share[k]], video_mass=float(mass[k]))
+    if args.json:
+        import json
+        with open(args.json, "w") as f:
+            json.dump(records, f)
     return answer
 
 

@@ -1,6 +1,6 @@
 // Body of the one-query-row attention of the generation path, shared by the stand-alone kernel (attn_decode.hip) and the
 // persistent per-token kernel (decode.hip): one 256-thread workgroup per (head h, sequence n). See attn_decode.hip for the
-// contract. LDS is the caller's: sc[SMAX] (text scores), sa[16], red[8], part[4][DH].
+// contract. LDS is the caller's: sc[SMAX] (text scores), sa[16], red[8], part[4][DH] and, with MASS, mred[8].
 #pragma once
 #include "common.h"
 
@@ -57,14 +57,45 @@ __device__ __forceinline__ void rope_chunk(float (&v)[CH], const float* cs, cons
 }
 
 
+// The summary of one row's text probabilities sc[j] * inv, j = 0..p (include/fvqa.h fvqa_attn_decode_mass): out[f] = the weight
+// of frame key vs + f, out[F] = the weight in front of the window, out[F + 1] = the weight behind it. Two steps around ONE
+// __syncthreads() of the caller: mass_partials stores the frame entries and leaves each wave's share of the two masked sums in
+// mred[0..3] / mred[4..7]; mass_finish adds them in a fixed order. No atomics: the same bits every launch.
+__device__ __forceinline__ void mass_partials(const float* sc, float inv, int p, int vs, int F, float* __restrict__ out,
+                                              float* mred) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int f = tid; f < F; f += 256) {
+    const int j = vs + f;
+    out[f] = (vs >= 0 && j <= p) ? sc[j] * inv : 0.f;
+  }
+  const int front = vs < 0 ? 0 : vs;               // keys [0, front) lie in front of the window
+  const int back = vs < 0 ? 0 : vs + F;            // keys [back, p] behind it (no window: the whole row)
+  float a = 0.f, b = 0.f;
+  for (int j = tid; j <= p; j += 256) {
+    const float pj = sc[j] * inv;
+    a += j < front ? pj : 0.f;
+    b += j >= back ? pj : 0.f;
+  }
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if (lane == 0) { mred[w] = a; mred[4 + w] = b; }
+}
+__device__ __forceinline__ void mass_finish(int F, float* __restrict__ out, const float* mred) {
+  out[F] = (mred[0] + mred[1]) + (mred[2] + mred[3]);
+  out[F + 1] = (mred[4] + mred[5]) + (mred[6] + mred[7]);
+}
+
 // WT: the output row is stored write-through at agent scope (the persistent kernel's readers sit on other XCDs).
-template <typename T, bool WT = false>
+// MASS: the row's frame-attention summary goes to mass (n_seq, H, F + 2) fp32 as well (mred: 8 floats of LDS); false compiles
+// none of it.
+template <typename T, bool WT = false, bool MASS = false>
 __device__ __forceinline__ void attn_decode_body(const T* __restrict__ qkv_row, T* __restrict__ cache, T* __restrict__ o_row,
                                                  const float* __restrict__ gate1, const float* __restrict__ gate2,
                                                  const int32_t* __restrict__ vstart, const int64_t* __restrict__ pos,
                                                  const float* __restrict__ cs, const float* __restrict__ sn, int n_seq, int S,
                                                  int H, int A, int F, int cache_rot, int h, int n, float* sc, float* sa,
-                                                 float* red, float (*part)[DH]) {
+                                                 float* red, float (*part)[DH], float* __restrict__ mass = nullptr,
+                                                 float* mred = nullptr) {
   constexpr int CH = Chunk<T>::CH;                 // head dims per 16-byte chunk
   constexpr int NCH = DH / CH;                     // chunks per row
   constexpr int CPL = NCH / 4;                     // chunks per lane of a key's quad
@@ -169,6 +200,7 @@ __device__ __forceinline__ void attn_decode_body(const T* __restrict__ qkv_row, 
   }
   __syncthreads();
   const float inv = 1.f / ((red[4] + red[5]) + (red[6] + red[7]));
+  if constexpr (MASS) mass_partials(sc, inv, p, vs, F, mass + ((size_t)n * H + h) * (F + 2), mred);
   // ---- values: lane = 2 head dims, wave w takes keys j = w, w+4, ...
   float o0 = 0.f, o1 = 0.f;
 #pragma unroll
@@ -219,6 +251,8 @@ __device__ __forceinline__ void attn_decode_body(const T* __restrict__ qkv_row, 
     }
     crow[D + d] = from_f32<T>(a); crow[D + d + 1] = from_f32<T>(b);
     crow[2 * D + d] = rowq[2 * D + d]; crow[2 * D + d + 1] = rowq[2 * D + d + 1];
+  } else if (MASS && tid == 128) {                   // (the partial sums crossed the barrier above)
+    mass_finish(F, mass + ((size_t)n * H + h) * (F + 2), mred);
   }
 }
 

@@ -105,7 +105,9 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     the accuracy of the blind twin's and of the plain prediction — are logged from the same single host read.
     `--gen_stream SLOTS` (generation task): the loader's batches are materialised and decoded through ONE stream of SLOTS rows
     with in-flight batching (`model.inference_stream`, fvqa/stream.py) before the per-batch body below runs on each batch's rows;
-    without the flag every call launches what it did."""
+    without the flag every call launches what it did.
+    `--gen_frame_attention` (generation task, through `generate`): a `video_mass` meter — the weight the answer rows' text softmax
+    puts on the frame keys (fvqa/attribution.py) — and `frame_share` in every entry of the extracted-answers file."""
     gen = bool(getattr(args, "is_generation_task", False))
     owner = None
     if not gen:
@@ -159,6 +161,8 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
             continue
         with torch.no_grad():
             best, extracted = next(streamed) if streamed is not None else model(data, inference=True)
+        if getattr(args, "gen_frame_attention", False) and extracted and "video_mass" in extracted[0]:
+            log.update(n=bsz, video_mass=sum(e["video_mass"] for e in extracted) / len(extracted))
         if getattr(args, "output_dir", None):
             import os
             os.makedirs(os.path.join(args.output_dir, "extracted_answers"), exist_ok=True)

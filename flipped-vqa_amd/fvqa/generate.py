@@ -16,7 +16,7 @@ from typing import List, Tuple
 
 import torch
 
-from . import constrain, ops, rowpass
+from . import attribution, constrain, ops, rowpass
 
 N_NEW = 31          # reference llama/model.py:438: positions prefix-1 .. prefix+29
 
@@ -77,13 +77,19 @@ def _prefill(eng, data: dict, twin=None) -> types.SimpleNamespace:
                                  rotated=rotated)
 
 
-def _one_row_attn(eng, p, kv, vstart, pos):
+def _one_row_attn(eng, p, kv, vstart, pos, mass=None):
     """rowpass.layers' attention for one new row per sequence: the row against the cached keys / values of `kv` (+ adapter
-    prefix); its k, v join the cache at `pos`."""
+    prefix); its k, v join the cache at `pos`. mass (None: the launch of every call before the keyword existed): a one-element
+    list that holds the (L, R, H, F + 2) fp32 tensor of the pass being queued — layer i writes its rows' frame-attention
+    summary into slice i (ops.attn_decode_mass: the same output and cache bits)."""
     def attn(i, qkv, o):
         ops.attn_decode(qkv, kv[i], o, *eng.model.gate_views(i), vstart, pos, (eng.cos, eng.sin), qkv.shape[0], p.S, eng.H,
                         eng.Dh, eng.A, eng.F, cache_rotated=p.rotated)
-    return attn
+
+    def attn_mass(i, qkv, o):
+        ops.attn_decode_mass(qkv, kv[i], o, mass[0][i], *eng.model.gate_views(i), vstart, pos, (eng.cos, eng.sin), qkv.shape[0],
+                             p.S, eng.H, eng.Dh, eng.A, eng.F, cache_rotated=p.rotated)
+    return attn if mass is None else attn_mass
 
 
 class _LagOneStop:
@@ -188,7 +194,8 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
              stop_at_eos: bool = True, seed=None, num_beams: int = 1, length_penalty: float = 0.0, top_k: int = 0,
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
              constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1,
-             lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None, jump_forward: int = 0) -> dict:
+             lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None, jump_forward: int = 0,
+             frame_attention: bool = False) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -271,7 +278,28 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       ValueError: no constraints, temperature > 0, num_beams > 1, top_k, repetition_penalty != 1, num_return_sequences > 1,
       contrast, lookahead >= 2, T > 16 (ops.SUFFIX_MAX) or < 0, B * T > 65535, stop_at_eos=False. Not built: sampling at the
       picks, beams, contrast; the LM head on each sample's last fed row only (the other rows' logits are computed and, without
-      return_logprobs, never read)."""
+      return_logprobs, never read).
+    frame_attention (False: every code path above runs untouched): where each generated token looked. The results gain
+      "frame_attention" (B[, n], steps, L, H, F + 2) fp32: per token, layer and head the weight of the text softmax
+      (llama/model.py:116-120, gate2 included; the adapter softmax is not part of it) on each of the F frame keys, in front of
+      the window (index F) and behind it (index F + 1) — include/fvqa.h fvqa_attn_decode_mass states it; the entries of a row sum
+      to 1. Index t is the summary of the row whose logits picked token t: index 0 is read from the prefill's arena
+      (attribution.arena_mass at `start`, one launch per layer and call; computed on the B prefill rows and repeated under
+      num_return_sequences), index t + 1 is written by the decode pass that follows token step t (ops.attn_decode_mass in place of
+      ops.attn_decode: the same launch count, the same output and cache bits, so "ids", "tokens" and "logprobs" are those of the
+      call without the keyword). Zero where "tokens" is -1. attribution.summarize reduces it to a frame profile per answer.
+      Served with greedy and sampled decoding, top_k, repetition_penalty, return_logprobs, num_return_sequences and constraints.
+      ValueError: num_beams > 1, contrast, lookahead >= 2, jump_forward >= 2. Not built: the summary for option scoring (the
+      suffix kernel's online softmax keeps no probabilities), under beams, twins, several rows per pass and the stream."""
+    if frame_attention:
+        if num_beams != 1:
+            raise ValueError("generate: frame_attention is not built for num_beams > 1")
+        if contrast is not None:
+            raise ValueError("generate: frame_attention is not built for contrast")
+        if lookahead >= 2 or draft_tokens is not None:
+            raise ValueError("generate: frame_attention is not built for lookahead")
+        if jump_forward >= 2:
+            raise ValueError("generate: frame_attention is not built for jump_forward")
     if int(lookahead) != lookahead or not 0 <= lookahead <= ops.SUFFIX_MAX:
         raise ValueError(f"generate: 0 <= lookahead <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
     if int(jump_forward) != jump_forward or not 0 <= jump_forward <= ops.SUFFIX_MAX:
@@ -319,7 +347,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                          "num_beams == 1 (beam search reports \"score\")")
     twin = None if contrast is None else _twin(data, contrast, contrast_alpha, contrast_beta, num_beams)
     trie = None if constraints is None else _compiled(eng, data, constraints, stop_at_eos, max_new_tokens)
-    if num_beams > 1 or (_BEAM_PATH_AT_ONE and twin is None):
+    if num_beams > 1 or (_BEAM_PATH_AT_ONE and twin is None and not frame_attention):
         kw = {} if trie is None else {"constraints": trie}
         return beam_search(eng, data, max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, num_beams=int(num_beams),
                            length_penalty=float(length_penalty), **kw)
@@ -343,6 +371,12 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
                          S=S, A=eng.A)
         vstart, ids, prefix, start = rep(vstart), rep(ids), rep(prefix), rep(start)
         first = first.unsqueeze(1).expand(p.B, n, V).reshape(B, V)
+    fa = cur_mass = None
+    if frame_attention:                                     # (steps, L, rows, H, F + 2): a pass writes the slice of its step
+        fa = torch.zeros(max_new_tokens, eng.L, B, eng.H, eng.F + 2, dtype=torch.float32, device=dev)
+        m0 = attribution.arena_mass(eng, p.B, S, p.rows, p.start.clamp(0, S - 1))      # the prefill's rows picked token 0
+        fa[0].copy_(m0 if n == 1 else m0.repeat_interleave(n, 1))
+        cur_mass = [fa[0]]
     b = rowpass.buffers(eng, B)
     lg, xin = b.lg, b.xin
     lg.copy_(first)
@@ -373,7 +407,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     kw_ex = dict(kw, top_k=int(top_k), repetition_penalty=float(repetition_penalty))
     # a finished row stays in the batch (it is rectangular): it goes through every layer on the embedding of its last token
     # and attn_decode rewrites its K/V at its frozen position — the same values each time, read by nobody
-    attn = _one_row_attn(eng, p, kv, vstart, pos64)
+    attn = _one_row_attn(eng, p, kv, vstart, pos64, cur_mass)
     stop = _LagOneStop(max_new_tokens)
     steps = 0
     for t in range(max_new_tokens):
@@ -396,9 +430,14 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         steps = t + 1
         if steps == max_new_tokens:
             break                                           # (the logits after the last token pick nothing)
+        if fa is not None:
+            cur_mass[0] = fa[t + 1]                         # this pass's rows pick token t + 1
         rowpass.head(eng, rowpass.layers(eng, b, attn), b.xn, lg)
     out = {"ids": ids, "n_generated": pos.to(torch.int64) - start, "steps": steps,
            "tokens": tokens[:steps].t().contiguous()}
+    if fa is not None:                                      # (rows, steps, L, H, F + 2); a finished row's passes are not tokens
+        live = (out["tokens"] != -1).view(B, steps, 1, 1, 1)
+        out["frame_attention"] = fa[:steps].permute(2, 0, 1, 3, 4).contiguous() * live
     B0 = NP // n                                            # the samples
     if twin is not None:                                    # the positive rows; the twins hold the same tokens
         out["ids"], out["n_generated"] = out["ids"][:NP].contiguous(), out["n_generated"][:NP]
@@ -407,7 +446,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         out["logprobs"] = logprobs[:steps].t().contiguous()
         out["sum_logprob"] = out["logprobs"].sum(1)
     if n > 1:
-        for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible"):
+        for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible", "frame_attention"):
             if k in out:
                 out[k] = out[k].view(B0, n, *out[k].shape[1:])
     if trie is not None:

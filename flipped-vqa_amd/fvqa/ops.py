@@ -522,24 +522,66 @@ def attn_fwd(qkv, o, lse_a, lse_t, gate1, gate2, vstart, n_seq, S, H, Dh, A, F, 
     return o
 
 
+def _attn_decode(what, qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_seq, S, H, Dh, A, F, cache_rotated, mass=None):
+    """attn_decode and attn_decode_mass (mass given): the same operands and checks but for the summary."""
+    _dev(qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, mass)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, what)
+    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
+    _need(cos_t is not None, f"{what}: rope tables")
+    _need(qkv_row.dtype == qkv_cache.dtype == o_row.dtype, f"{what}: dtype")
+    _need(tuple(qkv_row.shape) == (n_seq, 3 * D) and tuple(o_row.shape) == (n_seq, D), f"{what}: row shapes")
+    _need(pos.dtype == torch.int64 and pos.numel() == n_seq, f"{what}: pos")
+    _need(vstart.dtype == torch.int32 and vstart.numel() == n_seq, f"{what}: vstart")
+    for t in (gate1, gate2):
+        _need(t.dtype == torch.float32 and t.numel() == H, f"{what}: gate shape")
+    extra = ()
+    if mass is not None:
+        _need(F >= 0 and mass.dtype == torch.float32 and tuple(mass.shape) == (n_seq, H, F + 2),
+              f"{what}: mass must be fp32 (n_seq, H, F + 2)")
+        extra = (_ptr(mass),)
+    rc = getattr(_lib.load(qkv_cache.dtype), "fvqa_" + what)(
+        _ptr(qkv_row), _ptr(qkv_cache), _ptr(o_row), _ptr(gate1), _ptr(gate2), _ptr(vstart), _ptr(pos), _ptr(cos_t),
+        _ptr(sin_t), *extra, n_seq, S, H, Dh, A, F, 1 if cache_rotated else 0, dt_code(qkv_row.dtype), _stream())
+    _lib.check(rc, "fvqa_" + what)
+    return o_row
+
+
 def attn_decode(qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_seq, S, H, Dh, A, F, cache_rotated: bool):
     """One new token per sequence (generation path): attention of the new row over the cached keys / values + the
     adapter prefix; the new token's k, v are stored into cache row n*S + pos[n]. qkv_row holds RAW projections."""
-    _dev(qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos)
-    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_decode")
-    D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
-    _need(cos_t is not None, "attn_decode: rope tables")
-    _need(qkv_row.dtype == qkv_cache.dtype == o_row.dtype, "attn_decode: dtype")
-    _need(tuple(qkv_row.shape) == (n_seq, 3 * D) and tuple(o_row.shape) == (n_seq, D), "attn_decode: row shapes")
-    _need(pos.dtype == torch.int64 and pos.numel() == n_seq, "attn_decode: pos")
-    _need(vstart.dtype == torch.int32 and vstart.numel() == n_seq, "attn_decode: vstart")
-    for t in (gate1, gate2):
-        _need(t.dtype == torch.float32 and t.numel() == H, "attn_decode: gate shape")
-    rc = _lib.load(qkv_cache.dtype).fvqa_attn_decode(_ptr(qkv_row), _ptr(qkv_cache), _ptr(o_row), _ptr(gate1), _ptr(gate2),
-                                      _ptr(vstart), _ptr(pos), _ptr(cos_t), _ptr(sin_t), n_seq, S, H, Dh, A, F,
-                                      1 if cache_rotated else 0, dt_code(qkv_row.dtype), _stream())
-    _lib.check(rc, "fvqa_attn_decode")
-    return o_row
+    return _attn_decode("attn_decode", qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_seq, S, H, Dh, A, F,
+                        cache_rotated)
+
+
+def attn_decode_mass(qkv_row, qkv_cache, o_row, mass, gate1, gate2, vstart, pos, rope, n_seq, S, H, Dh, A, F,
+                     cache_rotated: bool):
+    """attn_decode — the same o_row and cache stores, bit for bit — that also writes each row's frame-attention summary into
+    mass (n_seq, H, F + 2) fp32: the text softmax's weight on each frame key, in front of the window and behind it
+    (include/fvqa.h fvqa_attn_decode_mass)."""
+    return _attn_decode("attn_decode_mass", qkv_row, qkv_cache, o_row, gate1, gate2, vstart, pos, rope, n_seq, S, H, Dh, A, F,
+                        cache_rotated, mass=mass)
+
+
+def attn_row_mass(qkv, seq, pos, mass, gate2, vstart, rope, n_seq, S, H, Dh, A, F, cache_rotated: bool):
+    """The summary of attn_decode_mass for R rows that already sit in a layer's arena buffer qkv (n_seq*S + A, 3*D), q and k in
+    the cache's convention: row r is the query at position pos[r] of sequence seq[r] (int32, R each). Writes mass (R, H, F + 2)
+    fp32 and nothing else (include/fvqa.h fvqa_attn_row_mass)."""
+    _dev(qkv, seq, pos, mass, gate2, vstart)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, "attn_row_mass")
+    _attn_shapes(qkv, n_seq, S, H, Dh, A)
+    _need(cos_t is not None, "attn_row_mass: rope tables")
+    R = seq.numel()
+    _need(seq.dtype == pos.dtype == torch.int32 and 1 <= R <= 65535 and pos.numel() == R,
+          "attn_row_mass: seq and pos are int32, 1..65535 rows each")
+    _need(vstart.dtype == torch.int32 and vstart.numel() == n_seq, "attn_row_mass: vstart")
+    _need(gate2.dtype == torch.float32 and gate2.numel() == H, "attn_row_mass: gate shape")
+    _need(F >= 0 and mass.dtype == torch.float32 and tuple(mass.shape) == (R, H, F + 2),
+          "attn_row_mass: mass must be fp32 (R, H, F + 2)")
+    rc = _lib.load(qkv.dtype).fvqa_attn_row_mass(_ptr(qkv), _ptr(seq), _ptr(pos), _ptr(gate2), _ptr(vstart), _ptr(cos_t),
+                                                 _ptr(sin_t), _ptr(mass), R, n_seq, S, H, Dh, A, F, 1 if cache_rotated else 0,
+                                                 dt_code(qkv.dtype), _stream())
+    _lib.check(rc, "fvqa_attn_row_mass")
+    return mass
 
 
 SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)

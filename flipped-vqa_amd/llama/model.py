@@ -122,6 +122,24 @@ class _StepFunction(torch.autograd.Function):
         return (None, None) + out
 
 
+def _frame_attention_kw(args) -> dict:
+    """--gen_frame_attention as generate's keyword ({} without the flag: the call made before it existed)."""
+    return {"frame_attention": True} if getattr(args, "gen_frame_attention", False) else {}
+
+
+def _report_frame_attention(model, out: dict, extracted) -> None:
+    """A result of generate with "frame_attention": the model's `last_generation` gains it, "tokens" and attribution.summarize's
+    "frame_share" / "video_mass"; every extracted answer gains its "frame_share" (F numbers) and "video_mass"."""
+    if "frame_attention" not in out:
+        return
+    from fvqa import attribution
+    s = attribution.summarize(out)
+    model.last_generation.update(frame_attention=out["frame_attention"], tokens=out["tokens"], **s)
+    share, total = s["frame_share"].cpu().tolist(), s["video_mass"].cpu().tolist()
+    for e, f, v in zip(extracted, share, total):
+        e["frame_share"], e["video_mass"] = f, v
+
+
 class Transformer(nn.Module):
     def __init__(self, params: ModelArgs, args):
         super().__init__()
@@ -235,6 +253,13 @@ class Transformer(nn.Module):
         mode = getattr(self.args, "gen_constrain", None)
         if int(getattr(self.args, "lookahead", 0) or 0) > 1 and (mode or getattr(self.args, "contrast", None)):
             raise ValueError("--lookahead verifies drafts against the greedy choice: not with --gen_constrain or --contrast")
+        if getattr(self.args, "gen_frame_attention", False) and not (mode or getattr(self.args, "gen_stop_eos", False)):
+            raise ValueError("--gen_frame_attention is reported by generate: it needs --gen_stop_eos or --gen_constrain")
+        if getattr(self.args, "gen_frame_attention", False) and (
+                int(getattr(self.args, "num_beams", 1) or 1) > 1 or getattr(self.args, "contrast", None)
+                or int(getattr(self.args, "lookahead", 0) or 0) > 1 or int(getattr(self.args, "gen_jump_forward", 0) or 0) > 1):
+            raise ValueError("--gen_frame_attention is served by the plain token loop: not with --num_beams > 1, --contrast, "
+                             "--lookahead > 1 or --gen_jump_forward > 1")
         if mode:                                            # --gen_constrain: decode under the allowed answers
             return self._constrained_inference(data, mode)
         if getattr(self.args, "contrast", None):            # --contrast blind: each token from the difference to the blind twin
@@ -253,17 +278,20 @@ class Transformer(nn.Module):
             self.last_generation = {"ids": ids, "similarities": sims, "n_committed": out["n_committed"],
                                     "n_drafted": out["n_drafted"]}
             return best, extracted
+        out = {}
         if int(getattr(self.args, "num_beams", 1) or 1) > 1:    # --num_beams N: the most likely answer under the model
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
                                     num_beams=int(self.args.num_beams))
             ids = out["ids"]
         elif getattr(self.args, "gen_stop_eos", False):     # --gen_stop_eos: the same tokens up to each row's EOS, which is
-            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True)
+            out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
+                                    **_frame_attention_kw(self.args))
             ids = out["ids"]                                # where both readers of the ids cut them (match_answers, engine)
         else:
             ids = generate.greedy_decode(eng, data)
         best, sims, extracted = generate.match_answers(self, data, ids)
         self.last_generation = {"ids": ids, "similarities": sims}
+        _report_frame_attention(self, out, extracted)
         return best, extracted
 
     @torch.no_grad()
@@ -354,7 +382,7 @@ class Transformer(nn.Module):
         kw = {"jump_forward": jump} if jump > 1 else {}                 # their own (0, 1: the call made before the flag existed)
         out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)), temperature=0.0,
                                 stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie,
-                                **self._contrast_kw(), **kw)
+                                **self._contrast_kw(), **_frame_attention_kw(self.args), **kw)
         ids, choice = out["ids"], out["choice"]
         best, sims, extracted = generate.match_answers(self, data, ids)
         if mode == "options":
@@ -362,6 +390,7 @@ class Transformer(nn.Module):
         self.last_generation = {"ids": ids, "similarities": sims, "choice": choice}
         if jump > 1:
             self.last_generation["n_committed"] = out["n_committed"]
+        _report_frame_attention(self, out, extracted)
         return best, extracted
 
     @torch.no_grad()
@@ -369,17 +398,19 @@ class Transformer(nn.Module):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
         return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta, lookahead, lookup_ngram,
-        draft_tokens, jump_forward) -> one answer per row, the
+        draft_tokens, jump_forward, frame_attention) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
         "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
-        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step; with jump_forward >= 2 "n_committed"). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step; with jump_forward >= 2 "n_committed"; with frame_attention "frame_attention" and "tokens", what fvqa.attribution.summarize reads). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",
-                                                     "n_plausible", "n_committed", "n_drafted")
+                                                     "n_plausible", "n_committed", "n_drafted", "frame_attention")
                                 if k in out}
+        if "frame_attention" in out:
+            self.last_generation["tokens"] = out["tokens"]
         ids, n = out["ids"].cpu(), out["n_generated"].cpu()
 
         def answer(row):

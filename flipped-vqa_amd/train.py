@@ -104,6 +104,12 @@ _FLAGS = [
     ("--gen_stream_admit", dict(type=int, default=None, metavar="M",
                                 help="--gen_stream (answer.py: --slots / --admit): questions admitted per prefill, 1 .. SLOTS "
                                      "(default: SLOTS // 2)")),
+    ("--gen_frame_attention", dict(action="store_true",
+                                   help="generation-task validation through fvqa.generate.generate(frame_attention=True) (needs "
+                                        "--gen_stop_eos or --gen_constrain): where the answer rows looked — a video_mass meter (the "
+                                        "text softmax's weight on the frame keys, mean over tokens, layers and heads) and "
+                                        "frame_share, the weight per frame, in every entry of the extracted-answers file. Not with "
+                                        "--num_beams > 1, --contrast, --lookahead > 1, --gen_jump_forward > 1 or --gen_stream")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -116,7 +122,8 @@ class ArgumentParser(argparse.ArgumentParser):
     """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
     --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead or
     --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for, and
-    --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too)."""
+    --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too), and
+    --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -159,6 +166,16 @@ class ArgumentParser(argparse.ArgumentParser):
                            or int(getattr(a, "num_samples", 1) or 1) > 1):
                 self.error(f"--{flag} decodes one token per row and pass: not with --num_beams > 1, --contrast, --lookahead > 1, "
                            "jump-forward or several samples per prompt")
+        for flag in ("gen_frame_attention", "frame_attention"):
+            if not getattr(a, flag, False):
+                continue
+            if flag == "gen_frame_attention" and not (getattr(a, "gen_stop_eos", False) or getattr(a, "gen_constrain", None)):
+                self.error("--gen_frame_attention is reported by fvqa.generate.generate: it needs --gen_stop_eos or --gen_constrain")
+            if (int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "contrast", None) or la > 1
+                    or int(getattr(a, "gen_jump_forward", 0) or 0) > 1 or int(getattr(a, "jump_forward", 0) or 0) > 1
+                    or int(getattr(a, "gen_stream", 0) or 0) >= 1 or int(getattr(a, "slots", 0) or 0) >= 1):
+                self.error(f"--{flag} is served by the plain token loop: not with --num_beams > 1, --contrast, --lookahead > 1, "
+                           "jump-forward or a stream")
         return a
 
 

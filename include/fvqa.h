@@ -236,6 +236,33 @@ int fvqa_attn_decode(const void* qkv_row, void* qkv_cache, void* o_row, const fl
                      const int32_t* vstart, const int64_t* pos, const float* cos_t, const float* sin_t, int n_seq,
                      int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
                      int dtype, void* stream);
+/* fvqa_attn_decode that also reports where each row looked (the same body with one more compile-time switch, csrc/
+ * attn_decode_body.h; generate(frame_attention=True)). Operands, limits and errors of fvqa_attn_decode; o_row and the cache stores
+ * come out bit for bit as fvqa_attn_decode writes them. In addition mass (n_seq, n_heads, max_feats + 2) fp32 receives, per
+ * sequence n and head h, the summary of P_t = the causal softmax over the text keys 0..p, p = pos[n] (the second softmax of
+ * Attention.forward, llama/model.py:120, gate2[h] on the window when p >= vs + F; the adapter softmax is not part of it), with
+ * vs = vstart[n], F = max_feats:
+ *   mass[f]     = P_t[vs + f] for f < F if vs >= 0 and vs + f <= p, else 0;
+ *   mass[F]     = sum of P_t[j] over j < vs, j <= p (0 when vs < 0): the weight in front of the window;
+ *   mass[F + 1] = sum of P_t[j] over vs + F <= j <= p (vs < 0: the whole row, 1): the weight behind it.
+ * The entries sum to 1 up to rounding. Each sum runs in one fixed order (per-thread strides of 256, the wave's butterfly, four
+ * wave partials added pairwise), no atomics: two launches give the same bits. The probabilities are the ones the value pass
+ * multiplies with (already in LDS): no key is read a second time. mass on a 4-byte boundary; max_feats <= 4096. */
+int fvqa_attn_decode_mass(const void* qkv_row, void* qkv_cache, void* o_row, const float* gate1, const float* gate2,
+                          const int32_t* vstart, const int64_t* pos, const float* cos_t, const float* sin_t, float* mass,
+                          int n_seq, int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats,
+                          int cache_rotated, int dtype, void* stream);
+/* The same summary for rows that ALREADY sit in an arena a forward left behind (the first generated token is picked from the
+ * prefill's logits row prefix - 1, which no decode pass computes). qkv: one layer's (n_seq*S + A, 3*dim) buffer holding the q | k |
+ * v thirds of every row, q and k in ONE convention: both rotated (cache_rotated = 1) or both raw (0, rotated here and rounded to
+ * the storage type) — the rule of fvqa_attn_decode. Row r (of n_rows) is the query at position pos[r] of sequence seq[r] (int32
+ * device arrays; both are clamped into range); it is scored against the keys 0..pos[r] of its sequence, key pos[r] read from the
+ * arena as well. gate2 (n_heads), vstart (n_seq). Writes mass (n_rows, n_heads, max_feats + 2) as defined above and NOTHING else:
+ * no values are loaded, the arena is read-only. One workgroup per (head, row), fvqa_attn_decode's score pass; no atomics, bitwise
+ * repeatable. head_dim 128, seq_len <= 4096, n_rows <= 65535, max_feats <= 4096. */
+int fvqa_attn_row_mass(const void* qkv, const int32_t* seq, const int32_t* pos, const float* gate2, const int32_t* vstart,
+                       const float* cos_t, const float* sin_t, float* mass, int n_rows, int n_seq, int seq_len, int n_heads,
+                       int head_dim, int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
 /* Attention of the option-scoring path (fvqa/score.py) at the SUFFIX rows: the O answer options of a sample share their prompt,
  * which is run once and left in qkv_cache exactly as fvqa_attn_decode takes it (same cache_rotated rule, adapter rows behind the
  * n_seq*S sequence rows); each option recomputes only its last rows. qkv_suf (n_seq*n_options*suffix_len, 3*dim): RAW q | k | v

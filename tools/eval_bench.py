@@ -35,7 +35,10 @@ committed something) of each arm, and whether the ids are the plain call's.
 requests (default 64) with stop_at_eos=False and per-request budgets cycling 3, 6, 12, 24 tokens, each arm interleaved (--pairs N
 times, default 3) with the plain arm: generate() over the same requests in batches of SLOTS, each at its batch's largest budget —
 what a rectangular batch must run. Prefills are included on both sides. Per line: ms per request, token steps, prefills and
-occupancy of each arm, beside what fvqa.stream.simulate predicts, and whether every request's tokens are the plain call's."""
+occupancy of each arm, beside what fvqa.stream.simulate predicts, and whether every request's tokens are the plain call's.
+--frame_attention times greedy generate(frame_attention=True, stop_at_eos=False) — the decode attention also writes each row's
+frame-attention summary, and the prefill's rows are summarised once per call — interleaved (--pairs N times, default 3) with the
+same call without the keyword; per round both arms, their ratio, and whether the ids are the same."""
 import argparse
 import os
 import sys
@@ -78,6 +81,8 @@ def main():
                     "with generate() over batches of SLOTS")
     ap.add_argument("--admit", type=int, nargs="*", default=[], help="--stream: requests admitted per prefill; several M: an arm each")
     ap.add_argument("--requests", type=int, default=64, help="--stream: the number of requests")
+    ap.add_argument("--frame_attention", action="store_true", help="generate(frame_attention=True) against the call without "
+                                                                   "the keyword, interleaved (--pairs rounds, default 3)")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -142,6 +147,19 @@ def main():
         return
     if a.stream:
         stream_lines(a, eng, cfg, timed)
+        return
+    if a.frame_attention:
+        tag = f"{a.model} L={eng.L} B={B} S=128 greedy, {generate.N_NEW} tokens"
+        out = {}
+        runs = (("off", lambda: out.update(off=generate.generate(eng, b, stop_at_eos=False))),
+                ("frame_attention=True", lambda: out.update(on=generate.generate(eng, b, stop_at_eos=False, frame_attention=True))))
+        for _, fn in runs:
+            timed(fn, reps=1)
+        for k in range(a.pairs or 3):
+            t = [timed(fn, warm=0) for _, fn in runs]
+            print(f"{tag} round {k}: " + " | ".join(f"{name}: {x * 1e3:7.1f} ms/batch" for (name, _), x in zip(runs, t))
+                  + f" | on / off {t[1] / t[0]:6.3f}, same ids: {bool(torch.equal(out['on']['ids'], out['off']['ids']))}",
+                  flush=True)
         return
     if a.contrast:
         import dataclasses
