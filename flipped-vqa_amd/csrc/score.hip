@@ -25,6 +25,9 @@
 //   rotated keys (rope_pair_as_decode: the bits fvqa_attn_decode stores for that row and position), the raw bits otherwise;
 //   v as it is. Nothing reads those rows in this launch: a workgroup reads the cache rows [0, start[n]) only.
 //
+// fvqa_attn_suffix_mass — the same body with MASS = true (APPEND = false): o_suf bit for bit, and per query row the summary of its
+//   text softmax over the frame window (include/fvqa.h); score_options(frame_attention=True), fvqa/score.py.
+//
 // fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
 //   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
 //   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
@@ -106,6 +109,8 @@ __device__ __forceinline__ void store16(float* dst, const float (&v)[16]) {
     *reinterpret_cast<float4*>(dst + 4 * u) = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
 }
 
+template <typename P> __device__ __forceinline__ P* pack_first(P* p) { return p; }      // the one element of a parameter pack
+
 __device__ __forceinline__ float half_max(float v) {       // over the 32 lanes of an aligned half wave
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -117,18 +122,34 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
-template <typename T, bool APPEND = false>
+constexpr int MFMAX = 64;                // max_feats under MASS (include/fvqa.h fvqa_attn_suffix_mass): F + 2 <= MLD
+constexpr int MLD = 72;                  // LDS row stride of the summary accumulators (floats): lanes (4 queries) x (8 entries) of a
+                                         // half wave on 32 distinct banks (72 = 8 mod 32); 32 x 72 x 4 B = 9 KiB, 62.6 KiB in all
+
+// MASS: each query row's frame-attention summary goes to mass (n_seq * n_options * suffix_len, n_heads, F + 2) fp32 as well
+// (include/fvqa.h fvqa_attn_suffix_mass states the quantity). The online softmax keeps no probabilities, so the F + 2 entries are
+// running accumulators per query of the tile (Ms), carried like acc: rescaled by alpha[q] in every text chunk, the chunk's Ps
+// added — a frame entry has at most one key per chunk that its query sees; the two sums in front of and behind the window run
+// over the half wave's butterfly in the score pass (fb) —, multiplied by 1 / lrun[q] and stored in the adapter chunk, where the
+// text softmax has closed. Thread (q = tid / 8, e = tid % 8 + 8 m) owns entry e of query q from the first chunk to the store.
+// false compiles none of it; the summary's pointer is an operand of the MASS instantiations only (M: `float` there, an empty
+// pack otherwise), so the other kernels keep their operands and their code.
+template <typename T, bool APPEND = false, bool MASS = false, typename... M>
 __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, const T* __restrict__ cache,
                                                      T* __restrict__ o_suf, const float* __restrict__ gate1,
                                                      const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
                                                      const int32_t* __restrict__ start_p, const int32_t* __restrict__ len_p,
                                                      const float* __restrict__ cs, const float* __restrict__ sn, int B, int O,
-                                                     int Tn, int S, int H, int A, int F, int cache_rot) {
+                                                     int Tn, int S, int H, int A, int F, int cache_rot,
+                                                     M* __restrict__... mass_p) {
+  static_assert(sizeof...(M) == (MASS ? 1 : 0) && !(APPEND && MASS), "mass: one fp32 pointer under MASS; never with APPEND");
   __shared__ __attribute__((aligned(16))) float Qs[QT][KLD];     // the tile's queries: rotated, rounded
   __shared__ __attribute__((aligned(16))) float Ks[KC][KLD];     // the chunk's keys, as the prefill holds them
   __shared__ __attribute__((aligned(16))) float Vs[KC][DH];
   __shared__ __attribute__((aligned(16))) float Ps[QT][KC];      // the chunk's probabilities (unnormalised)
   __shared__ float mrun[QT], lrun[QT], alpha[QT];
+  __shared__ float Ms[MASS ? QT : 1][MASS ? MLD : 1];            // (MASS) the summary's running accumulators
+  __shared__ float fb[MASS ? QT : 1][2];                         // (MASS) the chunk's sums in front of / behind the window
   const int tid = threadIdx.x;
   const int h = blockIdx.x, n = blockIdx.y;
   const int D = H * DH;
@@ -168,6 +189,8 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       }
       store16(&Qs[srow][sd0], v);
       if (tid < QT) { mrun[tid] = -1e30f; lrun[tid] = 0.f; }
+      if constexpr (MASS)
+        for (int e = tid & 7; e < F + 2; e += 8) Ms[srow][e] = 0.f;
     }
     float acc[16];
 #pragma unroll
@@ -276,6 +299,13 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         const float m_new = fmaxf(m_old, half_max(x));
         const float e = see ? __expf(x - m_new) : 0.f;
         const float sum = half_sum(e);
+        if constexpr (MASS) {
+          if (kind != 2) {                                 // (a key the query does not see has e = 0)
+            const float fr = half_sum(vs >= 0 && kpos < vs ? e : 0.f);
+            const float bk = half_sum(vs < 0 || kpos >= vs + F ? e : 0.f);
+            if (kk == 0) { fb[q][0] = fr; fb[q][1] = bk; }
+          }
+        }
         if (kind == 2) {
           Ps[q][kk] = sum > 0.f ? e / sum * tg1 : 0.f;
         } else {
@@ -289,6 +319,28 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         if (kk == 0) mrun[q] = m_new;      // (read above by this half wave only: each query belongs to one)
       }
       __syncthreads();
+      if constexpr (MASS) {
+        float* __restrict__ mass = pack_first(mass_p...);
+        // ---- the summary: Ms[q][e] = Ms[q][e] * alpha[q] + the chunk's weight on entry e; closed and stored in the adapter chunk
+        const int q = srow, qi = q0 + q;
+        const float al = alpha[q];
+        const int k1 = (qi / Tn) * Tn - start - k0;        // suffix chunk: the key at position kpos of the query's own option
+        for (int e = tid & 7; e < F + 2; e += 8) {
+          const float m = Ms[q][e] * al;
+          if (kind == 2) {
+            if (qi < NQ) mass[(((size_t)n * NQ + qi) * H + h) * (F + 2) + e] = qi % Tn < len ? m : 0.f;
+          } else {
+            float add = e == F ? fb[q][0] : fb[q][1];
+            if (e < F) {
+              const int kp = vs + e;                       // the frame key's position
+              const int k = kind == 0 ? kp - k0 : kp + k1;
+              const bool in = kind == 0 ? kp < start : (kp >= start && kp < start + Tn);
+              add = vs >= 0 && in && k >= 0 && k < KC ? Ps[q][k] : 0.f;
+            }
+            Ms[q][e] = m + add;
+          }
+        }
+      }
       // ---- values: acc[q] = acc[q] * alpha[q] + sum_k P[q][k] V[k][vd]
       float vcol[KC];
 #pragma unroll
@@ -371,22 +423,38 @@ __global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ r
 }  // namespace
 
 namespace {
-template <bool APPEND>
+template <bool APPEND, bool MASS = false>
 int suffix_launch(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
                   const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t, const float* sin_t,
                   int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim, int adapter_len,
-                  int max_feats, int cache_rotated, int dtype, void* stream) {
+                  int max_feats, int cache_rotated, int dtype, void* stream, float* mass = nullptr) {
+  static_assert(!(APPEND && MASS), "no instantiation writes the cache and the summary");
   if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !len || !cos_t || !sin_t)
     return FVQA_EINVAL;
+  if (MASS && !mass) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > TMAX || seq_len <= 0 || n_heads <= 0 ||
       head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
     return FVQA_ESHAPE;
   if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || n_options > 4096) return FVQA_ESHAPE;
   if (APPEND && n_options != 1) return FVQA_ESHAPE;      // (options share one cache: only a single continuation may join it)
+  if (MASS && max_feats > MFMAX) return FVQA_ESHAPE;     // (the accumulators' LDS rows)
   if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
+  if (MASS && ((uintptr_t)mass & 3)) return FVQA_EALIGN;
   dim3 grid(n_heads, n_seq), block(256);
   hipStream_t st = (hipStream_t)stream;
+  if constexpr (MASS) {
+    if (dtype == FVQA_H16)
+      hipLaunchKernelGGL((attn_suffix_k<bf16_t, false, true, float>), grid, block, 0, st, (const bf16_t*)qkv_suf,
+                         (const bf16_t*)qkv_cache, (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
+                         n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats, cache_rotated, mass);
+    else
+      hipLaunchKernelGGL((attn_suffix_k<float, false, true, float>), grid, block, 0, st, (const float*)qkv_suf,
+                         (const float*)qkv_cache, (float*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
+                         n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats, cache_rotated, mass);
+    FVQA_CHECK_LAUNCH();
+    return FVQA_OK;
+  }
   if (dtype == FVQA_H16)
     hipLaunchKernelGGL((attn_suffix_k<bf16_t, APPEND>), grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
                        (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
@@ -407,6 +475,16 @@ extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void
                                 int dtype, void* stream) {
   return suffix_launch<false>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options,
                               suffix_len, seq_len, n_heads, head_dim, adapter_len, max_feats, cache_rotated, dtype, stream);
+}
+
+extern "C" int fvqa_attn_suffix_mass(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
+                                     const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
+                                     const float* cos_t, const float* sin_t, int n_seq, int n_options, int suffix_len,
+                                     int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats,
+                                     int cache_rotated, int dtype, void* stream, float* mass) {
+  return suffix_launch<false, true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
+                                    n_options, suffix_len, seq_len, n_heads, head_dim, adapter_len, max_feats, cache_rotated,
+                                    dtype, stream, mass);
 }
 
 extern "C" int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, void* o_suf, const float* gate1,

@@ -2,6 +2,11 @@
 engine.py:10-56): per-iteration LR schedule, forward, sum of the three flipped losses, finite
 check, gradient accumulation through the loss scaler, meters.
 
+`--log_video_mass EVERY` (0: off) adds a `video_mass` meter: on every EVERY-th iteration, between the forward and the backward,
+the weight the text softmax of the vqa stream's scored rows puts on the frame keys is read off the step's arena
+(fvqa/attribution.py: training_video_mass — what a trained gate2 lets the answer rows see of the clip). It reads the arena only and
+rides in the losses' transfer: losses, gradients and the optimizer step are those of the run without the flag, bit for bit.
+
 Host-side differences that do not change results: the three loss values come back in ONE
 device->host transfer per iteration instead of four `.item()` calls + a full device sync; that
 transfer is WAITED FOR only after the backward (and, at an accumulation boundary, the optimizer
@@ -34,6 +39,7 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
     accum = args.accum_iter
     optimizer.zero_grad()
     host_vals, copied = None, None
+    watch = int(getattr(args, "log_video_mass", 0) or 0)      # --log_video_mass EVERY: a video_mass meter (fvqa/attribution.py)
 
     for it, data in enumerate(log.log_every(data_loader, n_iter // 4, f"Epoch: [{epoch}]")):
         boundary_start = it % accum == 0
@@ -43,17 +49,25 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
 
         vqa_loss, vaq_loss, qav_loss = model(data)
         loss = vqa_loss + vaq_loss + qav_loss
+        mass_dev = None
+        if watch and (it + 1) % watch == 0:                   # between the forward and the backward: the arena is read, not written
+            eng = getattr(getattr(model, "module", model), "_engine", None)
+            if eng is not None and eng.saved is not None:
+                from fvqa import attribution
+                with torch.no_grad():
+                    mass_dev = attribution.training_video_mass(eng, data["label"]["vqa"])
         # the three losses and — riding in the same transfer, at no cost of its own — the found-inf word the loss scaler
         # left on the device in the PREVIOUS iteration (2 = the GEMM error word was set: include/fvqa.h)
         found_dev = getattr(loss_scaler, "_found", None)
         prev_found = found_dev.reshape(()).float() if torch.is_tensor(found_dev) and found_dev.device == vqa_loss.device \
             else torch.zeros((), dtype=torch.float32, device=vqa_loss.device)
         vals_dev = torch.stack([vqa_loss.reshape(()).float(), vaq_loss.reshape(()).float(),
-                                qav_loss.reshape(()).float(), prev_found])
+                                qav_loss.reshape(()).float(), prev_found]
+                               + ([mass_dev.reshape(()).float()] if mass_dev is not None else []))      # (the meter rides along)
         if vals_dev.is_cuda:                                  # one asynchronous D2H copy into pinned memory
             if host_vals is None:
-                host_vals, copied = torch.empty(4, dtype=torch.float32, pin_memory=True), torch.cuda.Event()
-            host_vals.copy_(vals_dev, non_blocking=True)
+                host_vals, copied = torch.empty(5, dtype=torch.float32, pin_memory=True), torch.cuda.Event()
+            host_vals[:vals_dev.numel()].copy_(vals_dev, non_blocking=True)
             copied.record()
 
         loss_scaler(loss / accum, optimizer, parameters=model.parameters(), update_grad=boundary_end)
@@ -74,6 +88,8 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
             optimizer.zero_grad()
 
         log.update(loss=loss_value, vqa_loss=vals[0], vaq_loss=vals[1], qav_loss=vals[2])
+        if mass_dev is not None:
+            log.update(video_mass=vals[4])
         log.update(lr=optimizer.param_groups[0]["lr"])
         if getattr(args, "debug", False):
             break
@@ -103,6 +119,9 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     `last_scoring`: one host read per batch. Accuracy overall and per question type either way.
     `--contrast blind` (multiple choice): the prediction is the contrastive one (fvqa/score.py) and `acc_blind` / `acc_plain` —
     the accuracy of the blind twin's and of the plain prediction — are logged from the same single host read.
+    `--val_frame_attention` (multiple choice): a `video_mass` meter — the weight the text softmax of the predicted option's scored
+    rows puts on the frame keys (fvqa/attribution.py: summarize_options), mean over the samples, reduced on the device and read
+    with the prediction.
     `--gen_stream SLOTS` (generation task): the loader's batches are materialised and decoded through ONE stream of SLOTS rows
     with in-flight batching (`model.inference_stream`, fvqa/stream.py) before the per-batch body below runs on each batch's rows;
     without the flag every call launches what it did.
@@ -132,12 +151,12 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
         bsz = answer.shape[0]
         if not gen:
             contrast = getattr(args, "contrast", None)       # --contrast blind: the prediction discounts the blind twin's means
+            watch = bool(getattr(args, "val_frame_attention", False))
+            kw = {"contrast": contrast, "contrast_alpha": float(getattr(args, "contrast_alpha", 1.0))} if contrast else {}
+            if watch:                                        # (with --contrast: score_options' ValueError, as the parser's)
+                kw["frame_attention"] = True
             with torch.no_grad():
-                if contrast:
-                    individual_losses = owner.score_options(data, contrast=contrast,
-                                                            contrast_alpha=float(getattr(args, "contrast_alpha", 1.0)))
-                else:
-                    individual_losses = owner.score_options(data)
+                individual_losses = owner.score_options(data, **kw)
             last = getattr(owner, "last_scoring", None)
             if last is not None:
                 prediction = last["prediction"]
@@ -148,11 +167,19 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
             if contrast and last is not None and "prediction_blind" in last:
                 prediction = torch.stack([prediction, last["prediction_blind"], last["prediction_plain"]])
                 extra = True
-            pred_h = prediction.cpu()                        # the batch's one device->host read
+            mass_h = None
+            if watch and last is not None and "video_mass" in last:      # the meter rides behind the predictions
+                picked = last["video_mass"].gather(1, prediction.view(-1, 1)).mean()
+                packed = torch.cat([prediction.to(torch.float64), picked.to(torch.float64).view(1)]).cpu()
+                pred_h, mass_h = packed[:-1].to(torch.int64), float(packed[-1])
+            else:
+                pred_h = prediction.cpu()                    # the batch's one device->host read
             hit = answer.cpu() == (pred_h[0] if extra else pred_h)
             misc.log_qtype(data, hit, log, args)
             log.update(lr=optimizer.param_groups[0]["lr"])
             log.update(n=bsz, acc=hit.sum().item() / bsz)
+            if mass_h is not None:
+                log.update(n=bsz, video_mass=mass_h)
             if extra:                                        # what the model answers without looking, and without the contrast
                 log.update(n=bsz, acc_blind=(answer.cpu() == pred_h[1]).sum().item() / bsz,
                            acc_plain=(answer.cpu() == pred_h[2]).sum().item() / bsz)

@@ -48,6 +48,7 @@ SIGNATURES = {
     "fvqa_attn_decode_mass": (_i, [_p] * 10 + [_i] * 8 + [_p]),
     "fvqa_attn_row_mass": (_i, [_p] * 8 + [_i] * 9 + [_p]),
     "fvqa_attn_suffix": (_i, [_p] * 10 + [_i] * 10 + [_p]),
+    "fvqa_attn_suffix_mass": (_i, [_p] * 10 + [_i] * 10 + [_p] * 2),
     "fvqa_attn_suffix_append": (_i, [_p] * 10 + [_i] * 9 + [_p]),
     "fvqa_option_pick": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "fvqa_decode_next": (_i, [_p, _p, _p, _f, _f, _i, _i] + [_p] * 8 + [_i] * 5 + [_p]),

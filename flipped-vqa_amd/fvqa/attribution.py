@@ -3,7 +3,9 @@ row, layer and head as F + 2 numbers — the weight on each of the F frame keys 
 the weight behind it (include/fvqa.h fvqa_attn_decode_mass states the quantity). The decode attention already holds the
 probabilities in LDS; `generate(frame_attention=True)` has it write the summary (ops.attn_decode_mass) and takes the first
 token's row, which the prefill computed, from the arena (`arena_mass`, ops.attn_row_mass). `summarize` reduces a result of
-`generate` to one frame profile per answer. `contrast="blind"` says how much of an answer came from the clip; this says from
+`generate` to one frame profile per answer. Option scoring reports the same summary for the suffix rows of every option
+(`score_options(frame_attention=True)`: ops.attn_suffix_mass on the shared route, `arena_mass` on the dense one;
+`summarize_options`), and `training_video_mass` reads it off a training step's arena. `contrast="blind"` says how much of an answer came from the clip; this says from
 which frames, and whether a trained gate2 lets the answer rows look at the video at all."""
 from __future__ import annotations
 
@@ -34,6 +36,46 @@ def arena_mass(eng, n_seq: int, S: int, seq, pos) -> torch.Tensor:
         ops.attn_row_mass(qkv[i], seq, pos, mass[i], eng.model.gate_views(i)[1], vstart, (eng.cos, eng.sin), n_seq, S, eng.H,
                           eng.Dh, eng.A, eng.F, cache_rotated=rotated)
     return mass
+
+
+def training_video_mass(eng, label) -> torch.Tensor:
+    """The training-time meter: between a training forward and its backward (eng.saved: the step's arena, read only), the weight
+    the text softmax of the vqa stream's SCORED rows — row t of sample b with label[b, t + 1] > 0, the rows the vqa loss is made
+    of — puts on the frame keys, mean over those rows, the layers and the heads -> a 0-d fp32 device tensor (None: no scored
+    row). label: the batch's label["vqa"], (B, 1, S) or (B, S). The vqa stream is the arena's first B sequences (fvqa/step.py)."""
+    sv = eng.saved
+    if sv is None or "ar" not in sv:
+        raise ValueError("training_video_mass: no forward has left its arena behind (eng.saved is empty)")
+    B, S = sv["B"], sv["S"]
+    b, t = torch.nonzero(torch.as_tensor(label).reshape(B, S)[:, 1:] > 0, as_tuple=True)
+    if b.numel() == 0:
+        return None
+    n_seq = sv["ar"].qkv.shape[1] // S                       # every stream's sequences (the adapter rows are fewer than S)
+    total = None
+    for r0 in range(0, int(b.numel()), 65535):               # (ops.attn_row_mass takes 65535 rows a launch)
+        m = arena_mass(eng, n_seq, S, b[r0:r0 + 65535], t[r0:r0 + 65535])[..., :eng.F].sum(-1)        # (L, R, H)
+        total = m.sum() if total is None else total + m.sum()
+    return total / float(b.numel() * eng.L * eng.H)
+
+
+def summarize_options(out: dict) -> dict:
+    """A result of score_options(frame_attention=True) -> {"frame_share" (B, O, F): the weight on each frame, "video_mass" (B, O):
+    their sum}, both the mean over the option's SCORED rows (out["plan"].rows: the rows whose loss ranks the option), the layers
+    and the heads. An option without a scored row: zeros."""
+    if "frame_attention" not in out or "plan" not in out:
+        raise ValueError("summarize_options: the result has no \"frame_attention\" (score_options(..., frame_attention=True))")
+    fa, plan = out["frame_attention"], out["plan"]
+    if fa.dim() != 6 or fa.shape[0] != plan.start.numel() or fa.shape[2] != plan.T:
+        raise ValueError("summarize_options: \"frame_attention\" must be (B, O, plan.T, L, H, F + 2)")
+    B, O, T = fa.shape[:3]
+    F = fa.shape[-1] - 2
+    n, c, t = plan.rows.unbind(1)
+    live = torch.zeros(B, O, T, dtype=fa.dtype)
+    live[n, c, t - plan.start[n]] = 1                                           # (every scored row lies in the suffix)
+    live = live.to(fa.device)
+    per_row = fa[..., :F].mean(dim=(-3, -2))                                    # (B, O, T, F)
+    share = (per_row * live.unsqueeze(-1)).sum(-2) / live.sum(-1, keepdim=True).clamp(min=1)
+    return {"frame_share": share, "video_mass": share.sum(-1)}
 
 
 def summarize(out: dict) -> dict:

@@ -585,13 +585,15 @@ def attn_row_mass(qkv, seq, pos, mass, gate2, vstart, rope, n_seq, S, H, Dh, A, 
 
 
 SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)
+SUFFIX_MASS_FEATS = 64   # max_feats fvqa_attn_suffix_mass takes (csrc/score.hip MFMAX: the accumulators' LDS rows)
 
 
 def _attn_suffix(what, qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
-                 cache_rotated):
-    """attn_suffix (n_options >= 1 continuations per sequence, the cache only read) and attn_suffix_append (n_options None: one,
-    whose rows join the cache): the same operands but for the options."""
-    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length)
+                 cache_rotated, mass=None):
+    """attn_suffix (n_options >= 1 continuations per sequence, the cache only read), attn_suffix_mass (the same with the summary:
+    mass given) and attn_suffix_append (n_options None: one, whose rows join the cache): the same operands but for the options
+    and the summary."""
+    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, mass)
     cos_t, sin_t = _rope_tables(rope, S, Dh, what)
     D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
     R = n_seq * (n_options or 1) * T
@@ -603,10 +605,15 @@ def _attn_suffix(what, qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, l
         _need(t.dtype == torch.int32 and t.numel() == n_seq, f"{what}: vstart / start / len are int32 (n_seq)")
     for t in (gate1, gate2):
         _need(t.dtype == torch.float32 and t.numel() == H, f"{what}: gate shape")
+    extra = ()
+    if mass is not None:
+        _need(0 <= F <= SUFFIX_MASS_FEATS and mass.dtype == torch.float32 and mass.is_contiguous()
+              and tuple(mass.shape) == (R, H, F + 2), f"{what}: mass must be fp32 (rows, H, F + 2), F <= {SUFFIX_MASS_FEATS}")
+        extra = (_ptr(mass),)
     rc = getattr(_lib.load(qkv_cache.dtype), "fvqa_" + what)(
         _ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1), _ptr(gate2), _ptr(vstart), _ptr(start), _ptr(length),
         _ptr(cos_t), _ptr(sin_t), n_seq, *(() if n_options is None else (n_options,)), T, S, H, Dh, A, F,
-        1 if cache_rotated else 0, dt_code(qkv_suf.dtype), _stream())
+        1 if cache_rotated else 0, dt_code(qkv_suf.dtype), _stream(), *extra)
     _lib.check(rc, "fvqa_" + what)
     return o_suf
 
@@ -618,6 +625,16 @@ def attn_suffix(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, 
     (read only). Writes o_suf (n_seq*n_options*T, D); rows j >= length[n] are padding (zeros)."""
     return _attn_suffix("attn_suffix", qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq,
                         int(n_options), T, S, H, Dh, A, F, cache_rotated)
+
+
+def attn_suffix_mass(qkv_suf, qkv_cache, o_suf, mass, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A,
+                     F, cache_rotated: bool):
+    """attn_suffix — the same o_suf, bit for bit — that also writes each suffix row's frame-attention summary into mass
+    (n_seq*n_options*T, H, F + 2) fp32: the text softmax's weight on each frame key, in front of the window and behind it; zeros
+    at the rows j >= length[n] (include/fvqa.h fvqa_attn_suffix_mass). F <= SUFFIX_MASS_FEATS."""
+    _need(mass is not None, "attn_suffix_mass: mass is required")
+    return _attn_suffix("attn_suffix_mass", qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq,
+                        int(n_options), T, S, H, Dh, A, F, cache_rotated, mass=mass)
 
 
 def attn_suffix_append(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, T, S, H, Dh, A, F,

@@ -21,6 +21,9 @@ Both end in the same tail: the scored rows' losses in a compact array (fvqa_ce_f
 score_options(contrast=...) is the scoring sibling of generate(contrast=...): the batch and its twin (the same text, the twin's
 features) are scored with the same route, and the prediction is the argmin over the options with count > 0 of
 mean+ + alpha * (mean+ - mean-) — host composition and a (B, n_options)-sized reduction on the device, no new kernel.
+
+score_options(frame_attention=True) also reports where every suffix row of every option looked (fvqa/attribution.py): the shared
+form's suffix attention writes the summary itself (fvqa_attn_suffix_mass), the dense form reads it off its arena (arena_mass).
 """
 from __future__ import annotations
 
@@ -126,7 +129,7 @@ def contrast_pick(mean_pos: torch.Tensor, mean_neg: torch.Tensor, count: torch.T
 
 @torch.no_grad()
 def score_options(eng, data: dict, route: Optional[str] = None, events: Optional[list] = None, *, contrast=None,
-                  contrast_alpha: float = 1.0):
+                  contrast_alpha: float = 1.0, frame_attention: bool = False):
     """-> dict(individual_losses (B, O, S-1) fp32, sum, count (int64), mean (B, O), prediction (B,) int64 — all on the device —,
     route, plan). route: None = route_of(plan). events: a list that receives (name, start, end) torch.cuda.Event triples of the
     passes (tools/score_bench.py).
@@ -134,7 +137,16 @@ def score_options(eng, data: dict, route: Optional[str] = None, events: Optional
     as well, by the same route. "prediction" becomes contrast_pick(mean, mean_blind, count, contrast_alpha); the result gains
     "mean_blind" (B, O), "prediction_blind" (the argmin of the twin's means: what the model answers without looking) and
     "prediction_plain" (the argmin of the batch's own means: the prediction without `contrast`). individual_losses, sum, count
-    and mean stay the batch's own. Not built: negatives whose text differs."""
+    and mean stay the batch's own. Not built: negatives whose text differs.
+    frame_attention (False: every call launches what it did): the result gains "frame_attention" (B, O, T, L, H, F + 2) fp32, T =
+    plan.T — per suffix row j of option c of sample n (sequence position plan.start[n] + j), layer and head the summary of the
+    text softmax that include/fvqa.h fvqa_attn_decode_mass defines: the weight on each frame key, in front of the window (index
+    F) and behind it (index F + 1); rows j >= plan.length[n] are zeros. The shared route has the suffix attention write it
+    (ops.attn_suffix_mass: the same o rows, bit for bit); the dense route reads it off its arena (attribution.arena_mass: the
+    kernels generate() reports with), so the two routes check each other. attribution.summarize_options reduces it to one frame
+    profile per option. ValueError with `contrast`: which of the two passes would it describe?"""
+    if frame_attention and contrast is not None:
+        raise ValueError("score_options: frame_attention is not built for contrast (two passes, one summary)")
     if contrast is not None:
         from .generate import _twin
         twin = _twin(data, contrast, contrast_alpha, 0.0)
@@ -152,8 +164,11 @@ def score_options(eng, data: dict, route: Optional[str] = None, events: Optional
     if route == "shared" and not plan.shared:
         raise ValueError(f"score_options: this batch cannot take the shared form ({plan.why_dense})")
     fn = _shared if route == "shared" else _dense
-    il, s, cnt, mean, pred = fn(eng, data, ids_h, lab_h, vs_list, plan, events)
+    fa = {} if frame_attention else None
+    il, s, cnt, mean, pred = fn(eng, data, ids_h, lab_h, vs_list, plan, events, *(() if fa is None else (fa,)))
     out = dict(individual_losses=il, sum=s, count=cnt, mean=mean, prediction=pred, route=route, plan=plan)
+    if fa is not None:
+        out["frame_attention"] = fa["frame_attention"]
     if contrast is not None:
         blind = dict(data)
         blind.update(twin)
@@ -175,7 +190,29 @@ def _mark(events, name):
     return done
 
 
-def _dense(eng, data, ids_h, lab_h, vs_list, plan, events):
+def _suffix_rows(plan: OptionPlan, O: int):
+    """(seq, pos, at) int64 host tensors of the suffix rows j < length[n] of every option, row-major over (n, c, j): the dense
+    arena's sequence n * O + c, the position start[n] + j, and the row's index in a (B, O, T) array."""
+    B, T = plan.start.numel(), plan.T
+    live = (torch.arange(T)[None, :] < plan.length[:, None])[:, None, :].expand(B, O, T)
+    n, c, j = torch.nonzero(live).unbind(1)
+    return n * O + c, plan.start[n] + j, (n * O + c) * T + j
+
+
+def _dense_mass(eng, plan: OptionPlan, B: int, O: int, S: int) -> torch.Tensor:
+    """"frame_attention" of the dense form, from the arena its forward left (eng.saved): (B, O, T, L, H, F + 2)."""
+    from . import attribution
+    T = plan.T
+    out = torch.zeros(B * O * T, eng.L, eng.H, eng.F + 2, dtype=torch.float32, device=eng.device)
+    seq, pos, at = _suffix_rows(plan, O)
+    for r0 in range(0, int(seq.numel()), 65535):               # (ops.attn_row_mass takes 65535 rows a launch)
+        r1 = r0 + 65535
+        m = attribution.arena_mass(eng, B * O, S, seq[r0:r1], pos[r0:r1])
+        out[at[r0:r1].to(eng.device)] = m.permute(1, 0, 2, 3)
+    return out.view(B, O, T, eng.L, eng.H, eng.F + 2)
+
+
+def _dense(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
     B, O, S = ids_h.shape
     sub = _front_inputs(data, O)
     sub.update({"text_id": {"vqa": ids_h.reshape(B * O, 1, S)}, "label": {"vqa": lab_h.reshape(B * O, 1, S)},
@@ -184,6 +221,8 @@ def _dense(eng, data, ids_h, lab_h, vs_list, plan, events):
     with vqa_stream_only(eng, "_score_arena", "scored"):
         eng.forward(sub)                                   # tail rows: the last layer's second half and the head on scored rows
         tl, ar = eng.last_scored, eng.saved["ar"]
+        if fa is not None:
+            fa["frame_attention"] = _dense_mass(eng, plan, B, O, S)
         eng.saved = None                                   # (no backward follows)
     done()
     o0, rows = tl.segs[0]
@@ -195,7 +234,7 @@ def _dense(eng, data, ids_h, lab_h, vs_list, plan, events):
     return _pick(eng, ar.rowloss_c[o0:o0 + rows], row_map, rows, B, O, S)
 
 
-def _shared(eng, data, ids_h, lab_h, vs_list, plan, events):
+def _shared(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
     m_, pk, dev = eng.model, eng.pack, eng.device
     B, O, S = ids_h.shape
     T = plan.T
@@ -232,10 +271,18 @@ def _shared(eng, data, ids_h, lab_h, vs_list, plan, events):
     b = rowpass.buffers(eng, R, xin=False, lg=False)
     rotated = rowpass.cache_rotated(eng)
 
+    # frame_attention: the same attention, each layer writes its slice of the summary
+    mass = None if fa is None else torch.empty(eng.L, R, eng.H, eng.F + 2, dtype=torch.float32, device=dev)
+
     def attn(i, qkv, o):                                   # several continuations read one cached prompt, nothing is written
-        ops.attn_suffix(qkv, ar.qkv[i], o, *m_.gate_views(i), vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H,
-                        eng.Dh, eng.A, eng.F, cache_rotated=rotated)
+        rest = (*m_.gate_views(i), vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H, eng.Dh, eng.A, eng.F)
+        if mass is None:
+            ops.attn_suffix(qkv, ar.qkv[i], o, *rest, cache_rotated=rotated)
+        else:
+            ops.attn_suffix_mass(qkv, ar.qkv[i], o, mass[i], *rest, cache_rotated=rotated)
     x = rowpass.layers(eng, b, attn, x)
+    if fa is not None:
+        fa["frame_attention"] = mass.permute(1, 0, 2, 3).reshape(B, O, T, eng.L, eng.H, eng.F + 2)
     # ---- the scored rows: final norm, LM head, cross-entropy (one "sequence" of `rows` positions, fvqa/scored.py)
     e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
     xg, xf = e(rows, eng.D), e(rows, eng.D)

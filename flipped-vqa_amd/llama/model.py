@@ -453,7 +453,7 @@ class Transformer(nn.Module):
         return answers
 
     @torch.no_grad()
-    def score_options(self, data, contrast=None, contrast_alpha: float = 1.0):
+    def score_options(self, data, contrast=None, contrast_alpha: float = 1.0, frame_attention: bool = False):
         """The multiple-choice protocol's model half (reference llama/model_my_original_mod.py:332-377,506 with
         `inference=True`, not a generation task): -> individual_losses (B, n_options, S-1) fp32 on the device, the per-token
         cross-entropy (ignore_index 0) of every option, zero wherever a row is not scored. The reduction engine.py:86-93 makes of
@@ -461,12 +461,19 @@ class Transformer(nn.Module):
         that ran ("shared": the prompt once + each option's last rows; "dense": every option in full — fvqa/score.py).
         contrast ("blind", or a dict of replacement features; None: nothing changes), contrast_alpha: the batch's twin is scored
         too and the prediction is the argmin of mean+ + alpha * (mean+ - mean-); `last_scoring` gains "mean_blind",
-        "prediction_blind" and "prediction_plain" (fvqa/score.py: score_options). The returned losses stay the batch's own."""
-        from fvqa import score
+        "prediction_blind" and "prediction_plain" (fvqa/score.py: score_options). The returned losses stay the batch's own.
+        frame_attention (not with contrast): `last_scoring` gains "frame_attention" (B, n_options, T, L, H, F + 2) — where every
+        suffix row of every option looked — and fvqa.attribution.summarize_options' "frame_share" (B, n_options, F) and
+        "video_mass" (B, n_options)."""
+        from fvqa import attribution, score
         kw = {} if contrast is None else {"contrast": contrast, "contrast_alpha": contrast_alpha}
+        if frame_attention:
+            kw["frame_attention"] = True
         r = score.score_options(self.ensure_engine(), data, **kw)
         self.last_scoring = {k: r[k] for k in ("prediction", "mean", "count", "route", "mean_blind", "prediction_blind",
-                                               "prediction_plain") if k in r}
+                                               "prediction_plain", "frame_attention") if k in r}
+        if "frame_attention" in r:
+            self.last_scoring.update(attribution.summarize_options(r))
         return r["individual_losses"]
 
     def forward(self, data, inference=False):

@@ -110,6 +110,16 @@ _FLAGS = [
                                         "text softmax's weight on the frame keys, mean over tokens, layers and heads) and "
                                         "frame_share, the weight per frame, in every entry of the extracted-answers file. Not with "
                                         "--num_beams > 1, --contrast, --lookahead > 1, --gen_jump_forward > 1 or --gen_stream")),
+    ("--log_video_mass", dict(type=int, default=0, metavar="EVERY",
+                              help="training: on every EVERY-th iteration log a video_mass meter — the weight the text softmax "
+                                   "of the vqa stream's scored rows puts on the frame keys, mean over rows, layers and heads, "
+                                   "read off the step's arena between the forward and the backward (the step itself is "
+                                   "unchanged). 0: off")),
+    ("--val_frame_attention", dict(action="store_true",
+                                   help="multiple-choice validation (no --is_generation_task) through "
+                                        "score_options(frame_attention=True): a video_mass meter — the weight the text softmax of "
+                                        "the predicted option's scored rows puts on the frame keys, mean over rows, layers and "
+                                        "heads (fvqa.attribution.summarize_options). Not with --contrast")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -123,7 +133,8 @@ class ArgumentParser(argparse.ArgumentParser):
     --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead or
     --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for, and
     --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too), and
-    --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it."""
+    --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it, and --val_frame_attention
+    with a validation that does not score options or scores them twice."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -176,6 +187,14 @@ class ArgumentParser(argparse.ArgumentParser):
                     or int(getattr(a, "gen_stream", 0) or 0) >= 1 or int(getattr(a, "slots", 0) or 0) >= 1):
                 self.error(f"--{flag} is served by the plain token loop: not with --num_beams > 1, --contrast, --lookahead > 1, "
                            "jump-forward or a stream")
+        if int(getattr(a, "log_video_mass", 0) or 0) < 0:
+            self.error("--log_video_mass EVERY >= 0 (0: off)")
+        if getattr(a, "val_frame_attention", False):
+            if getattr(a, "is_generation_task", False):
+                self.error("--val_frame_attention belongs to multiple-choice validation: with --is_generation_task use "
+                           "--gen_frame_attention")
+            if getattr(a, "contrast", None):
+                self.error("--val_frame_attention describes one scoring pass: not with --contrast")
         return a
 
 

@@ -276,6 +276,24 @@ int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, co
                      const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
                      const float* sin_t, int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim,
                      int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
+/* fvqa_attn_suffix that also reports where each suffix row looked (the same kernel template in csrc/score.hip with one more
+ * compile-time switch; score_options(frame_attention=True), fvqa/score.py). Operands, limits and errors of fvqa_attn_suffix; o_suf
+ * comes out bit for bit as fvqa_attn_suffix writes it. In addition mass (n_seq*n_options*suffix_len, n_heads, max_feats + 2) fp32,
+ * row index as o_suf's, receives the summary fvqa_attn_decode_mass defines, of the query row (n, c, j) at p = start[n] + j: P_t =
+ * its softmax over the cached prompt keys [0, start[n]) and rows 0..j of its own option (gate2[h] on the window when p >= vs + F;
+ * the adapter softmax is not part of it), vs = vstart[n], F = max_feats, and a key at position kpos counts for entry kpos - vs if
+ * vs >= 0 and vs <= kpos < vs + F, for entry F if kpos < vs, for entry F + 1 otherwise (vs < 0: every key). The entries of a row
+ * sum to 1 up to rounding; the rows j >= len[n] are zeros. The kernel's online softmax keeps no probabilities: the F + 2 entries
+ * are running accumulators per query in LDS, rescaled in every key chunk by the factor the output accumulator takes, each chunk's
+ * unnormalised weights added in one fixed order (a frame entry meets at most one key per chunk; the two outer sums run over the
+ * half wave's butterfly), and multiplied by 1 / the softmax's sum once the last text chunk is in. No atomics, no key is read a
+ * second time: two launches give the same bits. mass is required, on a 4-byte boundary. The accumulators take 32 x 72 floats of
+ * LDS next to the kernel's 53.4 KiB (62.6 KiB of the 64 KiB a static allocation may take): max_feats <= 64 here, FVQA_ESHAPE
+ * beyond. There is no form that writes the cache and the summary. */
+int fvqa_attn_suffix_mass(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                          const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
+                          const float* sin_t, int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim,
+                          int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream, float* mass);
 /* fvqa_attn_suffix for ONE continuation per sequence whose rows JOIN the cache (the same kernel template in csrc/score.hip with one
  * more compile-time switch; the draft-and-verify pass of generate(lookahead=T), fvqa_spec_step below). The operands, limits and
  * errors of fvqa_attn_suffix hold with n_options == 1: qkv_suf (n_seq*suffix_len, 3*dim), row n*suffix_len + j at sequence

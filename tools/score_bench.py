@@ -4,7 +4,9 @@
 of each, every call bracketed by device events; the shared route's prompt pass and suffix pass on their own; which GEMM kernel
 took the suffix rows' projections (the library's launch record + fvqa_gemm_sk_describe). With --errors: the per-option-mean
 errors of both routes against the reference-generated 7B-width fixture in bf16 and fp16 — the figures the bounds of
-tests/test_score_gpu.py are set from. Everything is appended to --log (profiles/score_options.log)."""
+tests/test_score_gpu.py are set from. With --frame_attention: the cost of score_options(frame_attention=True), the keyword off and
+on in interleaved pairs on both routes (profiles/score_frame_attention.log). Everything is appended to --log
+(profiles/score_options.log)."""
 import argparse
 import ctypes as C
 import os
@@ -126,6 +128,39 @@ def timing(a, say):
     return med
 
 
+def frame_attention_cost(a, say):
+    """What score_options(frame_attention=True) costs: the keyword off and on, interleaved in pairs, on both routes (the shared
+    route swaps fvqa_attn_suffix for fvqa_attn_suffix_mass in every layer; the dense route adds one fvqa_attn_row_mass launch
+    per layer on its arena) — 7B, full depth, bf16, B x five options as `timing`."""
+    if a.reps < 3:
+        sys.exit("--frame_attention: at least 3 pairs (--reps)")
+    cfg = synth.preset("7b", vaq=False, qav=False, batch_size=a.batch_size, n_layers=a.n_layers, adapter_layer=a.n_layers)
+    model = make_model(cfg, torch.bfloat16)
+    eng = model.ensure_engine()
+    batch = synth.make_option_batch(cfg, n_options=a.n_options, seed=1)
+    say(f"frame_attention cost: 7B width, {a.n_layers} layers, bf16, B={a.batch_size} x {a.n_options} options, S={cfg.max_seq_len}, "
+        f"{a.reps} interleaved (off, on) pairs per route after {a.warmup} warm-up calls of each")
+    for r in score.ROUTES:
+        for kw in ({}, {"frame_attention": True}):
+            for _ in range(a.warmup):
+                out = score.score_options(eng, batch, route=r, **kw)
+        torch.cuda.synchronize()
+        fa = out["frame_attention"]
+        t = {False: [], True: []}
+        for _ in range(a.reps):
+            for on in (False, True):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                score.score_options(eng, batch, route=r, **({"frame_attention": True} if on else {}))
+                e1.record()
+                e1.synchronize()
+                t[on].append(e0.elapsed_time(e1))
+        m0, m1 = statistics.median(t[False]), statistics.median(t[True])
+        say(f"  {r:6s}: off median {m0:8.3f} ms (min {min(t[False]):8.3f}, max {max(t[False]):8.3f}); on median {m1:8.3f} ms "
+            f"(min {min(t[True]):8.3f}, max {max(t[True]):8.3f}); on - off = {m1 - m0:+.3f} ms = {100 * (m1 - m0) / m0:+.2f} %; "
+            f"frame_attention {tuple(fa.shape)}")
+
+
 def errors(say):
     g = dict(np.load(os.path.join(ROOT, "tests", "golden", PIN + ".npz")))
     cfg = synth.preset("7b_l2", vaq=False, qav=False, vocab_size=32000, max_seq_len=128, batch_size=4, peaked_perm=True)
@@ -158,8 +193,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--errors", action="store_true", help="also measure both routes' errors against the 7B-width fixture")
     ap.add_argument("--no_timing", action="store_true")
-    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "score_options.log"))
+    ap.add_argument("--frame_attention", action="store_true",
+                    help="measure score_options(frame_attention=True) against the call without it, interleaved, on both routes, and "
+                         "nothing else (--log defaults to profiles/score_frame_attention.log)")
+    ap.add_argument("--log", default=None)
     a = ap.parse_args()
+    if a.log is None:
+        a.log = os.path.join(ROOT, "profiles", "score_frame_attention.log" if a.frame_attention else "score_options.log")
     if not torch.cuda.is_available():
         sys.exit("score_bench.py measures on the GPU: no device found")
     os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
@@ -172,6 +212,9 @@ def main():
 
     say(f"# tools/score_bench.py on {torch.cuda.get_device_name(0)}, kernel sources {build.source_hash()[:12]}")
     with torch.no_grad():
+        if a.frame_attention:
+            frame_attention_cost(a, say)
+            return
         if a.errors:
             errors(say)
         if not a.no_timing:
