@@ -109,6 +109,25 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
     return {k: m.global_avg for k, m in log.meters.items()}
 
 
+def _val_flipped(owner, data, log, optimizer, args):
+    """One multiple-choice batch under --val_flipped: the four predictions and the gold option's losses in ONE host read."""
+    if not hasattr(owner, "score_flipped"):
+        raise NotImplementedError("--val_flipped needs a model with score_flipped (llama/model.py)")
+    answer = data["answer"]
+    bsz = answer.shape[0]
+    w = getattr(args, "val_flipped_weights", None) or (1.0, 1.0)
+    with torch.no_grad():
+        r = owner.score_flipped(data, weights=(1.0, float(w[0]), float(w[1])), answer=answer)
+    preds = torch.stack([r["prediction"], r["prediction_vqa"], r["prediction_vaq"], r["prediction_qav"]])      # (4, B)
+    packed = torch.cat([preds.reshape(-1).to(torch.float64), r["gold_loss"].to(torch.float64).mean(0)]).cpu()
+    pred_h = packed[: 4 * bsz].to(torch.int64).view(4, bsz)
+    hit = answer.cpu() == pred_h
+    misc.log_qtype(data, hit[0], log, args)
+    log.update(lr=optimizer.param_groups[0]["lr"])
+    log.update(n=bsz, acc=hit[0].sum().item() / bsz, acc_vqa=hit[1].sum().item() / bsz, acc_vaq=hit[2].sum().item() / bsz,
+               acc_qav=hit[3].sum().item() / bsz, vaq_loss=float(packed[-2]), qav_loss=float(packed[-1]))
+
+
 def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer, epoch: int,
                   args=None):
     """Validation with the reference's signature and return value (reference engine.py:59-145), both modes.
@@ -122,6 +141,9 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     `--val_frame_attention` (multiple choice): a `video_mass` meter — the weight the text softmax of the predicted option's scored
     rows puts on the frame keys (fvqa/attribution.py: summarize_options), mean over the samples, reduced on the device and read
     with the prediction.
+    `--val_flipped [--val_flipped_weights W_VAQ W_QAV]` (multiple choice): the options are scored by all three flipped tasks
+    (`model.score_flipped`, fvqa/flipped.py) and the prediction is the argmin of their weighted sum; `acc`, `acc_vqa`, `acc_vaq`,
+    `acc_qav` and `vaq_loss` / `qav_loss` — each task's mean loss at the gold option — come from the batch's one host read.
     `--gen_stream SLOTS` (generation task): the loader's batches are materialised and decoded through ONE stream of SLOTS rows
     with in-flight batching (`model.inference_stream`, fvqa/stream.py) before the per-batch body below runs on each batch's rows;
     without the flag every call launches what it did.
@@ -149,6 +171,11 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     for data in log.log_every(data_loader, max(1, len(data_loader) // 4), f"Epoch: [{epoch}]"):
         answer = data["answer"]
         bsz = answer.shape[0]
+        if not gen and getattr(args, "val_flipped", False):
+            _val_flipped(owner, data, log, optimizer, args)
+            if getattr(args, "debug", False):
+                break
+            continue
         if not gen:
             contrast = getattr(args, "contrast", None)       # --contrast blind: the prediction discounts the blind twin's means
             watch = bool(getattr(args, "val_frame_attention", False))

@@ -26,8 +26,17 @@ def vqa_stream_only(eng, arenas: str, lm_head_rows: str):
     """The engine as an evaluation path runs it — the VQA stream alone, in the arenas kept under the attribute `arenas`
     (`_gen_arena`, `_score_arena`: the training step's activations stay where they are), the LM head on `lm_head_rows` — with
     the training configuration (tasks / n_streams / _arena / _vstart / lm_head_rows) put back on the way out."""
+    with streams_only(eng, ["vqa"], arenas, lm_head_rows):
+        yield eng
+
+
+@contextlib.contextmanager
+def streams_only(eng, tasks, arenas: str, lm_head_rows: str):
+    """vqa_stream_only for any streams: the engine runs `tasks` (of vqa, vaq, qav, in that order) for the call, in the arenas kept
+    under the attribute `arenas`, and gets its training configuration back on the way out (fvqa/flipped.py: the VAQ and QAV
+    streams of the answer options)."""
     saved = (eng.tasks, eng.n_streams, eng._arena, eng._vstart, eng.lm_head_rows)
-    eng.tasks, eng.n_streams, eng._arena, eng._vstart = ["vqa"], 1, getattr(eng, arenas), {}
+    eng.tasks, eng.n_streams, eng._arena, eng._vstart = list(tasks), len(tasks), getattr(eng, arenas), {}
     eng.lm_head_rows = lm_head_rows
     try:
         yield eng

@@ -586,20 +586,21 @@ def attn_row_mass(qkv, seq, pos, mass, gate2, vstart, rope, n_seq, S, H, Dh, A, 
 
 SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)
 SUFFIX_MASS_FEATS = 64   # max_feats fvqa_attn_suffix_mass takes (csrc/score.hip MFMAX: the accumulators' LDS rows)
+SUFFIX_WIDE_MAX = 64     # suffix rows per option fvqa_attn_suffix_wide takes (csrc/flipped.hip TWIDE)
 
 
 def _attn_suffix(what, qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
-                 cache_rotated, mass=None):
+                 cache_rotated, mass=None, t_max=SUFFIX_MAX):
     """attn_suffix (n_options >= 1 continuations per sequence, the cache only read), attn_suffix_mass (the same with the summary:
-    mass given) and attn_suffix_append (n_options None: one, whose rows join the cache): the same operands but for the options
-    and the summary."""
+    mass given), attn_suffix_wide (up to t_max = SUFFIX_WIDE_MAX rows) and attn_suffix_append (n_options None: one, whose rows
+    join the cache): the same operands but for the options and the summary."""
     _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, mass)
     cos_t, sin_t = _rope_tables(rope, S, Dh, what)
     D = _attn_shapes(qkv_cache, n_seq, S, H, Dh, A)
     R = n_seq * (n_options or 1) * T
     _need(cos_t is not None, f"{what}: rope tables")
     _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, f"{what}: dtype")
-    _need(1 <= T <= SUFFIX_MAX and (n_options is None or n_options >= 1), f"{what}: 1 <= {'rows per sequence' if n_options is None else 'suffix rows'} <= {SUFFIX_MAX}")
+    _need(1 <= T <= t_max and (n_options is None or n_options >= 1), f"{what}: 1 <= {'rows per sequence' if n_options is None else 'suffix rows'} <= {t_max}")
     _need(tuple(qkv_suf.shape) == (R, 3 * D) and tuple(o_suf.shape) == (R, D), f"{what}: row shapes")
     for t in (vstart, start, length):
         _need(t.dtype == torch.int32 and t.numel() == n_seq, f"{what}: vstart / start / len are int32 (n_seq)")
@@ -647,6 +648,14 @@ def attn_suffix_append(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, l
                         T, S, H, Dh, A, F, cache_rotated)
 
 
+def attn_suffix_wide(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,
+                     cache_rotated: bool):
+    """attn_suffix for 1 <= T <= SUFFIX_WIDE_MAX suffix rows per option (include/fvqa.h fvqa_attn_suffix_wide): the same operands
+    and semantics; the frame window [vstart, vstart + F) may lie inside the suffix (vstart < 0: none)."""
+    return _attn_suffix("attn_suffix_wide", qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq,
+                        int(n_options), T, S, H, Dh, A, F, cache_rotated, t_max=SUFFIX_WIDE_MAX)
+
+
 def option_pick(rowloss, row_map, n_rows: int, n_seq: int, n_options: int, S: int):
     """The per-option reduction (include/fvqa.h fvqa_option_pick): rowloss fp32 compact per-row losses, row_map int32 (entry of
     (n_seq, n_options, S-1) each of the first n_rows rows belongs to, < 0 none) ->
@@ -681,6 +690,64 @@ def _of(dtype, numel, **tensors):
     return [(name, t, dtype, numel) for name, t in tensors.items()]
 
 
+def _table(what, table):
+    """The check of _of's rows: each named operand has its dtype and element count."""
+    for name, t, dtype, numel in table:
+        _need(t.dtype == dtype and t.numel() == numel, f"{what}: {name} is {_DTYPE_NAME.get(dtype, dtype)}, {numel} elements")
+
+
+def suffix_embed(ids, slot, emb, vf_tok, length, x, n_seq: int, n_options: int, T: int, F: int):
+    """The suffix rows' inputs (include/fvqa.h fvqa_suffix_embed): x (n_seq*n_options*T, D) <- emb[ids[r]], or the bits of
+    vf_tok[n, slot[r]] where slot[r] >= 0 (slot int32 (rows) or None; vf_tok (n_seq, F, D) of x's dtype), or zeros at the rows
+    j >= length[n]. ids (rows) int64 inside the table: checked on the host copy by the caller."""
+    _dev(ids, slot, emb, vf_tok, length, x)
+    R = n_seq * n_options * T
+    _need(n_seq >= 1 and n_options >= 1 and T >= 1 and R <= 0x7fffffff, "suffix_embed: rows")
+    _need(emb.dim() == 2 and x.dtype == emb.dtype and tuple(x.shape) == (R, emb.shape[1]), "suffix_embed: x (rows, D) of emb's dtype")
+    D = emb.shape[1]
+    _need(D * emb.element_size() % 16 == 0, "suffix_embed: rows of a multiple of 16 bytes")
+    _table("suffix_embed", _of(_I64, R, ids=ids) + _of(_I32, n_seq, length=length) +
+           (_of(_I32, R, slot=slot) + _of(emb.dtype, n_seq * F * D, vf_tok=vf_tok) if slot is not None else []))
+    _need(slot is None or F >= 1, "suffix_embed: frame rows need max_feats >= 1")
+    rc = _lib.load(emb.dtype).fvqa_suffix_embed(_ptr(ids), _ptr(slot), _ptr(emb), _ptr(vf_tok if slot is not None else None),
+                                                _ptr(length), _ptr(x), n_seq, n_options, T, D, emb.shape[0], F,
+                                                dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_suffix_embed")
+    return x
+
+
+FLIPPED_TASKS = ("vqa", "vaq", "qav")
+
+
+def flipped_pick(mean: dict, count: dict, weights, answer=None):
+    """The pick over the tasks' per-option means (include/fvqa.h fvqa_flipped_pick). mean / count: {task: (B, O) fp32 / int64} for
+    the requested tasks of FLIPPED_TASKS; weights: three floats (vqa, vaq, qav); answer (B,) int64 or None ->
+    (total (B, O) fp32, prediction (B,) int64, prediction_t (3, B) int64, gold_loss (B, 3) fp32 or None)."""
+    _need(len(mean) >= 1 and set(mean) == set(count) and set(mean) <= set(FLIPPED_TASKS), "flipped_pick: tasks of vqa, vaq, qav")
+    _need(len(weights) == 3, "flipped_pick: three weights")
+    first = next(iter(mean.values()))
+    _need(first.dim() == 2, "flipped_pick: means are (B, O)")
+    B, O = first.shape
+    _need(1 <= B <= 65535 and 1 <= O <= 64, "flipped_pick: 1..64 options")
+    _dev(*mean.values(), *count.values(), answer)
+    table = []
+    for t in mean:
+        table += _of(_F32, B * O, **{"mean_" + t: mean[t]}) + _of(_I64, B * O, **{"count_" + t: count[t]})
+    if answer is not None:
+        table += _of(_I64, B, answer=answer)
+    _table("flipped_pick", table)
+    dev = first.device
+    total = torch.empty(B, O, dtype=_F32, device=dev)
+    pred = torch.empty(B, dtype=_I64, device=dev)
+    pred_t = torch.empty(3, B, dtype=_I64, device=dev)
+    gold = None if answer is None else torch.empty(B, 3, dtype=_F32, device=dev)
+    rc = _lib.load().fvqa_flipped_pick(*[_ptr(mean.get(t)) for t in FLIPPED_TASKS], *[_ptr(count.get(t)) for t in FLIPPED_TASKS],
+                                       *[float(w) for w in weights], _ptr(answer), _ptr(total), _ptr(pred), _ptr(pred_t),
+                                       _ptr(gold), B, O, _stream())
+    _lib.check(rc, "fvqa_flipped_pick")
+    return total, pred, pred_t, gold
+
+
 def _token_step(what, logits, n_logits, emb, x_next, ids, n_ids, table, *, pos64=None, n_pos64=0, ids_name="ids",
                 temperature=0.0, u=None, u_shape=(), u_longer=False, top_k=0, repetition_penalty=1.0):
     """The operand checks of the token-step family (decode_next*, spec_step, trie_jump_step, beam_step*), under the entry's name
@@ -694,8 +761,7 @@ def _token_step(what, logits, n_logits, emb, x_next, ids, n_ids, table, *, pos64
     D = emb.shape[1]
     _need(tuple(x_next.shape) == (n_logits, D), f"{what}: x_next ({n_logits}, D), a row per row of logits")
     _need(ids.dim() == 2 and ids.shape[0] == n_ids and ids.dtype == _I64, f"{what}: {ids_name} (B, S) int64, B = {n_ids} rows")
-    for name, t, dtype, numel in table:
-        _need(t.dtype == dtype and t.numel() == numel, f"{what}: {name} is {_DTYPE_NAME[dtype]}, {numel} elements")
+    _table(what, table)
     _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == n_pos64), f"{what}: pos64 ({n_pos64},) int64")
     if temperature != 0:
         _need(u is not None and u.dtype == _F32 and

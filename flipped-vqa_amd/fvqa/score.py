@@ -52,14 +52,19 @@ class OptionPlan:
     rows: torch.Tensor             # (M, 3) int64: (n, c, t) of every scored row, row-major
 
 
-def plan_options(text_id, label, prefix_index=None, video_start=None, F: int = 0) -> OptionPlan:
+def plan_options(text_id, label, prefix_index=None, video_start=None, F: int = 0, *, suffix_max: Optional[int] = None,
+                 frames_in_suffix: bool = False, qav: bool = False) -> OptionPlan:
     """Host-only integer work. text_id, label: (B, O, S) int64 host tensors; video_start: per-sample first frame slot (or one
     int); prefix_index is not needed (the labels say where the answers are) and only checked for length when given.
     Per sample: lcp = the first position where any option differs from option 0 (S if none); row t is scored iff
     label[t + 1] > 0 (llama/model.py:348-350, ignore_index 0); start = min(lcp, first scored row) — every scored row then lies
     in the suffix, the prompt pass needs no LM head; length = last scored row of any option + 1 - start.
     Shared form iff every sample has a scored row, start >= video_start + F + 1 (no frame slot in a suffix: its inputs are token
-    embeddings) and length <= ops.SUFFIX_MAX."""
+    embeddings) and length <= ops.SUFFIX_MAX.
+    The keywords are fvqa/flipped.py's; their defaults decide as ever. suffix_max: the longest suffix (None: ops.SUFFIX_MAX;
+    ops.SUFFIX_WIDE_MAX for a caller that runs ops.attn_suffix_wide). frames_in_suffix: the suffix may hold frame slots (its
+    inputs come from ops.suffix_embed) — the start >= video_start + F + 1 rule is dropped. qav: the QAV head's rule for a scored
+    row, label[t + 1] >= 0 (ignore_index -1, llama/model.py:359-361)."""
     ids = torch.as_tensor(text_id)
     lab = torch.as_tensor(label)
     if ids.dim() != 3 or ids.shape != lab.shape:
@@ -76,7 +81,8 @@ def plan_options(text_id, label, prefix_index=None, video_start=None, F: int = 0
     differs = (ids != ids[:, :1]).any(1)                                  # (B, S)
     pos = torch.arange(S)
     lcp = torch.where(differs, pos, torch.full_like(pos, S)).min(1).values
-    ok = lab[:, :, 1:] > 0                                                # (B, O, S-1): row t scored
+    limit = ops.SUFFIX_MAX if suffix_max is None else int(suffix_max)
+    ok = (lab[:, :, 1:] >= 0) if qav else (lab[:, :, 1:] > 0)             # (B, O, S-1): row t scored
     any_t = ok.any(1)                                                     # (B, S-1)
     has = any_t.any(1)
     t = torch.arange(S - 1)
@@ -87,10 +93,10 @@ def plan_options(text_id, label, prefix_index=None, video_start=None, F: int = 0
     why = ""
     if not bool(has.all()):
         why = "a sample has no scored row"
-    elif bool((start < vs + F + 1).any()):
+    elif not frames_in_suffix and bool((start < vs + F + 1).any()):
         why = "an option differs (or is scored) inside or in front of the frame slots"
-    elif int(length.max()) > ops.SUFFIX_MAX:
-        why = f"a suffix of {int(length.max())} rows (> {ops.SUFFIX_MAX})"
+    elif int(length.max()) > limit:
+        why = f"a suffix of {int(length.max())} rows (> {limit})"
     return OptionPlan(start=start, length=length, T=int(length.max()) if B else 0, shared=not why, why_dense=why,
                       rows=torch.nonzero(ok))
 

@@ -505,7 +505,8 @@ class StepEngine:
             # the layers left the final-norm output of the tail rows in ar.xnf_c: LM segments first -> (M_lm, D) x W_out^T -> CE per
             # stream segment (one "sequence" each)
             lg = ar.logits_c[: tl.M_lm]
-            ops.gemm_nt(ar.xnf_c[: tl.M_lm], pk.wout, lg)
+            if tl.n_lm:                                         # (a QAV stream on its own, fvqa/flipped.py: no LM rows)
+                ops.gemm_nt(ar.xnf_c[: tl.M_lm], pk.wout, lg)
             for k in range(tl.n_lm):
                 o0, rows_k = tl.segs[k]
                 seg = slice(o0, o0 + rows_k)

@@ -349,6 +349,56 @@ def make_option_batch(cfg: SynthConfig, n_options: int = 5, seed: int = 0, batch
     return out
 
 
+Q_TOKEN, V_TOKEN = 16492, 15167       # "Question" / "Video" (reference llama/tokenizer.py:28-31): what fvqa.flipped.option_rows looks for
+
+
+def make_flipped_option_batch(cfg: SynthConfig, n_options: int = 5, seed: int = 0, batch_size: Optional[int] = None,
+                              question_len=(3, 20)) -> dict:
+    """make_option_batch with the VAQ and QAV streams of every option (the validation batch of the reference's reader,
+    llama/tokenizer.py:126-131,184-189; what fvqa.flipped.score_flipped reads):
+      vaq  prompt, frame slots at video_start, 1..3 answer tokens that differ per option, Q_TOKEN, a separator, the question
+           (question_len = (lo, hi): lo..hi-1 tokens per sample), an end token;
+      qav  prompt with the question, the same answer tokens, V_TOKEN, a separator, the F frame slots, an end token.
+    Options of a sample differ in length, so each option's marker sits at its own position. Needs vocab_size > Q_TOKEN."""
+    out = make_option_batch(cfg, n_options, seed, batch_size)
+    B, O, S = out["text_id"]["vqa"].shape
+    F, V = cfg.max_feats, cfg.vocab_size
+    assert V > Q_TOKEN, "the synthetic flipped streams use the reference's marker ids: vocab_size > 16492"
+    tag = f"flipped{seed}"
+    vs = int(out["video_start"]["vqa"][0])
+    nq = _rand_ints(tag + ".nq", B, question_len[0], question_len[1])
+    a = vs + F + 3                                                         # vaq: where the answers start
+    assert a + 3 + 2 + int(nq.max()) + 1 <= S and 4 + int(nq.max()) + 3 + 2 + F + 1 <= S, "sequence too short for the flipped streams"
+    plain = lambda name, n: _rand_ints(name, n, 3, V).apply_(lambda x: 3 if x in (Q_TOKEN, V_TOKEN) else x)      # noqa: E731
+    prompt = plain(tag + ".prompt", B * S).reshape(B, S)
+    quest = plain(tag + ".quest", B * S).reshape(B, S)
+    tail = plain(tag + ".tail", B * O * 3).reshape(B, O, 3)
+    n_tail = 1 + _rand_ints(tag + ".ntail", B * O, 0, 3).reshape(B, O)
+    vaq = torch.zeros(B, O, S, dtype=torch.int64)
+    qav = torch.zeros(B, O, S, dtype=torch.int64)
+    for b in range(B):
+        q = int(nq[b])
+        for c in range(O):
+            k = int(n_tail[b, c])
+            ans = tail[b, c, :k].clone()
+            ans[0] = 3 + (int(tail[b, 0, 0]) + c) % 15000                  # differs per option; below both markers
+            vaq[b, c, :a] = prompt[b, :a]
+            vaq[b, c, vs:vs + F] = 0
+            vaq[b, c, a:a + k] = ans
+            vaq[b, c, a + k], vaq[b, c, a + k + 1] = Q_TOKEN, 29901 % V
+            vaq[b, c, a + k + 2:a + k + 2 + q] = quest[b, :q]
+            vaq[b, c, a + k + 2 + q] = 2
+            e = 4 + q                                                      # qav: where the answers start
+            qav[b, c, :4] = prompt[b, :4]
+            qav[b, c, 4:e] = quest[b, :q]
+            qav[b, c, e:e + k] = ans
+            qav[b, c, e + k], qav[b, c, e + k + 1] = V_TOKEN, 29901 % V
+            qav[b, c, e + k + 2 + F] = 2                                   # (the F slots in front of it stay 0)
+    out["text_id"].update(vaq=vaq, qav=qav)
+    out["video_start"]["vaq"] = [vs] * B
+    return out
+
+
 class SyntheticLoader:
     """A fixed-length iterable of pre-built batches (stands in for DataLoader in tests/bench)."""
 

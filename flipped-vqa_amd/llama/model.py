@@ -476,6 +476,20 @@ class Transformer(nn.Module):
             self.last_scoring.update(attribution.summarize_options(r))
         return r["individual_losses"]
 
+    @torch.no_grad()
+    def score_flipped(self, data, **kw):
+        """The answer options ranked by all three flipped tasks (fvqa/flipped.py: score_flipped, whose keywords these are — tasks,
+        weights, route, answer, events): -> its result dict, all tensors on the device, also left in `last_scoring`: per task
+        mean_t / sum_t / count_t (B, n_options) and prediction_t, total = sum_t w_t * mean_t, prediction, gold_loss (B, 3) when
+        `answer` is given, route and plan per task. The token ids of "Question" / "Video" come from the model's tokenizer."""
+        from fvqa import flipped
+        tok = getattr(self, "tokenizer", None)
+        for k, attr in (("q_token_id", "q_token_id"), ("v_token_id", "v_token_id")):
+            if k not in kw and tok is not None and hasattr(tok, attr):
+                kw[k] = int(getattr(tok, attr))
+        self.last_scoring = flipped.score_flipped(self.ensure_engine(), data, **kw)
+        return self.last_scoring
+
     def forward(self, data, inference=False):
         if inference:
             return self.inference(data)

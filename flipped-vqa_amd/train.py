@@ -120,6 +120,14 @@ _FLAGS = [
                                         "score_options(frame_attention=True): a video_mass meter — the weight the text softmax of "
                                         "the predicted option's scored rows puts on the frame keys, mean over rows, layers and "
                                         "heads (fvqa.attribution.summarize_options). Not with --contrast")),
+    ("--val_flipped", dict(action="store_true",
+                           help="multiple-choice validation (no --is_generation_task) by all three flipped tasks "
+                                "(fvqa.flipped.score_flipped): the prediction is the argmin of vqa + W_VAQ * vaq + W_QAV * qav mean "
+                                "losses per option; logs acc, acc_vqa, acc_vaq, acc_qav and the vaq / qav losses at the gold "
+                                "option. Not with --contrast or --val_frame_attention")),
+    ("--val_flipped_weights", dict(type=float, nargs=2, default=None, metavar=("W_VAQ", "W_QAV"),
+                                   help="--val_flipped: the weights of the vaq and qav means (default 1 1, as the training loss "
+                                        "sums the three)")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -134,7 +142,8 @@ class ArgumentParser(argparse.ArgumentParser):
     --gen_jump_forward (answer.py: --jump_forward) out of range or together with a decode they are not built for, and
     --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too), and
     --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it, and --val_frame_attention
-    with a validation that does not score options or scores them twice."""
+    with a validation that does not score options or scores them twice, and --val_flipped with a validation that does not
+    score options or combines their scores another way."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -195,6 +204,13 @@ class ArgumentParser(argparse.ArgumentParser):
                            "--gen_frame_attention")
             if getattr(a, "contrast", None):
                 self.error("--val_frame_attention describes one scoring pass: not with --contrast")
+        if getattr(a, "val_flipped_weights", None) is not None and not getattr(a, "val_flipped", False):
+            self.error("--val_flipped_weights W_VAQ W_QAV belongs to --val_flipped")
+        if getattr(a, "val_flipped", False):
+            if getattr(a, "is_generation_task", False):
+                self.error("--val_flipped belongs to multiple-choice validation: not with --is_generation_task")
+            if getattr(a, "contrast", None) or getattr(a, "val_frame_attention", False):
+                self.error("--val_flipped combines the three tasks' scores: not with --contrast or --val_frame_attention")
         return a
 
 
@@ -231,7 +247,12 @@ def build_loaders(args, model):
                                 max_feats=args.max_feats, max_seq_len=args.max_seq_len, batch_size=args.batch_size,
                                 vaq=args.vaq, qav=args.qav, audio=model.audio_mode,
                                 audio_len=1 if model.audio_mode == "attention" else 0)   # (one audio row per clip, as MusicAVQA hands)
-        return synth.SyntheticLoader(cfg, args.synthetic_batches, misc.get_rank(), misc.get_world_size(), pin=True), None
+        val = None
+        if getattr(args, "val_flipped", False):          # --val_flipped validates on synthetic options with all three streams
+            val = [synth.make_flipped_option_batch(cfg, 5, seed=4321 + misc.get_rank() + misc.get_world_size() * i,
+                                                   batch_size=args.val_batch_size or args.batch_size)
+                   for i in range(min(2, args.synthetic_batches))]
+        return synth.SyntheticLoader(cfg, args.synthetic_batches, misc.get_rank(), misc.get_world_size(), pin=True), val
     from dataloader import load_data          # NExT-QA / MusicAVQA readers + collate of this package (dataloader/)
     return load_data(args, model.tokenizer, split="train"), load_data(args, model.tokenizer, split="val")
 

@@ -317,6 +317,40 @@ int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, void* o_suf, c
 int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,
                      float* option_sum, int64_t* option_count, float* option_mean, int64_t* prediction, int n_seq,
                      int n_options, int seq_len, void* stream);
+/* ---- option scoring by all three flipped tasks (csrc/flipped.hip; fvqa/flipped.py score_flipped) ----
+ * fvqa_attn_suffix for suffixes of up to 64 rows: the operands, semantics and errors of fvqa_attn_suffix with 1 <= suffix_len <= 64.
+ * The query at (n, c, j) sits at position start[n] + j; it sees the cache rows [0, start[n]), rows 0..j of its own option and the
+ * adapter keys under tanh(gate1). gate2 is added on the frame keys [vs, vs + max_feats), vs = vstart[n], for query positions
+ * >= vs + max_feats wherever the window lies — in the cache, across start[n] or inside the suffix (the QAV stream's frame rows
+ * follow its answer); vs < 0: no window. Rows j >= len[n] are never loaded and written as zeros. One workgroup per (head, sample,
+ * option x tile of 32 queries). Fixed summation order, no atomics: two launches give
+ * the same bits. Writes o_suf and nothing else. */
+int fvqa_attn_suffix_wide(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                          const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t,
+                          const float* sin_t, int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim,
+                          int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream);
+/* The inputs of the suffix rows: x (n_seq*n_options*suffix_len, dim) storage type, row r = (n*n_options + c)*suffix_len + j:
+ *   j >= len[n]           zeros (a padding row);
+ *   slot && slot[r] >= 0  the bits of vf_tok[n, slot[r]] (vf_tok (n_seq, max_feats, dim), storage type): a frame row of the QAV
+ *                         stream (llama/model.py:335-336 zeroes the token row and adds the frame token);
+ *   else                  emb[ids[r]] (emb (vocab, dim)).
+ * ids (rows) int64, slot (rows) int32 or NULL (then vf_tok may be NULL), len (n_seq) int32. dim * element size % 16 == 0. */
+int fvqa_suffix_embed(const int64_t* ids, const int32_t* slot, const void* emb, const void* vf_tok, const int32_t* len, void* x,
+                      int n_seq, int n_options, int suffix_len, int dim, int vocab, int max_feats, int dtype, void* stream);
+/* The pick over the tasks' per-option means. mean_t (n_seq, n_options) fp32 and count_t (n_seq, n_options) int64 for t = vqa,
+ * vaq, qav; a task that was not requested passes NULL for both (at least one is given). Writes
+ *   total (n_seq, n_options) fp32 = sum over the given tasks of w_t * mean_t, added in the order vqa, vaq, qav to +0, each product
+ *       and each sum rounded to fp32 (no fused multiply-add);
+ *   prediction (n_seq) int64 = argmin of total over the ELIGIBLE options — those with count_t > 0 for every given task — with
+ *       fvqa_option_pick's rule: the first NaN wins, ties go to the lowest index; 0 when no option is eligible;
+ *   prediction_t (3, n_seq) int64 = the same argmin of mean_t over the options with count_t > 0 (0 when none; -1 for a task not given);
+ *   gold_loss (n_seq, 3) fp32 = mean_t[n, answer[n]] (NaN for a task not given or an answer outside [0, n_options)) when answer
+ *       (n_seq) int64 is given; answer and gold_loss are both NULL otherwise.
+ * One workgroup per sample; n_options <= 64. */
+int fvqa_flipped_pick(const float* mean_vqa, const float* mean_vaq, const float* mean_qav, const int64_t* count_vqa,
+                      const int64_t* count_vaq, const int64_t* count_qav, float w_vqa, float w_vaq, float w_qav,
+                      const int64_t* answer, float* total, int64_t* prediction, int64_t* prediction_t, float* gold_loss,
+                      int n_seq, int n_options, void* stream);
 /* The token step of the generation API (csrc/sample.hip; reference llama/generation.py:17-68 and llama/model.py:438-470): one
  * launch per generated token, one workgroup per sequence, between the LM head and the next token's first RMSNorm.
  * In: logits (n_seq, vocab) fp32, finite; u (n_seq) fp32 in [0, 1) (may be NULL when temperature == 0); emb (vocab, dim) in the
