@@ -3,14 +3,15 @@
 //
 // The O option sequences of a sample are equal up to the first answer token, and with causal attention so are their hidden
 // states: the prompt is run ONCE (the training forward, which leaves every layer's k / v in the arena = the KV cache) and
-// each option only recomputes its last T rows, the "suffix" (fvqa/score.py). Two kernels serve that:
+// each option only recomputes its last T rows, the "suffix" (fvqa/score.py). One kernel template, attn_suffix_k, behind four entries:
 //
 // fvqa_attn_suffix — Attention.forward (llama/model.py:87-128) at the suffix rows. Query row (n, c, j) sits at position
 //   start[n] + j and attends to
 //     * the cached keys / values [0, start[n]) of sample n (read, never written: O continuations share one cache),
 //     * rows 0..j of its OWN option's suffix (rotated here and rounded to the storage type, as the prefill holds them),
 //     * the A adapter keys (no RoPE, own softmax scaled by tanh(gate1[h])),
-//   with gate2[h] added on the frame keys [vs, vs+F) when the query position is >= vs+F.
+//   with gate2[h] added on the frame keys [vs, vs+F) when the query position is >= vs+F, wherever that window lies — in the
+//   cache, across start[n] or inside the suffix; vs < 0: no window.
 //   One 256-thread workgroup per (head, sample): each cached key / value row is loaded ONCE for all O*T queries of the sample
 //   (a workgroup per option would read the prompt O times). Queries are taken in tiles of 32, keys in chunks of 32 staged in
 //   LDS as fp32; a running (max, sum) per query carries the softmax across chunks — the sums run in one fixed order, there
@@ -28,6 +29,14 @@
 // fvqa_attn_suffix_mass — the same body with MASS = true (APPEND = false): o_suf bit for bit, and per query row the summary of its
 //   text softmax over the frame window (include/fvqa.h); score_options(frame_attention=True), fvqa/score.py.
 //
+// fvqa_attn_suffix_wide — the same tile with WIDE = true, for 1 <= suffix_len <= 64 (fvqa/flipped.py: a VAQ option differs at its
+//   answer and the scored question follows it, a QAV option has its frame slots behind the answer). One workgroup per (head,
+//   sample, option x tile of 32 queries): the (head, sample) workgroup would walk O * T / 32 = 10 tiles in a row at five options
+//   of 64 rows; here the tiles run side by side and the prompt's keys are read once per tile, from L2 after the first. A tile
+//   stages the suffix keys of its own option up to its last query only. The tile is written in the kernel, not in a function of
+//   its own: which products hipcc contracts into fmas in the score and value passes changes when the same text is inlined from
+//   a __device__ function, and with it the last bit of the output (profiles/suffix_refactor.log).
+//
 // fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
 //   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
 //   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
@@ -36,8 +45,63 @@
 namespace {
 using namespace fvqa_decode;
 
-#include "suffix_rows.h"                 // QT, KC, KLD, load16, rope16, store16, half_max, half_sum
-constexpr int TMAX = 16;                 // suffix rows per option
+constexpr int TMAX = 16;                 // suffix rows per option (fvqa_attn_suffix, _mass, _append)
+constexpr int TWIDE = 64;                // suffix rows per option (fvqa_attn_suffix_wide)
+constexpr int QT = 32;                   // queries per tile
+constexpr int KC = 32;                   // keys per chunk
+constexpr int KLD = DH + 4;              // LDS row stride of q / k (floats): 16-byte rows, lanes of a key column on distinct banks
+
+// 16 consecutive head dims [d0, d0 + 16) of a row as floats
+template <typename T> __device__ __forceinline__ void load16(const T* p, float (&v)[16]);
+template <> __device__ __forceinline__ void load16<bf16_t>(const bf16_t* p, float (&v)[16]) {
+  float a[8], b[8];
+  Chunk<bf16_t>::load(p, a);
+  Chunk<bf16_t>::load(p + 8, b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v[e] = a[e]; v[8 + e] = b[e]; }
+}
+template <> __device__ __forceinline__ void load16<float>(const float* p, float (&v)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    float a[4];
+    Chunk<float>::load(p + 4 * u, a);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[4 * u + e] = a[e];
+  }
+}
+
+// rotate 16 head dims starting at d0 (a multiple of 16) of a row at position p, rounded to the storage type
+template <typename T>
+__device__ __forceinline__ void rope16(float (&v)[16], const float* cs, const float* sn, int p, int d0) {
+  const float4* cp = reinterpret_cast<const float4*>(cs + (size_t)p * HP + d0 / 2);
+  const float4* sp = reinterpret_cast<const float4*>(sn + (size_t)p * HP + d0 / 2);
+  const float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+  const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float a = v[2 * e], b = v[2 * e + 1];
+    v[2 * e] = round_to<T>(a * c[e] - b * s[e]);
+    v[2 * e + 1] = round_to<T>(a * s[e] + b * c[e]);
+  }
+}
+
+__device__ __forceinline__ void store16(float* dst, const float (&v)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    *reinterpret_cast<float4*>(dst + 4 * u) = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+}
+
+__device__ __forceinline__ float half_max(float v) {       // over the 32 lanes of an aligned half wave
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // RoPE of one pair (a, b) of a key that goes into the cache, operation by operation what fvqa_attn_decode's store of the new
 // token's key evaluates (csrc/attn_decode_body.h: `a * c - b * s`, `a * s + b * c`, as hipcc contracts them there: the second
@@ -80,7 +144,7 @@ constexpr int MLD = 72;                  // LDS row stride of the summary accumu
 // text softmax has closed. Thread (q = tid / 8, e = tid % 8 + 8 m) owns entry e of query q from the first chunk to the store.
 // false compiles none of it; the summary's pointer is an operand of the MASS instantiations only (M: `float` there, an empty
 // pack otherwise), so the other kernels keep their operands and their code.
-template <typename T, bool APPEND = false, bool MASS = false, typename... M>
+template <typename T, bool APPEND = false, bool MASS = false, bool WIDE = false, typename... M>
 __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, const T* __restrict__ cache,
                                                      T* __restrict__ o_suf, const float* __restrict__ gate1,
                                                      const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
@@ -120,13 +184,38 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
   // value role: head dim vd, queries 16*qh .. 16*qh + 15
   const int vd = tid & 127, qh = tid >> 7;
 
-  for (int q0 = 0; q0 < NQ; q0 += QT) {
+  // The sample's O * Tn suffix rows are numbered row-major ("flattened" row r is suffix row r % Tn of option r / Tn). A tile is
+  // 32 flattened rows from q0, its queries those below q_end; the flattened rows [s_lo, s_hi) are staged as its suffix keys, in
+  // chunks of KC from s_lo. A query sees a suffix key iff both are rows of one option, the key's suffix row is not behind the
+  // query's and is < len.
+  //   narrow: the workgroup walks the tiles of all NQ rows; a tile may run across options and stages the options it touches.
+  //   WIDE: the workgroup has the one tile blockIdx.z names, 32 rows from suffix row w_j0 of the option whose first row is w_lo,
+  //         and stages that option's rows up to its last query: suffix rows are differences, the option test is compiled out.
+  int w_lo = 0, w_j0 = 0;
+  if constexpr (WIDE) {
+    const int NT = (Tn + QT - 1) / QT;
+    w_lo = (blockIdx.z / NT) * Tn;
+    w_j0 = (blockIdx.z % NT) * QT;
+    if (w_j0 >= len) {                                   // a tile of padding rows (the whole workgroup takes this branch)
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int j = w_j0 + 16 * qh + u;
+        if (j < Tn) o_suf[((size_t)n * NQ + w_lo + j) * D + h * DH + vd] = from_f32<T>(0.f);
+      }
+      return;
+    }
+  }
+  const auto row_j = [&](int r) { return WIDE ? r - w_lo : r % Tn; };                  // a flattened row's suffix row,
+  const auto row_c = [&](int r) { return WIDE ? 0 : r / Tn; };                         // its option,
+  const auto row_first = [&](int r) { return WIDE ? w_lo : (r / Tn) * Tn; };           // its option's first row
+  const int q_first = WIDE ? w_lo + w_j0 : 0, q_last = WIDE ? q_first + 1 : NQ, q_end = WIDE ? w_lo + Tn : NQ;
+  for (int q0 = q_first; q0 < q_last; q0 += QT) {
     // ---- the tile's queries
     {
       const int qi = q0 + srow;
-      const int j = qi % Tn;
+      const int j = row_j(qi);
       float v[16];
-      if (qi < NQ && j < len) {
+      if (qi < q_end && j < len) {
         load16<T>(sufn + (size_t)qi * ld + sd0, v);
         rope16<T>(v, cs, sn, start + j, sd0);
       } else {
@@ -147,14 +236,14 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int qi = q0 + 4 * qg + u;
-      qc[u] = qi / Tn;
-      qj[u] = qi % Tn;
-      qok[u] = qi < NQ && qj[u] < len;
+      qc[u] = row_c(qi);
+      qj[u] = row_j(qi);
+      qok[u] = qi < q_end && qj[u] < len;
     }
-    // the suffix keys a query of this tile can see: the rows of the options the tile touches
-    const int s_lo = (q0 / Tn) * Tn;
+    const int s_lo = row_first(q0);
     int s_hi = ((q0 + QT - 1) / Tn + 1) * Tn;
     if (s_hi > NQ) s_hi = NQ;
+    if constexpr (WIDE) s_hi = w_lo + (w_j0 + QT < len ? w_j0 + QT : len);
     const int n_pre = (start + KC - 1) / KC, n_suf = (s_hi - s_lo + KC - 1) / KC;
     // chunks: [0, n_pre) cached prompt keys, [n_pre, n_pre + n_suf) suffix keys, then the adapter keys (own softmax)
     for (int ch = 0; ch <= n_pre + n_suf; ++ch) {
@@ -175,7 +264,7 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         if (kind == 0) {
           if (ki < start) { row = seq + (size_t)ki * ld; pos = ki; rot = !cache_rot; }
         } else if (kind == 1) {
-          const int j = ki % Tn;
+          const int j = row_j(ki);
           if (ki < s_hi && j < len) { row = sufn + (size_t)ki * ld; pos = start + j; rot = true; }
         } else if (ki < A) {
           row = arow + (size_t)ki * ld;
@@ -225,8 +314,8 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       if (kind == 0) {
         kok = ki < start;
       } else if (kind == 1) {
-        kc = ki / Tn;
-        kj = ki % Tn;
+        kc = row_c(ki);
+        kj = row_j(ki);
         kpos = start + kj;
         kok = ki < s_hi && kj < len;
       } else {
@@ -270,11 +359,11 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         // ---- the summary: Ms[q][e] = Ms[q][e] * alpha[q] + the chunk's weight on entry e; closed and stored in the adapter chunk
         const int q = srow, qi = q0 + q;
         const float al = alpha[q];
-        const int k1 = (qi / Tn) * Tn - start - k0;        // suffix chunk: the key at position kpos of the query's own option
+        const int k1 = row_first(qi) - start - k0;        // suffix chunk: the key at position kpos of the query's own option
         for (int e = tid & 7; e < F + 2; e += 8) {
           const float m = Ms[q][e] * al;
           if (kind == 2) {
-            if (qi < NQ) mass[(((size_t)n * NQ + qi) * H + h) * (F + 2) + e] = qi % Tn < len ? m : 0.f;
+            if (qi < q_end) mass[(((size_t)n * NQ + qi) * H + h) * (F + 2) + e] = row_j(qi) < len ? m : 0.f;
           } else {
             float add = e == F ? fb[q][0] : fb[q][1];
             if (e < F) {
@@ -310,12 +399,12 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int qi = q0 + 16 * qh + u;
-      if (qi < NQ) {
-        const bool ok = qi % Tn < len;
+      if (qi < q_end) {
+        const bool ok = row_j(qi) < len;
         o_suf[((size_t)n * NQ + qi) * D + h * DH + vd] = from_f32<T>(ok ? acc[u] : 0.f);
       }
     }
-    __syncthreads();                                     // Qs / mrun are rewritten by the next tile
+    if constexpr (!WIDE) __syncthreads();                // Qs / mrun are rewritten by the next tile
   }
 }
 
@@ -366,20 +455,18 @@ __global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ r
   }
 }
 
-}  // namespace
-
-namespace {
-template <bool APPEND, bool MASS = false>
+// validates and launches the four entries: WIDE differs in the row limit and the grid only
+template <bool APPEND, bool MASS = false, bool WIDE = false>
 int suffix_launch(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
                   const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t, const float* sin_t,
                   int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim, int adapter_len,
                   int max_feats, int cache_rotated, int dtype, void* stream, float* mass = nullptr) {
-  static_assert(!(APPEND && MASS), "no instantiation writes the cache and the summary");
+  static_assert(APPEND + MASS + WIDE <= 1, "one switch at a time");
   if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !len || !cos_t || !sin_t)
     return FVQA_EINVAL;
   if (MASS && !mass) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > TMAX || seq_len <= 0 || n_heads <= 0 ||
+  if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > (WIDE ? TWIDE : TMAX) || seq_len <= 0 || n_heads <= 0 ||
       head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
     return FVQA_ESHAPE;
   if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || n_options > 4096) return FVQA_ESHAPE;
@@ -387,31 +474,25 @@ int suffix_launch(const void* qkv_suf, const void* qkv_cache, void* o_suf, const
   if (MASS && max_feats > MFMAX) return FVQA_ESHAPE;     // (the accumulators' LDS rows)
   if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
   if (MASS && ((uintptr_t)mass & 3)) return FVQA_EALIGN;
-  dim3 grid(n_heads, n_seq), block(256);
+  const int tiles = (suffix_len + QT - 1) / QT;          // (WIDE: n_options * tiles <= 8192, inside the grid's third axis)
+  const dim3 grid(n_heads, n_seq, WIDE ? n_options * tiles : 1), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if constexpr (MASS) {
-    if (dtype == FVQA_H16)
-      hipLaunchKernelGGL((attn_suffix_k<bf16_t, false, true, float>), grid, block, 0, st, (const bf16_t*)qkv_suf,
-                         (const bf16_t*)qkv_cache, (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
-                         n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats, cache_rotated, mass);
-    else
-      hipLaunchKernelGGL((attn_suffix_k<float, false, true, float>), grid, block, 0, st, (const float*)qkv_suf,
-                         (const float*)qkv_cache, (float*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
-                         n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats, cache_rotated, mass);
-    FVQA_CHECK_LAUNCH();
-    return FVQA_OK;
-  }
-  if (dtype == FVQA_H16)
-    hipLaunchKernelGGL((attn_suffix_k<bf16_t, APPEND>), grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
-                       (bf16_t*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
-                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
-  else
-    hipLaunchKernelGGL((attn_suffix_k<float, APPEND>), grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
-                       (float*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options, suffix_len,
-                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
+  const auto launch = [&](auto* t) {                     // t: the storage type
+    using T = std::remove_pointer_t<decltype(t)>;
+    const auto kernel = [&](auto k, auto... more) {
+      hipLaunchKernelGGL(k, grid, block, 0, st, (const T*)qkv_suf, (const T*)qkv_cache, (T*)o_suf, gate1, gate2, vstart, start,
+                         len, cos_t, sin_t, n_seq, n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats,
+                         cache_rotated, more...);
+    };
+    if constexpr (MASS) kernel(attn_suffix_k<T, false, true, false, float>, mass);
+    else kernel(attn_suffix_k<T, APPEND, false, WIDE>);
+  };
+  if (dtype == FVQA_H16) launch((bf16_t*)nullptr);
+  else launch((float*)nullptr);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
+
 }  // namespace
 
 extern "C" int fvqa_attn_suffix(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
@@ -440,6 +521,16 @@ extern "C" int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, voi
                                        void* stream) {
   return suffix_launch<true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, 1, suffix_len,
                              seq_len, n_heads, head_dim, adapter_len, max_feats, cache_rotated, dtype, stream);
+}
+
+extern "C" int fvqa_attn_suffix_wide(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
+                                     const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* len,
+                                     const float* cos_t, const float* sin_t, int n_seq, int n_options, int suffix_len,
+                                     int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated,
+                                     int dtype, void* stream) {
+  return suffix_launch<false, false, true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
+                                           n_options, suffix_len, seq_len, n_heads, head_dim, adapter_len, max_feats,
+                                           cache_rotated, dtype, stream);
 }
 
 extern "C" int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,

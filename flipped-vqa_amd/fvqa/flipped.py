@@ -25,8 +25,7 @@ from typing import Optional
 
 import torch
 
-from . import ops, rowpass, score, scored
-from .generate import streams_only
+from . import ops, score
 
 TASKS = ("vqa", "vaq", "qav")
 # The route a task takes when neither `route` nor FVQA_SCORE names one: shared for all three — measured faster than dense in
@@ -124,118 +123,66 @@ def _route(task: str, plan, route: Optional[str]) -> str:
     return want if plan.shared else "dense"
 
 
-def _sums(eng, rowloss, n_rows: int, seq, t, B: int, O: int, S: int, rows_at=None):
-    """Per-option sums (B, O) fp32 of the scored rows' losses through fvqa_option_pick's fixed-order reduction: rowloss holds
-    n_rows rows, row rows_at[i] (default i) is row t[i] of option sequence seq[i] = n * O + c."""
-    row_map = torch.full((n_rows,), -1, dtype=torch.int64)
-    at = torch.arange(seq.numel()) if rows_at is None else rows_at
-    row_map[at] = seq * (S - 1) + t
-    return ops.option_pick(rowloss, row_map.to(torch.int32).to(eng.device, non_blocking=True), n_rows, B, O, S)[1]
-
-
 def _dense(eng, data, task, ids_h, lab_h, rows, plan, events):
     """The B * O option sequences as one stream of `task` through the existing forward -> per-option sums (B, O)."""
     B, O, S = ids_h.shape
-    flat = ids_h.reshape(B * O, 1, S)
-    sub = score._front_inputs(data, O)
+    qav = task == "qav"
     vs = [int(v) for v in data["video_start"].get(task, data["video_start"]["vqa"])]
-    sub.update({"text_id": {"vqa": flat, task: flat}, "label": {task: lab_h.reshape(B * O, 1, S)},
-                "video_start": {"vqa": [vs[0]] * (B * O), "vaq": [vs[0]] * (B * O)}})
-    if task == "qav":
-        sub["video_index"] = {"qav": rows["video_index"]["qav"].reshape(B * O, -1)}
     done = score._mark(events, f"{task} dense forward")
-    with streams_only(eng, [task], "_score_arena", "scored"):
-        eng.forward(sub)
-        tl, ar = eng.last_scored, eng.saved["ar"]
-        eng.saved = None                                   # (no backward follows)
-    n, c, t = plan.rows.unbind(1)                          # the same row-major order as scored.lists_of over (B*O, S)
-    if task == "qav":                                      # the QAV head leaves its losses at the dense rows
-        out = _sums(eng, ar.rowloss[: B * O * S], B * O * S, n * O + c, t, B, O, S, rows_at=(n * O + c) * S + t)
+    tl, ar = score._dense_pass(eng, data, task, ids_h, lab_h, vs, rows["video_index"]["qav"] if qav else None)
+    if qav:                                                # the QAV head leaves its losses at the dense rows
+        n, c, t = plan.rows.unbind(1)
+        out = score._pick(eng, ar.rowloss[: B * O * S], B * O * S, (n * O + c) * S + t, (n * O + c) * (S - 1) + t, B, O, S)[1]
     else:
-        o0, m_rows = tl.segs[0]
-        assert tl.counts[0] == n.numel()
-        out = _sums(eng, ar.rowloss_c[o0:o0 + m_rows], m_rows, n * O + c, t, B, O, S)
+        out = score._dense_pick(eng, tl, ar, plan, B, O, S)[1]
     done()
     return out
 
 
 def _shared(eng, data, task, ids_h, lab_h, rows, plan, events):
-    """The prompt pass once (option 0, no scored row), then the suffix rows of every option -> per-option sums (B, O)."""
-    pk, dev, m_ = eng.pack, eng.device, eng.model
+    """The prompt pass once (option 0, no scored row; for QAV its own frame rows lie at or behind start, no prompt row sees them),
+    then the suffix rows of every option -> per-option sums (B, O)."""
+    dev = eng.device
     B, O, S = ids_h.shape
     qav = task == "qav"
     # QAV: the head scores row j against the label of row j + 1 and never its last row: one padding row behind the suffix
     T = plan.T + (1 if qav else 0)
     start, length = plan.start, plan.length
-    sub = score._front_inputs(data)
-    ids0 = ids_h[:, 0:1]
-    vs = [int(v) for v in data["video_start"].get(task, data["video_start"]["vqa"])]
-    sub.update({"text_id": {"vqa": ids0, task: ids0}, "video_start": {"vqa": vs, "vaq": vs},
-                "label": {task: torch.full((B, 1, S), -1 if qav else 0, dtype=torch.int64)}})
-    if qav:       # option 0's own frame rows: they lie at or behind start, no prompt row sees them
-        sub["video_index"] = {"qav": rows["video_index"]["qav"][:, 0]}
-    # ---- the suffix rows (host integers, staged while the prompt pass runs)
-    j = torch.arange(T)
-    live = (j[None, :] < length[:, None])[:, None, :].expand(B, O, T)
-    pos = (start[:, None] + j[None, :]).clamp(max=S - 1)[:, None, :].expand(B, O, T)     # (B, O, T)
-    ids_suf = torch.where(live, ids_h.gather(2, pos), torch.zeros_like(pos))
+    live, pos, ids_suf = score._suffix_ids(plan, ids_h, T)
     slot = None
     if qav:
         f = pos - rows["prefix_index"]["qav"][..., None]
         slot = torch.where(live & (f >= 0) & (f < eng.F), f, torch.full_like(f, -1)).to(torch.int32)
-    n, c, t = plan.rows.unbind(1)
-    M = int(n.numel())
-    done = score._mark(events, f"{task} prompt pass")
-    with streams_only(eng, [task], "_score_arena", "scored"):
-        eng.forward(sub)
-        ar, vstart, vf_raw = eng.saved["ar"], eng.saved["vstart"], eng.saved["vf_raw"]
-        eng.saved = None                                   # (no backward follows)
-    done()
+    vs = [int(v) for v in data["video_start"].get(task, data["video_start"]["vqa"])]
+    saved = score._prompt_pass(eng, data, task, ids_h, vs, events, f"{task} prompt pass",
+                               rows["video_index"]["qav"][:, 0] if qav else None)
     done = score._mark(events, f"{task} suffix pass")
     mv = lambda x: x.to(dev, non_blocking=True)            # noqa: E731
     e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
-    start_d, len_d = mv(start.to(torch.int32)), mv(length.to(torch.int32))
+    start_d, len_d = score._suffix_lengths(eng, plan)
     R = B * O * T
     x = e(R, eng.D)
     vf_tok = eng._front_fwd(data, B)[1] if qav else None   # (the frame tokens once more: the forward keeps vf_raw only)
-    ops.suffix_embed(mv(ids_suf.reshape(-1).contiguous()), None if slot is None else mv(slot.reshape(-1).contiguous()), pk.emb,
-                     vf_tok, len_d, x, B, O, T, eng.F)
-    b = rowpass.buffers(eng, R, xin=False, lg=False)
-    rotated = rowpass.cache_rotated(eng)
-
-    def attn(i, qkv, o):                                   # several continuations read one cached prompt, nothing is written
-        ops.attn_suffix_wide(qkv, ar.qkv[i], o, *m_.gate_views(i), vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H,
-                             eng.Dh, eng.A, eng.F, cache_rotated=rotated)
-    x = rowpass.layers(eng, b, attn, x)
-    f32 = torch.float32
-    if qav:
+    ops.suffix_embed(mv(ids_suf.reshape(-1).contiguous()), None if slot is None else mv(slot.reshape(-1).contiguous()),
+                     eng.pack.emb, vf_tok, len_d, x, B, O, T, eng.F)
+    x = score._suffix_layers(eng, saved, start_d, len_d, x, B, O, T, S, wide=True)
+    if not qav:
+        out = score._scored_head(eng, x, plan, lab_h, B, O, T, S)[1]
+    else:
         # ---- the QAV head on the suffix rows: B * O "sequences" of T rows, each option against its sample's frames
+        f32 = torch.float32
         xn = e(R, eng.D)
-        ops.rmsnorm_fwd(x, pk.norm, xn, None, eng.eps, rows=R)
+        ops.rmsnorm_fwd(x, eng.pack.norm, xn, None, eng.eps, rows=R)
         # row j reads the label of row j + 1: the labels of positions start .. start + length (<= S - 1: a scored row is <= S - 2)
-        has_lab = (j[None, :] <= length[:, None])[:, None, :].expand(B, O, T)
+        has_lab = (torch.arange(T)[None, :] <= length[:, None])[:, None, :].expand(B, O, T)
         lab_suf = torch.where(has_lab, lab_h.gather(2, pos), torch.full_like(pos, -1))
-        vf_rep = vf_raw.view(B, eng.F, eng.D).repeat_interleave(O, 0).contiguous()
+        vf_rep = saved["vf_raw"].view(B, eng.F, eng.D).repeat_interleave(O, 0).contiguous()
         probs, rowloss = e(R * eng.F, dtype=f32), torch.zeros(R, dtype=f32, device=dev)
         loss_sum = torch.zeros(2, dtype=f32, device=dev)
         ops.qav_head_fwd(xn, vf_rep, mv(lab_suf.reshape(B * O, T).contiguous()), probs, rowloss, loss_sum, B * O, T, eng.D, eng.F,
                          eng.tau)
-        out = _sums(eng, rowloss, R, n * O + c, t - start[n], B, O, T, rows_at=(n * O + c) * T + (t - start[n]))
-    else:
-        # ---- the scored rows: final norm, LM head, cross-entropy (one "sequence" of `m_rows` positions, fvqa/scored.py)
-        m_rows = scored.rows_of(M)
-        gidx = torch.zeros(m_rows, dtype=torch.int32)
-        gidx[:M] = ((n * O + c) * T + (t - start[n])).to(torch.int32)
-        lab_shift = torch.zeros(m_rows, dtype=torch.int64)
-        lab_shift[1:M + 1] = lab_h[n, c, t + 1]
-        xg, xf = e(m_rows, eng.D), e(m_rows, eng.D)
-        lg = e(m_rows, eng.V, dtype=f32)
-        lse, rowloss = e(m_rows, dtype=f32), e(m_rows, dtype=f32)
-        loss_sum = torch.zeros(2, dtype=f32, device=dev)
-        ops.gather_rows(x, xg, ops.row_segs([mv(gidx)], [0, m_rows], R))
-        rowpass.head(eng, xg, xf, lg)
-        ops.ce_fwd(lg, mv(lab_shift), lse, rowloss, loss_sum, 1, m_rows, eng.V, 0)
-        out = _sums(eng, rowloss, m_rows, n * O + c, t, B, O, S)
+        n, c, t = plan.rows.unbind(1)
+        out = score._pick(eng, rowloss, R, (n * O + c) * T + (t - start[n]), (n * O + c) * (T - 1) + (t - start[n]), B, O, T)[1]
     done()
     return out
 

@@ -586,7 +586,7 @@ def attn_row_mass(qkv, seq, pos, mass, gate2, vstart, rope, n_seq, S, H, Dh, A, 
 
 SUFFIX_MAX = 16          # suffix rows per option fvqa_attn_suffix takes (csrc/score.hip TMAX)
 SUFFIX_MASS_FEATS = 64   # max_feats fvqa_attn_suffix_mass takes (csrc/score.hip MFMAX: the accumulators' LDS rows)
-SUFFIX_WIDE_MAX = 64     # suffix rows per option fvqa_attn_suffix_wide takes (csrc/flipped.hip TWIDE)
+SUFFIX_WIDE_MAX = 64     # suffix rows per option fvqa_attn_suffix_wide takes (csrc/score.hip TWIDE)
 
 
 def _attn_suffix(what, qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, length, rope, n_seq, n_options, T, S, H, Dh, A, F,

@@ -34,7 +34,7 @@ from typing import Optional
 import torch
 
 from . import ops, rowpass, scored
-from .generate import vqa_stream_only
+from .generate import streams_only
 
 ROUTES = ("shared", "dense")
 DEFAULT_ROUTE = "shared"
@@ -117,9 +117,12 @@ def _front_inputs(data: dict, repeat: int = 1) -> dict:
     return sub
 
 
-def _pick(eng, rowloss, row_map_host, n_rows, B, O, S):
-    row_map = row_map_host.to(torch.int32).to(eng.device, non_blocking=True)
-    return ops.option_pick(rowloss, row_map, n_rows, B, O, S)
+def _pick(eng, rowloss, n_rows: int, at, entry, B: int, O: int, S: int):
+    """fvqa_option_pick over rowloss (n_rows fp32 losses): its rows `at` (a slice or an int64 tensor; every other row is skipped)
+    land at the entries `entry` = (n * O + c) * (S - 1) + t of individual_losses (B, O, S - 1) -> ops.option_pick's five."""
+    row_map = torch.full((n_rows,), -1, dtype=torch.int64)
+    row_map[at] = entry
+    return ops.option_pick(rowloss, row_map.to(torch.int32).to(eng.device, non_blocking=True), n_rows, B, O, S)
 
 
 def contrast_pick(mean_pos: torch.Tensor, mean_neg: torch.Tensor, count: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -205,6 +208,17 @@ def _suffix_rows(plan: OptionPlan, O: int):
     return n * O + c, plan.start[n] + j, (n * O + c) * T + j
 
 
+def _suffix_ids(plan: OptionPlan, ids_h, T: int):
+    """Host integers of the suffix rows, (B, O, T) each: pos = start[n] + j (kept inside the sequence), ids = the token there, 0 at
+    the padding rows j >= length[n]; and live (B, 1, T): j < length[n]. T >= plan.T."""
+    B, O, S = ids_h.shape
+    j = torch.arange(T)
+    pos = (plan.start[:, None] + j[None, :]).clamp(max=S - 1)[:, None, :].expand(B, O, T)
+    ids_suf = ids_h.gather(2, pos)
+    live = (j[None, :] < plan.length[:, None])[:, None, :]
+    return live, pos, torch.where(live, ids_suf, torch.zeros_like(ids_suf))
+
+
 def _dense_mass(eng, plan: OptionPlan, B: int, O: int, S: int) -> torch.Tensor:
     """"frame_attention" of the dense form, from the arena its forward left (eng.saved): (B, O, T, L, H, F + 2)."""
     from . import attribution
@@ -218,86 +232,121 @@ def _dense_mass(eng, plan: OptionPlan, B: int, O: int, S: int) -> torch.Tensor:
     return out.view(B, O, T, eng.L, eng.H, eng.F + 2)
 
 
-def _dense(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
+def _dense_pass(eng, data, task, ids_h, lab_h, vs_list, video_index=None, fa=None, plan=None):
+    """The B * O option sequences as ONE stream of `task` through the existing forward (tail rows: the last layer's second half
+    and the head on scored rows) -> (eng.last_scored, the arena)."""
     B, O, S = ids_h.shape
+    flat = ids_h.reshape(B * O, 1, S)
     sub = _front_inputs(data, O)
-    sub.update({"text_id": {"vqa": ids_h.reshape(B * O, 1, S)}, "label": {"vqa": lab_h.reshape(B * O, 1, S)},
+    sub.update({"text_id": {"vqa": flat, task: flat}, "label": {task: lab_h.reshape(B * O, 1, S)},
                 "video_start": {"vqa": [vs_list[0]] * (B * O), "vaq": [vs_list[0]] * (B * O)}})
-    done = _mark(events, "dense forward")
-    with vqa_stream_only(eng, "_score_arena", "scored"):
-        eng.forward(sub)                                   # tail rows: the last layer's second half and the head on scored rows
+    if video_index is not None:
+        sub["video_index"] = {"qav": video_index.reshape(B * O, -1)}
+    with streams_only(eng, [task], "_score_arena", "scored"):
+        eng.forward(sub)
         tl, ar = eng.last_scored, eng.saved["ar"]
         if fa is not None:
             fa["frame_attention"] = _dense_mass(eng, plan, B, O, S)
         eng.saved = None                                   # (no backward follows)
-    done()
+    return tl, ar
+
+
+def _dense_pick(eng, tl, ar, plan, B: int, O: int, S: int):
+    """The dense forward's compact scored rows -> ops.option_pick's five."""
     o0, rows = tl.segs[0]
-    m = tl.counts[0]
     n, c, t = plan.rows.unbind(1)                          # the same row-major order as scored.lists_of over (B*O, S)
-    assert m == n.numel()
-    row_map = torch.full((rows,), -1, dtype=torch.int64)
-    row_map[:m] = (n * O + c) * (S - 1) + t
-    return _pick(eng, ar.rowloss_c[o0:o0 + rows], row_map, rows, B, O, S)
+    assert tl.counts[0] == n.numel()
+    return _pick(eng, ar.rowloss_c[o0:o0 + rows], rows, slice(0, n.numel()), (n * O + c) * (S - 1) + t, B, O, S)
 
 
-def _shared(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
-    m_, pk, dev = eng.model, eng.pack, eng.device
+def _dense(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
     B, O, S = ids_h.shape
-    T = plan.T
-    # ---- the prompt pass: option 0, no scored row (its labels are all ignored: the head sees pad rows only)
+    done = _mark(events, "dense forward")
+    tl, ar = _dense_pass(eng, data, "vqa", ids_h, lab_h, vs_list, fa=fa, plan=plan)
+    done()
+    return _dense_pick(eng, tl, ar, plan, B, O, S)
+
+
+def _prompt_pass(eng, data, task, ids_h, vs_list, events, name, video_index=None) -> dict:
+    """The prompt pass: option 0 of every sample as one stream of `task`, no scored row (its labels are all ignored: the head sees
+    pad rows only) -> what the forward saved: ar (every layer's k / v stay in the arena = the KV cache), vstart, vf_raw."""
+    B, _, S = ids_h.shape
+    ids0 = ids_h[:, 0:1]
     sub = _front_inputs(data)
-    sub.update({"text_id": {"vqa": ids_h[:, 0:1]}, "label": {"vqa": torch.zeros(B, 1, S, dtype=torch.int64)},
-                "video_start": {"vqa": vs_list, "vaq": vs_list}})
-    # ---- the suffix rows (host integers, staged while the prompt pass runs)
-    start, length = plan.start, plan.length
-    j = torch.arange(T)
-    pos = (start[:, None] + j[None, :]).clamp(max=S - 1)                                   # (B, T)
-    ids_suf = ids_h.gather(2, pos[:, None, :].expand(B, O, T))
-    ids_suf = torch.where((j[None, :] < length[:, None])[:, None, :], ids_suf, torch.zeros_like(ids_suf))
+    sub.update({"text_id": {"vqa": ids0, task: ids0}, "video_start": {"vqa": vs_list, "vaq": vs_list},
+                "label": {task: torch.full((B, 1, S), -1 if task == "qav" else 0, dtype=torch.int64)}})
+    if video_index is not None:
+        sub["video_index"] = {"qav": video_index}
+    done = _mark(events, name)
+    with streams_only(eng, [task], "_score_arena", "scored"):
+        eng.forward(sub)
+        saved, eng.saved = eng.saved, None                 # (no backward follows)
+    done()
+    return saved
+
+
+def _suffix_lengths(eng, plan: OptionPlan):
+    """plan.start and plan.length as the suffix kernels take them: (B,) int32 on the device."""
+    mv = lambda t: t.to(eng.device, non_blocking=True)     # noqa: E731
+    return mv(plan.start.to(torch.int32)), mv(plan.length.to(torch.int32))
+
+
+def _suffix_layers(eng, saved: dict, start_d, len_d, x, B: int, O: int, T: int, S: int, *, wide: bool = False, mass=None):
+    """x (B * O * T, D), the suffix rows' inputs, through the L layers against the cache the prompt pass left (several continuations
+    read one cached prompt, nothing is written) -> the last layer's output. The one place that picks the suffix attention:
+    ops.attn_suffix (T <= ops.SUFFIX_MAX), ops.attn_suffix_wide (wide: T <= ops.SUFFIX_WIDE_MAX) or ops.attn_suffix_mass (mass
+    (L, rows, H, F + 2) fp32: the same attention, each layer writes its slice of the frame-attention summary)."""
+    ar, m_ = saved["ar"], eng.model
+    b = rowpass.buffers(eng, B * O * T, xin=False, lg=False)
+    rotated = rowpass.cache_rotated(eng)
+
+    def attn(i, qkv, o):
+        rest = (*m_.gate_views(i), saved["vstart"], start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H, eng.Dh, eng.A, eng.F)
+        if mass is not None:
+            ops.attn_suffix_mass(qkv, ar.qkv[i], o, mass[i], *rest, cache_rotated=rotated)
+        else:
+            (ops.attn_suffix_wide if wide else ops.attn_suffix)(qkv, ar.qkv[i], o, *rest, cache_rotated=rotated)
+    return rowpass.layers(eng, b, attn, x)
+
+
+def _scored_head(eng, x, plan: OptionPlan, lab_h, B: int, O: int, T: int, S: int):
+    """The scored rows of x (B * O * T, D): gather -> final norm -> LM head -> cross-entropy (one "sequence" of `rows` positions,
+    fvqa/scored.py) -> ops.option_pick's five."""
+    dev = eng.device
+    mv = lambda t: t.to(dev, non_blocking=True)            # noqa: E731
+    e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
     n, c, t = plan.rows.unbind(1)
     M = int(n.numel())
     rows = scored.rows_of(M)
     gidx = torch.zeros(rows, dtype=torch.int32)
-    gidx[:M] = ((n * O + c) * T + (t - start[n])).to(torch.int32)
+    gidx[:M] = ((n * O + c) * T + (t - plan.start[n])).to(torch.int32)
     lab_shift = torch.zeros(rows, dtype=torch.int64)
     lab_shift[1:M + 1] = lab_h[n, c, t + 1]
-    row_map = torch.full((rows,), -1, dtype=torch.int64)
-    row_map[:M] = (n * O + c) * (S - 1) + t
-    done = _mark(events, "prompt pass")
-    with vqa_stream_only(eng, "_score_arena", "scored"):
-        eng.forward(sub)
-        ar, vstart = eng.saved["ar"], eng.saved["vstart"]
-        eng.saved = None                                   # (no backward follows)
-    done()
-    done = _mark(events, "suffix pass")
-    mv = lambda x: x.to(dev, non_blocking=True)            # noqa: E731
-    start_d, len_d = mv(start.to(torch.int32)), mv(length.to(torch.int32))
-    R = B * O * T
-    x = pk.emb[mv(ids_suf.reshape(-1))].contiguous()       # token embeddings: the planner keeps frame slots out of a suffix
-    b = rowpass.buffers(eng, R, xin=False, lg=False)
-    rotated = rowpass.cache_rotated(eng)
-
-    # frame_attention: the same attention, each layer writes its slice of the summary
-    mass = None if fa is None else torch.empty(eng.L, R, eng.H, eng.F + 2, dtype=torch.float32, device=dev)
-
-    def attn(i, qkv, o):                                   # several continuations read one cached prompt, nothing is written
-        rest = (*m_.gate_views(i), vstart, start_d, len_d, (eng.cos, eng.sin), B, O, T, S, eng.H, eng.Dh, eng.A, eng.F)
-        if mass is None:
-            ops.attn_suffix(qkv, ar.qkv[i], o, *rest, cache_rotated=rotated)
-        else:
-            ops.attn_suffix_mass(qkv, ar.qkv[i], o, mass[i], *rest, cache_rotated=rotated)
-    x = rowpass.layers(eng, b, attn, x)
-    if fa is not None:
-        fa["frame_attention"] = mass.permute(1, 0, 2, 3).reshape(B, O, T, eng.L, eng.H, eng.F + 2)
-    # ---- the scored rows: final norm, LM head, cross-entropy (one "sequence" of `rows` positions, fvqa/scored.py)
-    e = lambda *s, dtype=eng.dtype: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
     xg, xf = e(rows, eng.D), e(rows, eng.D)
     lg = e(rows, eng.V, dtype=torch.float32)
     lse, rowloss = e(rows, dtype=torch.float32), e(rows, dtype=torch.float32)
     loss_sum = torch.zeros(2, dtype=torch.float32, device=dev)
-    ops.gather_rows(x, xg, ops.row_segs([mv(gidx)], [0, rows], R))
+    ops.gather_rows(x, xg, ops.row_segs([mv(gidx)], [0, rows], B * O * T))
     rowpass.head(eng, xg, xf, lg)
     ops.ce_fwd(lg, mv(lab_shift), lse, rowloss, loss_sum, 1, rows, eng.V, 0)
-    out = _pick(eng, rowloss, row_map, rows, B, O, S)
+    return _pick(eng, rowloss, rows, slice(0, M), (n * O + c) * (S - 1) + t, B, O, S)
+
+
+def _shared(eng, data, ids_h, lab_h, vs_list, plan, events, fa=None):
+    dev = eng.device
+    B, O, S = ids_h.shape
+    T = plan.T
+    ids_suf = _suffix_ids(plan, ids_h, T)[2]               # (host integers, staged in front of the prompt pass)
+    saved = _prompt_pass(eng, data, "vqa", ids_h, vs_list, events, "prompt pass")
+    done = _mark(events, "suffix pass")
+    start_d, len_d = _suffix_lengths(eng, plan)
+    R = B * O * T
+    # token embeddings: the planner keeps frame slots out of a suffix
+    x = eng.pack.emb[ids_suf.reshape(-1).to(dev, non_blocking=True)].contiguous()
+    mass = None if fa is None else torch.empty(eng.L, R, eng.H, eng.F + 2, dtype=torch.float32, device=dev)
+    x = _suffix_layers(eng, saved, start_d, len_d, x, B, O, T, S, mass=mass)
+    if fa is not None:
+        fa["frame_attention"] = mass.permute(1, 0, 2, 3).reshape(B, O, T, eng.L, eng.H, eng.F + 2)
+    out = _scored_head(eng, x, plan, lab_h, B, O, T, S)
     done()
     return out

@@ -317,8 +317,8 @@ int fvqa_attn_suffix_append(const void* qkv_suf, void* qkv_cache, void* o_suf, c
 int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,
                      float* option_sum, int64_t* option_count, float* option_mean, int64_t* prediction, int n_seq,
                      int n_options, int seq_len, void* stream);
-/* ---- option scoring by all three flipped tasks (csrc/flipped.hip; fvqa/flipped.py score_flipped) ----
- * fvqa_attn_suffix for suffixes of up to 64 rows: the operands, semantics and errors of fvqa_attn_suffix with 1 <= suffix_len <= 64.
+/* ---- option scoring by all three flipped tasks (fvqa/flipped.py score_flipped; csrc/flipped.hip, the attention in csrc/score.hip) ----
+ * fvqa_attn_suffix for suffixes of up to 64 rows (the same kernel template in csrc/score.hip with the tiles on a third grid axis): the operands, semantics and errors of fvqa_attn_suffix with 1 <= suffix_len <= 64.
  * The query at (n, c, j) sits at position start[n] + j; it sees the cache rows [0, start[n]), rows 0..j of its own option and the
  * adapter keys under tanh(gate1). gate2 is added on the frame keys [vs, vs + max_feats), vs = vstart[n], for query positions
  * >= vs + max_feats wherever the window lies — in the cache, across start[n] or inside the suffix (the QAV stream's frame rows

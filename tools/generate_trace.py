@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
-"""What every mode of the generation API launches and returns, as one line per mode that two trees can be diffed by: the tests'
-tiny fixture (tiny_peakedperm on rows 0 and 3 of its golden batch: B = 2, S = 128; fp32 and bf16), and per mode
+"""What every mode of the generation and option-scoring API launches and returns, as one line per mode that two trees can be
+diffed by: the tests' tiny fixture (tiny_peakedperm on rows 0 and 3 of its golden batch: B = 2, S = 128; fp32 and bf16) and, for
+score_flipped, the first three samples of the flipped_tiny fixture (S = 192: the batch that takes the shared form), and per mode
 
   mode | ops calls | sha256 over the sequence of ops.* calls | torch operator dispatches | sha256 of every tensor in the result
 
 An ops.* call enters the hash with its entry name, every tensor operand's shape, dtype and strides (no pointers) and every scalar
 argument (keywords by name). The torch dispatches are counted as tests/test_generate_gpu.py counts them (TorchDispatchMode). The
 same kernels on the same inputs in the same order give the same line: there is no tolerance. The tool uses the public API only
-(fvqa.generate, fvqa.score and the fixtures of tests/), so it runs unchanged in any tree that has it. One thing of the engine's own
+(fvqa.generate, fvqa.score, the model's score_flipped and the fixtures of tests/), so it runs unchanged in any tree that has it. One thing of the engine's own
 is taken out of the picture: it keeps a layer plan per arena under a key of device ADDRESSES (StepEngine.layer_plan), and every
 evaluation call makes its video_start tensor anew, so whether a prefill finds the plan or builds it again hangs on where the
-allocator put eight bytes. The tool drops the kept plans in front of every recorded call: each prefill then builds its plan, and
-no address decides what the trace holds.
+allocator put eight bytes. The tool drops the kept plans in front of every forward of a recorded call (a call may hold several:
+the twin's pass, one prompt pass per task): each prefill then builds its plan, and no address decides what the trace holds.
 
-  python tools/generate_trace.py [--out FILE] [--rehearse]      (--rehearse: build the modes and their inputs, launch nothing)"""
+  python tools/generate_trace.py [--out FILE] [--modes TEXT] [--rehearse]
+  (--modes: only the modes whose name holds TEXT; --rehearse: build the modes and their inputs, launch nothing)"""
 import argparse
 import hashlib
 import os
@@ -90,6 +92,16 @@ def forget_plans(eng) -> None:
             vars(ar).pop("_plan_key", None)
 
 
+def forgetful(eng) -> None:
+    """From here on every forward of this engine finds no kept plan."""
+    real = eng.forward
+
+    def forward(*a, **k):
+        forget_plans(eng)
+        return real(*a, **k)
+    eng.forward = forward
+
+
 def result_hash(out) -> str:
     """sha256 over every tensor of a result (nested dicts by key; numbers and names as they print)."""
     sha = hashlib.sha256()
@@ -115,6 +127,7 @@ def modes(eng, batch, full, drafts):
     branchy, _ = sets_of(fx, "branchy")
     long_, _ = sets_of(fx, "long")
     g = lambda **kw: (lambda: generate.generate(eng, batch, **kw))  # noqa: E731
+    so = lambda **kw: (lambda: {k: v for k, v in score.score_options(eng, full, **kw).items() if k != "plan"})  # noqa: E731
     return [
         ("greedy_decode", lambda: generate.greedy_decode(eng, batch)),
         ("generate", g()),
@@ -136,17 +149,34 @@ def modes(eng, batch, full, drafts):
         ("jump_forward=4", g(constraints=branchy, jump_forward=4)),
         ("jump_forward=4 return_logprobs", g(constraints=branchy, jump_forward=4, return_logprobs=True)),
         ("jump_forward=16", g(constraints=long_, jump_forward=16)),
-        ("score_options shared", lambda: {k: v for k, v in score.score_options(eng, full, route="shared").items() if k != "plan"}),
+        ("score_options shared", so(route="shared")),
+        ("score_options shared frame_attention", so(route="shared", frame_attention=True)),
+        ("score_options dense frame_attention", so(route="dense", frame_attention=True)),
+        ("score_options contrast=blind", so(contrast="blind")),
     ]
+
+
+FLIPPED, FLIPPED_ROWS = "flipped_tiny", (0, 1, 2)
+FLIPPED_TASKS = (("vqa", "vaq", "qav"), ("vqa",), ("vaq",), ("qav",))
+
+
+def flipped_modes(model, batch):
+    """score_flipped in both routes: all three tasks and each task alone."""
+    f = lambda **kw: (lambda: {k: v for k, v in model.score_flipped(batch, **kw).items() if k != "plan"})  # noqa: E731
+    return [(f"score_flipped {route} {'+'.join(tasks)}", f(route=route, tasks=tasks, answer=batch["answer"]))
+            for route in ("shared", "dense") for tasks in FLIPPED_TASKS]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="", help="also write the lines to this file")
+    ap.add_argument("--modes", default="", help="only the modes whose name holds this text")
     ap.add_argument("--rehearse", action="store_true", help="stop in front of the first device call")
     a = ap.parse_args()
+    from tests import flipped_util as FU
     from tests.test_beam_gpu import ROWS, eos_batch
     batch, full = eos_batch(PRESET, ROWS), eos_batch(PRESET, ROWS)
+    fbatch = FU.golden_batch(FU.load(FLIPPED), FLIPPED_ROWS)
     lines = []
     for dtype in (torch.float32, torch.bfloat16):
         eng = None
@@ -163,15 +193,24 @@ def main():
             if "t" not in answer:
                 answer["t"] = generate.generate(eng, batch, stop_at_eos=False)["tokens"].to(torch.int32)
             return answer["t"]
-        todo = modes(eng, batch, full, drafts)
+        todo = [(name, fn, eng) for name, fn in modes(eng, batch, full, drafts)]
+        fmodel = None
+        if not a.rehearse:
+            from tests.gpu_util import build_model
+            fmodel = build_model(FU.fixture_cfg(FLIPPED), dtype)[0].eval()
+        todo += [(name, fn, fmodel and fmodel.ensure_engine()) for name, fn in flipped_modes(fmodel, fbatch)]
+        todo = [m for m in todo if a.modes in m[0]]
         if a.rehearse:
             print(f"{dtype}: {len(todo)} modes built, B = {len(batch['prefix_index']['vqa'])}, S = {batch['text_id']['vqa'].shape[2]}, "
-                  f"prompts of {batch['prefix_index']['vqa']} tokens; nothing launched")
+                  f"prompts of {batch['prefix_index']['vqa']} tokens; score_flipped on {len(FLIPPED_ROWS)} samples of {FLIPPED}, "
+                  f"S = {fbatch['text_id']['vqa'].shape[2]}; nothing launched")
             continue
-        drafts()
-        for name, fn in todo:
+        if any("lookahead" in m[0] for m in todo):
+            drafts()
+        for e in {id(m[2]): m[2] for m in todo}.values():
+            forgetful(e)
+        for name, fn, _ in todo:
             fn()                                            # once unrecorded: caches of the engine's own (arenas, beam cache) exist
-            forget_plans(eng)
             tr = Trace()
             out = tr.run(fn)
             lines.append(f"{str(dtype)[6:]:9s}| {name:46s}| ops calls {tr.calls:5d} {tr.sha.hexdigest()[:16]} | torch dispatches "
