@@ -1,160 +1,76 @@
-// Input/output heads of the Flipped-VQA step on gfx950: visual projection (+ temporal embedding),
-// LM-head cross-entropy over fp32 logits, and the QAV frame-ordering head. All fp32 arithmetic,
-// one wave (or workgroup) per row, fixed-order reductions (no float atomics ⇒ bitwise repeatable).
+// Input/output heads of the Flipped-VQA step on gfx950: the front-end projections (one kernel family for the video-only
+// step and the audio modes, + temporal embedding), the audio cross-attention, LM-head cross-entropy over fp32 logits, and
+// the QAV frame-ordering head. All fp32 arithmetic, fixed-order reductions (no float atomics ⇒ bitwise repeatable).
 #include "common.h"
 
 namespace {
 
-// ---- visual projection: vf_raw[r,d] = video[r,:]·W[d,:]   (reference llama/model.py:322,324) --
-// one wave per output feature d keeps W[d,:] in registers and sweeps the (few) frame rows
-template <typename T, int KMAX>
-__global__ __launch_bounds__(256) void visual_proj_fwd_k(const float* __restrict__ video, const float* __restrict__ W,
-                                                         const float* __restrict__ temporal,
-                                                         float* __restrict__ vf_raw, T* __restrict__ vf_tok, int R,
-                                                         int F, int K, int D) {
-  const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= D) return;
-  const int lane = threadIdx.x & 63;
-  float w[KMAX];
-#pragma unroll
-  for (int t = 0; t < KMAX / 4; ++t) {
-    const int k = t * 256 + lane * 4;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (k < K) Vec4<float>::load(W + (size_t)d * K + k, v);
-    w[4 * t] = v[0]; w[4 * t + 1] = v[1]; w[4 * t + 2] = v[2]; w[4 * t + 3] = v[3];
-  }
-  for (int r = 0; r < R; ++r) {
-    float acc = 0.f;
-#pragma unroll
-    for (int t = 0; t < KMAX / 4; ++t) {
-      const int k = t * 256 + lane * 4;
-      if (k < K) {
-        float v[4];
-        Vec4<float>::load(video + (size_t)r * K + k, v);
-        acc += v[0] * w[4 * t] + v[1] * w[4 * t + 1] + v[2] * w[4 * t + 2] + v[3] * w[4 * t + 3];
-      }
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) {
-      vf_raw[(size_t)r * D + d] = acc;
-      vf_tok[(size_t)r * D + d] = from_f32<T>(acc + temporal[(size_t)(r % F) * D + d]);
-    }
-  }
-}
+// ---- front-end projections (reference llama/model.py:209-227,306-324) -------------------------------------------------
+// out[r,d] = sum over 1..2 sources of X_s[r,:]·W_s[d,:] (+ bias[d]), every operand read where it lies — a source is (pointer,
+// row pitch, K), its weight (pointer, row pitch). The video-only step is one contiguous source (pitch = K, no bias), `concat`
+// two sources against two column ranges of one weight, `sum` two sources against two weights, `audio_only` and the projections
+// of `attention` one. One kernel family serves them all: what the video-only entries launch is the one-source instantiation.
+struct ProjSrc { const float* x; const float* w; int ldx, ldw, k; };
+struct ProjSrcs { ProjSrc s[2]; int n; };
 
-// dW[d,k] += sum_r (d_tok[r,d] + d_qav[r,d]) * video[r,k]   (the weight gradient of llama/model.py:322).
-// One wave owns DB output features and the whole K row of each in registers (DB x K/64 accumulators), so a frame row of
-// `video` fetched from L2 feeds DB features (DB x fewer bytes through L2 than one feature per wave), four rows per trip.
-template <int KMAX, int DB, int RT>   // RT frame rows per trip
-__global__ __launch_bounds__(256) void visual_proj_bwd_k(const float* __restrict__ d_tok,
-                                                         const float* __restrict__ d_qav,
-                                                         const float* __restrict__ video, float* __restrict__ dW,
-                                                         int R, int K, int D) {
-  const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * DB;
-  if (d0 >= D) return;
-  const int lane = threadIdx.x & 63;
-  float acc[DB][KMAX];
-#pragma unroll
-  for (int j = 0; j < DB; ++j)
-#pragma unroll
-    for (int t = 0; t < KMAX; ++t) acc[j][t] = 0.f;
-  for (int r0 = 0; r0 < R; r0 += RT) {                     // RT frame rows per trip: their loads are all in flight together (round 5: 8, was 4 —
-                                                           // the kernel is a chain of R / RT load latencies: 40.6 us at 20 trips)
-    float g[RT][DB];
-    float v[RT][KMAX];
-#pragma unroll
-    for (int rr = 0; rr < RT; ++rr) {
-      const int r = r0 + rr < R ? r0 + rr : R - 1;
-      const float live = r0 + rr < R ? 1.f : 0.f;
-#pragma unroll
-      for (int j = 0; j < DB; ++j) {
-        const int d = d0 + j < D ? d0 + j : D - 1;
-        float gv = d_tok[(size_t)r * D + d];
-        if (d_qav) gv += d_qav[(size_t)r * D + d];
-        g[rr][j] = gv * live;
-      }
-#pragma unroll
-      for (int t = 0; t < KMAX / 4; ++t) {
-        const int k = t * 256 + lane * 4;
-        float q[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k < K) Vec4<float>::load(video + (size_t)r * K + k, q);
-        v[rr][4 * t] = q[0]; v[rr][4 * t + 1] = q[1]; v[rr][4 * t + 2] = q[2]; v[rr][4 * t + 3] = q[3];
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < RT; ++rr)                        // rows in order: the same fma chain as a row-by-row loop
-#pragma unroll
-      for (int j = 0; j < DB; ++j)
-#pragma unroll
-        for (int t = 0; t < KMAX; ++t) acc[j][t] += g[rr][j] * v[rr][t];
-  }
-#pragma unroll
-  for (int j = 0; j < DB; ++j) {
-    if (d0 + j >= D) break;
-#pragma unroll
-    for (int t = 0; t < KMAX / 4; ++t) {
-      const int k = t * 256 + lane * 4;
-      if (k < K) {
-        float v[4];
-        Vec4<float>::load(dW + (size_t)(d0 + j) * K + k, v);
-        v[0] += acc[j][4 * t]; v[1] += acc[j][4 * t + 1]; v[2] += acc[j][4 * t + 2]; v[3] += acc[j][4 * t + 3];
-        Vec4<float>::store(dW + (size_t)(d0 + j) * K + k, v);
-      }
-    }
-  }
-}
-
-// vf_raw[r,d] = video[r,:]·W[d,:] on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32: the same fma chain per
-// output as a scalar loop over k in 16-element strides), then vf_tok = cast(vf_raw + temporal[r % F]). One workgroup
-// per 16 output features: its 4 waves split K, each keeps the R <= 128 frame rows as 16-row MFMA blocks; the 4
-// partial sums meet in LDS. 256 workgroups instead of the 32 tiles of a 128x128 GEMM at M = 80: 69 -> ~8 us.
-template <typename T>
-__global__ __launch_bounds__(256) void visual_proj_fwd_mfma_k(const float* __restrict__ video,
-                                                              const float* __restrict__ W,
-                                                              const float* __restrict__ temporal,
-                                                              float* __restrict__ vf_raw, T* __restrict__ vf_tok,
-                                                              int R, int F, int K, int D) {
+// raw[r,d] on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32: the same fma chain per output as a scalar loop over k in
+// 16-element strides), then tok = cast(raw + temporal[r % F]). One workgroup per 16 output features: its 4 waves split EACH
+// source's K (K_s % 64 == 0), each keeps the R <= 128 rows as 16-row MFMA blocks; the 4 partial sums meet in LDS. 256
+// workgroups instead of the 32 tiles of a 128x128 GEMM at M = 80: 69 -> ~8 us. Per output the fma chain of a wave is source
+// 0's k ascending, then source 1's; the four partials are added in wave order: fixed, bitwise repeatable. NSRC is a
+// compile-time count: with it at run time both K-loops are live at once, 280 VGPRs and one wave per SIMD instead of two.
+// OPT: bias and tok are optional and asked for at run time. The step's own projections (no bias, tokens written) launch
+// OPT = false, the epilogue the video-only kernels had: with the two branches in it the same loop measured 0.7 us of 20.4
+// slower here and 5 us of 163 in proj_fwd_k, where they sit in every row's chain (profiles/front_refactor.log, section 4).
+template <typename T, int NSRC, bool OPT>
+__global__ __launch_bounds__(256) void proj_fwd_mfma_k(ProjSrcs S, const float* __restrict__ bias,
+                                                       const float* __restrict__ temporal, float* __restrict__ raw,
+                                                       T* __restrict__ tok, int R, int F, int D) {
   __shared__ float part[4][8][16][17];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int nrb = (R + 15) >> 4;                           // 16-row blocks of frame rows (<= 8)
-  const int kw = K / 4;                                    // this wave's K range (K % 64 == 0)
+  const int nrb = (R + 15) >> 4;                           // 16-row blocks of rows (<= 8)
   int bn = n0 + li; bn = bn < D ? bn : D - 1;
-  const float* bp = W + (size_t)bn * K + (size_t)w * kw + 4 * g;
   f32x4 acc[8];
 #pragma unroll
   for (int b = 0; b < 8; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
   // four k-steps of 16 per trip, every load of the trip in flight before its first MFMA (round 5: one step per trip was a chain of
   // twelve dependent load latencies, 28.9 us in the step); the accumulation order per output is unchanged (k ascending)
   constexpr int VU = 4;
-  const float* ap[8];
 #pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    int ar = b * 16 + li; ar = ar < R ? ar : R - 1;
-    ap[b] = video + (size_t)ar * K + (size_t)w * kw + 4 * g;
-  }
-  for (int k0 = 0; k0 < kw; k0 += 16 * VU) {
-    float4 bf[VU], af[VU][8];
+  for (int s = 0; s < NSRC; ++s) {
+    const ProjSrc& P = S.s[s];
+    const int kw = P.k / 4;                                // this wave's K range of the source
+    const float* bp = P.w + (size_t)bn * P.ldw + (size_t)w * kw + 4 * g;
+    const float* ap[8];
 #pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      const int k = k0 + 16 * u;
-      const bool in = k < kw;
-      bf[u] = in ? *reinterpret_cast<const float4*>(bp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int b = 0; b < 8; ++b)
-        af[u][b] = (in && b < nrb) ? *reinterpret_cast<const float4*>(ap[b] + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int b = 0; b < 8; ++b) {
+      int ar = b * 16 + li; ar = ar < R ? ar : R - 1;
+      ap[b] = P.x + (size_t)ar * P.ldx + (size_t)w * kw + 4 * g;
     }
+    for (int k0 = 0; k0 < kw; k0 += 16 * VU) {
+      float4 bf[VU], af[VU][8];
 #pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      if (k0 + 16 * u >= kw) break;
+      for (int u = 0; u < VU; ++u) {
+        const int k = k0 + 16 * u;
+        const bool in = k < kw;
+        bf[u] = in ? *reinterpret_cast<const float4*>(bp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        if (b >= nrb) break;
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].x, bf[u].x, acc[b], 0, 0, 0);     // D[row 4g+e][feature li]
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].y, bf[u].y, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].z, bf[u].z, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].w, bf[u].w, acc[b], 0, 0, 0);
+        for (int b = 0; b < 8; ++b)
+          af[u][b] = (in && b < nrb) ? *reinterpret_cast<const float4*>(ap[b] + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < VU; ++u) {
+        if (k0 + 16 * u >= kw) break;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+          if (b >= nrb) break;
+          acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].x, bf[u].x, acc[b], 0, 0, 0);     // D[row 4g+e][feature li]
+          acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].y, bf[u].y, acc[b], 0, 0, 0);
+          acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].z, bf[u].z, acc[b], 0, 0, 0);
+          acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].w, bf[u].w, acc[b], 0, 0, 0);
+        }
       }
     }
   }
@@ -167,9 +83,141 @@ __global__ __launch_bounds__(256) void visual_proj_fwd_mfma_k(const float* __res
     const int b = i >> 8, rr = (i >> 4) & 15, c = i & 15;
     const int r = b * 16 + rr, d = n0 + c;
     if (r < R && d < D) {
-      const float v = ((part[0][b][rr][c] + part[1][b][rr][c]) + part[2][b][rr][c]) + part[3][b][rr][c];
-      vf_raw[(size_t)r * D + d] = v;
-      vf_tok[(size_t)r * D + d] = from_f32<T>(v + temporal[(size_t)(r % F) * D + d]);
+      float v = ((part[0][b][rr][c] + part[1][b][rr][c]) + part[2][b][rr][c]) + part[3][b][rr][c];
+      if (OPT && bias) v += bias[d];
+      raw[(size_t)r * D + d] = v;
+      if (!OPT || tok) tok[(size_t)r * D + d] = from_f32<T>(v + temporal[(size_t)(r % F) * D + d]);
+    }
+  }
+}
+
+// any row count, K_s % 4 == 0: one wave per output feature sweeps the rows (the fallback beyond 128 rows or off K_s % 64 == 0).
+// HELD, for ONE source of at most 64 * KMAX = 2048 columns: W[d,:] stays in registers (161 against 198 us at R = 160, K = 768,
+// D = 4096, the video-only step at batch 16: profiles/front_refactor.log). Otherwise the weight row is read again for every
+// row, any K, one or two sources. Either way a lane's chain is k = 4 * lane + 256 t ascending, source 0 then source 1.
+template <typename T, bool HELD, bool OPT>
+__global__ __launch_bounds__(256) void proj_fwd_k(ProjSrcs S, const float* __restrict__ bias,
+                                                  const float* __restrict__ temporal, float* __restrict__ raw,
+                                                  T* __restrict__ tok, int R, int F, int D) {
+  const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (d >= D) return;
+  const int lane = threadIdx.x & 63;
+  constexpr int KMAX = 32;
+  const int K0 = S.s[0].k;
+  float w[KMAX];
+#pragma unroll
+  for (int t = 0; t < KMAX / 4; ++t) {
+    const int k = t * 256 + lane * 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (HELD && k < K0) Vec4<float>::load(S.s[0].w + (size_t)d * S.s[0].ldw + k, v);
+    w[4 * t] = v[0]; w[4 * t + 1] = v[1]; w[4 * t + 2] = v[2]; w[4 * t + 3] = v[3];
+  }
+  for (int r = 0; r < R; ++r) {
+    float acc = 0.f;
+    if (HELD) {
+#pragma unroll
+      for (int t = 0; t < KMAX / 4; ++t) {
+        const int k = t * 256 + lane * 4;
+        if (k < K0) {
+          float v[4];
+          Vec4<float>::load(S.s[0].x + (size_t)r * S.s[0].ldx + k, v);
+          acc += v[0] * w[4 * t] + v[1] * w[4 * t + 1] + v[2] * w[4 * t + 2] + v[3] * w[4 * t + 3];
+        }
+      }
+    } else {
+      for (int s = 0; s < S.n; ++s) {
+        const float* x = S.s[s].x + (size_t)r * S.s[s].ldx;
+        const float* wr = S.s[s].w + (size_t)d * S.s[s].ldw;
+        for (int k = lane * 4; k < S.s[s].k; k += 256) {
+          float a[4], b[4];
+          Vec4<float>::load(x + k, a);
+          Vec4<float>::load(wr + k, b);
+          acc += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+        }
+      }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      if (OPT && bias) acc += bias[d];
+      raw[(size_t)r * D + d] = acc;
+      if (!OPT || tok) tok[(size_t)r * D + d] = from_f32<T>(acc + temporal[(size_t)(r % F) * D + d]);
+    }
+  }
+}
+
+// dW_s[d,k] += sum_r (g0[r,d] + g1[r,d]) * X_s[r,k] for source blockIdx.y (the weight gradient of llama/model.py:322), dW_s a
+// weight gradient or a column range of one with its own row pitch (S.s[].w / ldw). One wave owns DB output features and the
+// whole K row of each in registers (DB x K/64 accumulators), so a row of X fetched from L2 feeds DB features (DB x fewer bytes
+// through L2 than one feature per wave), RT rows per trip. Per output the fma chain is rows ascending. The gradient rows have
+// pitch ldg (fvqa_av_linear_bwd: a column range of a wider matrix); BIAS: dbias[d] += sum_r g[r,d], rows ascending, by the
+// waves of source 0 (a compile-time switch: the sums cost the <16, 4, 8> form nine registers).
+template <int KMAX, int DB, int RT, bool BIAS>   // RT rows per trip
+__global__ __launch_bounds__(256) void proj_bwd_k(const float* __restrict__ g0, const float* __restrict__ g1, ProjSrcs S,
+                                                  int R, int D, int ldg, float* __restrict__ dbias) {
+  const ProjSrc src = blockIdx.y == 0 ? S.s[0] : S.s[1];
+  const float* __restrict__ X = src.x;
+  float* __restrict__ dW = const_cast<float*>(src.w);
+  const int K = src.k, ldx = src.ldx, ldw = src.ldw;
+  const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * DB;
+  if (d0 >= D) return;
+  const int lane = threadIdx.x & 63;
+  float acc[DB][KMAX];
+  float bsum[DB];
+#pragma unroll
+  for (int j = 0; j < DB; ++j) {
+    bsum[j] = 0.f;
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t) acc[j][t] = 0.f;
+  }
+  for (int r0 = 0; r0 < R; r0 += RT) {                     // RT rows per trip: their loads are all in flight together (round 5: 8, was 4 —
+                                                           // the kernel is a chain of R / RT load latencies: 40.6 us at 20 trips)
+    float g[RT][DB];
+    float v[RT][KMAX];
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr) {
+      const int r = r0 + rr < R ? r0 + rr : R - 1;
+      const float live = r0 + rr < R ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < DB; ++j) {
+        const int d = d0 + j < D ? d0 + j : D - 1;
+        float gv = g0[(size_t)r * ldg + d];
+        if (g1) gv += g1[(size_t)r * ldg + d];
+        g[rr][j] = gv * live;
+      }
+#pragma unroll
+      for (int t = 0; t < KMAX / 4; ++t) {
+        const int k = t * 256 + lane * 4;
+        float q[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k < K) Vec4<float>::load(X + (size_t)r * ldx + k, q);
+        v[rr][4 * t] = q[0]; v[rr][4 * t + 1] = q[1]; v[rr][4 * t + 2] = q[2]; v[rr][4 * t + 3] = q[3];
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)                        // rows in order: the same fma chain as a row-by-row loop
+#pragma unroll
+      for (int j = 0; j < DB; ++j) {
+        if (BIAS) bsum[j] += g[rr][j];
+#pragma unroll
+        for (int t = 0; t < KMAX; ++t) acc[j][t] += g[rr][j] * v[rr][t];
+      }
+  }
+  if (BIAS && blockIdx.y == 0 && lane == 0) {
+#pragma unroll
+    for (int j = 0; j < DB; ++j)
+      if (d0 + j < D) dbias[d0 + j] += bsum[j];
+  }
+#pragma unroll
+  for (int j = 0; j < DB; ++j) {
+    if (d0 + j >= D) break;
+#pragma unroll
+    for (int t = 0; t < KMAX / 4; ++t) {
+      const int k = t * 256 + lane * 4;
+      if (k < K) {
+        float v[4];
+        Vec4<float>::load(dW + (size_t)(d0 + j) * ldw + k, v);
+        v[0] += acc[j][4 * t]; v[1] += acc[j][4 * t + 1]; v[2] += acc[j][4 * t + 2]; v[3] += acc[j][4 * t + 3];
+        Vec4<float>::store(dW + (size_t)(d0 + j) * ldw + k, v);
+      }
     }
   }
 }
@@ -424,113 +472,7 @@ __global__ __launch_bounds__(256) void qav_bwd_v_k(const T* __restrict__ xn, con
 }
 
 
-// ---- audio-visual front end (reference llama/model.py:209-227,306-324) ------------------------------------------------
-// The projections of the audio modes: out[r,d] = sum over 1..2 sources of X_s[r,:]·W_s[d,:] (+ bias[d]), every operand read
-// where it lies — a source is (pointer, row pitch, K), its weight (pointer, row pitch): `concat` is two sources against two
-// column ranges of one weight, `sum` two sources against two weights, `audio_only` and the projections of `attention` one.
-struct AvSrc { const float* x; const float* w; int ldx, ldw, k; };
-struct AvSrcs { AvSrc s[2]; int n; };
-
-// visual_proj_fwd_mfma_k grown to pitched sources: one workgroup per 16 output features, its 4 waves split EACH source's K
-// (K_s % 64 == 0), the R <= 128 rows as 16-row MFMA blocks, partials meet in LDS. Per output the fma chain of a wave is source
-// 0's k ascending, then source 1's; the four partials are added in wave order: fixed, bitwise repeatable.
-template <int VU>
-__device__ __forceinline__ void av_accumulate(f32x4 (&acc)[8], const AvSrc& S, int R, int nrb, int bn, int w, int li, int g) {
-  const int kw = S.k / 4;                                  // this wave's K range of the source
-  const float* bp = S.w + (size_t)bn * S.ldw + (size_t)w * kw + 4 * g;
-  const float* ap[8];
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    int ar = b * 16 + li; ar = ar < R ? ar : R - 1;
-    ap[b] = S.x + (size_t)ar * S.ldx + (size_t)w * kw + 4 * g;
-  }
-  for (int k0 = 0; k0 < kw; k0 += 16 * VU) {               // every load of a trip in flight before its first MFMA
-    float4 bf[VU], af[VU][8];
-#pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      const int k = k0 + 16 * u;
-      const bool in = k < kw;
-      bf[u] = in ? *reinterpret_cast<const float4*>(bp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int b = 0; b < 8; ++b)
-        af[u][b] = (in && b < nrb) ? *reinterpret_cast<const float4*>(ap[b] + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      if (k0 + 16 * u >= kw) break;
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        if (b >= nrb) break;
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].x, bf[u].x, acc[b], 0, 0, 0);     // D[row 4g+e][feature li]
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].y, bf[u].y, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].z, bf[u].z, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][b].w, bf[u].w, acc[b], 0, 0, 0);
-      }
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void av_proj_fwd_mfma_k(AvSrcs S, const float* __restrict__ bias,
-                                                          const float* __restrict__ temporal, float* __restrict__ raw,
-                                                          T* __restrict__ tok, int R, int F, int D) {
-  __shared__ float part[4][8][16][17];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int li = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * 16;
-  const int nrb = (R + 15) >> 4;
-  int bn = n0 + li; bn = bn < D ? bn : D - 1;
-  f32x4 acc[8];
-#pragma unroll
-  for (int b = 0; b < 8; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  av_accumulate<4>(acc, S.s[0], R, nrb, bn, w, li, g);
-  if (S.n > 1) av_accumulate<4>(acc, S.s[1], R, nrb, bn, w, li, g);
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) part[w][b][4 * g + e][li] = acc[b][e];
-  __syncthreads();
-  for (int i = threadIdx.x; i < nrb * 256; i += 256) {
-    const int b = i >> 8, rr = (i >> 4) & 15, c = i & 15;
-    const int r = b * 16 + rr, d = n0 + c;
-    if (r < R && d < D) {
-      float v = ((part[0][b][rr][c] + part[1][b][rr][c]) + part[2][b][rr][c]) + part[3][b][rr][c];
-      if (bias) v += bias[d];
-      raw[(size_t)r * D + d] = v;
-      if (tok) tok[(size_t)r * D + d] = from_f32<T>(v + temporal[(size_t)(r % F) * D + d]);
-    }
-  }
-}
-
-// any row count, K_s % 4 == 0: one wave per output feature sweeps the rows (the fallback beyond 128 rows, as visual_proj_fwd_k is)
-template <typename T>
-__global__ __launch_bounds__(256) void av_proj_fwd_k(AvSrcs S, const float* __restrict__ bias,
-                                                     const float* __restrict__ temporal, float* __restrict__ raw,
-                                                     T* __restrict__ tok, int R, int F, int D) {
-  const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= D) return;
-  const int lane = threadIdx.x & 63;
-  for (int r = 0; r < R; ++r) {
-    float acc = 0.f;
-    for (int s = 0; s < S.n; ++s) {
-      const float* x = S.s[s].x + (size_t)r * S.s[s].ldx;
-      const float* wr = S.s[s].w + (size_t)d * S.s[s].ldw;
-      for (int k = lane * 4; k < S.s[s].k; k += 256) {
-        float a[4], b[4];
-        Vec4<float>::load(x + k, a);
-        Vec4<float>::load(wr + k, b);
-        acc += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-      }
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) {
-      if (bias) acc += bias[d];
-      raw[(size_t)r * D + d] = acc;
-      if (tok) tok[(size_t)r * D + d] = from_f32<T>(acc + temporal[(size_t)(r % F) * D + d]);
-    }
-  }
-}
-
+// ---- audio-visual front end: cross-attention (reference llama/model.py:153-169) ---------------------------------------
 // X[n,f,:] = softmax_t(Q[n,f,:]·K[n,t,:] * scale) · V[n,:,:] over the T <= 16 keys of the same sample (reference
 // llama/model.py:153-169), fp32 throughout, max subtracted. One workgroup per query row; scores are block sums in key order.
 __global__ __launch_bounds__(256) void av_cross_attn_fwd_k(const float* __restrict__ q, const float* __restrict__ k,
@@ -574,80 +516,6 @@ __global__ __launch_bounds__(256) void av_cross_attn_fwd_k(const float* __restri
         o[0] += p * va[0]; o[1] += p * va[1]; o[2] += p * va[2]; o[3] += p * va[3];
       }
     Vec4<float>::store(x + (size_t)row * dim + c, o);
-  }
-}
-
-// visual_proj_bwd_k with pitches: dW_s[d, k] += sum_r (d_tok[r,d] + d_qav[r,d]) * X_s[r,k] for source blockIdx.y, dW_s a column
-// range of a weight gradient with its own row pitch (S.s[].w / ldw). Same fma chain per output: rows ascending. The gradient
-// rows have pitch ldg (fvqa_av_linear_bwd: a column range of a wider matrix); with dbias, dbias[d] += sum_r g[r,d], rows
-// ascending, by the waves of source 0.
-template <int KMAX, int DB, int RT>
-__global__ __launch_bounds__(256) void av_proj_bwd_k(const float* __restrict__ d_tok, const float* __restrict__ d_qav,
-                                                     AvSrcs S, int R, int D, int ldg, float* __restrict__ dbias) {
-  const AvSrc src = blockIdx.y == 0 ? S.s[0] : S.s[1];
-  const float* __restrict__ X = src.x;
-  float* __restrict__ dW = const_cast<float*>(src.w);
-  const int K = src.k, ldx = src.ldx, ldw = src.ldw;
-  const int d0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * DB;
-  if (d0 >= D) return;
-  const int lane = threadIdx.x & 63;
-  float acc[DB][KMAX];
-  float bsum[DB];
-#pragma unroll
-  for (int j = 0; j < DB; ++j) {
-    bsum[j] = 0.f;
-#pragma unroll
-    for (int t = 0; t < KMAX; ++t) acc[j][t] = 0.f;
-  }
-  for (int r0 = 0; r0 < R; r0 += RT) {
-    float g[RT][DB];
-    float v[RT][KMAX];
-#pragma unroll
-    for (int rr = 0; rr < RT; ++rr) {
-      const int r = r0 + rr < R ? r0 + rr : R - 1;
-      const float live = r0 + rr < R ? 1.f : 0.f;
-#pragma unroll
-      for (int j = 0; j < DB; ++j) {
-        const int d = d0 + j < D ? d0 + j : D - 1;
-        float gv = d_tok[(size_t)r * ldg + d];
-        if (d_qav) gv += d_qav[(size_t)r * ldg + d];
-        g[rr][j] = gv * live;
-      }
-#pragma unroll
-      for (int t = 0; t < KMAX / 4; ++t) {
-        const int k = t * 256 + lane * 4;
-        float q[4] = {0.f, 0.f, 0.f, 0.f};
-        if (k < K) Vec4<float>::load(X + (size_t)r * ldx + k, q);
-        v[rr][4 * t] = q[0]; v[rr][4 * t + 1] = q[1]; v[rr][4 * t + 2] = q[2]; v[rr][4 * t + 3] = q[3];
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < RT; ++rr)
-#pragma unroll
-      for (int j = 0; j < DB; ++j) {
-        bsum[j] += g[rr][j];
-#pragma unroll
-        for (int t = 0; t < KMAX; ++t) acc[j][t] += g[rr][j] * v[rr][t];
-      }
-  }
-  if (dbias && blockIdx.y == 0 && lane == 0) {
-#pragma unroll
-    for (int j = 0; j < DB; ++j)
-      if (d0 + j < D) dbias[d0 + j] += bsum[j];
-  }
-#pragma unroll
-  for (int j = 0; j < DB; ++j) {
-    if (d0 + j >= D) break;
-#pragma unroll
-    for (int t = 0; t < KMAX / 4; ++t) {
-      const int k = t * 256 + lane * 4;
-      if (k < K) {
-        float v[4];
-        Vec4<float>::load(dW + (size_t)(d0 + j) * ldw + k, v);
-        v[0] += acc[j][4 * t]; v[1] += acc[j][4 * t + 1]; v[2] += acc[j][4 * t + 2]; v[3] += acc[j][4 * t + 3];
-        Vec4<float>::store(dW + (size_t)(d0 + j) * ldw + k, v);
-      }
-    }
   }
 }
 
@@ -818,7 +686,7 @@ __global__ __launch_bounds__(256) void av_proj_dx_k(const float* __restrict__ g0
 }
 
 // host side: the C sources checked and packed for a launch (16-byte rows everywhere: float4 loads)
-static int av_pack(const fvqa_proj_src* src, int n_src, AvSrcs* out, bool* mfma_ok) {
+static int proj_pack(const fvqa_proj_src* src, int n_src, ProjSrcs* out, bool* mfma_ok) {
   if (n_src < 1 || n_src > 2 || !src) return FVQA_EINVAL;
   *mfma_ok = true;
   out->n = n_src;
@@ -827,10 +695,62 @@ static int av_pack(const fvqa_proj_src* src, int n_src, AvSrcs* out, bool* mfma_
     if (src[s].k <= 0 || src[s].k % 4 || src[s].ldx < src[s].k || src[s].ldw < src[s].k) return FVQA_ESHAPE;
     if (src[s].ldx % 4 || src[s].ldw % 4 || (((uintptr_t)src[s].x | (uintptr_t)src[s].w) & 15)) return FVQA_EALIGN;
     if (src[s].k % 64) *mfma_ok = false;
-    out->s[s] = AvSrc{src[s].x, src[s].w, src[s].ldx, src[s].ldw, src[s].k};
+    out->s[s] = ProjSrc{src[s].x, src[s].w, src[s].ldx, src[s].ldw, src[s].k};
   }
   if (n_src == 1) out->s[1] = out->s[0];
   return FVQA_OK;
+}
+
+// The forward launch of every projection entry. The wave-per-feature kernel re-reads the whole source matrix for every output
+// feature (1 GB of L2 traffic at D = 4096: 120 us). Shapes of the step (every K_s % 64 == 0, at most 128 rows) run on the
+// exact-fp32 matrix cores instead, temporal embedding and cast included.
+template <typename T, bool OPT>
+static void proj_fwd_launch_t(const ProjSrcs& S, bool mfma, const float* bias, const float* temporal, float* raw, void* tok,
+                              int R, int F, int D, hipStream_t st) {
+  const dim3 block(256);
+  if (!mfma && S.n == 1 && S.s[0].k <= 2048)
+    hipLaunchKernelGGL((proj_fwd_k<T, true, OPT>), dim3((D + 3) / 4), block, 0, st, S, bias, temporal, raw, (T*)tok, R, F, D);
+  else if (!mfma)
+    hipLaunchKernelGGL((proj_fwd_k<T, false, OPT>), dim3((D + 3) / 4), block, 0, st, S, bias, temporal, raw, (T*)tok, R, F, D);
+  else if (S.n == 1)
+    hipLaunchKernelGGL((proj_fwd_mfma_k<T, 1, OPT>), dim3((D + 15) / 16), block, 0, st, S, bias, temporal, raw, (T*)tok, R, F, D);
+  else
+    hipLaunchKernelGGL((proj_fwd_mfma_k<T, 2, OPT>), dim3((D + 15) / 16), block, 0, st, S, bias, temporal, raw, (T*)tok, R, F, D);
+}
+static void proj_fwd_launch(const ProjSrcs& S, bool mfma_ok, const float* bias, const float* temporal, float* raw, void* tok,
+                            int R, int F, int D, int dtype, hipStream_t st) {
+  const bool mfma = mfma_ok && R <= 128;
+  const bool opt = bias || !tok;                            // OPT = false: no bias, tokens written, nothing asked at run time
+  if (dtype == FVQA_H16 && opt) proj_fwd_launch_t<bf16_t, true>(S, mfma, bias, temporal, raw, tok, R, F, D, st);
+  else if (dtype == FVQA_H16) proj_fwd_launch_t<bf16_t, false>(S, mfma, bias, temporal, raw, tok, R, F, D, st);
+  else if (opt) proj_fwd_launch_t<float, true>(S, mfma, bias, temporal, raw, tok, R, F, D, st);
+  else proj_fwd_launch_t<float, false>(S, mfma, bias, temporal, raw, tok, R, F, D, st);
+}
+
+// The backward launch of every projection entry (each K_s <= 2048, checked by the entry). Every source <= 1024 columns: one
+// launch, the sources on grid.y, 4 features per wave (4 x 16 accumulators), 4 waves per CU at D = 4096; else one <32, 2, 4>
+// launch per source. dbias rides on the first source only (blockIdx.y == 0 of the first launch).
+template <int KMAX, int DB, int RT>
+static void proj_bwd_launch_one(const float* g0, const float* g1, const ProjSrcs& S, int ny, int R, int D, int ldg, float* dbias,
+                                hipStream_t st) {
+  const dim3 grid((D + 4 * DB - 1) / (4 * DB), ny), block(256);
+  if (dbias) hipLaunchKernelGGL((proj_bwd_k<KMAX, DB, RT, true>), grid, block, 0, st, g0, g1, S, R, D, ldg, dbias);
+  else hipLaunchKernelGGL((proj_bwd_k<KMAX, DB, RT, false>), grid, block, 0, st, g0, g1, S, R, D, ldg, dbias);
+}
+static void proj_bwd_launch(const float* g0, const float* g1, const ProjSrcs& S, int R, int D, int ldg, float* dbias,
+                            hipStream_t st) {
+  bool narrow = true;
+  for (int s = 0; s < S.n; ++s) narrow = narrow && S.s[s].k <= 1024;
+  if (narrow) {
+    proj_bwd_launch_one<16, 4, 8>(g0, g1, S, S.n, R, D, ldg, dbias, st);
+    return;
+  }
+  for (int s = 0; s < S.n; ++s) {
+    ProjSrcs one = S;
+    one.s[0] = S.s[s];
+    one.n = 1;
+    proj_bwd_launch_one<32, 2, 4>(g0, g1, one, 1, R, D, ldg, s == 0 ? dbias : nullptr, st);
+  }
 }
 
 }  // namespace
@@ -845,28 +765,9 @@ extern "C" int fvqa_visual_proj_fwd(const float* video, const float* W, const fl
   // both kernels read video and W 16 bytes at a time; the outputs and the temporal table are element accesses
   if (!fvqa_aligned(16, video, W) || !fvqa_aligned(4, temporal, vf_raw) || !fvqa_aligned(fvqa_dtype_size(dtype), vf_tok))
     return FVQA_EALIGN;
-  dim3 grid((dim + 3) / 4), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  // The wave-per-feature kernel re-reads the whole frame matrix for every output feature (1 GB of L2 traffic at
-  // D = 4096: 120 us). Shapes of the step (K % 64 == 0, at most 128 frame rows, 16-byte rows) run on the exact-fp32
-  // matrix cores instead, temporal embedding and cast included.
-  if (in_dim % 64 == 0 && n_frames_total <= 128) {
-    const dim3 g16((dim + 15) / 16);
-    if (dtype == FVQA_H16)
-      hipLaunchKernelGGL(visual_proj_fwd_mfma_k<bf16_t>, g16, block, 0, st, video, W, temporal, vf_raw, (bf16_t*)vf_tok,
-                         n_frames_total, max_feats, in_dim, dim);
-    else
-      hipLaunchKernelGGL(visual_proj_fwd_mfma_k<float>, g16, block, 0, st, video, W, temporal, vf_raw, (float*)vf_tok,
-                         n_frames_total, max_feats, in_dim, dim);
-    FVQA_CHECK_LAUNCH();
-    return FVQA_OK;
-  }
-  if (dtype == FVQA_H16)
-    hipLaunchKernelGGL((visual_proj_fwd_k<bf16_t, 32>), grid, block, 0, st, video, W, temporal, vf_raw,
-                       (bf16_t*)vf_tok, n_frames_total, max_feats, in_dim, dim);
-  else
-    hipLaunchKernelGGL((visual_proj_fwd_k<float, 32>), grid, block, 0, st, video, W, temporal, vf_raw,
-                       (float*)vf_tok, n_frames_total, max_feats, in_dim, dim);
+  const ProjSrc one{video, W, in_dim, in_dim, in_dim};      // one contiguous source, no bias
+  proj_fwd_launch(ProjSrcs{{one, one}, 1}, in_dim % 64 == 0, nullptr, temporal, vf_raw, vf_tok, n_frames_total, max_feats, dim,
+                  dtype, (hipStream_t)stream);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
@@ -880,12 +781,8 @@ extern "C" int fvqa_visual_proj_bwd(const float* d_tok, const float* d_qav, cons
     return FVQA_ESHAPE;
   if (!fvqa_aligned(16, video, dW) || !fvqa_aligned(4, d_tok, d_qav, dtemporal)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (in_dim <= 1024)        // 4 features per wave (4 x 16 accumulators), 4 waves per CU at D = 4096
-    hipLaunchKernelGGL((visual_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16), dim3(256), 0, st, d_tok, d_qav, video, dW,
-                       n_frames_total, in_dim, dim);
-  else
-    hipLaunchKernelGGL((visual_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8), dim3(256), 0, st, d_tok, d_qav, video, dW,
-                       n_frames_total, in_dim, dim);
+  const ProjSrc one{video, dW, in_dim, in_dim, in_dim};     // one contiguous source, gradient pitch = dim, no dbias
+  proj_bwd_launch(d_tok, d_qav, ProjSrcs{{one, one}, 1}, n_frames_total, dim, dim, nullptr, st);
   hipLaunchKernelGGL(temporal_bwd_k, dim3((max_feats * dim + 255) / 256), dim3(256), 0, st, d_tok, dtemporal,
                      n_frames_total / max_feats, max_feats, dim);
   FVQA_CHECK_LAUNCH();
@@ -897,25 +794,11 @@ extern "C" int fvqa_av_proj_fwd(const fvqa_proj_src* src, int n_src, const float
   if (!out_raw || (temporal != nullptr) != (out_tok != nullptr)) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (rows <= 0 || dim <= 0 || (temporal && max_feats <= 0)) return FVQA_ESHAPE;
-  AvSrcs S;
+  ProjSrcs S;
   bool mfma_ok;
-  if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int F = max_feats > 0 ? max_feats : 1;
-  const dim3 block(256);
-  if (mfma_ok && rows <= 128) {
-    const dim3 g16((dim + 15) / 16);
-    if (dtype == FVQA_H16)
-      hipLaunchKernelGGL(av_proj_fwd_mfma_k<bf16_t>, g16, block, 0, st, S, bias, temporal, out_raw, (bf16_t*)out_tok, rows, F, dim);
-    else
-      hipLaunchKernelGGL(av_proj_fwd_mfma_k<float>, g16, block, 0, st, S, bias, temporal, out_raw, (float*)out_tok, rows, F, dim);
-  } else {
-    const dim3 grid((dim + 3) / 4);
-    if (dtype == FVQA_H16)
-      hipLaunchKernelGGL(av_proj_fwd_k<bf16_t>, grid, block, 0, st, S, bias, temporal, out_raw, (bf16_t*)out_tok, rows, F, dim);
-    else
-      hipLaunchKernelGGL(av_proj_fwd_k<float>, grid, block, 0, st, S, bias, temporal, out_raw, (float*)out_tok, rows, F, dim);
-  }
+  if (int rc = proj_pack(src, n_src, &S, &mfma_ok)) return rc;
+  proj_fwd_launch(S, mfma_ok, bias, temporal, out_raw, out_tok, rows, max_feats > 0 ? max_feats : 1, dim, dtype,
+                  (hipStream_t)stream);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
@@ -938,26 +821,12 @@ extern "C" int fvqa_av_proj_bwd(const float* d_tok, const float* d_qav, const fv
   if (rows <= 0 || max_feats <= 0 || rows % max_feats || dim <= 0) return FVQA_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
   if (n_src) {                                              // (audio_only has no trainable projection: the temporal sum alone)
-    AvSrcs S;
+    ProjSrcs S;
     bool mfma_ok;
-    if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
-    bool narrow = true;
-    for (int s = 0; s < n_src; ++s) {
+    if (int rc = proj_pack(src, n_src, &S, &mfma_ok)) return rc;
+    for (int s = 0; s < n_src; ++s)
       if (src[s].k > 2048) return FVQA_ESHAPE;
-      narrow = narrow && src[s].k <= 1024;
-    }
-    if (narrow) {              // every source in one launch (grid.y)
-      hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, d_tok, d_qav, S, rows, dim, dim,
-                         (float*)nullptr);
-    } else {
-      for (int s = 0; s < n_src; ++s) {
-        AvSrcs one = S;
-        one.s[0] = S.s[s];
-        one.n = 1;
-        hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, d_tok, d_qav, one, rows, dim, dim,
-                           (float*)nullptr);
-      }
-    }
+    proj_bwd_launch(d_tok, d_qav, S, rows, dim, dim, nullptr, st);
   }
   hipLaunchKernelGGL(temporal_bwd_k, dim3((max_feats * dim + 255) / 256), dim3(256), 0, st, d_tok, dtemporal,
                      rows / max_feats, max_feats, dim);
@@ -998,27 +867,12 @@ extern "C" int fvqa_av_linear_bwd(const float* g, int ldg, const fvqa_proj_src* 
   if (!g) return FVQA_EINVAL;
   if (rows <= 0 || dim <= 0 || ldg < dim) return FVQA_ESHAPE;
   if (ldg % 4 || (((uintptr_t)g | (uintptr_t)dbias) & 15)) return FVQA_EALIGN;
-  AvSrcs S;
+  ProjSrcs S;
   bool mfma_ok;
-  if (int rc = av_pack(src, n_src, &S, &mfma_ok)) return rc;
-  bool narrow = true;
-  for (int s = 0; s < n_src; ++s) {
+  if (int rc = proj_pack(src, n_src, &S, &mfma_ok)) return rc;
+  for (int s = 0; s < n_src; ++s)
     if (src[s].k > 2048) return FVQA_ESHAPE;
-    narrow = narrow && src[s].k <= 1024;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (narrow) {
-    hipLaunchKernelGGL((av_proj_bwd_k<16, 4, 8>), dim3((dim + 15) / 16, n_src), dim3(256), 0, st, g, (const float*)nullptr, S,
-                       rows, dim, ldg, dbias);
-  } else {
-    for (int s = 0; s < n_src; ++s) {                         // (blockIdx.y == 0 in each: the bias rides on the first only)
-      AvSrcs one = S;
-      one.s[0] = S.s[s];
-      one.n = 1;
-      hipLaunchKernelGGL((av_proj_bwd_k<32, 2, 4>), dim3((dim + 7) / 8, 1), dim3(256), 0, st, g, (const float*)nullptr, one,
-                         rows, dim, ldg, s == 0 ? dbias : (float*)nullptr);
-    }
-  }
+  proj_bwd_launch(g, nullptr, S, rows, dim, ldg, dbias, (hipStream_t)stream);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

@@ -691,13 +691,15 @@ int fvqa_attn_bwd_rotated(const void* d_o, const void* qkv, const void* o, const
 
 /* ---- visual projection + temporal embedding (llama/model.py:322,324) ------------------
  * vf_raw[b,f,:] = video[b,f,:]·W^T (fp32, kept for the QAV head); vf_tok = storage-dtype
- * cast of vf_raw + temporal[f,:]. video (BF, in_dim) fp32, W (dim, in_dim) fp32. */
+ * cast of vf_raw + temporal[f,:]. video (BF, in_dim) fp32, W (dim, in_dim) fp32, in_dim <= 2048.
+ * The launch of fvqa_av_proj_fwd on one contiguous source (both pitches = in_dim), no bias. */
 int fvqa_visual_proj_fwd(const float* video, const float* W, const float* temporal, float* vf_raw,
                          void* vf_tok, int n_frames_total, int max_feats, int in_dim, int dim,
                          int dtype, void* stream);
 /* d_tok (BF,dim) fp32: gradient wrt the spliced frame tokens (fvqa_splice_bwd); d_qav (BF,dim)
  * fp32 or NULL: extra gradient wrt vf_raw from the QAV head.
- * dW (dim,in_dim) += (d_tok + d_qav)^T·video ; dtemporal (F,dim) += sum_b d_tok[b]. */
+ * dW (dim,in_dim) += (d_tok + d_qav)^T·video ; dtemporal (F,dim) += sum_b d_tok[b].
+ * The launches of fvqa_av_proj_bwd on one contiguous source. */
 int fvqa_visual_proj_bwd(const float* d_tok, const float* d_qav, const float* video, float* dW,
                          float* dtemporal, int n_frames_total, int max_feats, int in_dim, int dim,
                          void* stream);
@@ -740,7 +742,7 @@ int fvqa_av_cross_attn_bwd(const float* q, const float* k, const float* v, const
 int fvqa_av_proj_dx(const float* g0, const float* g1, const float* w, float* dx, int rows, int dim, int k, int ldg, int ldw,
                     int lddx, void* stream);
 /* Weight (+ bias) gradient of a linear layer: dW_s (dim, k_s | ldw) += g^T·x_s for each of n_src = 1..2 sources, g (rows, dim |
- * ldg) — fvqa_av_proj_bwd's kernel for a general, pitched g; dbias (dim) += sum_rows g, or NULL. */
+ * ldg) — fvqa_av_proj_bwd's kernel and launches for a general, pitched g; dbias (dim) += sum_rows g, or NULL. */
 int fvqa_av_linear_bwd(const float* g, int ldg, const fvqa_proj_src* src, int n_src, float* dbias, int rows, int dim,
                        void* stream);
 

@@ -34,14 +34,16 @@ def _layout(layout, R, D, seed):
         v, a = rnd(R, KV, seed=seed), rnd(R, KA, seed=seed + 1)
         Wv, Wa = rnd(D, KV, scale=1 / math.sqrt(KV), seed=seed + 2), rnd(D, KA, scale=1 / math.sqrt(KA), seed=seed + 3)
         return [(a, Wa, 0), (v, Wv, 0)], a.double() @ Wa.double().T + v.double() @ Wv.double().T
-    k = KA if layout == "only" else KV                       # "proj": the one-source projections of `attention`
+    # "proj": the one-source projections of `attention`; "wide": one source past the 2048 columns the wave-per-feature kernel
+    # holds in registers, K % 64 != 0: streamed by it at every row count
+    k = {"only": KA, "proj": KV, "wide": 2052}[layout]
     x, W = rnd(R, k, seed=seed), rnd(D, k, scale=1 / math.sqrt(k), seed=seed + 2)
     return [(x, W, 0)], x.double() @ W.double().T
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("rows", [8, 80, 128, 130])           # 130: beyond the MFMA form's 128 rows, the wave-per-feature fallback
-@pytest.mark.parametrize("layout", ["concat", "sum", "only", "proj"])
+@pytest.mark.parametrize("layout", ["concat", "sum", "only", "proj", "wide"])
 def test_av_proj_fwd_against_fp64(layout, rows, dtype):
     F = 10 if rows % 10 == 0 else 8
     for D in (256, 4096, 5120):

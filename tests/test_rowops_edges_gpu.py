@@ -613,7 +613,9 @@ VP_SHAPES = [(128, 8, 64, 520),       # nrb = 8 on the MFMA kernel, D % 16 = 8, 
              (120, 10, 832, 512),     # MFMA kernel, K / 4 = 208: three full trips of four k-steps and a partial one
              (129, 3, 768, 520),      # one row past the MFMA kernel: the wave kernel with K % 64 == 0
              (160, 10, 768, 512),     # batch 16
-             (30, 10, 1792, 40)]      # K > 1024: the <32, 2, 4> backward; D % 16 = 8
+             (30, 10, 1792, 40),      # K > 1024: the <32, 2, 4> backward; D % 16 = 8
+             (30, 10, 100, 24)]       # K % 64 != 0 at few rows: the wave kernel on a ragged K; 6 live rows in the last <16, 4, 8>
+                                      # trip; D % 16 = 8 in a grid of two workgroups
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

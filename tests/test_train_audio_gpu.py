@@ -158,6 +158,10 @@ def test_linear_bwd_weight_and_bias_against_fp64(rows):
     dW, db = torch.ones(D, E + KA, device=DEV), torch.ones(D, device=DEV)
     ops.av_linear_bwd(gd, [(dev(w), dW)], db)
     assert rel(dW - 1, G.T @ w.double()) < VP_F32 and rel(db - 1, G.sum(0)) < VP_F32
+    # a wide source and a narrow one in one call: one launch each, the bias still added once
+    dW, db = torch.ones(D, 2 * E + KA, device=DEV), torch.ones(D, device=DEV)
+    ops.av_linear_bwd(gd, [(dev(w), dW[:, :E + KA]), (dev(x), dW[:, E + KA:])], db)
+    assert rel(dW - 1, G.T @ torch.cat([w, x], 1).double()) < VP_F32 and rel(db - 1, G.sum(0)) < VP_F32
 
 
 def test_av_proj_bwd_keeps_its_results_beside_the_grown_kernel():
