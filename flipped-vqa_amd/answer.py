@@ -7,7 +7,10 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
         [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
         [--lookahead T --lookup_ngram G] [--jump_forward T] [--frame_attention] [--json FILE]
     python answer.py ... --features clip.pth --questions FILE --slots N [--admit M]
+    python answer.py ... --question "..." --answer_vocab FILE --rank N [--contrast blind]
 
+`--answer_vocab FILE --rank N` decodes nothing: every answer of the file is scored exactly in one pass over their trie
+(fvqa.vocab.score_vocab) and the N best (1 .. 8, by the mean log-probability of their tokens) are printed with their posterior.
 `--constrain` (with --options) makes the answer one of the options and prints its index; `--answer_vocab FILE` (one answer per
 line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
 `--contrast blind` (train.py's flag) picks every token from the difference to the prompt's video-blind twin — the same text with
@@ -72,6 +75,9 @@ def get_args_parser():
                         "(0, 1: off)")
     p.add_argument("--frame_attention", action="store_true",
                    help="print the share of attention each frame of the clip received from the answer's tokens, and their sum")
+    p.add_argument("--rank", type=int, default=0, metavar="N",
+                   help="with --answer_vocab: print the N best answers of the vocabulary (1 .. 8) with their posterior — every "
+                        "allowed answer is scored exactly in one pass (fvqa.vocab.score_vocab), nothing is decoded")
     p.add_argument("--json", type=str, default=None, metavar="FILE",
                    help="write the answers (with --frame_attention: frame_share and video_mass too) as a JSON list")
     p.set_defaults(max_seq_len=128, seed=None)
@@ -140,6 +146,23 @@ def main(args):
         allowed = list(args.options)
     elif args.answer_vocab:
         allowed = constrain.read_answer_vocab(args.answer_vocab)
+    if args.rank:                                 # the classifier over the vocabulary: the N best members with their posterior
+        kw = {"contrast": args.contrast, "contrast_alpha": args.contrast_alpha} if args.contrast else {}
+        r = model.score_vocab(batch, constrain.encode_answers(tok, allowed), top=args.rank, **kw)
+        rank, post, mean = r["ranking"].cpu(), r["log_posterior"].exp().cpu(), r["mean"].cpu()
+        records = []
+        for b, q in enumerate(questions):
+            best = [(int(c), float(post[b, c]), float(mean[b, c])) for c in rank[b].tolist() if c >= 0]
+            if n_q > 1:
+                print(q)
+            for c, p, m in best:
+                print(f"{p:.4f}\t{allowed[c]}\t[member {c}, mean log-probability {m:.4f}]")
+            records.append({"ranking": [{"answer": allowed[c], "posterior": p} for c, p, _ in best]})
+        if args.json:
+            import json
+            with open(args.json, "w") as f:
+                json.dump(records, f)
+        return records
     kw = {} if allowed is None else {"constraints": constrain.encode_answers(tok, allowed)}
     if args.contrast:
         kw.update(contrast=args.contrast, contrast_alpha=args.contrast_alpha, contrast_beta=args.contrast_beta)
@@ -212,5 +235,7 @@ if __name__ == "__main__":
         parser.error("one of --question TEXT and --questions FILE")
     if (a.questions is not None) != (a.slots >= 1):
         parser.error("--questions FILE and --slots N come together")
+    if a.rank and (not a.answer_vocab or a.constrain or not 1 <= a.rank <= 8 or a.slots >= 1):
+        parser.error("--rank N (1 .. 8) ranks the answers of --answer_vocab FILE: not with --constrain or --slots")
     train.validate_args(a)
     main(a)

@@ -37,6 +37,9 @@
 //   its own: which products hipcc contracts into fmas in the score and value passes changes when the same text is inlined from
 //   a __device__ function, and with it the last bit of the output (profiles/suffix_refactor.log).
 //
+// fvqa_attn_suffix_tree — a kernel of its own beside the template (attn_suffix_tree_k, below it): the suffix rows of a sample are the
+//   nodes of a tree, a row sees the cache and its ancestors-or-self (fvqa/vocab.py: every allowed answer in one pass).
+//
 // fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
 //   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
 //   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
@@ -408,6 +411,209 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
   }
 }
 
+constexpr int TREE_DEPTH = FVQA_TREE_DEPTH_MAX;      // deepest row of fvqa_attn_suffix_tree: a tile's ancestor chain fits one chunk
+static_assert(TREE_DEPTH < KC, "the chain of a tile's first row is one chunk of keys");
+
+// fvqa_attn_suffix_tree — the suffix rows of a sample are the nodes of a TREE (fvqa/vocab.py: the internal nodes of a trie of
+// allowed answers, numbered in pre-order). Row r sits at position start[n] + depth[r] and sees the cache rows [0, start[n]), the
+// rows that are its ancestors-or-self and the adapter keys. In pre-order, a is an ancestor-or-self of q iff a <= q < end[a], and
+// every ancestor of a row of the 32-row tile from q0 lies in the tile or is an ancestor of q0: the tile's suffix keys are ONE
+// chunk of q0's ancestors (anc, root first: depth[q0] <= 31 of them) and ONE chunk of the tile's own rows, both under the interval
+// test. One workgroup per (head, sample, tile), as WIDE has them. The tile is attn_suffix_k's, written out again (a kernel of its
+// own: the four entries above keep their text and their code): what differs is where a key row and its position come from and
+// who sees it. Every index read from depth / end / anc is clamped before it is used.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_suffix_tree_k(const T* __restrict__ suf, const T* __restrict__ cache,
+                                                          T* __restrict__ o_suf, const float* __restrict__ gate1,
+                                                          const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
+                                                          const int32_t* __restrict__ start_p, const int32_t* __restrict__ rows_p,
+                                                          const int32_t* __restrict__ depth_p, const int32_t* __restrict__ end_p,
+                                                          const int32_t* __restrict__ anc_p, const float* __restrict__ cs,
+                                                          const float* __restrict__ sn, int B, int R, int S, int H, int A, int F,
+                                                          int cache_rot) {
+  __shared__ __attribute__((aligned(16))) float Qs[QT][KLD];
+  __shared__ __attribute__((aligned(16))) float Ks[KC][KLD];
+  __shared__ __attribute__((aligned(16))) float Vs[KC][DH];
+  __shared__ __attribute__((aligned(16))) float Ps[QT][KC];
+  __shared__ float mrun[QT], lrun[QT], alpha[QT];
+  const int tid = threadIdx.x;
+  const int h = blockIdx.x, n = blockIdx.y, q0 = blockIdx.z * QT;
+  const int D = H * DH;
+  const size_t ld = (size_t)3 * D;
+  int start = start_p[n];
+  start = start < 0 ? 0 : (start > S - 1 ? S - 1 : start);
+  int NR = rows_p[n];
+  NR = NR < 0 ? 0 : (NR > R ? R : NR);
+  const int dmax = S - 1 - start < TREE_DEPTH ? S - 1 - start : TREE_DEPTH;     // a row's position stays inside the sequence
+  const T* seq = cache + (size_t)n * S * ld + h * DH;
+  const T* arow = cache + (size_t)B * S * ld + h * DH;
+  const T* sufn = suf + (size_t)n * R * ld + h * DH;
+  const int32_t* depth = depth_p + (size_t)n * R;
+  const int32_t* end = end_p + (size_t)n * R;
+  const int32_t* anc = anc_p + ((size_t)n * gridDim.z + blockIdx.z) * KC;
+  const auto depth_of = [&](int r) { const int d = depth[r]; return d < 0 ? 0 : (d > dmax ? dmax : d); };
+  const auto end_of = [&](int r) { const int e = end[r]; return e < r + 1 ? r + 1 : (e > NR ? NR : e); };
+  const float scale = rsqrtf((float)DH);
+  const int vs = vstart[n];
+  const float g2 = gate2[h];
+  const float tg1 = tanhf(gate1[h]);
+  const int srow = tid >> 3, sd0 = (tid & 7) * 16;         // staging role: 8 threads per row, 16 head dims each
+  const int kk = tid & 31, qg = tid >> 5;                  // score role: key column kk, queries 4*qg .. 4*qg + 3
+  const int vd = tid & 127, qh = tid >> 7;                 // value role: head dim vd, queries 16*qh .. 16*qh + 15
+  if (q0 >= NR) {                                          // a tile of padding rows (the whole workgroup takes this branch)
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int r = q0 + 16 * qh + u;
+      if (r < R) o_suf[((size_t)n * R + r) * D + h * DH + vd] = from_f32<T>(0.f);
+    }
+    return;
+  }
+  const int n_anc = depth_of(q0);                          // q0's proper ancestors: the keys of the chain chunk
+  // ---- the tile's queries
+  {
+    const int qi = q0 + srow;
+    float v[16];
+    if (qi < NR) {
+      load16<T>(sufn + (size_t)qi * ld + sd0, v);
+      rope16<T>(v, cs, sn, start + depth_of(qi), sd0);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = 0.f;
+    }
+    store16(&Qs[srow][sd0], v);
+    if (tid < QT) { mrun[tid] = -1e30f; lrun[tid] = 0.f; }
+  }
+  float acc[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) acc[u] = 0.f;
+  int qr[4], qpos[4];                                      // what this thread's four score queries are
+  bool qok[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    qr[u] = q0 + 4 * qg + u;
+    qok[u] = qr[u] < NR;
+    qpos[u] = start + (qok[u] ? depth_of(qr[u]) : 0);
+  }
+  const int n_pre = (start + KC - 1) / KC, n_chain = n_anc > 0 ? 1 : 0;
+  // chunks: [0, n_pre) cached prompt keys, the chain of q0 (if it has one), the tile's own rows, then the adapter keys (own softmax)
+  for (int ch = 0; ch <= n_pre + n_chain + 1; ++ch) {
+    const int kind = ch < n_pre ? 0 : (ch < n_pre + n_chain ? 1 : (ch == n_pre + n_chain ? 2 : 3));
+    __syncthreads();                                       // the previous chunk's readers are done (and Qs / mrun are written)
+    if (kind == 3 && tid < QT) {                           // text softmax closed: o = acc / l, then the adapter's share is added
+      alpha[tid] = lrun[tid] > 0.f ? 1.f / lrun[tid] : 0.f;
+      mrun[tid] = -1e30f;
+    }
+    // the suffix row a key column of this chunk holds (kinds 1 and 2), -1: none
+    const auto key_row = [&](int c) {
+      if (kind == 1) {
+        if (c >= n_anc) return -1;
+        const int a = anc[c];
+        return a < 0 || a >= q0 ? -1 : a;                  // (an ancestor of q0 lies in front of it)
+      }
+      return q0 + c < NR ? q0 + c : -1;
+    };
+    // ---- stage the chunk's keys and values
+    {
+      float k[16], v[16];
+      const T* row = nullptr;
+      int pos = 0;
+      bool rot = false;
+      if (kind == 0) {
+        const int ki = ch * KC + srow;
+        if (ki < start) { row = seq + (size_t)ki * ld; pos = ki; rot = !cache_rot; }
+      } else if (kind == 3) {
+        if (srow < A) row = arow + (size_t)srow * ld;
+      } else {
+        const int r = key_row(srow);
+        if (r >= 0) { row = sufn + (size_t)r * ld; pos = start + depth_of(r); rot = true; }
+      }
+      if (row) {
+        load16<T>(row + D + sd0, k);
+        load16<T>(row + 2 * D + sd0, v);
+        if (rot) rope16<T>(k, cs, sn, pos, sd0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) k[e] = v[e] = 0.f;
+      }
+      store16(&Ks[srow][sd0], k);
+      store16(&Vs[srow][sd0], v);
+    }
+    __syncthreads();
+    // ---- scores of (4 queries) x (key kk)
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int d = 0; d < DH; d += 4) {
+      const float4 k4 = *reinterpret_cast<const float4*>(&Ks[kk][d]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float4 q4 = *reinterpret_cast<const float4*>(&Qs[4 * qg + u][d]);
+        s[u] += q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
+      }
+    }
+    int kpos = ch * KC + kk, kr = -1, kend = 0;
+    bool kok;
+    if (kind == 0) {
+      kok = kpos < start;
+    } else if (kind == 3) {
+      kok = kk < A;
+    } else {
+      kr = key_row(kk);
+      kok = kr >= 0;
+      if (kok) { kpos = start + depth_of(kr); kend = end_of(kr); }
+    }
+    const bool frame_key = kind != 3 && kok && vs >= 0 && kpos >= vs && kpos < vs + F;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      bool see = qok[u] && kok;
+      if (kind == 1 || kind == 2) see = see && kr <= qr[u] && qr[u] < kend;      // ancestor-or-self
+      float x = s[u] * scale;
+      if (frame_key && qpos[u] >= vs + F) x += g2;
+      x = see ? x : -1e30f;
+      const int q = 4 * qg + u;
+      const float m_old = mrun[q];
+      const float m_new = fmaxf(m_old, half_max(x));
+      const float e = see ? __expf(x - m_new) : 0.f;
+      const float sum = half_sum(e);
+      if (kind == 3) {
+        Ps[q][kk] = sum > 0.f ? e / sum * tg1 : 0.f;
+      } else {
+        Ps[q][kk] = e;
+        if (kk == 0) {
+          const float a = __expf(m_old - m_new);
+          alpha[q] = a;
+          lrun[q] = lrun[q] * a + sum;
+        }
+      }
+      if (kk == 0) mrun[q] = m_new;        // (read above by this half wave only: each query belongs to one)
+    }
+    __syncthreads();
+    // ---- values: acc[q] = acc[q] * alpha[q] + sum_k P[q][k] V[k][vd]
+    float vcol[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) vcol[k] = Vs[k][vd];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int q = 16 * qh + u;
+      float a = acc[u] * alpha[q];
+#pragma unroll
+      for (int k = 0; k < KC; k += 4) {
+        const float4 p4 = *reinterpret_cast<const float4*>(&Ps[q][k]);
+        a += p4.x * vcol[k];
+        a += p4.y * vcol[k + 1];
+        a += p4.z * vcol[k + 2];
+        a += p4.w * vcol[k + 3];
+      }
+      acc[u] = a;
+    }
+  }
+  // ---- the tile's output rows (padding rows: zeros)
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int r = q0 + 16 * qh + u;
+    if (r < R) o_suf[((size_t)n * R + r) * D + h * DH + vd] = from_f32<T>(r < NR ? acc[u] : 0.f);
+  }
+}
+
 // one workgroup per sample: clear, scatter, reduce per option, pick
 __global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ rowloss, const int32_t* __restrict__ map, int M,
                                                      float* __restrict__ il, float* __restrict__ sum_o,
@@ -531,6 +737,36 @@ extern "C" int fvqa_attn_suffix_wide(const void* qkv_suf, const void* qkv_cache,
   return suffix_launch<false, false, true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq,
                                            n_options, suffix_len, seq_len, n_heads, head_dim, adapter_len, max_feats,
                                            cache_rotated, dtype, stream);
+}
+
+extern "C" int fvqa_attn_suffix_tree(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1,
+                                     const float* gate2, const int32_t* vstart, const int32_t* start, const int32_t* n_rows,
+                                     const int32_t* depth, const int32_t* end, const int32_t* tile_anc, const float* cos_t,
+                                     const float* sin_t, int n_seq, int rows, int seq_len, int n_heads, int head_dim,
+                                     int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream) {
+  if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !n_rows || !depth || !end || !tile_anc ||
+      !cos_t || !sin_t)
+    return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (n_seq <= 0 || rows <= 0 || rows > FVQA_TREE_ROWS_MAX || seq_len <= 0 || n_heads <= 0 || head_dim != DH || adapter_len < 0 ||
+      adapter_len > 16 || max_feats < 0)
+    return FVQA_ESHAPE;
+  if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || (long long)n_seq * rows > FVQA_TREE_TOTAL_ROWS_MAX) return FVQA_ESHAPE;
+  if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
+  if (((uintptr_t)vstart | (uintptr_t)start | (uintptr_t)n_rows | (uintptr_t)depth | (uintptr_t)end | (uintptr_t)tile_anc) & 3)
+    return FVQA_EALIGN;
+  const dim3 grid(n_heads, n_seq, (rows + QT - 1) / QT), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FVQA_H16)
+    hipLaunchKernelGGL(attn_suffix_tree_k<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
+                       (bf16_t*)o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc, cos_t, sin_t, n_seq, rows,
+                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
+  else
+    hipLaunchKernelGGL(attn_suffix_tree_k<float>, grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
+                       (float*)o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc, cos_t, sin_t, n_seq, rows,
+                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
 }
 
 extern "C" int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,

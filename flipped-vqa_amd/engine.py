@@ -128,6 +128,40 @@ def _val_flipped(owner, data, log, optimizer, args):
                acc_qav=hit[3].sum().item() / bsz, vaq_loss=float(packed[-2]), qav_loss=float(packed[-1]))
 
 
+def vocab_gold(data, answers) -> list:
+    """Per sample the index of its gold answer's text in `answers` (the --answer_vocab list), -1 if it is not a member. The gold
+    text is the option the batch's `answer` names (MusicAVQA: its one free-text option)."""
+    where = {}
+    for i, a in enumerate(answers):
+        where.setdefault(str(a).strip(), i)
+    return [where.get(str(t["options"][int(g)]).strip(), -1) for t, g in zip(data["text"], data["answer"].tolist())]
+
+
+def _val_vocab(owner, data, log, optimizer, args):
+    """One generation batch under --val_vocab: the prediction, the top-5 hit, the gold answer's -log posterior and whether it is
+    in the vocabulary, in ONE host read."""
+    if not hasattr(owner, "score_vocab") or not hasattr(owner, "answer_vocab"):
+        raise NotImplementedError("--val_vocab needs a model with score_vocab and answer_vocab (llama/model.py)")
+    bsz = data["answer"].shape[0]
+    answers, cons = owner.answer_vocab()
+    contrast = getattr(args, "contrast", None)
+    kw = {"contrast": contrast, "contrast_alpha": float(getattr(args, "contrast_alpha", 1.0))} if contrast else {}
+    with torch.no_grad():
+        r = owner.score_vocab(data, cons, top=min(5, len(answers)), **kw)
+    gold = torch.as_tensor(vocab_gold(data, answers), dtype=torch.int64).to(r["prediction"].device, non_blocking=True)
+    inside = gold >= 0
+    nll = -r["log_posterior"].gather(1, gold.clamp(min=0).view(-1, 1)).view(-1)
+    f = lambda t: t.to(torch.float64)                      # noqa: E731
+    packed = torch.stack([f((r["prediction"] == gold) & inside), f((r["ranking"] == gold.view(-1, 1)).any(1) & inside), f(inside),
+                          torch.where(inside, f(nll), torch.zeros_like(f(nll)))]).cpu()
+    hit, n_in = packed[0].bool(), int(packed[2].sum())
+    misc.log_qtype(data, hit, log, args)
+    log.update(lr=optimizer.param_groups[0]["lr"])
+    log.update(n=bsz, acc=float(packed[0].sum()) / bsz, acc_top5=float(packed[1].sum()) / bsz, gold_in_vocab=n_in / bsz)
+    if n_in:
+        log.update(n=n_in, gold_nll=float(packed[3].sum()) / n_in)
+
+
 def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer, epoch: int,
                   args=None):
     """Validation with the reference's signature and return value (reference engine.py:59-145), both modes.
@@ -147,6 +181,10 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     `--gen_stream SLOTS` (generation task): the loader's batches are materialised and decoded through ONE stream of SLOTS rows
     with in-flight batching (`model.inference_stream`, fvqa/stream.py) before the per-batch body below runs on each batch's rows;
     without the flag every call launches what it did.
+    `--val_vocab` (generation task, with `--answer_vocab FILE`): the batch is classified over the answer vocabulary
+    (`model.score_vocab`, fvqa/vocab.py: every member's exact log-probability in one pass); `acc`, `acc_top5`, `gold_nll` — the
+    gold answer's -log posterior, over the samples whose gold answer is in the vocabulary — and `gold_in_vocab` come from the
+    batch's one host read. Nothing is decoded.
     `--gen_frame_attention` (generation task, through `generate`): a `video_mass` meter — the weight the answer rows' text softmax
     puts on the frame keys (fvqa/attribution.py) — and `frame_share` in every entry of the extracted-answers file."""
     gen = bool(getattr(args, "is_generation_task", False))
@@ -171,6 +209,12 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     for data in log.log_every(data_loader, max(1, len(data_loader) // 4), f"Epoch: [{epoch}]"):
         answer = data["answer"]
         bsz = answer.shape[0]
+        if gen and getattr(args, "val_vocab", False):
+            owner = owner or next((m for m in (model, getattr(model, "module", None)) if hasattr(m, "score_vocab")), None)
+            _val_vocab(owner, data, log, optimizer, args)
+            if getattr(args, "debug", False):
+                break
+            continue
         if not gen and getattr(args, "val_flipped", False):
             _val_flipped(owner, data, log, optimizer, args)
             if getattr(args, "debug", False):

@@ -54,6 +54,8 @@ SIGNATURES = {
     "fvqa_attn_suffix_wide": (_i, [_p] * 10 + [_i] * 10 + [_p]),
     "fvqa_suffix_embed": (_i, [_p] * 6 + [_i] * 7 + [_p]),
     "fvqa_flipped_pick": (_i, [_p] * 6 + [_f] * 3 + [_p] * 5 + [_i] * 2 + [_p]),
+    "fvqa_attn_suffix_tree": (_i, [_p] * 13 + [_i] * 9 + [_p]),
+    "fvqa_trie_score": (_i, [_p] * 2 + [_i] * 2 + [_p] * 14 + [_i] * 9 + [_p]),
     "fvqa_decode_next": (_i, [_p, _p, _p, _f, _f, _i, _i] + [_p] * 8 + [_i] * 5 + [_p]),
     "fvqa_decode_next_ex": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p]),
     "fvqa_decode_next_trie": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 7 + [_p]),

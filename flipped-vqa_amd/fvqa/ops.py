@@ -716,6 +716,87 @@ def suffix_embed(ids, slot, emb, vf_tok, length, x, n_seq: int, n_options: int, 
     return x
 
 
+TREE_DEPTH_MAX = 31          # depth of a row fvqa_attn_suffix_tree takes (include/fvqa.h FVQA_TREE_DEPTH_MAX)
+TREE_ROWS_MAX = 4096         # rows (and members) per sample (FVQA_TREE_ROWS_MAX)
+TREE_TOTAL_ROWS_MAX = 65536  # n_seq * rows of one pass (FVQA_TREE_TOTAL_ROWS_MAX)
+TREE_TILE = 32               # rows per tile (csrc/score.hip QT)
+TREE_TOP_MAX = 8             # members fvqa_trie_score ranks (csrc/tree.hip TOPMAX)
+
+
+def attn_suffix_tree(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc, rope, n_seq, R, S, H,
+                     Dh, A, F, cache_rotated: bool):
+    """The tree-masked suffix attention (include/fvqa.h fvqa_attn_suffix_tree): qkv_suf (n_seq*R, 3*D) RAW projections of row r of
+    sample n at position start[n] + depth[n, r]; a row sees the cache rows [0, start[n]), its ancestors-or-self among the rows and
+    the adapter keys. n_rows (n_seq), depth / end (n_seq*R), tile_anc (n_seq * ceil(R / 32) * 32): int32, fvqa.vocab.plan_vocab's.
+    Writes o_suf (n_seq*R, D); rows r >= n_rows[n] are padding (zeros). The shapes, dtypes and alignment are checked here; the
+    VALUES of the plan's arrays are the planner's (the kernel clamps what it reads)."""
+    what = "attn_suffix_tree"
+    _need(all(torch.is_tensor(t) for t in (qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc)),
+          f"{what}: tensors")
+    _need(int(n_seq) >= 1 and 1 <= int(R) <= TREE_ROWS_MAX and n_seq * R <= TREE_TOTAL_ROWS_MAX,
+          f"{what}: 1 <= rows per sample <= {TREE_ROWS_MAX}, n_seq * rows <= {TREE_TOTAL_ROWS_MAX}")
+    _need(qkv_cache.dim() == 2 and qkv_suf.dim() == 2 and o_suf.dim() == 2, f"{what}: 2-D rows")
+    D = H * Dh
+    _need(Dh == 128 and 0 <= A <= 16 and F >= 0 and 1 <= S <= 4096, f"{what}: head_dim 128, adapter_len <= 16, seq_len <= 4096")
+    _need(qkv_suf.dtype == qkv_cache.dtype == o_suf.dtype, f"{what}: dtype")
+    _need(tuple(qkv_cache.shape) == (n_seq * S + A, 3 * D), f"{what}: qkv_cache is (n_seq * S + A, 3 * D)")
+    _need(tuple(qkv_suf.shape) == (n_seq * R, 3 * D) and tuple(o_suf.shape) == (n_seq * R, D), f"{what}: row shapes")
+    tiles = (R + TREE_TILE - 1) // TREE_TILE
+    _table(what, _of(_I32, n_seq, vstart=vstart, start=start, n_rows=n_rows) + _of(_I32, n_seq * R, depth=depth, end=end) +
+           _of(_I32, n_seq * tiles * TREE_TILE, tile_anc=tile_anc) + _of(_F32, H, gate1=gate1, gate2=gate2))
+    for name, t in (("qkv_suf", qkv_suf), ("qkv_cache", qkv_cache), ("o_suf", o_suf)):
+        _need(t.data_ptr() % 16 == 0, f"{what}: {name} on a 16-byte boundary")
+    _dev(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc)
+    cos_t, sin_t = _rope_tables(rope, S, Dh, what)
+    _need(cos_t is not None, f"{what}: rope tables")
+    rc = _lib.load(qkv_cache.dtype).fvqa_attn_suffix_tree(
+        _ptr(qkv_suf), _ptr(qkv_cache), _ptr(o_suf), _ptr(gate1), _ptr(gate2), _ptr(vstart), _ptr(start), _ptr(n_rows),
+        _ptr(depth), _ptr(end), _ptr(tile_anc), _ptr(cos_t), _ptr(sin_t), n_seq, R, S, H, Dh, A, F, 1 if cache_rotated else 0,
+        dt_code(qkv_suf.dtype), _stream())
+    _lib.check(rc, "fvqa_attn_suffix_tree")
+    return o_suf
+
+
+def trie_score(tables: dict, edge_lp, n_seq: int, R: int, V: int, *, logits=None, lse=None, row0: int = 0, n_block_rows: int = 0,
+               reduce: bool = False, n_columns: int = 0, top: int = 1, by_mean: bool = True):
+    """The reduction of the tree pass (include/fvqa.h fvqa_trie_score). tables: the int32 device arrays of a plan — edge_parent,
+    edge_token (n_seq, E), n_edges (n_seq,), member_path (n_seq, MU, 32), member_len, member_index (n_seq, MU), n_members
+    (n_seq,); edge_lp (n_seq, E) fp32, in and out. logits (>= n_block_rows, V) fp32 with lse: the block of head rows [row0, row0 +
+    n_block_rows) fills its edges. reduce: -> dict(logprob_sum, count (int64), mean, log_posterior (n_seq, n_columns), ranking
+    (n_seq, top) int64, prediction (n_seq,) int64); None otherwise."""
+    what = "trie_score"
+    ep, et, ne = tables["edge_parent"], tables["edge_token"], tables["n_edges"]
+    mp, ml, mi, nm = tables["member_path"], tables["member_len"], tables["member_index"], tables["n_members"]
+    _need(ep.dim() == 2 and ep.shape[0] == n_seq and ep.shape[1] >= 1, f"{what}: edge_parent is (n_seq, E)")
+    E = int(ep.shape[1])
+    _need(mp.dim() == 3 and mp.shape[0] == n_seq and mp.shape[2] == TREE_DEPTH_MAX + 1 and 1 <= mp.shape[1] <= TREE_ROWS_MAX,
+          f"{what}: member_path is (n_seq, members <= {TREE_ROWS_MAX}, {TREE_DEPTH_MAX + 1})")
+    MU = int(mp.shape[1])
+    _table(what, _of(_I32, n_seq * E, edge_parent=ep, edge_token=et) + _of(_I32, n_seq, n_edges=ne, n_members=nm) +
+           _of(_I32, n_seq * MU, member_len=ml, member_index=mi) + _of(_F32, n_seq * E, edge_lp=edge_lp))
+    _need(1 <= R <= TREE_ROWS_MAX and n_seq * R <= TREE_TOTAL_ROWS_MAX and V >= 1, f"{what}: rows")
+    _need((logits is None) == (lse is None) and (logits is not None or reduce), f"{what}: logits come with lse; nothing to do")
+    if logits is not None:
+        _need(logits.dtype == torch.float32 and lse.dtype == torch.float32 and n_block_rows >= 1 and row0 >= 0
+              and row0 + n_block_rows <= n_seq * R and logits.numel() >= n_block_rows * V and lse.numel() >= n_block_rows,
+              f"{what}: logits (n_block_rows, V) fp32 and lse of a block inside the pass's rows")
+    _need(not reduce or (1 <= top <= TREE_TOP_MAX and n_columns >= 1), f"{what}: 1 <= top <= {TREE_TOP_MAX}, columns >= 1")
+    _dev(logits, lse, ep, et, ne, edge_lp, mp, ml, mi, nm)
+    out, ptrs = None, (None,) * 6
+    if reduce:
+        dev = edge_lp.device
+        f = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=dev)  # noqa: E731
+        out = dict(logprob_sum=f(n_seq, n_columns), count=f(n_seq, n_columns, dtype=torch.int64), mean=f(n_seq, n_columns),
+                   log_posterior=f(n_seq, n_columns), ranking=f(n_seq, top, dtype=torch.int64),
+                   prediction=f(n_seq, dtype=torch.int64))
+        ptrs = tuple(_ptr(out[k]) for k in ("logprob_sum", "count", "mean", "log_posterior", "ranking", "prediction"))
+    rc = _lib.load().fvqa_trie_score(_ptr(logits), _ptr(lse), int(row0), int(n_block_rows), _ptr(ep), _ptr(et), _ptr(ne),
+                                     _ptr(edge_lp), _ptr(mp), _ptr(ml), _ptr(mi), _ptr(nm), *ptrs, n_seq, R, E, MU,
+                                     max(int(n_columns), 1), V, int(top), 1 if by_mean else 0, 1 if reduce else 0, _stream())
+    _lib.check(rc, "fvqa_trie_score")
+    return out
+
+
 FLIPPED_TASKS = ("vqa", "vaq", "qav")
 
 

@@ -490,6 +490,29 @@ class Transformer(nn.Module):
         self.last_scoring = flipped.score_flipped(self.ensure_engine(), data, **kw)
         return self.last_scoring
 
+    def answer_vocab(self):
+        """--answer_vocab FILE, read once: -> (the answers as text, their token sequences as they stand behind a prompt)."""
+        from fvqa import constrain
+        if getattr(self, "_answer_vocab", None) is None:
+            path = getattr(self.args, "answer_vocab", None)
+            if not path:
+                raise ValueError("--val_vocab needs --answer_vocab FILE")
+            answers = constrain.read_answer_vocab(path)
+            self._answer_vocab = (answers, constrain.encode_answers(self.tokenizer, answers))
+        return self._answer_vocab
+
+    @torch.no_grad()
+    def score_vocab(self, data, constraints, **kw):
+        """Every allowed answer's exact log-probability behind the prompts of a generation batch, in one pass over the trie of
+        `constraints` (fvqa/vocab.py: score_vocab, whose keywords these are — route, top, length_penalty, contrast,
+        contrast_alpha, events): -> its result dict, all tensors on the device; the reductions — logprob_sum, count, mean,
+        log_posterior (B, M), ranking (B, top), prediction (B,), route and, under `contrast`, mean_blind / prediction_blind /
+        prediction_plain — are left in `last_scoring`."""
+        from fvqa import vocab
+        r = vocab.score_vocab(self.ensure_engine(), data, constraints, **kw)
+        self.last_scoring = {k: v for k, v in r.items() if k not in ("edge_logprob", "plan")}
+        return r
+
     def forward(self, data, inference=False):
         if inference:
             return self.inference(data)

@@ -128,6 +128,13 @@ _FLAGS = [
     ("--val_flipped_weights", dict(type=float, nargs=2, default=None, metavar=("W_VAQ", "W_QAV"),
                                    help="--val_flipped: the weights of the vaq and qav means (default 1 1, as the training loss "
                                         "sums the three)")),
+    ("--val_vocab", dict(action="store_true",
+                         help="generation-task validation as a classifier over --answer_vocab (fvqa.vocab.score_vocab): every "
+                              "allowed answer's exact log-probability in one pass over their trie; the prediction is the member "
+                              "with the highest mean; logs acc, acc_top5, gold_nll (-log posterior of the gold answer, over the "
+                              "samples whose gold answer is in the vocabulary) and gold_in_vocab. Needs --answer_vocab and "
+                              "--is_generation_task. Not with --num_beams > 1, --lookahead, --gen_jump_forward, --gen_stream or "
+                              "--gen_frame_attention")),
     ("--val_batch_size", dict(type=int, default=None, help="batch size of every split but train (default: --batch_size)")),
     ("--dtype", dict(type=str, choices=["bf16", "fp32"], default="bf16", help="storage dtype of frozen weights/activations")),
     ("--random_init", dict(action="store_true", help="closed-form weights instead of a checkpoint")),
@@ -143,7 +150,8 @@ class ArgumentParser(argparse.ArgumentParser):
     --gen_stream (answer.py: --slots) with a decode the stream does not run (answer.py uses it too), and
     --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it, and --val_frame_attention
     with a validation that does not score options or scores them twice, and --val_flipped with a validation that does not
-    score options or combines their scores another way."""
+    score options or combines their scores another way, and --val_vocab without its vocabulary and generation prompts or with
+    a decode (it runs none)."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -211,6 +219,14 @@ class ArgumentParser(argparse.ArgumentParser):
                 self.error("--val_flipped belongs to multiple-choice validation: not with --is_generation_task")
             if getattr(a, "contrast", None) or getattr(a, "val_frame_attention", False):
                 self.error("--val_flipped combines the three tasks' scores: not with --contrast or --val_frame_attention")
+        if getattr(a, "val_vocab", False):
+            if not getattr(a, "answer_vocab", None) or not getattr(a, "is_generation_task", False):
+                self.error("--val_vocab scores the answers of --answer_vocab FILE behind generation prompts: it needs "
+                           "--answer_vocab and --is_generation_task")
+            if (int(getattr(a, "num_beams", 1) or 1) > 1 or la > 1 or int(getattr(a, "gen_jump_forward", 0) or 0) > 1
+                    or int(getattr(a, "gen_stream", 0) or 0) >= 1 or getattr(a, "gen_frame_attention", False)):
+                self.error("--val_vocab scores every member in one pass, nothing is decoded: not with --num_beams > 1, "
+                           "--lookahead, --gen_jump_forward, --gen_stream or --gen_frame_attention")
         return a
 
 

@@ -351,6 +351,51 @@ int fvqa_flipped_pick(const float* mean_vqa, const float* mean_vaq, const float*
                       const int64_t* count_vaq, const int64_t* count_qav, float w_vqa, float w_vaq, float w_qav,
                       const int64_t* answer, float* total, int64_t* prediction, int64_t* prediction_t, float* gold_loss,
                       int n_seq, int n_options, void* stream);
+/* ---- exact answer-vocabulary scoring (fvqa/vocab.py score_vocab; the attention in csrc/score.hip, the reduction in csrc/tree.hip) ----
+ * The allowed answers of a sample form a trie; its INTERNAL nodes are the suffix rows of the sample, numbered in pre-order (children
+ * in ascending token order), the root — whose input is the prompt's last token — first. Limits of a plan: */
+#define FVQA_TREE_DEPTH_MAX 31         /* depth of a row (root 0): the ancestors of a tile's first row fit one chunk of 32 keys */
+#define FVQA_TREE_ROWS_MAX 4096        /* rows per sample (and members per sample) */
+#define FVQA_TREE_TOTAL_ROWS_MAX 65536 /* n_seq * rows of one pass */
+/* fvqa_attn_suffix_wide's semantics with ONE change: who sees whom among the suffix rows. qkv_suf (n_seq*rows, 3*dim): RAW q | k | v
+ * of row r of sample n — row n*rows + r, sequence position start[n] + depth[n*rows + r]. A query row attends to the cache rows
+ * [0, start[n]) of its sample, to the suffix rows that are its ancestors-or-self (rotated here at their own positions, rounded to
+ * the storage type) and to the adapter keys (own softmax x tanh(gate1)); gate2 on the frame window, cache_rotated and the output
+ * are as the other fvqa_attn_suffix* entries have them. The plan's arrays, int32 on the device:
+ *   n_rows (n_seq)           live rows of the sample; rows r >= n_rows[n] are padding — never loaded, their o rows are zeros;
+ *   depth, end (n_seq*rows)  end[r] = the exclusive end of r's subtree in pre-order: a is an ancestor-or-self of q iff
+ *                            a <= q < end[a];
+ *   tile_anc (n_seq * ceil(rows / 32) * 32)  per tile of 32 rows from q0 the proper ancestors of q0, root first (depth[q0] entries
+ *                            are read): every ancestor of a row of the tile lies in the tile or in this chain.
+ * Every index read from them is clamped (depth to [0, min(31, seq_len - 1 - start[n])], end[r] to [r + 1, n_rows[n]], a chain
+ * entry outside [0, q0) is skipped): a wrong plan gives wrong numbers, never an access outside the operands. One workgroup per
+ * (head, sample, tile); key chunks: the prompt's, the chain's, the tile's own rows, the adapter's. Fixed summation order, no
+ * atomics: two launches give the same bits. Writes o_suf (n_seq*rows, dim) and nothing else. head_dim 128, seq_len <= 4096,
+ * rows <= FVQA_TREE_ROWS_MAX, n_seq*rows <= FVQA_TREE_TOTAL_ROWS_MAX. */
+int fvqa_attn_suffix_tree(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
+                          const int32_t* vstart, const int32_t* start, const int32_t* n_rows, const int32_t* depth,
+                          const int32_t* end, const int32_t* tile_anc, const float* cos_t, const float* sin_t, int n_seq, int rows,
+                          int seq_len, int n_heads, int head_dim, int adapter_len, int max_feats, int cache_rotated, int dtype,
+                          void* stream);
+/* The reduction of the tree pass. An EDGE e of sample n is (edge_parent, edge_token)[n*max_edges + e], e < n_edges[n]: the token
+ * that leads from row edge_parent on. A MEMBER m < n_members[n] is the path member_path[(n*max_members + m)*32 ..] of member_len
+ * edges (root first, its EOS edge last) and lands in column member_index of the (n_seq, n_columns) outputs (the member's index in
+ * the caller's list; each column at most once, in ascending order of m).
+ *   edges    (logits given) lp[e] = logits[g - row0][edge_token] - lse[g - row0] for the edges whose parent row g = n*rows +
+ *            edge_parent lies in [row0, row0 + n_block_rows): logits (n_block_rows, vocab) fp32 and lse (fvqa_ce_fwd's) are one
+ *            block of the head's rows; a launch per block fills edge_lp (n_seq*max_edges) fp32. logits == lse == NULL: edge_lp is
+ *            taken as it stands.
+ *   members  (reduce != 0, the last launch) sum = lp along the path added in that order in fp32, count (int64) = member_len, mean
+ *            = sum / count, log_posterior = sum - logsumexp of the sample's sums; ranking (n_seq, top) int64 = the columns of the
+ *            best `top` <= 8 members, best first, by mean (by_mean != 0) or by sum — the larger wins, a NaN beats every number,
+ *            equal keys and NaNs go to the lower column; -1 behind the sample's last member —, prediction (n_seq) int64 =
+ *            ranking[:, 0]. Columns that are no member's: sum = mean = log_posterior = -inf, count = 0.
+ * One workgroup per sample; fixed order, no float atomics: two launches give the same bits. Indices read from the arrays are clamped. */
+int fvqa_trie_score(const float* logits, const float* lse, int row0, int n_block_rows, const int32_t* edge_parent,
+                    const int32_t* edge_token, const int32_t* n_edges, float* edge_lp, const int32_t* member_path,
+                    const int32_t* member_len, const int32_t* member_index, const int32_t* n_members, float* sum, int64_t* count,
+                    float* mean, float* log_posterior, int64_t* ranking, int64_t* prediction, int n_seq, int rows, int max_edges,
+                    int max_members, int n_columns, int vocab, int top, int by_mean, int reduce, void* stream);
 /* The token step of the generation API (csrc/sample.hip; reference llama/generation.py:17-68 and llama/model.py:438-470): one
  * launch per generated token, one workgroup per sequence, between the LM head and the next token's first RMSNorm.
  * In: logits (n_seq, vocab) fp32, finite; u (n_seq) fp32 in [0, 1) (may be NULL when temperature == 0); emb (vocab, dim) in the

@@ -5,8 +5,10 @@ of each, every call bracketed by device events; the shared route's prompt pass a
 took the suffix rows' projections (the library's launch record + fvqa_gemm_sk_describe). With --errors: the per-option-mean
 errors of both routes against the reference-generated 7B-width fixture in bf16 and fp16 — the figures the bounds of
 tests/test_score_gpu.py are set from. With --frame_attention: the cost of score_options(frame_attention=True), the keyword off and
-on in interleaved pairs on both routes (profiles/score_frame_attention.log). Everything is appended to --log
-(profiles/score_options.log)."""
+on in interleaved pairs on both routes (profiles/score_frame_attention.log). With --vocab N_MEMBERS: fvqa.vocab.score_vocab's tree
+route, its dense route and generate(constraints=..., num_beams=8) on one vocabulary, interleaved, and the tree attention's time per
+layer beside the layer's projections; with --vocab_errors: the errors its tests' bounds are set from (profiles/score_vocab.log).
+Everything is appended to --log (profiles/score_options.log)."""
 import argparse
 import ctypes as C
 import os
@@ -184,8 +186,132 @@ def errors(say):
         torch.cuda.empty_cache()
 
 
+def vocab_members(n: int, seed: int = 5):
+    """n distinct answers of one to four tokens over a pool of 64 tokens: shared prefixes, members that are prefixes of others."""
+    rng = np.random.default_rng(seed)
+    pool = rng.choice(np.arange(1000, 30000), 64, replace=False)
+    out, seen = [], set()
+    while len(out) < n:
+        m = tuple(int(t) for t in rng.choice(pool, int(rng.integers(1, 5))))
+        if m not in seen:
+            seen.add(m)
+            out.append(list(m))
+    return out
+
+
+def vocab_timing(a, say):
+    """score_vocab's tree route, its dense route and generate(constraints=..., num_beams=8) on one vocabulary of --vocab members,
+    interleaved, --reps triples after --warmup calls of each; then one tree call with every projection and every tree attention
+    between device events: the attention's time per layer beside the layer's four projections."""
+    from fvqa import generate, vocab
+    cfg = synth.preset("7b", vaq=False, qav=False, batch_size=a.batch_size, n_layers=a.n_layers, adapter_layer=a.n_layers)
+    eng = make_model(cfg, torch.bfloat16).ensure_engine()
+    opt = synth.make_option_batch(cfg, n_options=1, seed=1)
+    prefix = [int(p) for p in opt["prefix_index"]["vqa"]]
+    ids = opt["text_id"]["vqa"][:, 0:1].clone()
+    for b, p in enumerate(prefix):
+        ids[b, 0, p:] = 0
+    batch = {"video": opt["video"], "text_id": {"vqa": ids}, "label": {"vqa": opt["label"]["vqa"][:, 0:1]},
+             "video_start": opt["video_start"], "prefix_index": {"vqa": prefix}}
+    members = vocab_members(a.vocab)
+    plan = vocab.plan_vocab(vocab.constrain.compile_constraints(members, 2, cfg.vocab_size), a.batch_size, prefix, cfg.max_seq_len)
+    B, S, R = a.batch_size, cfg.max_seq_len, plan.R
+    say(f"vocabulary: {a.vocab} members of 1..4 tokens, {R} rows (internal nodes) and {int(plan.n_edges[0])} edges per sample; "
+        f"7B width, {a.n_layers} layers, bf16, B={B}, S={S}")
+    say(f"rows through the layers: tree {B * S + B * R} (prompt {B * S} + tree {B * R}), dense {B * a.vocab * S}, "
+        f"beam of 8: {B * S} + up to 5 token steps of {8 * B} rows")
+    arms = {"tree": lambda ev=None: vocab.score_vocab(eng, batch, members, route="tree", events=ev),
+            "dense": lambda ev=None: vocab.score_vocab(eng, batch, members, route="dense", events=ev),
+            "beam8": lambda ev=None: generate.generate(eng, batch, temperature=0.0, constraints=members, num_beams=8,
+                                                       length_penalty=1.0, max_new_tokens=8)}
+    for k in arms:
+        for _ in range(a.warmup):
+            arms[k]()
+    torch.cuda.synchronize()
+    rt, rd, rb = arms["tree"](), arms["dense"](), arms["beam8"]()
+    d = float((rt["mean"] - rd["mean"]).abs().max() / rd["mean"][rd["count"] > 0].abs().max())
+    say(f"outputs: mean, tree vs dense, largest difference over the largest |mean| {d:.3e}; predictions equal on "
+        f"{int((rt['prediction'] == rd['prediction']).sum())} of {B}; the beam's choice equals the tree's prediction on "
+        f"{int((rb['choice'].to(rt['prediction'].device) == rt['prediction']).sum())} of {B} (the beam is approximate: 8 slots)")
+    total, parts = {k: [] for k in arms}, {}
+    for _ in range(a.reps):
+        for k in arms:
+            ev = []
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            arms[k](ev)
+            e1.record()
+            e1.synchronize()
+            total[k].append(e0.elapsed_time(e1))
+            for x in ev:
+                parts.setdefault((k, x[0]), []).append(ms(x))
+    med = {k: statistics.median(v) for k, v in total.items()}
+    for k, v in total.items():
+        say(f"{k:6s}: median {med[k]:10.3f} ms  min {min(v):10.3f}  max {max(v):10.3f}  ({a.reps} reps, interleaved)")
+    for (k, name), v in parts.items():
+        say(f"  {k} route, {name}: median {statistics.median(v):10.3f} ms")
+    say(f"  dense / tree = {med['dense'] / med['tree']:.2f}x, beam8 / tree = {med['beam8'] / med['tree']:.2f}x")
+    # one tree call, each projection and each tree attention between events
+    seen = {"attn": [], "gemm": []}
+    real = {"attn": ops.attn_suffix_tree, "gemm": ops.gemm_nt}
+
+    def spy(kind):
+        def f(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = real[kind](*args, **kw)
+            e1.record()
+            seen[kind].append((args[0].shape[0], e0, e1))
+            return out
+        return f
+    ops.attn_suffix_tree, ops.gemm_nt = spy("attn"), spy("gemm")
+    try:
+        arms["tree"]()
+        torch.cuda.synchronize()
+    finally:
+        ops.attn_suffix_tree, ops.gemm_nt = real["attn"], real["gemm"]
+    t_attn = sum(e0.elapsed_time(e1) for _, e0, e1 in seen["attn"])
+    t_proj = sum(e0.elapsed_time(e1) for rows, e0, e1 in seen["gemm"] if rows == B * R)
+    n_proj = sum(1 for rows, _, _ in seen["gemm"] if rows == B * R)
+    say(f"  tree pass per layer ({B * R} rows): fvqa_attn_suffix_tree {t_attn / a.n_layers:8.3f} ms, the layer's projections "
+        f"(QKV, WO, W1|W3, W2: {n_proj} launches in all) {t_proj / a.n_layers:8.3f} ms")
+
+
+def vocab_errors(say):
+    """The figures tests/vocab_util.py's DENSE_MEAN_ERR is set from: the PARENT's dense teacher-forced pass (score_options'
+    dense route on the members written out as options) against the reference-generated vocab fixtures, and both routes of
+    score_vocab by the same figure (tests/test_vocab_gpu.py scale_err)."""
+    sys.path.insert(0, ROOT)
+    from fvqa import vocab
+    from tests import vocab_util as VU
+    from tests.test_vocab_gpu import scale_err
+    for name in VU.FIXTURES:
+        g = VU.load(name)
+        cols = VU.first_columns(g)
+        cfg = synth.preset(VU.MODEL_OF[name].replace("_peakedperm", ""), vaq=False, qav=False, vocab_size=32000, max_seq_len=128,
+                           batch_size=4, peaked_perm=True)
+        say(f"errors against {name} (reference-generated; gaps {np.array2string(g['gap'], precision=4)}):")
+        for dtype in (torch.float32, torch.bfloat16, torch.float16):
+            eng = make_model(cfg, dtype).ensure_engine()
+            r = score.score_options(eng, VU.option_batch(g), route="dense")
+            e = scale_err(-r["sum"].cpu().numpy() / np.maximum(g["count"], 1), g["mean"], cols)
+            say(f"  {str(dtype):15s} parent's dense pass: mean {e:.4e}")
+            for route in vocab.ROUTES:
+                o = vocab.score_vocab(eng, VU.fixture_batch(g), VU.fixture_sets(g), route=route)
+                say(f"  {str(dtype):15s} score_vocab {route:5s}: mean {scale_err(o['mean'].cpu().numpy(), g['mean'], cols):.4e} sum "
+                    f"{scale_err(o['logprob_sum'].cpu().numpy(), g['logprob_sum'], cols):.4e}; prediction "
+                    f"{o['prediction'].tolist()} (fixture {g['prediction'].tolist()})")
+            del eng
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--vocab", type=int, default=0, metavar="N_MEMBERS",
+                    help="measure score_vocab (tree route, dense route) and generate(constraints=..., num_beams=8) on one vocabulary of "
+                         "N members, interleaved, and nothing else (--log defaults to profiles/score_vocab.log)")
+    ap.add_argument("--vocab_errors", action="store_true",
+                    help="the parent's dense pass and both routes of score_vocab against the vocab fixtures (profiles/score_vocab.log)")
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--n_options", type=int, default=5)
     ap.add_argument("--n_layers", type=int, default=32)
@@ -198,6 +324,8 @@ def main():
                          "nothing else (--log defaults to profiles/score_frame_attention.log)")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
+    if a.log is None and (a.vocab or a.vocab_errors):
+        a.log = os.path.join(ROOT, "profiles", "score_vocab.log")
     if a.log is None:
         a.log = os.path.join(ROOT, "profiles", "score_frame_attention.log" if a.frame_attention else "score_options.log")
     if not torch.cuda.is_available():
@@ -214,6 +342,12 @@ def main():
     with torch.no_grad():
         if a.frame_attention:
             frame_attention_cost(a, say)
+            return
+        if a.vocab or a.vocab_errors:
+            if a.vocab_errors:
+                vocab_errors(say)
+            if a.vocab:
+                vocab_timing(a, say)
             return
         if a.errors:
             errors(say)
