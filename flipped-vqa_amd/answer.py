@@ -5,7 +5,7 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
         --question "..." [--options a b c] [--max_new_tokens 31 --temperature 0 --top_p 1 --seed 0] \
         [--num_beams N --length_penalty A] [--top_k K --repetition_penalty R --num_samples N --logprobs] \
         [--constrain | --answer_vocab FILE] [--contrast blind --contrast_alpha A --contrast_beta B] \
-        [--lookahead T --lookup_ngram G] [--jump_forward T] [--frame_attention] [--json FILE]
+        [--lookahead T --lookup_ngram G] [--draft options|vocab --lookahead R] [--jump_forward T] [--frame_attention] [--json FILE]
     python answer.py ... --features clip.pth --questions FILE --slots N [--admit M]
     python answer.py ... --question "..." --answer_vocab FILE --rank N [--contrast blind]
 
@@ -17,6 +17,9 @@ line) makes it one of the file's answers (fvqa.generate.generate(constraints=...
 zero features — and prints how many tokens were plausible per step (fvqa.generate.generate(contrast="blind")).
 `--lookahead T` (train.py's flag; greedy only) verifies a prompt-lookup draft of up to T - 1 tokens per pass and prints how many
 tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
+`--draft options|vocab --lookahead R` (greedy only) drafts the --options, or the answers of --answer_vocab FILE, as a trie and
+verifies it in one tree pass of up to R rows (fvqa.generate.generate(lookahead=R, draft_answers=...)): the plain greedy answer,
+whatever the model says, in about three passes where it is one of the drafted answers.
 `--jump_forward T` (with --constrain or --answer_vocab; greedy only) commits the tokens the trie of allowed answers fixes without
 a pass of their own, up to T per step, and prints the tokens committed per step (fvqa.generate.generate(jump_forward=T)).
 `--frame_attention` prints, under each answer, the weight its tokens' text softmax put on each of the clip's frame keys and their
@@ -73,6 +76,9 @@ def get_args_parser():
     p.add_argument("--jump_forward", type=int, default=0,
                    help="with --constrain / --answer_vocab: up to T tokens per pass where the allowed answers leave no choice "
                         "(0, 1: off)")
+    p.add_argument("--draft", type=str, choices=["options", "vocab"], default=None,
+                   help="with --lookahead R (2 .. 64): draft a trie of likely answers — the --options, or the answers of "
+                        "--answer_vocab — and verify it in one tree pass: greedy's own answer, whatever it is, in fewer passes")
     p.add_argument("--frame_attention", action="store_true",
                    help="print the share of attention each frame of the clip received from the answer's tokens, and their sum")
     p.add_argument("--rank", type=int, default=0, metavar="N",
@@ -140,7 +146,10 @@ def main(args):
     if args.audio_only:
         batch.pop("video", None)
     allowed = None                                # --constrain / --answer_vocab: the allowed answers, as text
-    if args.constrain:
+    drafted = None                                # --draft: likely answers, as text (a draft, not a rule)
+    if args.draft:
+        drafted = list(args.options) if args.draft == "options" else constrain.read_answer_vocab(args.answer_vocab)
+    elif args.constrain:
         if not args.options:
             raise SystemExit("--constrain needs --options")
         allowed = list(args.options)
@@ -181,7 +190,9 @@ def main(args):
                 line += f"\t[choice {c}: {allowed[c]}]" if c >= 0 else "\t[choice -1]"
             print(line)
         return answers
-    if args.lookahead > 1:
+    if drafted is not None:
+        kw.update(lookahead=args.lookahead, draft_answers=constrain.encode_answers(tok, drafted))
+    elif args.lookahead > 1:
         kw.update(lookahead=args.lookahead, lookup_ngram=args.lookup_ngram)
     if args.jump_forward > 1:
         kw.update(jump_forward=args.jump_forward)

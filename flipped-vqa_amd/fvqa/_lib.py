@@ -65,7 +65,9 @@ SIGNATURES = {
     "fvqa_slot_seat": (_i, [_p] * 3 + [_i] + [_p] * 5 + [_i] + [_p] * 10 + [_i] * 3 + [_p]),
     "fvqa_spec_step": (_i, [_p, _p, _p, _i, _i, _i, _i] + [_p] * 15 + [_i] * 6 + [_p]),
     "fvqa_trie_jump_step": (_i, [_p] * 5 + [_i] * 6 + [_p] * 16 + [_i] * 6 + [_p]),
-    "fvqa_beam_step": (_i, [_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
+    "fvqa_tree_spec_step": (_i, [_p] * 7 + [_i] * 5 + [_p] * 22 + [_i] * 7 + [_p]),
+    "fvqa_kv_tree_commit": (_i, [_p] * 7 + [_i] * 9 + [_p]),
+    "fvqa_beam_step": (_i,[_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
     "fvqa_beam_step_trie": (_i, [_p, _p, _i, _i, _i] + [_p] * 16 + [_i] * 8 + [_p]),
     "fvqa_kv_beam_move_scratch": (_sz, [_i, _i, _i, _i, _i]),
     "fvqa_kv_beam_move": (_i, [_p, _p, _p, _sz, _p, _p, _p] + [_i] * 9 + [_p]),

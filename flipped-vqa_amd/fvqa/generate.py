@@ -204,7 +204,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
              constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1,
              lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None, jump_forward: int = 0,
-             frame_attention: bool = False) -> dict:
+             frame_attention: bool = False, draft_answers=None) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -274,6 +274,20 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       contrast, lookahead > 16 (ops.SUFFIX_MAX) or < 0, draft_tokens of another shape or without lookahead >= 2, lookup_ngram
       outside [1, 4], B * T > 65535. Not built: drafts under sampling (they need the rejection rule), under beam search, a trie
       or a contrastive pick; a draft model.
+    draft_answers C (None: every code path above runs untouched; needs lookahead = R, 2 <= R <= 64): the drafts are a TRIE of
+      likely answers — what `constraints` accepts: one list of token sequences, or one list per sample —, verified in one tree pass,
+      `_generate_tree_draft` below. The trie is a draft, not a rule: "ids", "n_generated" and "tokens" are the plain greedy call's,
+      token for token, whatever the model says. A pass feeds up to R rows per sample: a pre-order prefix of the subtree under the
+      row's trie node (ops.attn_suffix_tree: a row sees the cache and its ancestors); the token step walks the tree along the
+      model's own picks (include/fvqa.h fvqa_tree_spec_step states the rule) and ops.kv_tree_commit appends the accepted path to
+      the cache. A row that leaves the trie goes on one token per pass and does not re-enter; once every running row has left
+      (known one step late, as the stop is) the passes carry one row per sample and launch what lookahead's loop launches at T = 1.
+      The results gain "n_committed", "n_drafted" (B, steps) int32 — rows fed minus one — and "rows_per_pass" (steps,) int32: the
+      rows per sample of the pass each step verified (step 0: the prefill's row, 1). return_logprobs is served as under lookahead.
+      ValueError: no lookahead >= 2, R > 64, B * R > 65535, draft_tokens, temperature > 0, top_k, repetition_penalty != 1,
+      num_return_sequences > 1, num_beams > 1, constraints, contrast, jump_forward, frame_attention. Not built: drafts under
+      sampling, beams, constraints or contrast; tree drafts in the stream; a draft root other than the start of the answer;
+      compacting a pass to the live rows of each sample.
     jump_forward T (0 or 1: every code path above runs untouched; needs `constraints`): jump-forward constrained greedy decoding,
       `_generate_jump` below. Once a row's trie node has a single child the next token is fixed whatever the logits say, so a
       token step picks the one token that is a decision and commits the tokens the trie fixes behind it, up to T per step; the
@@ -305,10 +319,25 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
             raise ValueError("generate: frame_attention is not built for num_beams > 1")
         if contrast is not None:
             raise ValueError("generate: frame_attention is not built for contrast")
-        if lookahead >= 2 or draft_tokens is not None:
+        if lookahead >= 2 or draft_tokens is not None or draft_answers is not None:
             raise ValueError("generate: frame_attention is not built for lookahead")
         if jump_forward >= 2:
             raise ValueError("generate: frame_attention is not built for jump_forward")
+    if draft_answers is not None:
+        if int(lookahead) != lookahead or not 2 <= lookahead <= ops.TREE_SPEC_ROWS_MAX:
+            raise ValueError(f"generate: draft_answers are verified by 2 <= lookahead <= {ops.TREE_SPEC_ROWS_MAX} rows per pass")
+        if draft_tokens is not None:
+            raise ValueError("generate: draft_answers and draft_tokens are two drafts: one of them")
+        if jump_forward >= 2:
+            raise ValueError("generate: draft_answers are not built for jump_forward")
+        if temperature > 0 or num_beams != 1:
+            raise ValueError("generate: draft_answers are verified against the GREEDY choice: temperature == 0, num_beams == 1")
+        if top_k != 0 or repetition_penalty != 1 or num_return_sequences != 1:
+            raise ValueError("generate: draft_answers are not built for top_k, repetition_penalty or num_return_sequences")
+        if constraints is not None or contrast is not None:
+            raise ValueError("generate: draft_answers are not built for constraints or contrast (a draft is not a rule)")
+        return _generate_tree_draft(eng, data, R=int(lookahead), draft_answers=draft_answers, max_new_tokens=max_new_tokens,
+                                    stop_at_eos=stop_at_eos, return_logprobs=return_logprobs)
     if int(lookahead) != lookahead or not 0 <= lookahead <= ops.SUFFIX_MAX:
         raise ValueError(f"generate: 0 <= lookahead <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
     if int(jump_forward) != jump_forward or not 0 <= jump_forward <= ops.SUFFIX_MAX:
@@ -556,6 +585,104 @@ def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_ne
     out.update({"n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()})
     if return_logprobs:
         out["logprobs"] = _token_order(st.tokens[:steps], logprobs[:steps], st.inside)
+        out["sum_logprob"] = out["logprobs"].sum(1)
+    return out
+
+
+class _LagOneNarrow(_LagOneStop):
+    """_LagOneStop that also carries the count of running rows still on their draft trie, by the same copy and event."""
+
+    def __init__(self, max_steps: int):
+        super().__init__(max_steps)
+        self.on_trie = torch.empty(max_steps, dtype=torch.int32).pin_memory()
+
+    def queued(self, t: int, n_active: torch.Tensor, n_on_trie: torch.Tensor) -> None:   # noqa: D102
+        self.on_trie[t:t + 1].copy_(n_on_trie, non_blocking=True)
+        super().queued(t, n_active)
+
+    def off_trie(self, t: int) -> bool:
+        """After may_launch(t): has the snapshot of step t - 2 shown no running row on its trie? (It never rises again.)"""
+        return t >= 2 and int(self.on_trie[t - 2]) == 0
+
+
+@torch.no_grad()
+def _generate_tree_draft(eng, data: dict, *, R: int, draft_answers, max_new_tokens: int, stop_at_eos: bool,
+                         return_logprobs: bool) -> dict:
+    """generate(lookahead=R, draft_answers=C): the loop of `_pass_loop` with fvqa_tree_spec_step as its token step and two kinds
+    of pass. WIDE (R rows per sample): the layers with ops.attn_suffix_tree, which writes no cache row — siblings share a position
+    —; every layer's raw q | k | v rows stay in a per-layer buffer (L, B * R, 3 D) — 403 MB at B = 8, R = 64, 7B in 16 bits:
+    rowpass.layers is handed layer i + 1's slice by layer i's attention callback, nothing is copied —, and after the NEXT step
+    ops.kv_tree_commit appends the accepted path to the cache in one launch: step, commit, layers. NARROW (one row per sample,
+    from the step after a snapshot shows no running row on its trie): ops.attn_suffix_append at T = 1 and no commit, what
+    lookahead's loop launches at T = 1."""
+    from . import vocab
+    B = _pass_checks(data, R, max_new_tokens, "lookahead")
+    eos = eng.model.tokenizer.eos_id
+    trie = constrain.compile_constraints(draft_answers, eos, eng.V)
+    trie.roots(B)                                           # (a per-sample set built for another batch size)
+    hp = vocab.plan_draft(trie, B)
+    p = _prefill(eng, data)
+    dev, S, V, L, D = eng.device, p.S, eng.V, eng.L, eng.D
+    plan = {k: torch.as_tensor(hp[k], dtype=torch.int32).to(dev).contiguous() for k in ("n_plan", "token", "depth", "end", "parent")}
+    i32 = dict(dtype=torch.int32, device=dev)
+    W = ops.TREE_SPEC_WALK
+    wide, narrow = rowpass.buffers(eng, B * R, lg=False), rowpass.buffers(eng, B, lg=False)
+    wide.lg = torch.empty(B * R, V, dtype=torch.float32, device=dev)
+    narrow.lg = p.first.to(torch.float32).contiguous().clone()   # the first step finds one row per sample: the prefill's
+    qkv_all = torch.empty(L, B * R, 3 * D, dtype=eng.dtype, device=dev)
+    tiles = lambda r: (r + ops.TREE_TILE - 1) // ops.TREE_TILE    # noqa: E731
+    tree = {r: (torch.zeros(B * r, **i32), torch.zeros(B * r, **i32), torch.full((B * tiles(r) * ops.TREE_TILE,), -1, **i32))
+            for r in (R, 1)}                                # depth, end, tile_anc of the next pass, at either width
+    ids, pos, pos64 = p.ids, p.start.to(torch.int32), p.start.clone()
+    done, n_gen, node, at, n_path, start_old = (torch.zeros(B, **i32) for _ in range(6))
+    length = torch.ones(B, **i32)
+    path = torch.zeros(B, W, **i32)
+    tokens = torch.full((max_new_tokens, B, W), -1, **i32)
+    logprobs = torch.zeros(max_new_tokens, B, W, dtype=torch.float32, device=dev)
+    n_committed, n_drafted = (torch.zeros(max_new_tokens, B, **i32) for _ in range(2))
+    n_active, n_on_trie = torch.zeros(max_new_tokens, **i32), torch.zeros(max_new_tokens, **i32)
+    counter = torch.zeros(2, **i32)
+    rope, gates = (eng.cos, eng.sin), eng.model.gate_views
+
+    def attn_tree(i, qkv, o):
+        ops.attn_suffix_tree(qkv, p.ar.qkv[i], o, *gates(i), p.vstart, at, length, *tree[R], rope, B, R, S, eng.H, eng.Dh, eng.A,
+                             eng.F, cache_rotated=p.rotated)
+        wide.qkv = qkv_all[(i + 1) % L]                     # layer i + 1 projects into its own slice: the rows stay for the commit
+
+    def attn_one(i, qkv, o):
+        ops.attn_suffix_append(qkv, p.ar.qkv[i], o, *gates(i), p.vstart, at, length, rope, B, 1, S, eng.H, eng.Dh, eng.A, eng.F,
+                               cache_rotated=p.rotated)
+    stop = _LagOneNarrow(max_new_tokens)
+    steps, fed, r_out, cur, widths = 0, 1, R, narrow, []
+    for t in range(max_new_tokens):
+        if not stop.may_launch(t):
+            break
+        if r_out > 1 and stop.off_trie(t):
+            r_out = 1
+        nxt = wide if r_out > 1 else narrow
+        ops.tree_spec_step(cur.lg, eng.pack.emb, plan, ids, pos, done, n_gen, node, length, at, nxt.xin, *tree[r_out], path, n_path,
+                           start_old, tokens[t], logprobs[t], n_committed[t], n_drafted[t], n_active[t:t + 1], n_on_trie[t:t + 1],
+                           counter, max_new_tokens=int(max_new_tokens), pos64=pos64, eos_id=eos, stop_at_eos=stop_at_eos)
+        stop.queued(t, n_active[t:t + 1], n_on_trie[t:t + 1])
+        widths.append(fed)
+        steps = t + 1
+        if fed > 1:                                         # the pass this step verified was a tree pass: its accepted rows
+            ops.kv_tree_commit(p.ar.qkv, qkv_all, path, n_path, start_old, rope, n_seq=B, S=S, H=eng.H, Dh=eng.Dh, A=eng.A,
+                               cache_rotated=p.rotated)
+        if steps == max_new_tokens:
+            break                                           # (every row has committed at least one token per step)
+        if r_out > 1:
+            wide.qkv = qkv_all[0]
+        rowpass.head(eng, rowpass.layers(eng, nxt, attn_tree if r_out > 1 else attn_one), nxt.xn, nxt.lg)
+        cur, fed = nxt, r_out
+    n_generated = n_gen.to(torch.int64)
+    col = torch.arange(int(n_generated.max()), device=dev).unsqueeze(0)
+    tok, inside = _read_back(ids, p.prefix, n_generated, col)
+    out = {"ids": ids, "n_generated": n_generated, "steps": steps, "tokens": tok,
+           "n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous(),
+           "rows_per_pass": torch.as_tensor(widths, **i32)}
+    if return_logprobs:
+        out["logprobs"] = _token_order(tokens[:steps], logprobs[:steps], inside)
         out["sum_logprob"] = out["logprobs"].sum(1)
     return out
 

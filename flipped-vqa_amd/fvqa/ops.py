@@ -986,6 +986,92 @@ def trie_jump_step(logits, emb, ids, pos, done, n_generated, node, w, length, st
     return token
 
 
+TREE_SPEC_ROWS_MAX = 64      # rows of a sequence per pass fvqa_tree_spec_step takes (csrc/treespec.hip RMAX)
+TREE_SPEC_WALK = 32          # tokens one step commits at the most: columns of token / logprob / path (csrc/treespec.hip WALK)
+
+
+def tree_spec_step(logits, emb, plan, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
+                   n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, *,
+                   max_new_tokens: int, pos64=None, eos_id: int = 2, stop_at_eos: bool = True):
+    """The token step of tree-shaped draft verification (include/fvqa.h fvqa_tree_spec_step states the rule). logits (B*R_in, V)
+    fp32: row n*R_in + j is local row j of the pass the step verifies. plan: dict of int32 device tensors — n_plan (1,) with
+    token, depth, end, parent (P,): ONE plan shared by every sequence; or n_plan (B,) with (B, P) tables: a plan per sequence.
+    In/out: ids (B, S) int64, pos / done / n_generated / node / length (B,) int32. Out: start (B,) int32, x_next (B*R_out, D) —
+    R_out, the rows per sequence of the NEXT pass, is read off x_next —, depth / end (B*R_out) and tile_anc (B * ceil(R_out / 32)
+    * 32) int32: the next pass's operands of attn_suffix_tree (with `length` as its n_rows); path (B, 32), n_path, start_old (B,)
+    int32 for kv_tree_commit; token (B, 32) int32 (-1 padded), logprob (B, 32) fp32 (0 padded), n_committed / n_drafted (B,) int32,
+    n_active / n_on_trie (1,) int32, pos64 (B,) int64 or None. counter: TWO int32 words the caller zeroed once."""
+    what = "tree_spec_step"
+    names = ("n_plan", "token", "depth", "end", "parent")
+    _need(isinstance(plan, dict) and all(torch.is_tensor(plan.get(k)) for k in names), f"{what}: plan holds {names}")
+    pn, pt, pd, pe, pp = (plan[k] for k in names)
+    _dev(logits, emb, pn, pt, pd, pe, pp, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
+         n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64)
+    B = pos.numel()
+    _need(B >= 1 and logits.dim() == 2 and logits.shape[0] % B == 0 and x_next.dim() == 2 and x_next.shape[0] % B == 0,
+          f"{what}: logits (B*R_in, V) and x_next (B*R_out, D) for the B of pos")
+    R_in, R_out = logits.shape[0] // B, x_next.shape[0] // B
+    _need(1 <= R_in <= TREE_SPEC_ROWS_MAX and 1 <= R_out <= TREE_SPEC_ROWS_MAX and B * max(R_in, R_out) <= 65535,
+          f"{what}: 1 <= rows per sequence <= {TREE_SPEC_ROWS_MAX}, B * rows <= 65535")
+    _need(pt.dim() in (1, 2) and pt.shape[-1] >= 1 and (pt.dim() == 1 or pt.shape[0] == B),
+          f"{what}: plan tables are (P,) — shared — or (B, P)")
+    P, per = int(pt.shape[-1]), pt.dim() == 2
+    tiles = (R_out + TREE_TILE - 1) // TREE_TILE
+    W = TREE_SPEC_WALK
+    # (_token_step's checks with x_next at the rows of the NEXT pass: R_out need not be R_in)
+    _need(logits.dtype == _F32, f"{what}: logits ({B * R_in}, V) fp32")
+    V = logits.shape[1]
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype and x_next.shape[1] == emb.shape[1],
+          f"{what}: emb (V, D) and x_next ({B * R_out}, D) of one dtype")
+    D = emb.shape[1]
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == _I64, f"{what}: ids (B, S) int64, B = {B} rows")
+    S = ids.shape[1]
+    _table(what, _of(_I32, B if per else 1, n_plan=pn) +
+           _of(_I32, (B if per else 1) * P, plan_token=pt, plan_depth=pd, plan_end=pe, plan_parent=pp) +
+           _of(_I32, B, pos=pos, done=done, n_generated=n_generated, node=node, len=length, start=start, n_path=n_path,
+               start_old=start_old, n_committed=n_committed, n_drafted=n_drafted) +
+           _of(_I32, 1, n_active=n_active, n_on_trie=n_on_trie) + _of(_I32, 2, counter=counter) +
+           _of(_I32, B * R_out, depth=depth, end=end) + _of(_I32, B * tiles * TREE_TILE, tile_anc=tile_anc) +
+           _of(_I32, B * W, token=token, path=path) + _of(_F32, B * W, logprob=logprob))
+    _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == B), f"{what}: pos64 ({B},) int64")
+    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
+    rc = _lib.load(emb.dtype).fvqa_tree_spec_step(
+        _ptr(logits), _ptr(emb), _ptr(pn), _ptr(pt), _ptr(pd), _ptr(pe), _ptr(pp), P, P if per else 0, int(eos_id),
+        1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated), _ptr(node),
+        _ptr(length), _ptr(start), _ptr(x_next), _ptr(depth), _ptr(end), _ptr(tile_anc), _ptr(path), _ptr(n_path),
+        _ptr(start_old), _ptr(token), _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(n_on_trie),
+        _ptr(counter), _ptr(pos64), B, R_in, R_out, V, D, S, dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_tree_spec_step")
+    return token
+
+
+def kv_tree_commit(qkv_cache, qkv_rows, path, n_path, start_old, rope, *, n_seq: int, S: int, H: int, Dh: int, A: int,
+                   cache_rotated: bool):
+    """The cache append of the accepted path (include/fvqa.h fvqa_kv_tree_commit): qkv_cache (L, n_seq*S + A, 3*D), qkv_rows
+    (L, n_seq*R, 3*D) the RAW rows every layer of the tree pass kept; path (n_seq, 32), n_path, start_old (n_seq,) int32 as
+    tree_spec_step wrote them. One launch over all layers: the k (in the cache's convention) and v of row path[n, i] go to cache
+    row n*S + start_old[n] + i for i < n_path[n]; nothing else is written."""
+    what = "kv_tree_commit"
+    _dev(qkv_cache, qkv_rows, path, n_path, start_old)
+    D = H * Dh
+    _need(qkv_cache.dim() == 3 and qkv_rows.dim() == 3 and qkv_cache.dtype == qkv_rows.dtype
+          and qkv_cache.shape[0] == qkv_rows.shape[0] and qkv_cache.shape[2] == qkv_rows.shape[2] == 3 * D,
+          f"{what}: qkv_cache (L, n_seq*S + A, 3*D) and qkv_rows (L, n_seq*R, 3*D) of one dtype")
+    L = qkv_cache.shape[0]
+    _need(Dh == 128 and n_seq >= 1 and qkv_cache.shape[1] == n_seq * S + A and qkv_rows.shape[1] % n_seq == 0 and A >= 0,
+          f"{what}: head_dim 128, cache rows = n_seq*S + A, rows a multiple of n_seq")
+    R = qkv_rows.shape[1] // n_seq
+    _need(1 <= R <= TREE_SPEC_ROWS_MAX and n_seq <= 65535 and L <= 65535, f"{what}: 1 <= rows per sequence <= {TREE_SPEC_ROWS_MAX}")
+    _table(what, _of(_I32, n_seq * TREE_SPEC_WALK, path=path) + _of(_I32, n_seq, n_path=n_path, start_old=start_old))
+    cos_t, sin_t = _rope_tables(rope, S, Dh, what)
+    _need(cos_t is not None or not cache_rotated, f"{what}: a rotated cache needs the rope tables")
+    rc = _lib.load(qkv_cache.dtype).fvqa_kv_tree_commit(_ptr(qkv_cache), _ptr(qkv_rows), _ptr(path), _ptr(n_path),
+                                                        _ptr(start_old), _ptr(cos_t), _ptr(sin_t), n_seq, R, S, H, Dh, A, L,
+                                                        1 if cache_rotated else 0, dt_code(qkv_cache.dtype), _stream())
+    _lib.check(rc, "fvqa_kv_tree_commit")
+    return qkv_cache
+
+
 def decode_next_trie(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, node, trie, *,
                      u=None, pos64=None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0,
                      repetition_penalty: float = 1.0, eos_id: int = 2, stop_at_eos: bool = True):

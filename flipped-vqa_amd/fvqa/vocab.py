@@ -127,6 +127,39 @@ def _plan_one(h: constrain.TokenTrie, root: int):
     return token, depth, parent, end, e_parent, e_token, e_child, members
 
 
+def plan_draft(trie, B: int) -> dict:
+    """The plan of a DRAFT trie (generate(draft_answers=C); include/fvqa.h fvqa_tree_spec_step): `_plan_one`'s pre-order walk
+    without plan_vocab's limits — a draft trie may be deeper than 32 tokens and larger than one pass, the token step cuts every
+    pass to what fits. -> host int32 arrays: shared (bool); a shared trie is planned ONCE — n_plan (1,), token, depth, end, parent
+    (P,): the kernel reads it with a sample stride of 0 —; per-sample tries give n_plan (B,) and (B, P) tables, padded behind a
+    sample's rows (token 0, depth 0, end = own index + 1, parent -1; never read: n_plan bounds every index). The root's token
+    (-1) is not read: its input is the prompt's last token. The plan is kept on the host trie: a caller that compiles its
+    TokenTrie once pays for the walk once."""
+    h = trie.host()
+    kept = h.__dict__.setdefault("_draft_plans", {})
+    if int(B) not in kept:
+        kept[int(B)] = _plan_draft(h, int(B))
+    return kept[int(B)]
+
+
+def _plan_draft(h: constrain.TokenTrie, B: int) -> dict:
+    roots = [int(r) for r in h.roots(int(B))]
+    per = {r: _plan_one(h, r)[:4] for r in set(roots)}
+    ones = [per[roots[0]]] if h.shared else [per[r] for r in roots]
+    P = max(len(o[0]) for o in ones)
+    n = len(ones)
+    out = dict(n_plan=np.zeros(n, dtype=np.int32), token=np.zeros((n, P), dtype=np.int32), depth=np.zeros((n, P), dtype=np.int32),
+               end=np.tile(np.arange(1, P + 1, dtype=np.int32), (n, 1)), parent=np.full((n, P), -1, dtype=np.int32))
+    for b, (token, depth, parent, end) in enumerate(ones):
+        k = len(token)
+        out["n_plan"][b] = k
+        out["token"][b, :k], out["depth"][b, :k], out["end"][b, :k], out["parent"][b, :k] = token, depth, end, parent
+    if h.shared:
+        out = {k: (v if k == "n_plan" else v[0]) for k, v in out.items()}
+    out["shared"] = bool(h.shared)
+    return out
+
+
 def plan_vocab(trie, B: int, prefix=None, S: Optional[int] = None, n_listed=None) -> VocabPlan:
     """Host-only integer work. trie: a constrain.TokenTrie; B: the batch size (a per-sample trie built for another one is a
     ValueError). prefix (one int per sample) and S: where each answer starts and the sequence length — given, the plan checks that

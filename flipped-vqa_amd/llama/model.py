@@ -260,6 +260,13 @@ class Transformer(nn.Module):
                 or int(getattr(self.args, "lookahead", 0) or 0) > 1 or int(getattr(self.args, "gen_jump_forward", 0) or 0) > 1):
             raise ValueError("--gen_frame_attention is served by the plain token loop: not with --num_beams > 1, --contrast, "
                              "--lookahead > 1 or --gen_jump_forward > 1")
+        draft = getattr(self.args, "gen_draft", None)
+        if draft:                                           # --gen_draft: greedy's tokens, a trie of likely answers as the draft
+            if (mode or getattr(self.args, "contrast", None) or int(getattr(self.args, "num_beams", 1) or 1) > 1
+                    or int(getattr(self.args, "gen_jump_forward", 0) or 0) > 1 or getattr(self.args, "gen_frame_attention", False)):
+                raise ValueError("--gen_draft verifies a draft trie against the greedy choice: not with --gen_constrain, "
+                                 "--contrast, --num_beams > 1, --gen_jump_forward > 1 or --gen_frame_attention")
+            return self._drafted_inference(data, draft)
         if mode:                                            # --gen_constrain: decode under the allowed answers
             return self._constrained_inference(data, mode)
         if getattr(self.args, "contrast", None):            # --contrast blind: each token from the difference to the blind twin
@@ -354,6 +361,43 @@ class Transformer(nn.Module):
         return {"contrast": c, "contrast_alpha": float(getattr(self.args, "contrast_alpha", 1.0)),
                 "contrast_beta": float(getattr(self.args, "contrast_beta", 0.1))}
 
+    def _answer_sets(self, data, mode, eng):
+        """'options': each sample's own option token sequences (an option cut off by the end of the row keeps room for its EOS);
+        'vocab': the encoded answers of --answer_vocab, one list for the batch."""
+        from fvqa import constrain
+        if mode == "options":
+            S = data["text_id"]["vqa"].shape[2]
+            return [[o[: max(S - int(p) - 1, 0)] for o in opts]
+                    for opts, p in zip(constrain.options_of(data, self.tokenizer), data["prefix_index"]["vqa"])]
+        if mode == "vocab":
+            path = getattr(self.args, "answer_vocab", None)
+            if not path:
+                raise ValueError("--gen_draft vocab needs --answer_vocab FILE")
+            return constrain.encode_answers(self.tokenizer, constrain.read_answer_vocab(path))
+        raise ValueError(f"gen_draft: 'options' or 'vocab', not {mode!r}")
+
+    def _drafted_inference(self, data, mode):
+        """--gen_draft options | vocab with --lookahead R: the validation protocol as it stands — the plain greedy tokens (up to
+        each row's EOS with --gen_stop_eos, else all N_NEW), `match_answers` — with the sample's options or the answer vocabulary
+        as a draft trie (generate(lookahead=R, draft_answers=...)): fewer passes, the same answers file."""
+        from fvqa import constrain, generate
+        eng = self.ensure_engine()
+        trie = getattr(self, "_draft_vocab_trie", None) if mode == "vocab" else None
+        if trie is None:
+            sets = [[o for o in opts if o] for opts in self._answer_sets(data, mode, eng)] if mode == "options" else \
+                self._answer_sets(data, mode, eng)
+            trie = constrain.TokenTrie.from_sequences(sets, self.tokenizer.eos_id, eng.V)
+            if mode == "vocab":
+                self._draft_vocab_trie = trie
+        out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0,
+                                stop_at_eos=bool(getattr(self.args, "gen_stop_eos", False)), lookahead=int(self.args.lookahead),
+                                draft_answers=trie)
+        ids = out["ids"]
+        best, sims, extracted = generate.match_answers(self, data, ids)
+        self.last_generation = {"ids": ids, "similarities": sims, "n_committed": out["n_committed"],
+                                "n_drafted": out["n_drafted"], "rows_per_pass": out["rows_per_pass"], "steps": out["steps"]}
+        return best, extracted
+
     def _constrained_inference(self, data, mode):
         """--gen_constrain options | vocab: every sample decodes under its own answer options (-> best = the index of the option
         generated; a row that completed none falls back to the cosine pick) or under the shared answers of --answer_vocab (the
@@ -398,16 +442,17 @@ class Transformer(nn.Module):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
         return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta, lookahead, lookup_ngram,
-        draft_tokens, jump_forward, frame_attention) -> one answer per row, the
+        draft_tokens, draft_answers, jump_forward, frame_attention) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
         "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
-        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step; with jump_forward >= 2 "n_committed"; with frame_attention "frame_attention" and "tokens", what fvqa.attribution.summarize reads). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step, and with draft_answers "rows_per_pass"; with jump_forward >= 2 "n_committed"; with frame_attention "frame_attention" and "tokens", what fvqa.attribution.summarize reads). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",
-                                                     "n_plausible", "n_committed", "n_drafted", "frame_attention")
+                                                     "n_plausible", "n_committed", "n_drafted", "rows_per_pass",
+                                                     "frame_attention")
                                 if k in out}
         if "frame_attention" in out:
             self.last_generation["tokens"] = out["tokens"]
@@ -433,13 +478,13 @@ class Transformer(nn.Module):
         stop_at_eos, seed): `batches` is one batch of `prompt_batch` / a validation batch or a list of them, their rows are the
         requests, and a finished row hands its slot of the decode batch to the next request. -> one answer per request, formed as
         `generate` forms them. `last_generation`: "ids", "n_generated", "tokens", "steps", "n_prefills", "occupancy", "seated"
-        (and "logprobs", "sum_logprob", "choice" where asked). ValueError: num_beams, contrast, lookahead, jump_forward and
-        num_return_sequences are not built into the stream."""
+        (and "logprobs", "sum_logprob", "choice" where asked). ValueError: num_beams, contrast, lookahead, draft_answers,
+        jump_forward and num_return_sequences are not built into the stream."""
         from fvqa import stream
-        for k in ("num_beams", "contrast", "lookahead", "jump_forward", "num_return_sequences"):
+        for k in ("num_beams", "contrast", "lookahead", "draft_answers", "jump_forward", "num_return_sequences"):
             if k in kw:
-                raise ValueError(f"generate_stream: {k} is not built into the stream (beams, contrast, lookahead, jump-forward "
-                                 "and several samples per prompt run through generate())")
+                raise ValueError(f"generate_stream: {k} is not built into the stream (beams, contrast, lookahead, tree drafts, "
+                                 "jump-forward and several samples per prompt run through generate())")
         out = stream.generate_stream(self.ensure_engine(), batches, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "tokens", "steps", "n_prefills", "occupancy", "seated",
                                                      "logprobs", "sum_logprob", "choice") if k in out}

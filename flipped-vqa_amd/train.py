@@ -91,6 +91,13 @@ _FLAGS = [
                               "--gen_constrain or --contrast")),
     ("--lookup_ngram", dict(type=int, default=2, help="--lookahead: the longest n-gram of committed tokens the prompt lookup "
                                                       "matches (1 .. 4)")),
+    ("--gen_draft", dict(type=str, choices=["options", "vocab"], default=None,
+                         help="generation-task validation with --lookahead R (2 .. 64): the drafts are a trie of likely answers, "
+                              "verified in one tree pass (fvqa.generate.generate(lookahead=R, draft_answers=...)): 'options' — each "
+                              "sample's own answer options as the prompt asks for them; 'vocab' — the answers of --answer_vocab. "
+                              "A draft, not a rule: the protocol, the tokens and the answers file are the plain run's, in fewer "
+                              "passes where the model answers with a drafted answer. Not with --num_beams > 1, --gen_constrain, "
+                              "--contrast, --gen_jump_forward, --gen_stream, --val_vocab or --gen_frame_attention")),
     ("--gen_jump_forward", dict(type=int, default=0,
                                 help="--gen_constrain: jump-forward decoding with up to T rows per pass (fvqa.generate.generate("
                                      "constraints=..., jump_forward=T)): the tokens the trie of allowed answers fixes are committed "
@@ -151,7 +158,8 @@ class ArgumentParser(argparse.ArgumentParser):
     --gen_frame_attention (answer.py: --frame_attention) with a decode that does not report it, and --val_frame_attention
     with a validation that does not score options or scores them twice, and --val_flipped with a validation that does not
     score options or combines their scores another way, and --val_vocab without its vocabulary and generation prompts or with
-    a decode (it runs none)."""
+    a decode (it runs none), and --gen_draft (answer.py: --draft) without its --lookahead R, its prompts or its vocabulary, or
+    with a decode the tree drafts are not built for; --lookahead may reach 64 only with it."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -163,8 +171,30 @@ class ArgumentParser(argparse.ArgumentParser):
             if not a.contrast_alpha >= 0 or not 0 <= a.contrast_beta <= 1:
                 self.error("--contrast_alpha >= 0, 0 <= --contrast_beta <= 1")
         la = int(getattr(a, "lookahead", 0) or 0)
-        if la < 0 or la > 16:
-            self.error("0 <= --lookahead <= 16")
+        drafted = getattr(a, "gen_draft", None) or getattr(a, "draft", None)
+        if la < 0 or la > (64 if drafted else 16):
+            self.error("0 <= --lookahead <= 16 (64 rows per pass with --gen_draft / --draft)")
+        for flag in ("gen_draft", "draft"):
+            d = getattr(a, flag, None)
+            if not d:
+                continue
+            if la < 2:
+                self.error(f"--{flag} drafts a trie of answers for a tree pass: it needs --lookahead R, 2 <= R <= 64")
+            if flag == "gen_draft" and not getattr(a, "is_generation_task", False):
+                self.error("--gen_draft belongs to generation-task validation: it needs --is_generation_task")
+            if d == "vocab" and not getattr(a, "answer_vocab", None):
+                self.error(f"--{flag} vocab needs --answer_vocab FILE (one answer per line)")
+            if flag == "draft" and d == "options" and not getattr(a, "options", None):
+                self.error("--draft options needs --options")
+            if (int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "gen_constrain", None) or getattr(a, "constrain", False)
+                    or getattr(a, "contrast", None) or int(getattr(a, "gen_jump_forward", 0) or 0) > 1
+                    or int(getattr(a, "jump_forward", 0) or 0) > 1 or int(getattr(a, "gen_stream", 0) or 0) >= 1
+                    or int(getattr(a, "slots", 0) or 0) >= 1 or getattr(a, "val_vocab", False)
+                    or getattr(a, "gen_frame_attention", False) or getattr(a, "frame_attention", False)
+                    or int(getattr(a, "rank", 0) or 0) or int(getattr(a, "num_samples", 1) or 1) > 1
+                    or float(getattr(a, "temperature", 0.0) or 0.0) > 0):
+                self.error(f"--{flag} verifies a draft trie against the greedy choice: not with --num_beams > 1, constrained or "
+                           "contrastive decoding, jump-forward, a stream, --val_vocab / --rank, frame attention or sampling")
         if la > 1:
             if int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "gen_constrain", None) or getattr(a, "contrast", None):
                 self.error("--lookahead verifies drafts against the greedy choice: not with --num_beams > 1, --gen_constrain "

@@ -648,6 +648,75 @@ int fvqa_trie_jump_step(const float* logits, const void* emb, const int32_t* nod
                         int32_t* w, int32_t* len, int32_t* start, int64_t* pos64, void* x_next, int32_t* token,
                         float* logprob_pick, float* logprob_fed, int32_t* n_committed, int32_t* n_active, uint32_t* counter,
                         int n_seq, int jump_forward, int vocab, int dim, int seq_len, int dtype, void* stream);
+/* The token step of TREE-shaped draft verification (csrc/treespec.hip; generate(lookahead=R, draft_answers=C)): one launch where
+ * fvqa_spec_step sits, one 256-thread workgroup per sequence. The likely answers of a sample are a trie; its internal nodes in
+ * pre-order (children in ascending token order; fvqa/vocab.py _plan_one) are the sample's PLAN, read only, int32: plan_n (the
+ * rows of the plan), plan_token (a row's input token; the root's is not read), plan_depth, plan_end (the exclusive end of the
+ * row's subtree: the subtree of g is the contiguous range [g, end[g]), and any prefix of it is closed under ancestors — the whole
+ * design rests on that) and plan_parent, each (.., plan_rows). plan_stride is the sample stride of the four tables in elements:
+ * 0 — ONE plan shared by every sequence, plan_n one word — or plan_rows — a plan per sequence, plan_n (n_seq). The trie is a
+ * DRAFT, not a rule: the tokens committed are the plain greedy call's whatever the plan holds.
+ * State per sequence, in and out: fvqa_spec_step's ids (n_seq, seq_len) int64, pos, done, n_generated, len (n_seq) int32 and
+ * node (n_seq) int32: >= 0 the plan row whose input token is the last committed token (0 before the first step: the root, whose
+ * input is the prompt's last token), -1 once the row has left the trie (a value outside [0, plan_n) reads as -1).
+ * The incoming pass fed m = len[n] rows (clamped into [1, rows_in] and to the plan's end; 1 when node == -1): local row j is plan
+ * row a + j, a the incoming node, at position q + depth[a + j] - depth[a], q = pos[n]; logits (n_seq*rows_in, vocab) fp32, row
+ * n*rows_in + j. (The first step: len = 1 and row 0 = the prefill's row at prefix - 1.) A row is live under fvqa_spec_step's
+ * condition. Per live row:
+ *   1. walk, from j = 0: g = argmax L_j, the first index on exact ties; it is committed — ids[pos + 1] = g, pos += 1,
+ *      n_generated += 1 — and j is the next entry of path. The row is done if stop_at_eos and g == eos_id, or if n_generated ==
+ *      max_new_tokens; the walk also stops if pos + 1 >= seq_len (fvqa_spec_step's rule: m' = 0, done at the next step). In these
+ *      three cases node becomes -1. Otherwise, with a >= 0, the child c of plan row G = a + j under g is the lowest row r in
+ *      (G, min(end[G], plan_n)) with parent[r] == G and token[r] == g — on a sound plan the one the chain G + 1, end[G + 1], ...
+ *      reaches; the workgroup looks at the rows side by side. None: node = -1, stop. Found: node = c; if c - a < m (the child was
+ *      fed in this pass) and fewer than 32 tokens were committed, j = c - a and the walk goes on; else it stops: the child had been
+ *      cut from the pass and is the next pass's root. Row L_j is scanned only if the walk reaches it. The log-probability of a
+ *      committed token is L_j[g] - lse(L_j) in fvqa_spec_step's summation order (the same bits).
+ *   2. the next pass, P = pos after the commit: Dmax = min(31, max_new_tokens - n_generated - 1, seq_len - 2 - P). A done row or
+ *      Dmax < 0: m' = 0, as fvqa_spec_step has it. node == -1: m' = 1. Otherwise the plan rows [node, e), e = min(end[node], node +
+ *      rows_out, plan_n), cut in front of the first row whose depth exceeds depth[node] + Dmax; m' = e - node >= 1.
+ *   3. outputs. x_next (n_seq*rows_out, dim): row 0 = emb[last committed token], row j >= 1 = emb[token[node + j]] (clamped into
+ *      the vocabulary), zeros behind m'. fvqa_attn_suffix_tree's operands for that pass: len[n] = m' (its n_rows), start[n] =
+ *      pos64[n] = P, depth / end (n_seq*rows_out) — depth[node + j] - depth[node] clamped into [0, 31], end[node + j] - node
+ *      clamped into [j + 1, m']; padding rows depth 0, end j + 1 —, tile_anc (n_seq * ceil(rows_out / 32) * 32): per tile the proper
+ *      ancestors of its first row, root first, found by walking `parent` from that row for as many steps as its local depth (a
+ *      parent outside [node, child) ends the walk), -1 elsewhere. For fvqa_kv_tree_commit: path (n_seq, 32) the local rows the
+ *      walk took (0 behind), n_path = n_committed, start_old = the incoming pos clamped into the sequence (local row path[i] sat
+ *      at start_old + i). token / logprob (n_seq, 32): the committed tokens and their log-probabilities, -1 / 0 behind;
+ *      n_committed; n_drafted = m - 1; done.
+ *   4. A row that is not live behaves as in fvqa_spec_step: nothing of its state is written but done = 1, len = 0, start = pos64
+ *      = pos clamped; n_path = n_committed = n_drafted = 0, row n*rows_out of x_next is the embedding of its current token.
+ * n_active = the rows with done == 0 after the step, n_on_trie = those of them with node >= 0 (it never rises: a node >= 0 can
+ * only turn into -1), counted as fvqa_spec_step counts through TWO consecutive 32-bit words at `counter`, owned and zeroed once by
+ * the caller: word 0 for n_active, word 1 for n_on_trie; calls that share them must be ordered.
+ * With rows_in == rows_out == 1 (and max_new_tokens never reached) token, ids, pos, pos64, done, x_next and n_active are those of
+ * fvqa_decode_next at temperature 0, bit for bit. No float atomics, fixed summation orders: bitwise repeatable. Every index read
+ * from the plan, node or ids is clamped: a broken plan gives wrong drafts — which still give greedy's tokens — and never an
+ * access outside an operand.
+ * Limits: 1 <= rows_in, rows_out <= 64, n_seq * rows <= 65535, plan_rows >= 1, plan_stride 0 or plan_rows (else FVQA_ESHAPE).
+ * FVQA_EINVAL: a null pointer (pos64 may be NULL), a bad dtype code; FVQA_EALIGN: an operand off its element's boundary. */
+int fvqa_tree_spec_step(const float* logits, const void* emb, const int32_t* plan_n, const int32_t* plan_token,
+                        const int32_t* plan_depth, const int32_t* plan_end, const int32_t* plan_parent, int plan_rows,
+                        int plan_stride, int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos,
+                        int32_t* done, int32_t* n_generated, int32_t* node, int32_t* len, int32_t* start, void* x_next,
+                        int32_t* depth, int32_t* end, int32_t* tile_anc, int32_t* path, int32_t* n_path, int32_t* start_old,
+                        int32_t* token, float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active,
+                        int32_t* n_on_trie, uint32_t* counter, int64_t* pos64, int n_seq, int rows_in, int rows_out, int vocab,
+                        int dim, int seq_len, int dtype, void* stream);
+/* The cache append of the accepted path (csrc/treespec.hip). fvqa_attn_suffix_tree writes nothing but o — siblings share a
+ * position, so a tree pass must not write its rows into the cache —; the pass keeps every layer's RAW q | k | v rows instead:
+ * qkv_rows (n_layers, n_seq*rows, 3*dim). After the token step ONE launch over all layers copies, for sequence n and i <
+ * n_path[n] (at most 32), the k and v thirds of row n*rows + path[n*32 + i] to row n*seq_len + start_old[n] + i of every layer of
+ * qkv_cache (n_layers, n_seq*seq_len + adapter_len, 3*dim: fvqa_kv_beam_move's layout). k follows the cache's convention: with
+ * cache_rotated != 0 rotated at position start_old[n] + i and rounded to the storage type — the operations fvqa_attn_suffix_append
+ * performs, contraction off: the same bits —, raw otherwise; v as it is. Nothing else is written: not the rows behind n_path, the
+ * q third, other sequences or the adapter rows. An entry with path outside [0, rows) or a position outside [0, seq_len) appends
+ * nothing. 16-byte accesses. head_dim 128, rows <= 64, n_seq, n_layers <= 65535 (else FVQA_ESHAPE); FVQA_EINVAL: a null pointer
+ * (cos_t / sin_t only when cache_rotated), qkv_cache == qkv_rows, a bad dtype code; FVQA_EALIGN: the buffers off a 16-byte
+ * boundary, the tables off 4. */
+int fvqa_kv_tree_commit(void* qkv_cache, const void* qkv_rows, const int32_t* path, const int32_t* n_path,
+                        const int32_t* start_old, const float* cos_t, const float* sin_t, int n_seq, int rows, int seq_len,
+                        int n_heads, int head_dim, int adapter_len, int n_layers, int cache_rotated, int dtype, void* stream);
 /* One step of beam search (csrc/beam.hip; generate(num_beams > 1)): one launch per token where fvqa_decode_next sits in the greedy
  * loop, one workgroup per SAMPLE. A sample owns n_beams = K consecutive slots (rows b*K .. b*K + K-1 of every operand).
  * In: logits (n_samples*K, vocab) fp32 at each slot's position; emb (vocab, dim) storage type; ids_in (n_samples*K, seq_len)

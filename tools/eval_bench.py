@@ -19,6 +19,8 @@ plain sampling `generate` of the same batch — for N > 1 also N calls of it, wh
 --contrast times greedy `generate(contrast="blind", stop_at_eos=False)` — contrastive decoding runs twice the rows — interleaved
 (--pairs N times, default 3) with its two comparison points: the plain greedy `generate` of the same batch (B rows) and of a
 batch of 2 * B rows (the same layer pass as the pairs).
+--tree_draft R [R ...] times tree-shaped draft verification, generate(lookahead=R, draft_answers=...), four arms interleaved with
+the plain call in three pairs each (tree_draft_lines states them).
 --lookahead T [T ...] times draft-and-verify greedy decoding, generate(lookahead=T, stop_at_eos=False), each arm interleaved
 (--pairs N times, default 3) with the same call without the keyword: the run's own answer as draft (full acceptance: the upper
 bound), drafts that are all wrong (the price of the wasted rows) and prompt lookup (--lookup_ngram G) on the synthetic batch as it
@@ -75,6 +77,8 @@ def main():
     ap.add_argument("--lookahead", type=int, nargs="*", default=[], help="draft-and-verify decoding with up to T rows per pass; "
                                                                          "several T: three arms each, interleaved with plain generate")
     ap.add_argument("--lookup_ngram", type=int, default=2, help="--lookahead: the prompt-lookup arm's longest n-gram")
+    ap.add_argument("--tree_draft", type=int, nargs="*", default=[], help="tree-shaped draft verification with up to R rows per "
+                    "pass (generate(lookahead=R, draft_answers=...)); several R: the four arms for each")
     ap.add_argument("--jump_forward", type=int, nargs="*", default=[], help="jump-forward constrained decoding with up to T rows "
                     "per pass; several T: a line per round each, interleaved with the plain constrained call")
     ap.add_argument("--stream", type=int, default=0, metavar="SLOTS", help="in-flight batching through SLOTS rows, interleaved "
@@ -105,7 +109,7 @@ def main():
     b = synth.make_batch(cfg, seed=5)
     B = a.batch_size
     b["prefix_index"] = {"vqa": [60 + i % 32 for i in range(B)]}
-    if a.eos_at or a.lookahead or a.jump_forward or a.stream:   # decided tokens: what a draft is verified against must not hang on a near tie
+    if a.eos_at or a.lookahead or a.jump_forward or a.stream or a.tree_draft:   # decided tokens: what a draft is verified against must not hang on a near tie
         import dataclasses
         from llama_vqa import fill_closed_form
         fill_closed_form(model, dataclasses.replace(cfg, max_feats=margs.max_feats, bias=margs.bias, tau=margs.tau,
@@ -141,6 +145,9 @@ def main():
         return
     if a.lookahead:
         lookahead_lines(a, eng, b, timed)
+        return
+    if a.tree_draft:
+        tree_draft_lines(a, eng, b, model, timed)
         return
     if a.jump_forward:
         jump_lines(a, eng, b, timed)
@@ -273,6 +280,55 @@ def lookahead_lines(a, eng, b, timed):
                       f"lookahead={T}, {name}: {t_l * 1e3:7.1f} ms/batch, {t_l / N * 1e3:6.3f} ms per committed token, "
                       f"{N / passes:5.2f} tokens per pass ({passes} passes, {out['steps']} steps launched), {t_p / t_l:5.2f}x; "
                       f"ids {'equal' if same else 'DIFFER from'} the plain call's", flush=True)
+
+
+def tree_draft_lines(a, eng, b, model, timed):
+    """Four arms against the plain generate(stop_at_eos=True), interleaved: the model answers with ANSWER tokens and its EOS (the
+    prompt's last token is set as --eos_at sets it); the drafts are five options of 8 to 12 tokens with the answer among them,
+    a 329-answer vocabulary with the answer in it, five options without it, and — the yardstick — the chain lookahead=16 with
+    the answer as draft_tokens."""
+    import numpy as np
+    ANSWER = 10
+    B, V, eos = a.batch_size, eng.V, model.tokenizer.eos_id
+    tag = f"{a.model} L={eng.L} B={B} S=128 greedy to the EOS"
+    pi = synth.vocab_permutation(V)
+    mul, add = int((pi[1] - pi[0]) % V), int(pi[0])
+    t = eos
+    for _ in range(ANSWER + 1):                                                 # the EOS is token ANSWER + 1 of every row
+        t = ((t - add) * pow(mul, -1, V)) % V
+    for i, pre in enumerate(b["prefix_index"]["vqa"]):
+        b["text_id"]["vqa"][i, :, pre - 1] = t
+    ref = generate.generate(eng, b, stop_at_eos=True)
+    rows = [[x for x in r if x >= 0 and x != eos] for r in ref["tokens"].cpu().tolist()]
+    rng = np.random.default_rng(3)
+    other = lambda n: [int(x) for x in rng.integers(3, V, n)]                   # noqa: E731
+    options = [[r] + [other(int(rng.integers(8, 13))) for _ in range(4)] for r in rows]
+    wrong = [[other(int(rng.integers(8, 13))) for _ in range(5)] for _ in rows]
+    vocab329 = [[r] + [other(int(rng.integers(1, 4))) for _ in range(328)] for r in rows]
+    from fvqa import constrain
+    options, wrong, vocab329 = (constrain.TokenTrie.from_sequences(c, eos, V) for c in (options, wrong, vocab329))   # compiled once
+    chain = torch.full((B, generate.N_NEW), -1, dtype=torch.int32)
+    for i, r in enumerate(rows):
+        chain[i, :len(r) + 1] = torch.tensor(r + [eos], dtype=torch.int32)
+    for R in a.tree_draft:
+        arms = ((f"tree R={R}, the answer among five options", dict(lookahead=R, draft_answers=options)),
+                (f"tree R={R}, the answer in a vocabulary of 329", dict(lookahead=R, draft_answers=vocab329)),
+                (f"tree R={R}, five options without the answer", dict(lookahead=R, draft_answers=wrong)),
+                ("chain lookahead=16, the answer as draft", dict(lookahead=16, draft_tokens=chain)))
+        for name, kw in arms:
+            out, base = {}, {}
+            plain = lambda: base.update(generate.generate(eng, b, stop_at_eos=True))                   # noqa: E731
+            fn = lambda: out.update(generate.generate(eng, b, stop_at_eos=True, **kw))                 # noqa: E731
+            timed(plain, reps=1)
+            timed(fn, reps=1)
+            same = bool(torch.equal(out["ids"], base["ids"]))
+            width = out["rows_per_pass"].tolist() if "rows_per_pass" in out else []
+            for k in range(a.pairs or 3):
+                t_p, t_l = timed(plain, warm=0), timed(fn, warm=0)
+                print(f"{tag} round {k}: generate: {t_p * 1e3:7.1f} ms/batch ({base['steps']} steps) | {name}: {t_l * 1e3:7.1f} "
+                      f"ms/batch ({out['steps']} steps, committed per step, row 0: {out['n_committed'][0].tolist()}"
+                      + (f", rows per pass {width}" if width else "") + f"), {t_p / t_l:5.2f}x; ids "
+                      f"{'equal' if same else 'DIFFER from'} the plain call's", flush=True)
 
 
 def stream_lines(a, eng, cfg, timed):
