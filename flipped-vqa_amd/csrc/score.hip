@@ -3,7 +3,7 @@
 //
 // The O option sequences of a sample are equal up to the first answer token, and with causal attention so are their hidden
 // states: the prompt is run ONCE (the training forward, which leaves every layer's k / v in the arena = the KV cache) and
-// each option only recomputes its last T rows, the "suffix" (fvqa/score.py). One kernel template, attn_suffix_k, behind four entries:
+// each option only recomputes its last T rows, the "suffix" (fvqa/score.py). One kernel template, attn_suffix_k, behind five entries:
 //
 // fvqa_attn_suffix — Attention.forward (llama/model.py:87-128) at the suffix rows. Query row (n, c, j) sits at position
 //   start[n] + j and attends to
@@ -23,8 +23,8 @@
 //   none of the following exists), for ONE continuation per sample (draft-and-verify decoding, fvqa/generate.py): the suffix
 //   rows join the cache. The (head, sample) workgroup already stages its head's slice of every suffix key and value once; the
 //   threads that stage row j < len[n] also store it to cache row n*S + start[n] + j — k rotated and rounded when the cache holds
-//   rotated keys (rope_pair_as_decode: the bits fvqa_attn_decode stores for that row and position), the raw bits otherwise;
-//   v as it is. Nothing reads those rows in this launch: a workgroup reads the cache rows [0, start[n]) only.
+//   rotated keys (csrc/cache_row.h rope_pair_as_decode: the bits fvqa_attn_decode stores for that row and position), the raw bits
+//   otherwise; v as it is. Nothing reads those rows in this launch: a workgroup reads the cache rows [0, start[n]) only.
 //
 // fvqa_attn_suffix_mass — the same body with MASS = true (APPEND = false): o_suf bit for bit, and per query row the summary of its
 //   text softmax over the frame window (include/fvqa.h); score_options(frame_attention=True), fvqa/score.py.
@@ -37,13 +37,16 @@
 //   its own: which products hipcc contracts into fmas in the score and value passes changes when the same text is inlined from
 //   a __device__ function, and with it the last bit of the output (profiles/suffix_refactor.log).
 //
-// fvqa_attn_suffix_tree — a kernel of its own beside the template (attn_suffix_tree_k, below it): the suffix rows of a sample are the
-//   nodes of a tree, a row sees the cache and its ancestors-or-self (fvqa/vocab.py: every allowed answer in one pass).
+// fvqa_attn_suffix_tree — the same tile with TREE = true: the suffix rows of a sample are the nodes of a tree, a row sees the cache
+//   and its ancestors-or-self (fvqa/vocab.py: every allowed answer in one pass; fvqa/generate.py: a trie of drafts). WIDE's grid
+//   with one "option"; what differs is where a key row and its position come from (depth, the chain of a tile's first row) and who
+//   sees it (the pre-order interval test) — stated at the template.
 //
 // fvqa_option_pick — the per-option reduction: compact per-row losses (fvqa_ce_fwd) -> individual_losses (B, O, S-1) with
 //   zeros wherever no row was scored, per option sum / count of non-zero entries / mean, and argmin over options with torch's
 //   rule (first NaN wins, ties to the lowest index). One workgroup per sample, fixed summation order.
 #include "attn_decode_body.h"
+#include "cache_row.h"
 
 namespace {
 using namespace fvqa_decode;
@@ -106,18 +109,6 @@ __device__ __forceinline__ float half_sum(float v) {
   return v;
 }
 
-// RoPE of one pair (a, b) of a key that goes into the cache, operation by operation what fvqa_attn_decode's store of the new
-// token's key evaluates (csrc/attn_decode_body.h: `a * c - b * s`, `a * s + b * c`, as hipcc contracts them there: the second
-// always into one fma on the rounded a * s; the first into an fma on the rounded b * s in the 16-bit kernels and not at all in
-// the fp32 kernel). Spelled out with contraction off so that the row fvqa_attn_suffix_append stores has the bits the one-row
-// kernel stores for the same raw row and position — in fp32 the last bit shows; tests/test_lookahead_gpu.py compares them.
-template <typename T> __device__ __forceinline__ void rope_pair_as_decode(float a, float b, float c, float s, float& ra, float& rb) {
-#pragma clang fp contract(off)
-  const float bs = b * s, as = a * s;
-  if constexpr (sizeof(T) == 4) ra = a * c - bs;
-  else ra = __builtin_fmaf(a, c, -bs);
-  rb = __builtin_fmaf(b, c, as);
-}
 // 16 values to 16 consecutive elements of a row, rounded to the storage type
 template <typename T> __device__ __forceinline__ void store16_as(T* dst, const float (&v)[16]) {
 #pragma unroll
@@ -126,14 +117,12 @@ template <typename T> __device__ __forceinline__ void store16_as(T* dst, const f
     Vec4<T>::store(dst + 4 * u, q);
   }
 }
-// 16 consecutive elements of a row, bit for bit
-template <typename T> __device__ __forceinline__ void copy16(T* dst, const T* src) {
-#pragma unroll
-  for (int u = 0; u < (int)(16 * sizeof(T) / 16); ++u)
-    reinterpret_cast<uint4*>(dst)[u] = reinterpret_cast<const uint4*>(src)[u];
-}
 
-template <typename P> __device__ __forceinline__ P* pack_first(P* p) { return p; }      // the one element of a parameter pack
+// element I of a parameter pack
+template <int I, typename P, typename... Ps> __device__ __forceinline__ auto pack_at(P p, Ps... ps) {
+  if constexpr (I == 0) return p;
+  else return pack_at<I - 1>(ps...);
+}
 
 constexpr int MFMAX = 64;                // max_feats under MASS (include/fvqa.h fvqa_attn_suffix_mass): F + 2 <= MLD
 constexpr int MLD = 72;                  // LDS row stride of the summary accumulators (floats): lanes (4 queries) x (8 entries) of a
@@ -147,15 +136,29 @@ constexpr int MLD = 72;                  // LDS row stride of the summary accumu
 // text softmax has closed. Thread (q = tid / 8, e = tid % 8 + 8 m) owns entry e of query q from the first chunk to the store.
 // false compiles none of it; the summary's pointer is an operand of the MASS instantiations only (M: `float` there, an empty
 // pack otherwise), so the other kernels keep their operands and their code.
-template <typename T, bool APPEND = false, bool MASS = false, bool WIDE = false, typename... M>
+//
+// TREE (fvqa_attn_suffix_tree): the Tn suffix rows of a sample (O = 1, len[n] of them real) are the nodes of a tree in pre-order
+// (fvqa/vocab.py: the internal nodes of a trie of allowed answers). Row r sits at position start[n] + depth[r] and sees the cache
+// rows [0, start[n]), the rows that are its ancestors-or-self and the adapter keys. In pre-order, a is an ancestor-or-self of q
+// iff a <= q < end[a], and every ancestor of a row of the 32-row tile from q0 lies in the tile or is an ancestor of q0: the tile's
+// suffix keys are ONE chunk of q0's ancestors (anc, root first: depth[q0] <= 31 of them; none for a root) and ONE chunk of the
+// tile's own rows, both under the interval test. One tile per workgroup, as WIDE has them. depth, end (n_seq, Tn) and the tiles'
+// chains anc (n_seq, tiles, 32) are operands of this instantiation only (M: three `const int32_t`); every index read from them is
+// clamped before it is used.
+constexpr int TREE_DEPTH = FVQA_TREE_DEPTH_MAX;      // deepest row under TREE: a tile's ancestor chain fits one chunk
+static_assert(TREE_DEPTH < KC, "the chain of a tile's first row is one chunk of keys");
+
+template <typename T, bool APPEND = false, bool MASS = false, bool WIDE = false, bool TREE = false, typename... M>
 __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, const T* __restrict__ cache,
                                                      T* __restrict__ o_suf, const float* __restrict__ gate1,
                                                      const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
                                                      const int32_t* __restrict__ start_p, const int32_t* __restrict__ len_p,
                                                      const float* __restrict__ cs, const float* __restrict__ sn, int B, int O,
                                                      int Tn, int S, int H, int A, int F, int cache_rot,
-                                                     M* __restrict__... mass_p) {
-  static_assert(sizeof...(M) == (MASS ? 1 : 0) && !(APPEND && MASS), "mass: one fp32 pointer under MASS; never with APPEND");
+                                                     M* __restrict__... more) {
+  static_assert(APPEND + MASS + WIDE + TREE <= 1 && sizeof...(M) == (MASS ? 1 : TREE ? 3 : 0),
+                "one switch at a time; mass: one fp32 pointer under MASS; depth, end, anc under TREE");
+  constexpr bool TILED = WIDE || TREE;                           // one tile per workgroup, named by blockIdx.z
   __shared__ __attribute__((aligned(16))) float Qs[QT][KLD];     // the tile's queries: rotated, rounded
   __shared__ __attribute__((aligned(16))) float Ks[KC][KLD];     // the chunk's keys, as the prefill holds them
   __shared__ __attribute__((aligned(16))) float Vs[KC][DH];
@@ -168,10 +171,12 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
   const int D = H * DH;
   const size_t ld = (size_t)3 * D;
   int start = start_p[n];
-  start = start < 0 ? 0 : (start > S ? S : start);
+  const int start_max = TREE ? S - 1 : S;                  // (TREE: the root's position is inside the sequence)
+  start = start < 0 ? 0 : (start > start_max ? start_max : start);
   int len = len_p[n];
   len = len < 0 ? 0 : (len > Tn ? Tn : len);
-  if (len > S - start) len = S - start;
+  if constexpr (!TREE)
+    if (len > S - start) len = S - start;
   const int NQ = O * Tn;
   const T* seq = cache + (size_t)n * S * ld + h * DH;
   const T* arow = cache + (size_t)B * S * ld + h * DH;
@@ -194,11 +199,13 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
   //   narrow: the workgroup walks the tiles of all NQ rows; a tile may run across options and stages the options it touches.
   //   WIDE: the workgroup has the one tile blockIdx.z names, 32 rows from suffix row w_j0 of the option whose first row is w_lo,
   //         and stages that option's rows up to its last query: suffix rows are differences, the option test is compiled out.
+  //   TREE: WIDE's tile of the one option (w_lo = 0); it stages its own rows only, behind the chunk of q0's chain, and a row's
+  //         position and who sees it come from depth / end.
   int w_lo = 0, w_j0 = 0;
-  if constexpr (WIDE) {
+  if constexpr (TILED) {
     const int NT = (Tn + QT - 1) / QT;
-    w_lo = (blockIdx.z / NT) * Tn;
-    w_j0 = (blockIdx.z % NT) * QT;
+    w_lo = TREE ? 0 : (blockIdx.z / NT) * Tn;
+    w_j0 = TREE ? blockIdx.z * QT : (blockIdx.z % NT) * QT;
     if (w_j0 >= len) {                                   // a tile of padding rows (the whole workgroup takes this branch)
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
@@ -208,10 +215,22 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       return;
     }
   }
-  const auto row_j = [&](int r) { return WIDE ? r - w_lo : r % Tn; };                  // a flattened row's suffix row,
-  const auto row_c = [&](int r) { return WIDE ? 0 : r / Tn; };                         // its option,
-  const auto row_first = [&](int r) { return WIDE ? w_lo : (r / Tn) * Tn; };           // its option's first row
-  const int q_first = WIDE ? w_lo + w_j0 : 0, q_last = WIDE ? q_first + 1 : NQ, q_end = WIDE ? w_lo + Tn : NQ;
+  const auto row_j = [&](int r) { return TILED ? r - w_lo : r % Tn; };                 // a flattened row's suffix row,
+  const auto row_c = [&](int r) { return TILED ? 0 : r / Tn; };                        // its option,
+  const auto row_first = [&](int r) { return TILED ? w_lo : (r / Tn) * Tn; };          // its option's first row
+  // (TREE) the depth and the subtree's end of a real row r < len, clamped: a position stays inside the sequence, end in (r, len]
+  const int32_t *depth = nullptr, *end = nullptr, *anc = nullptr;
+  int dmax = 0;
+  if constexpr (TREE) {
+    depth = pack_at<0>(more...) + (size_t)n * Tn;
+    end = pack_at<1>(more...) + (size_t)n * Tn;
+    anc = pack_at<2>(more...) + ((size_t)n * gridDim.z + blockIdx.z) * KC;
+    dmax = S - 1 - start < TREE_DEPTH ? S - 1 - start : TREE_DEPTH;
+  }
+  const auto depth_of = [&](int r) { const int d = depth[r]; return d < 0 ? 0 : (d > dmax ? dmax : d); };
+  const auto end_of = [&](int r) { const int e = end[r]; return e < r + 1 ? r + 1 : (e > len ? len : e); };
+  const auto row_pos = [&](int r) { return start + (TREE ? depth_of(r) : row_j(r)); };  // a (TREE: real) row's position
+  const int q_first = TILED ? w_lo + w_j0 : 0, q_last = TILED ? q_first + 1 : NQ, q_end = TILED ? w_lo + Tn : NQ;
   for (int q0 = q_first; q0 < q_last; q0 += QT) {
     // ---- the tile's queries
     {
@@ -220,7 +239,7 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       float v[16];
       if (qi < q_end && j < len) {
         load16<T>(sufn + (size_t)qi * ld + sd0, v);
-        rope16<T>(v, cs, sn, start + j, sd0);
+        rope16<T>(v, cs, sn, row_pos(qi), sd0);
       } else {
 #pragma unroll
         for (int e = 0; e < 16; ++e) v[e] = 0.f;
@@ -234,7 +253,7 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
 #pragma unroll
     for (int u = 0; u < 16; ++u) acc[u] = 0.f;
     // what this thread's four score queries are
-    int qj[4], qc[4];
+    int qj[4], qc[4], qpos[4];
     bool qok[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -242,16 +261,32 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       qc[u] = row_c(qi);
       qj[u] = row_j(qi);
       qok[u] = qi < q_end && qj[u] < len;
+      qpos[u] = !TREE || qok[u] ? row_pos(qi) : start;
     }
-    const int s_lo = row_first(q0);
+    const int s_lo = TREE ? q0 : row_first(q0);
     int s_hi = ((q0 + QT - 1) / Tn + 1) * Tn;
     if (s_hi > NQ) s_hi = NQ;
-    if constexpr (WIDE) s_hi = w_lo + (w_j0 + QT < len ? w_j0 + QT : len);
-    const int n_pre = (start + KC - 1) / KC, n_suf = (s_hi - s_lo + KC - 1) / KC;
-    // chunks: [0, n_pre) cached prompt keys, [n_pre, n_pre + n_suf) suffix keys, then the adapter keys (own softmax)
+    if constexpr (TILED) s_hi = w_lo + (w_j0 + QT < len ? w_j0 + QT : len);
+    int n_anc = 0;                                       // (TREE) q0's proper ancestors: the keys of the chain chunk
+    if constexpr (TREE) n_anc = depth_of(q0);
+    const int n_chain = n_anc > 0 ? 1 : 0;
+    const int n_pre = (start + KC - 1) / KC, n_suf = n_chain + (s_hi - s_lo + KC - 1) / KC;
+    // chunks: [0, n_pre) cached prompt keys, [n_pre, n_pre + n_suf) suffix keys (TREE: the chain of q0 if it has one, then the
+    // tile's own rows), then the adapter keys (own softmax)
     for (int ch = 0; ch <= n_pre + n_suf; ++ch) {
       const int kind = ch < n_pre ? 0 : (ch < n_pre + n_suf ? 1 : 2);
-      const int k0 = kind == 0 ? ch * KC : (kind == 1 ? s_lo + (ch - n_pre) * KC : 0);
+      const int k0 = kind == 0 ? ch * KC : (kind == 1 ? s_lo + (ch - n_pre - n_chain) * KC : 0);
+      const bool chain = TREE && kind == 1 && ch < n_pre + n_chain;
+      // r: the suffix row that key column c of a suffix chunk holds, if it holds one (the chain's rows come from anc, the others
+      // lie in order)
+      const auto key_row = [&](int c, int& r) {
+        r = k0 + c;
+        if (chain) {
+          r = c < n_anc ? anc[c] : -1;
+          return r >= 0 && r < q0;                       // (an ancestor of q0 lies in front of it)
+        }
+        return r < s_hi && row_j(r) < len;
+      };
       __syncthreads();                                   // the previous chunk's readers are done (and Qs / mrun are written)
       if (kind == 2 && tid < QT) {                       // text softmax closed: o = acc / l, then the adapter's share is added
         alpha[tid] = lrun[tid] > 0.f ? 1.f / lrun[tid] : 0.f;
@@ -267,8 +302,8 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         if (kind == 0) {
           if (ki < start) { row = seq + (size_t)ki * ld; pos = ki; rot = !cache_rot; }
         } else if (kind == 1) {
-          const int j = row_j(ki);
-          if (ki < s_hi && j < len) { row = sufn + (size_t)ki * ld; pos = start + j; rot = true; }
+          int r;
+          if (key_row(srow, r)) { row = sufn + (size_t)r * ld; pos = row_pos(r); rot = true; }
         } else if (ki < A) {
           row = arow + (size_t)ki * ld;
         }
@@ -286,9 +321,9 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
                                          sn[(size_t)pos * HP + sd0 / 2 + e], kr[2 * e], kr[2 * e + 1]);
                 store16_as<T>(crow + D + sd0, kr);
               } else {
-                copy16<T>(crow + D + sd0, row + D + sd0);
+                copy_bits<16>(crow + D + sd0, row + D + sd0);
               }
-              copy16<T>(crow + 2 * D + sd0, row + 2 * D + sd0);
+              copy_bits<16>(crow + 2 * D + sd0, row + 2 * D + sd0);
             }
           }
           if (rot) rope16<T>(k, cs, sn, pos, sd0);
@@ -312,25 +347,31 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         }
       }
       const int ki = k0 + kk;
-      int kpos = ki, kc = -1, kj = 0;
+      int kpos = ki, kc = -1, kj = 0, kend = 0;
       bool kok;
       if (kind == 0) {
         kok = ki < start;
       } else if (kind == 1) {
-        kc = row_c(ki);
-        kj = row_j(ki);
-        kpos = start + kj;
-        kok = ki < s_hi && kj < len;
+        int r;
+        kok = key_row(kk, r);
+        if constexpr (TREE) {
+          kj = r;
+          if (kok) { kpos = row_pos(r); kend = end_of(r); }
+        } else {
+          kc = row_c(ki);
+          kj = row_j(ki);
+          kpos = start + kj;
+        }
       } else {
         kok = ki < A;
       }
       const bool frame_key = kind != 2 && vs >= 0 && kpos >= vs && kpos < vs + F;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        bool see = qok[u] && kok;
-        if (kind == 1) see = see && kc == qc[u] && kj <= qj[u];
+        bool see = qok[u] && kok;                          // suffix keys: rows of one option (TREE: ancestor-or-self), not behind
+        if (kind == 1) see = see && kj <= qj[u] && (TREE ? qj[u] < kend : kc == qc[u]);
         float x = s[u] * scale;
-        if (frame_key && start + qj[u] >= vs + F) x += g2;
+        if (frame_key && qpos[u] >= vs + F) x += g2;
         x = see ? x : -1e30f;
         const int q = 4 * qg + u;
         const float m_old = mrun[q];
@@ -358,7 +399,7 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
       }
       __syncthreads();
       if constexpr (MASS) {
-        float* __restrict__ mass = pack_first(mass_p...);
+        float* __restrict__ mass = pack_at<0>(more...);
         // ---- the summary: Ms[q][e] = Ms[q][e] * alpha[q] + the chunk's weight on entry e; closed and stored in the adapter chunk
         const int q = srow, qi = q0 + q;
         const float al = alpha[q];
@@ -407,210 +448,7 @@ __global__ __launch_bounds__(256) void attn_suffix_k(const T* __restrict__ suf, 
         o_suf[((size_t)n * NQ + qi) * D + h * DH + vd] = from_f32<T>(ok ? acc[u] : 0.f);
       }
     }
-    if constexpr (!WIDE) __syncthreads();                // Qs / mrun are rewritten by the next tile
-  }
-}
-
-constexpr int TREE_DEPTH = FVQA_TREE_DEPTH_MAX;      // deepest row of fvqa_attn_suffix_tree: a tile's ancestor chain fits one chunk
-static_assert(TREE_DEPTH < KC, "the chain of a tile's first row is one chunk of keys");
-
-// fvqa_attn_suffix_tree — the suffix rows of a sample are the nodes of a TREE (fvqa/vocab.py: the internal nodes of a trie of
-// allowed answers, numbered in pre-order). Row r sits at position start[n] + depth[r] and sees the cache rows [0, start[n]), the
-// rows that are its ancestors-or-self and the adapter keys. In pre-order, a is an ancestor-or-self of q iff a <= q < end[a], and
-// every ancestor of a row of the 32-row tile from q0 lies in the tile or is an ancestor of q0: the tile's suffix keys are ONE
-// chunk of q0's ancestors (anc, root first: depth[q0] <= 31 of them) and ONE chunk of the tile's own rows, both under the interval
-// test. One workgroup per (head, sample, tile), as WIDE has them. The tile is attn_suffix_k's, written out again (a kernel of its
-// own: the four entries above keep their text and their code): what differs is where a key row and its position come from and
-// who sees it. Every index read from depth / end / anc is clamped before it is used.
-template <typename T>
-__global__ __launch_bounds__(256) void attn_suffix_tree_k(const T* __restrict__ suf, const T* __restrict__ cache,
-                                                          T* __restrict__ o_suf, const float* __restrict__ gate1,
-                                                          const float* __restrict__ gate2, const int32_t* __restrict__ vstart,
-                                                          const int32_t* __restrict__ start_p, const int32_t* __restrict__ rows_p,
-                                                          const int32_t* __restrict__ depth_p, const int32_t* __restrict__ end_p,
-                                                          const int32_t* __restrict__ anc_p, const float* __restrict__ cs,
-                                                          const float* __restrict__ sn, int B, int R, int S, int H, int A, int F,
-                                                          int cache_rot) {
-  __shared__ __attribute__((aligned(16))) float Qs[QT][KLD];
-  __shared__ __attribute__((aligned(16))) float Ks[KC][KLD];
-  __shared__ __attribute__((aligned(16))) float Vs[KC][DH];
-  __shared__ __attribute__((aligned(16))) float Ps[QT][KC];
-  __shared__ float mrun[QT], lrun[QT], alpha[QT];
-  const int tid = threadIdx.x;
-  const int h = blockIdx.x, n = blockIdx.y, q0 = blockIdx.z * QT;
-  const int D = H * DH;
-  const size_t ld = (size_t)3 * D;
-  int start = start_p[n];
-  start = start < 0 ? 0 : (start > S - 1 ? S - 1 : start);
-  int NR = rows_p[n];
-  NR = NR < 0 ? 0 : (NR > R ? R : NR);
-  const int dmax = S - 1 - start < TREE_DEPTH ? S - 1 - start : TREE_DEPTH;     // a row's position stays inside the sequence
-  const T* seq = cache + (size_t)n * S * ld + h * DH;
-  const T* arow = cache + (size_t)B * S * ld + h * DH;
-  const T* sufn = suf + (size_t)n * R * ld + h * DH;
-  const int32_t* depth = depth_p + (size_t)n * R;
-  const int32_t* end = end_p + (size_t)n * R;
-  const int32_t* anc = anc_p + ((size_t)n * gridDim.z + blockIdx.z) * KC;
-  const auto depth_of = [&](int r) { const int d = depth[r]; return d < 0 ? 0 : (d > dmax ? dmax : d); };
-  const auto end_of = [&](int r) { const int e = end[r]; return e < r + 1 ? r + 1 : (e > NR ? NR : e); };
-  const float scale = rsqrtf((float)DH);
-  const int vs = vstart[n];
-  const float g2 = gate2[h];
-  const float tg1 = tanhf(gate1[h]);
-  const int srow = tid >> 3, sd0 = (tid & 7) * 16;         // staging role: 8 threads per row, 16 head dims each
-  const int kk = tid & 31, qg = tid >> 5;                  // score role: key column kk, queries 4*qg .. 4*qg + 3
-  const int vd = tid & 127, qh = tid >> 7;                 // value role: head dim vd, queries 16*qh .. 16*qh + 15
-  if (q0 >= NR) {                                          // a tile of padding rows (the whole workgroup takes this branch)
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int r = q0 + 16 * qh + u;
-      if (r < R) o_suf[((size_t)n * R + r) * D + h * DH + vd] = from_f32<T>(0.f);
-    }
-    return;
-  }
-  const int n_anc = depth_of(q0);                          // q0's proper ancestors: the keys of the chain chunk
-  // ---- the tile's queries
-  {
-    const int qi = q0 + srow;
-    float v[16];
-    if (qi < NR) {
-      load16<T>(sufn + (size_t)qi * ld + sd0, v);
-      rope16<T>(v, cs, sn, start + depth_of(qi), sd0);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = 0.f;
-    }
-    store16(&Qs[srow][sd0], v);
-    if (tid < QT) { mrun[tid] = -1e30f; lrun[tid] = 0.f; }
-  }
-  float acc[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) acc[u] = 0.f;
-  int qr[4], qpos[4];                                      // what this thread's four score queries are
-  bool qok[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    qr[u] = q0 + 4 * qg + u;
-    qok[u] = qr[u] < NR;
-    qpos[u] = start + (qok[u] ? depth_of(qr[u]) : 0);
-  }
-  const int n_pre = (start + KC - 1) / KC, n_chain = n_anc > 0 ? 1 : 0;
-  // chunks: [0, n_pre) cached prompt keys, the chain of q0 (if it has one), the tile's own rows, then the adapter keys (own softmax)
-  for (int ch = 0; ch <= n_pre + n_chain + 1; ++ch) {
-    const int kind = ch < n_pre ? 0 : (ch < n_pre + n_chain ? 1 : (ch == n_pre + n_chain ? 2 : 3));
-    __syncthreads();                                       // the previous chunk's readers are done (and Qs / mrun are written)
-    if (kind == 3 && tid < QT) {                           // text softmax closed: o = acc / l, then the adapter's share is added
-      alpha[tid] = lrun[tid] > 0.f ? 1.f / lrun[tid] : 0.f;
-      mrun[tid] = -1e30f;
-    }
-    // the suffix row a key column of this chunk holds (kinds 1 and 2), -1: none
-    const auto key_row = [&](int c) {
-      if (kind == 1) {
-        if (c >= n_anc) return -1;
-        const int a = anc[c];
-        return a < 0 || a >= q0 ? -1 : a;                  // (an ancestor of q0 lies in front of it)
-      }
-      return q0 + c < NR ? q0 + c : -1;
-    };
-    // ---- stage the chunk's keys and values
-    {
-      float k[16], v[16];
-      const T* row = nullptr;
-      int pos = 0;
-      bool rot = false;
-      if (kind == 0) {
-        const int ki = ch * KC + srow;
-        if (ki < start) { row = seq + (size_t)ki * ld; pos = ki; rot = !cache_rot; }
-      } else if (kind == 3) {
-        if (srow < A) row = arow + (size_t)srow * ld;
-      } else {
-        const int r = key_row(srow);
-        if (r >= 0) { row = sufn + (size_t)r * ld; pos = start + depth_of(r); rot = true; }
-      }
-      if (row) {
-        load16<T>(row + D + sd0, k);
-        load16<T>(row + 2 * D + sd0, v);
-        if (rot) rope16<T>(k, cs, sn, pos, sd0);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) k[e] = v[e] = 0.f;
-      }
-      store16(&Ks[srow][sd0], k);
-      store16(&Vs[srow][sd0], v);
-    }
-    __syncthreads();
-    // ---- scores of (4 queries) x (key kk)
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int d = 0; d < DH; d += 4) {
-      const float4 k4 = *reinterpret_cast<const float4*>(&Ks[kk][d]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float4 q4 = *reinterpret_cast<const float4*>(&Qs[4 * qg + u][d]);
-        s[u] += q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
-      }
-    }
-    int kpos = ch * KC + kk, kr = -1, kend = 0;
-    bool kok;
-    if (kind == 0) {
-      kok = kpos < start;
-    } else if (kind == 3) {
-      kok = kk < A;
-    } else {
-      kr = key_row(kk);
-      kok = kr >= 0;
-      if (kok) { kpos = start + depth_of(kr); kend = end_of(kr); }
-    }
-    const bool frame_key = kind != 3 && kok && vs >= 0 && kpos >= vs && kpos < vs + F;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      bool see = qok[u] && kok;
-      if (kind == 1 || kind == 2) see = see && kr <= qr[u] && qr[u] < kend;      // ancestor-or-self
-      float x = s[u] * scale;
-      if (frame_key && qpos[u] >= vs + F) x += g2;
-      x = see ? x : -1e30f;
-      const int q = 4 * qg + u;
-      const float m_old = mrun[q];
-      const float m_new = fmaxf(m_old, half_max(x));
-      const float e = see ? __expf(x - m_new) : 0.f;
-      const float sum = half_sum(e);
-      if (kind == 3) {
-        Ps[q][kk] = sum > 0.f ? e / sum * tg1 : 0.f;
-      } else {
-        Ps[q][kk] = e;
-        if (kk == 0) {
-          const float a = __expf(m_old - m_new);
-          alpha[q] = a;
-          lrun[q] = lrun[q] * a + sum;
-        }
-      }
-      if (kk == 0) mrun[q] = m_new;        // (read above by this half wave only: each query belongs to one)
-    }
-    __syncthreads();
-    // ---- values: acc[q] = acc[q] * alpha[q] + sum_k P[q][k] V[k][vd]
-    float vcol[KC];
-#pragma unroll
-    for (int k = 0; k < KC; ++k) vcol[k] = Vs[k][vd];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int q = 16 * qh + u;
-      float a = acc[u] * alpha[q];
-#pragma unroll
-      for (int k = 0; k < KC; k += 4) {
-        const float4 p4 = *reinterpret_cast<const float4*>(&Ps[q][k]);
-        a += p4.x * vcol[k];
-        a += p4.y * vcol[k + 1];
-        a += p4.z * vcol[k + 2];
-        a += p4.w * vcol[k + 3];
-      }
-      acc[u] = a;
-    }
-  }
-  // ---- the tile's output rows (padding rows: zeros)
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int r = q0 + 16 * qh + u;
-    if (r < R) o_suf[((size_t)n * R + r) * D + h * DH + vd] = from_f32<T>(r < NR ? acc[u] : 0.f);
+    if constexpr (!TILED) __syncthreads();               // Qs / mrun are rewritten by the next tile
   }
 }
 
@@ -661,37 +499,36 @@ __global__ __launch_bounds__(256) void option_pick_k(const float* __restrict__ r
   }
 }
 
-// validates and launches the four entries: WIDE differs in the row limit and the grid only
-template <bool APPEND, bool MASS = false, bool WIDE = false>
+// validates and launches the five entries: WIDE and TREE differ in the row limit and the grid, TREE in its operand limits too.
+// more: the operands of one instantiation (MASS: the summary; TREE: depth, end, tile_anc)
+template <bool APPEND, bool MASS = false, bool WIDE = false, bool TREE = false, typename... M>
 int suffix_launch(const void* qkv_suf, const void* qkv_cache, void* o_suf, const float* gate1, const float* gate2,
                   const int32_t* vstart, const int32_t* start, const int32_t* len, const float* cos_t, const float* sin_t,
                   int n_seq, int n_options, int suffix_len, int seq_len, int n_heads, int head_dim, int adapter_len,
-                  int max_feats, int cache_rotated, int dtype, void* stream, float* mass = nullptr) {
-  static_assert(APPEND + MASS + WIDE <= 1, "one switch at a time");
+                  int max_feats, int cache_rotated, int dtype, void* stream, M*... more) {
+  static_assert(APPEND + MASS + WIDE + TREE <= 1 && sizeof...(M) == (MASS ? 1 : TREE ? 3 : 0), "one switch at a time");
   if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !len || !cos_t || !sin_t)
     return FVQA_EINVAL;
-  if (MASS && !mass) return FVQA_EINVAL;
+  if ((... || !more)) return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > (WIDE ? TWIDE : TMAX) || seq_len <= 0 || n_heads <= 0 ||
-      head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
+  if (n_seq <= 0 || n_options <= 0 || suffix_len <= 0 || suffix_len > (TREE ? FVQA_TREE_ROWS_MAX : WIDE ? TWIDE : TMAX) ||
+      seq_len <= 0 || n_heads <= 0 || head_dim != DH || adapter_len < 0 || adapter_len > 16 || max_feats < 0)
     return FVQA_ESHAPE;
   if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || n_options > 4096) return FVQA_ESHAPE;
+  if (TREE && (long long)n_seq * suffix_len > FVQA_TREE_TOTAL_ROWS_MAX) return FVQA_ESHAPE;
   if (APPEND && n_options != 1) return FVQA_ESHAPE;      // (options share one cache: only a single continuation may join it)
   if (MASS && max_feats > MFMAX) return FVQA_ESHAPE;     // (the accumulators' LDS rows)
   if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
-  if (MASS && ((uintptr_t)mass & 3)) return FVQA_EALIGN;
-  const int tiles = (suffix_len + QT - 1) / QT;          // (WIDE: n_options * tiles <= 8192, inside the grid's third axis)
-  const dim3 grid(n_heads, n_seq, WIDE ? n_options * tiles : 1), block(256);
+  if ((0 | ... | (uintptr_t)more) & 3) return FVQA_EALIGN;
+  if (TREE && (((uintptr_t)vstart | (uintptr_t)start | (uintptr_t)len) & 3)) return FVQA_EALIGN;
+  const int tiles = (suffix_len + QT - 1) / QT;          // (WIDE: n_options * tiles <= 8192, TREE: 128, inside the grid's third axis)
+  const dim3 grid(n_heads, n_seq, WIDE || TREE ? n_options * tiles : 1), block(256);
   hipStream_t st = (hipStream_t)stream;
   const auto launch = [&](auto* t) {                     // t: the storage type
     using T = std::remove_pointer_t<decltype(t)>;
-    const auto kernel = [&](auto k, auto... more) {
-      hipLaunchKernelGGL(k, grid, block, 0, st, (const T*)qkv_suf, (const T*)qkv_cache, (T*)o_suf, gate1, gate2, vstart, start,
-                         len, cos_t, sin_t, n_seq, n_options, suffix_len, seq_len, n_heads, adapter_len, max_feats,
-                         cache_rotated, more...);
-    };
-    if constexpr (MASS) kernel(attn_suffix_k<T, false, true, false, float>, mass);
-    else kernel(attn_suffix_k<T, APPEND, false, WIDE>);
+    hipLaunchKernelGGL((attn_suffix_k<T, APPEND, MASS, WIDE, TREE, M...>), grid, block, 0, st, (const T*)qkv_suf,
+                       (const T*)qkv_cache, (T*)o_suf, gate1, gate2, vstart, start, len, cos_t, sin_t, n_seq, n_options,
+                       suffix_len, seq_len, n_heads, adapter_len, max_feats, cache_rotated, more...);
   };
   if (dtype == FVQA_H16) launch((bf16_t*)nullptr);
   else launch((float*)nullptr);
@@ -744,29 +581,9 @@ extern "C" int fvqa_attn_suffix_tree(const void* qkv_suf, const void* qkv_cache,
                                      const int32_t* depth, const int32_t* end, const int32_t* tile_anc, const float* cos_t,
                                      const float* sin_t, int n_seq, int rows, int seq_len, int n_heads, int head_dim,
                                      int adapter_len, int max_feats, int cache_rotated, int dtype, void* stream) {
-  if (!qkv_suf || !qkv_cache || !o_suf || !gate1 || !gate2 || !vstart || !start || !n_rows || !depth || !end || !tile_anc ||
-      !cos_t || !sin_t)
-    return FVQA_EINVAL;
-  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (n_seq <= 0 || rows <= 0 || rows > FVQA_TREE_ROWS_MAX || seq_len <= 0 || n_heads <= 0 || head_dim != DH || adapter_len < 0 ||
-      adapter_len > 16 || max_feats < 0)
-    return FVQA_ESHAPE;
-  if (seq_len > SMAX || n_heads > 65535 || n_seq > 65535 || (long long)n_seq * rows > FVQA_TREE_TOTAL_ROWS_MAX) return FVQA_ESHAPE;
-  if (((uintptr_t)qkv_suf | (uintptr_t)qkv_cache | (uintptr_t)o_suf) & 15) return FVQA_EALIGN;
-  if (((uintptr_t)vstart | (uintptr_t)start | (uintptr_t)n_rows | (uintptr_t)depth | (uintptr_t)end | (uintptr_t)tile_anc) & 3)
-    return FVQA_EALIGN;
-  const dim3 grid(n_heads, n_seq, (rows + QT - 1) / QT), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == FVQA_H16)
-    hipLaunchKernelGGL(attn_suffix_tree_k<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv_suf, (const bf16_t*)qkv_cache,
-                       (bf16_t*)o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc, cos_t, sin_t, n_seq, rows,
-                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
-  else
-    hipLaunchKernelGGL(attn_suffix_tree_k<float>, grid, block, 0, st, (const float*)qkv_suf, (const float*)qkv_cache,
-                       (float*)o_suf, gate1, gate2, vstart, start, n_rows, depth, end, tile_anc, cos_t, sin_t, n_seq, rows,
-                       seq_len, n_heads, adapter_len, max_feats, cache_rotated);
-  FVQA_CHECK_LAUNCH();
-  return FVQA_OK;
+  return suffix_launch<false, false, false, true>(qkv_suf, qkv_cache, o_suf, gate1, gate2, vstart, start, n_rows, cos_t, sin_t,
+                                                  n_seq, 1, rows, seq_len, n_heads, head_dim, adapter_len, max_feats,
+                                                  cache_rotated, dtype, stream, depth, end, tile_anc);
 }
 
 extern "C" int fvqa_option_pick(const float* rowloss, const int32_t* row_map, int n_rows, float* individual_losses,

@@ -3,8 +3,8 @@
 // sequence — the last committed token and a draft of what follows it — and this step keeps every draft token the model would
 // have picked itself, so that the ids are greedy's, token for token (include/fvqa.h fvqa_spec_step states the rule).
 //
-//   verify   row i of the sequence's logits is scanned only if the drafts 1..i were all accepted: the largest logit (lowest
-//            index on exact ties, fvqa_decode_next's loop), then the row's lse for the log-probability (fvqa_decode_next_ex's
+//   verify   row i of the sequence's logits is scanned only if the drafts 1..i were all accepted (csrc/token_step.h row_verify:
+//            the largest logit, lowest index on exact ties, then the row's lse for the log-probability — fvqa_decode_next_ex's
 //            rule 5: maximum, sum of expf in strided order, shuffles, the four waves in order). The token committed at row i is
 //            argmax L_i whether it was drafted or not — a draft only decides whether row i + 1 may be used —, so there is one
 //            commit loop and no separate "fresh token" case.
@@ -46,10 +46,8 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
   const int32_t* wrow = w + (size_t)b * Tn;
   const int p0 = pos[b];
   int ngen = n_generated[b];
-  int m = len_p[b];
-  m = m < 1 ? 1 : (m > Tn ? Tn : m);
-  // a finished row, one with no room for another token and one whose budget is spent commit nothing
-  const bool live = done[b] == 0 && p0 >= -1 && p0 + 1 < S && ngen < max_new;
+  const int m = verify_rows(len_p[b], Tn);
+  const bool live = verify_live(done[b], p0, S, ngen, max_new);
   int now_done = live ? 0 : 1;
   int p = p0, nc = 0;
 
@@ -57,18 +55,8 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
   if (live) {
     for (int i = 0; i < m; ++i) {
       const float* lg = logits + ((size_t)b * Tn + i) * V;
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int v = tid; v < V; v += NT) {
-        const float x = lg[v];
-        if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
-      }
-      const float mx = block_max_256(bv, redf);
-      int g = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
-      if (g >= V) g = 0;                                           // (a row of NaNs)
-      float z = 0.f;                                               // row_lse's second half on the arg-max's maximum: a call
-      for (int v = tid; v < V; v += NT) z += expf(lg[v] - mx);     // would add a pass over the row (the same operations and bits)
-      const float lse = mx + logf(block_sum_256(z, redf));
+      float lse;
+      const int g = row_verify(lg, V, redf, redi, lse);
       p += 1;
       ngen += 1;
       if (tid == 0) {
@@ -144,10 +132,7 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
     len_p[b] = mlen;
     start_p[b] = at;
     if (pos64) pos64[b] = at;
-    for (int j = nc; j < Tn; ++j) {
-      token_out[(size_t)b * Tn + j] = -1;
-      logprob_out[(size_t)b * Tn + j] = 0.f;
-    }
+    verify_pad(token_out, logprob_out, (size_t)b * Tn, nc, Tn);
     n_committed[b] = nc;
     n_drafted[b] = live ? m - 1 : 0;
     ticket_arrive(counter, n_active, B, !now_done);

@@ -1,8 +1,9 @@
-// What the token-step kernels share (csrc/sample.hip, beam.hip, spec.hip, jump.hip: one 256-thread workgroup per sequence or
-// sample, everything between the LM head and the next pass's first RMSNorm in one launch), each rule written once: the integer
-// block reductions and the lse of a raw row, the view of a trie with its two clamps, the clamps that keep a finished row's reads
-// inside its arrays, the ticket word that counts running rows across workgroups, the embedding rows of the next pass, and the
-// host side's operand rules (16-byte rows, storage-type dispatch, "no trie or a whole one").
+// What the token-step kernels share (csrc/sample.hip, beam.hip, spec.hip, treespec.hip, jump.hip: one 256-thread workgroup per
+// sequence or sample, everything between the LM head and the next pass's first RMSNorm in one launch), each rule written once: the
+// integer block reductions and the lse of a raw row, the verify scan of the draft-and-verify steps, the view of a trie with its
+// two clamps, the clamps that keep a finished row's reads inside its arrays, the ticket word that counts running rows across
+// workgroups, the embedding rows of the next pass, and the host side's operand rules (16-byte rows, storage-type dispatch, "no
+// trie or a whole one").
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -32,8 +33,8 @@ __device__ __forceinline__ int block_min_int(int v, int* red) {
 __device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
 
 // m + log(sum exp(l - m)) of one raw row: the maximum, then the sum of expf over a thread's strided elements in order, a shuffle
-// tree, the four waves in order. Every log-probability of the token steps is taken against this value (csrc/spec.hip fuses the
-// same operations into its arg-max pass).
+// tree, the four waves in order. Every log-probability of the token steps is taken against this value (row_verify below fuses
+// the same operations into its arg-max pass).
 __device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, float* red) {
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < V; i += NT) mx = fmaxf(mx, lg[i]);
@@ -41,6 +42,40 @@ __device__ __forceinline__ float row_lse(const float* __restrict__ lg, int V, fl
   float z = 0.f;
   for (int i = threadIdx.x; i < V; i += NT) z += expf(lg[i] - m);
   return m + logf(block_sum_256(z, red));
+}
+
+// The verify scan of one raw row by the whole workgroup (csrc/spec.hip, csrc/treespec.hip): the largest logit, the lowest index on
+// exact ties (fvqa_decode_next's loop; 0 for a row of NaNs), and into `lse` row_lse's second half on the arg-max's maximum — a
+// call of row_lse would add a pass over the row; the operations and the bits are the same.
+__device__ __forceinline__ int row_verify(const float* lg, int V, float* redf, int* redi, float& lse) {
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int v = threadIdx.x; v < V; v += NT) {
+    const float x = lg[v];
+    if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
+  }
+  const float mx = block_max_256(bv, redf);
+  int g = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
+  if (g >= V) g = 0;                                               // (a row of NaNs)
+  float z = 0.f;
+  for (int v = threadIdx.x; v < V; v += NT) z += expf(lg[v] - mx);
+  lse = mx + logf(block_sum_256(z, redf));
+  return g;
+}
+
+// What the draft-and-verify steps say of a sequence before they scan: a finished row, one with no room for another token and
+// one whose budget is spent commit nothing; a pass fed between 1 and `rows` rows, whatever len says.
+__device__ __forceinline__ bool verify_live(int done, int p0, int S, int ngen, int max_new) {
+  return done == 0 && p0 >= -1 && p0 + 1 < S && ngen < max_new;
+}
+__device__ __forceinline__ int verify_rows(int len, int rows) { return len < 1 ? 1 : (len > rows ? rows : len); }
+// ... and behind the nc tokens a step committed, in its `width` result slots from `at`: token -1, log-probability 0 (one thread
+// per workgroup calls this)
+__device__ __forceinline__ void verify_pad(int32_t* token, float* logprob, size_t at, int nc, int width) {
+  for (int j = nc; j < width; ++j) {
+    token[at + j] = -1;
+    logprob[at + j] = 0.f;
+  }
 }
 
 // A trie of allowed answers in CSR form (fvqa/constrain.py). Every index read from it is clamped before it is used.

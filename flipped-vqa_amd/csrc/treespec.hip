@@ -4,11 +4,11 @@
 // entries here do what lies between two such passes (include/fvqa.h states both rules):
 //
 // fvqa_tree_spec_step — one launch where fvqa_spec_step sits, one 256-thread workgroup per sequence.
-//   walk     from local row 0: the largest logit of the row (lowest index on exact ties; the lse for the log-probability as
-//            fvqa_spec_step fuses it) is committed whatever the trie says; the child of the row's plan node under that token is
-//            looked for by the whole workgroup (rows r of the node's subtree with parent[r] == node and token[r] == g: on a sound
-//            plan the one the end chain G + 1, end[G + 1], ... reaches; the lowest r on a broken one), and the walk goes on at the
-//            child's row if this pass fed it. A row's logits are scanned only if the walk reaches it.
+//   walk     from local row 0: the largest logit of the row (csrc/token_step.h row_verify, with fvqa_spec_step: lowest index on
+//            exact ties, the lse for the log-probability fused) is committed whatever the trie says; the child of the row's plan
+//            node under that token is looked for by the whole workgroup (rows r of the node's subtree with parent[r] == node and
+//            token[r] == g: on a sound plan the one the end chain G + 1, end[G + 1], ... reaches; the lowest r on a broken one),
+//            and the walk goes on at the child's row if this pass fed it. A row's logits are scanned only if the walk reaches it.
 //   cut      the next pass is the plan rows [node, e): a prefix of the node's subtree, cut by the rows of a pass, by the depth a
 //            tile's ancestor chain may have, by the budget and by the end of the sequence. A prefix of a pre-order range is closed
 //            under ancestors, so it is a tree again.
@@ -16,10 +16,11 @@
 //            `parent`), the path of local rows the walk took (what fvqa_kv_tree_commit appends), tokens, log-probabilities and the
 //            two counts across workgroups (running rows; running rows still on their trie) through two ticket words.
 // fvqa_kv_tree_commit — the cache append of the accepted path: ONE launch over all layers copies the k | v of the stashed raw rows
-//   path[n, i] to cache row start_old[n] + i, k in the cache's convention (rope_pair_as_decode of csrc/score.hip restated: the
-//   same operations with contraction off, so the bits are fvqa_attn_suffix_append's).
+//   path[n, i] to cache row start_old[n] + i, k in the cache's convention (csrc/cache_row.h: the store fvqa_attn_suffix_append
+//   does, so the bits are its bits).
 // No float atomics, fixed summation orders: two launches give the same bits. Every index read from the plan, node, ids or path is
 // clamped or skipped before it is used.
+#include "cache_row.h"
 #include "token_step.h"
 
 namespace {
@@ -59,10 +60,9 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
   int ngen = n_generated[b];
   int a = node_p[b];
   if (a < 0 || a >= NP) a = -1;          // (a node outside the plan: the row has left the trie)
-  int m = len_p[b];
-  m = m < 1 ? 1 : (m > Rin ? Rin : m);
+  int m = verify_rows(len_p[b], Rin);
   m = a < 0 ? 1 : min(m, NP - a);
-  const bool live = done[b] == 0 && p0 >= -1 && p0 + 1 < S && ngen < max_new;
+  const bool live = verify_live(done[b], p0, S, ngen, max_new);
   int now_done = live ? 0 : 1;
   int p = p0, nc = 0, nd = a;
 
@@ -71,18 +71,8 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
     int j = 0;
     for (;;) {
       const float* lg = logits + ((size_t)b * Rin + j) * V;
-      float bv = -INFINITY;
-      int bi = NONE;
-      for (int v = tid; v < V; v += NT) {
-        const float x = lg[v];
-        if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
-      }
-      const float mx = block_max_256(bv, redf);
-      int g = block_min_int(bv == mx ? bi : NONE, redi);
-      if (g >= V) g = 0;                                           // (a row of NaNs)
-      float z = 0.f;                                               // row_lse's second half on the arg-max's maximum, as
-      for (int v = tid; v < V; v += NT) z += expf(lg[v] - mx);     // fvqa_spec_step has it (the same operations and bits)
-      const float lse = mx + logf(block_sum_256(z, redf));
+      float lse;
+      const int g = row_verify(lg, V, redf, redi, lse);
       p += 1;
       ngen += 1;
       if (tid == 0) {
@@ -169,11 +159,8 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
     len_p[b] = m2;
     start_p[b] = at;
     if (pos64) pos64[b] = at;
-    for (int j = nc; j < WALK; ++j) {
-      token_out[(size_t)b * WALK + j] = -1;
-      logprob_out[(size_t)b * WALK + j] = 0.f;
-      path_o[(size_t)b * WALK + j] = 0;
-    }
+    verify_pad(token_out, logprob_out, (size_t)b * WALK, nc, WALK);
+    for (int j = nc; j < WALK; ++j) path_o[(size_t)b * WALK + j] = 0;
     n_path[b] = nc;
     start_old[b] = valid_pos(p0, S);
     n_committed[b] = nc;
@@ -184,22 +171,6 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
   __syncthreads();
   // ---- the next pass's input rows: emb of the last committed token, then of the plan rows' tokens; zeros behind
   next_pass_rows(x_next, emb, b, Rout, D, vec16, tid, m2 < 1 ? 1 : m2, [&](int j) { return wn[j]; });
-}
-
-// eight consecutive elements of a row, bit for bit
-template <typename T> __device__ __forceinline__ void copy8(T* dst, const T* src) {
-#pragma unroll
-  for (int u = 0; u < (int)(8 * sizeof(T) / 16); ++u) reinterpret_cast<uint4*>(dst)[u] = reinterpret_cast<const uint4*>(src)[u];
-}
-
-// RoPE of one pair of a key that goes into the cache: csrc/score.hip's rope_pair_as_decode, operation by operation (contraction
-// off, the fmas written out), so that this kernel stores the bits fvqa_attn_suffix_append and fvqa_attn_decode store.
-template <typename T> __device__ __forceinline__ void rope_pair_as_decode(float a, float b, float c, float s, float& ra, float& rb) {
-#pragma clang fp contract(off)
-  const float bs = b * s, as = a * s;
-  if constexpr (sizeof(T) == 4) ra = a * c - bs;
-  else ra = __builtin_fmaf(a, c, -bs);
-  rb = __builtin_fmaf(b, c, as);
 }
 
 // grid (WALK, n_seq, n_layers): workgroup (i, n, l) appends path entry i of sequence n in layer l, 8 elements per thread and turn
@@ -230,9 +201,9 @@ __global__ __launch_bounds__(NT) void kv_tree_commit_k(T* __restrict__ cache, co
         Vec4<T>::store(dst + D + d + 4 * u, kr);
       }
     } else {
-      copy8<T>(dst + D + d, src + D + d);
+      copy_bits<8>(dst + D + d, src + D + d);
     }
-    copy8<T>(dst + 2 * D + d, src + 2 * D + d);
+    copy_bits<8>(dst + 2 * D + d, src + 2 * D + d);
   }
 }
 

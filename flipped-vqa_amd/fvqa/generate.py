@@ -542,10 +542,16 @@ def _pass_loop(eng, st, max_new_tokens: int, token_step) -> dict:
         if steps == max_new_tokens:
             break                                           # (every row has committed at least one token per step)
         rowpass.head(eng, rowpass.layers(eng, b, attn), b.xn, b.lg)
-    n_generated = st.n_gen.to(torch.int64)
+    out, st.inside = _pass_result(eng, st.ids, p.prefix, st.n_gen, steps)
+    return out
+
+
+def _pass_result(eng, ids, prefix, n_gen, steps: int):
+    """A stopped loop of passes -> (ids, n_generated, steps and tokens (B, longest row) read back from ids; `inside`, their mask)."""
+    n_generated = n_gen.to(torch.int64)
     col = torch.arange(int(n_generated.max()), device=eng.device).unsqueeze(0)
-    tokens, st.inside = _read_back(st.ids, p.prefix, n_generated, col)
-    return {"ids": st.ids, "n_generated": n_generated, "steps": steps, "tokens": tokens}
+    tokens, inside = _read_back(ids, prefix, n_generated, col)
+    return {"ids": ids, "n_generated": n_generated, "steps": steps, "tokens": tokens}, inside
 
 
 def _token_order(tokens, values, inside):
@@ -556,6 +562,16 @@ def _token_order(tokens, values, inside):
     order = (flat < 0).to(torch.int8).argsort(dim=1, stable=True)[:, :inside.shape[1]]
     v = values.permute(1, 0, 2).reshape(B, steps * T).gather(1, order)
     return torch.where(inside, v, torch.zeros_like(v))
+
+
+def _draft_results(out: dict, tokens, logprobs, n_committed, n_drafted, inside, return_logprobs: bool) -> dict:
+    """What draft-and-verify adds to a result: the steps' counts as (B, steps), on request the log-probabilities in token order."""
+    steps = out["steps"]
+    out.update({"n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()})
+    if return_logprobs:
+        out["logprobs"] = _token_order(tokens[:steps], logprobs[:steps], inside)
+        out["sum_logprob"] = out["logprobs"].sum(1)
+    return out
 
 
 @torch.no_grad()
@@ -581,12 +597,7 @@ def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_ne
                       draft_tokens=draft_tokens, lookup_ngram=G, pos64=st.pos64, eos_id=eng.model.tokenizer.eos_id,
                       stop_at_eos=stop_at_eos)
     out = _pass_loop(eng, st, max_new_tokens, token_step)
-    steps = out["steps"]
-    out.update({"n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous()})
-    if return_logprobs:
-        out["logprobs"] = _token_order(st.tokens[:steps], logprobs[:steps], st.inside)
-        out["sum_logprob"] = out["logprobs"].sum(1)
-    return out
+    return _draft_results(out, st.tokens, logprobs, n_committed, n_drafted, st.inside, return_logprobs)
 
 
 class _LagOneNarrow(_LagOneStop):
@@ -675,16 +686,9 @@ def _generate_tree_draft(eng, data: dict, *, R: int, draft_answers, max_new_toke
             wide.qkv = qkv_all[0]
         rowpass.head(eng, rowpass.layers(eng, nxt, attn_tree if r_out > 1 else attn_one), nxt.xn, nxt.lg)
         cur, fed = nxt, r_out
-    n_generated = n_gen.to(torch.int64)
-    col = torch.arange(int(n_generated.max()), device=dev).unsqueeze(0)
-    tok, inside = _read_back(ids, p.prefix, n_generated, col)
-    out = {"ids": ids, "n_generated": n_generated, "steps": steps, "tokens": tok,
-           "n_committed": n_committed[:steps].t().contiguous(), "n_drafted": n_drafted[:steps].t().contiguous(),
-           "rows_per_pass": torch.as_tensor(widths, **i32)}
-    if return_logprobs:
-        out["logprobs"] = _token_order(tokens[:steps], logprobs[:steps], inside)
-        out["sum_logprob"] = out["logprobs"].sum(1)
-    return out
+    out, inside = _pass_result(eng, ids, p.prefix, n_gen, steps)
+    out["rows_per_pass"] = torch.as_tensor(widths, **i32)
+    return _draft_results(out, tokens, logprobs, n_committed, n_drafted, inside, return_logprobs)
 
 
 @torch.no_grad()

@@ -8,7 +8,7 @@ score_flipped, the first three samples of the flipped_tiny fixture (S = 192: the
 An ops.* call enters the hash with its entry name, every tensor operand's shape, dtype and strides (no pointers) and every scalar
 argument (keywords by name). The torch dispatches are counted as tests/test_generate_gpu.py counts them (TorchDispatchMode). The
 same kernels on the same inputs in the same order give the same line: there is no tolerance. The tool uses the public API only
-(fvqa.generate, fvqa.score, the model's score_flipped and the fixtures of tests/), so it runs unchanged in any tree that has it. One thing of the engine's own
+(fvqa.generate, fvqa.score, fvqa.vocab, the model's score_flipped and the fixtures of tests/), so it runs unchanged in any tree that has it. One thing of the engine's own
 is taken out of the picture: it keeps a layer plan per arena under a key of device ADDRESSES (StepEngine.layer_plan), and every
 evaluation call makes its video_start tensor anew, so whether a prefill finds the plan or builds it again hangs on where the
 allocator put eight bytes. The tool drops the kept plans in front of every forward of a recorded call (a call may hold several:
@@ -30,7 +30,7 @@ os.environ.setdefault("FVQA_SYNTHETIC_TOKENIZER", "1")
 import torch  # noqa: E402
 from torch.utils._python_dispatch import TorchDispatchMode  # noqa: E402
 
-from fvqa import generate, ops, score  # noqa: E402
+from fvqa import generate, ops, score, vocab  # noqa: E402
 
 PRESET = "tiny_peakedperm"
 
@@ -121,13 +121,30 @@ def result_hash(out) -> str:
 
 
 def modes(eng, batch, full, drafts):
-    """-> [(name, callable)]. The member sets are those of tests/test_jump_gpu.py: they fit behind the 40 / 41-token prompts."""
+    """-> [(name, callable)]. The member sets are those of tests/test_jump_gpu.py, tests/vocab_util.py (46 rows that cross a tile
+    edge, 33 rows) and tests/test_treedraft_gpu.py (each sample's greedy answer among four decoys; a set the answer leaves at its
+    first token: the narrow passes): they fit behind the 40 / 41-token prompts."""
+    from tests import vocab_util as VU
     from tests.test_jump_gpu import sets_of
+    from tests.test_treedraft_gpu import answers_of, decoys
     fx = types.SimpleNamespace(eng=eng, batch=batch, prefix=batch["prefix_index"]["vqa"])
     branchy, _ = sets_of(fx, "branchy")
     long_, _ = sets_of(fx, "long")
     g = lambda **kw: (lambda: generate.generate(eng, batch, **kw))  # noqa: E731
     so = lambda **kw: (lambda: {k: v for k, v in score.score_options(eng, full, **kw).items() if k != "plan"})  # noqa: E731
+    members = [VU.crossing_members(), VU.random_members(33, 3, max_depth=12)]
+    sv = lambda route: (lambda: {k: v for k, v in vocab.score_vocab(eng, batch, members, route=route).items() if k != "plan"})  # noqa: E731
+    greedy = {}
+
+    def drafted(kind, **kw):                                # draft sets around the greedy answers, which the unrecorded run finds
+        def run():
+            if "a" not in greedy:
+                greedy["a"] = answers_of(generate.generate(eng, batch, temperature=0.0, stop_at_eos=True, max_new_tokens=31))
+            ans = greedy["a"]
+            sets = ([[a] + decoys(a, max(2, len(a) // 2)) for a in ans] if kind == "answer" else
+                    decoys(ans[0], max(2, len(ans[0]) // 2))[:1] + [[9, 9, 9]])
+            return generate.generate(eng, batch, max_new_tokens=31, draft_answers=sets, **kw)
+        return run
     return [
         ("greedy_decode", lambda: generate.greedy_decode(eng, batch)),
         ("generate", g()),
@@ -153,6 +170,11 @@ def modes(eng, batch, full, drafts):
         ("score_options shared frame_attention", so(route="shared", frame_attention=True)),
         ("score_options dense frame_attention", so(route="dense", frame_attention=True)),
         ("score_options contrast=blind", so(contrast="blind")),
+        ("score_vocab tree", sv("tree")),
+        ("score_vocab dense", sv("dense")),
+        ("lookahead=4 draft_answers", drafted("answer", lookahead=4)),
+        ("lookahead=64 draft_answers return_logprobs", drafted("answer", lookahead=64, return_logprobs=True)),
+        ("lookahead=4 draft_answers without the answer", drafted("none", lookahead=4)),
     ]
 
 
