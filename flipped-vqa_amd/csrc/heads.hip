@@ -866,7 +866,8 @@ extern "C" int fvqa_av_linear_bwd(const float* g, int ldg, const fvqa_proj_src* 
                                   int dim, void* stream) {
   if (!g) return FVQA_EINVAL;
   if (rows <= 0 || dim <= 0 || ldg < dim) return FVQA_ESHAPE;
-  if (ldg % 4 || (((uintptr_t)g | (uintptr_t)dbias) & 15)) return FVQA_EALIGN;
+  // (no condition on ldg: proj_bwd_k reads g and dbias element by element — fvqa_av_proj_bwd runs it at ldg = dim, any dim)
+  if ((((uintptr_t)g | (uintptr_t)dbias) & 15)) return FVQA_EALIGN;
   ProjSrcs S;
   bool mfma_ok;
   if (int rc = proj_pack(src, n_src, &S, &mfma_ok)) return rc;
