@@ -15,11 +15,13 @@ Transformer.generate; KV-cached decode, greedy or temperature / nucleus sampling
 line) makes it one of the file's answers (fvqa.generate.generate(constraints=...): decoding over a trie of the allowed answers).
 `--contrast blind` (train.py's flag) picks every token from the difference to the prompt's video-blind twin — the same text with
 zero features — and prints how many tokens were plausible per step (fvqa.generate.generate(contrast="blind")).
-`--lookahead T` (train.py's flag; greedy only) verifies a prompt-lookup draft of up to T - 1 tokens per pass and prints how many
+`--lookahead T` (train.py's flag) verifies a prompt-lookup draft of up to T - 1 tokens per pass and prints how many
 tokens each token step committed (fvqa.generate.generate(lookahead=T)): the same answer in fewer passes.
-`--draft options|vocab --lookahead R` (greedy only) drafts the --options, or the answers of --answer_vocab FILE, as a trie and
-verifies it in one tree pass of up to R rows (fvqa.generate.generate(lookahead=R, draft_answers=...)): the plain greedy answer,
+`--draft options|vocab --lookahead R` drafts the --options, or the answers of --answer_vocab FILE, as a trie and
+verifies it in one tree pass of up to R rows (fvqa.generate.generate(lookahead=R, draft_answers=...)): the plain answer,
 whatever the model says, in about three passes where it is one of the drafted answers.
+Both take --temperature, --top_p, --top_k and --repetition_penalty together with a --seed (required: without one they stay
+refused): the answer is then the plain SAMPLED call's for the same seed, token for token (a draft is kept iff it is the token the plain sampler draws there). Not with --num_samples > 1.
 `--jump_forward T` (with --constrain or --answer_vocab; greedy only) commits the tokens the trie of allowed answers fixes without
 a pass of their own, up to T per step, and prints the tokens committed per step (fvqa.generate.generate(jump_forward=T)).
 `--frame_attention` prints, under each answer, the weight its tokens' text softmax put on each of the clip's frame keys and their
@@ -78,7 +80,7 @@ def get_args_parser():
                         "(0, 1: off)")
     p.add_argument("--draft", type=str, choices=["options", "vocab"], default=None,
                    help="with --lookahead R (2 .. 64): draft a trie of likely answers — the --options, or the answers of "
-                        "--answer_vocab — and verify it in one tree pass: greedy's own answer, whatever it is, in fewer passes")
+                        "--answer_vocab — and verify it in one tree pass: the plain call's own answer, whatever it is, in fewer passes")
     p.add_argument("--frame_attention", action="store_true",
                    help="print the share of attention each frame of the clip received from the answer's tokens, and their sum")
     p.add_argument("--rank", type=int, default=0, metavar="N",

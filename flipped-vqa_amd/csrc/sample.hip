@@ -73,39 +73,6 @@ constexpr size_t ROW_LDS_MAX = 144 * 1024;       // beside ~100 bytes of reducti
 
 __device__ unsigned g_ticket = 0;
 
-// exclusive prefix of v over the 256 threads in thread order (fixed tree); *total = the sum over all of them
-__device__ __forceinline__ float block_scan_f(float v, float* wtot, float* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  float base = 0.f;
-  for (int k = 0; k < w; ++k) base += wtot[k];
-  *total = ((wtot[0] + wtot[1]) + wtot[2]) + wtot[3];
-  return base + (x - v);
-}
-__device__ __forceinline__ int block_scan_i(int v, int* wtot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int base = 0;
-  for (int k = 0; k < w; ++k) base += wtot[k];
-  return base + x - v;
-}
-
 // the operands fvqa_decode_next_pair adds (PAIR = true)
 struct PairArgs {
   float alpha, beta;

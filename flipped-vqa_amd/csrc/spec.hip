@@ -17,7 +17,14 @@
 //   outputs  the rows of the next pass (embeddings; zeros behind the draft), start / len for fvqa_attn_suffix_append, the step's
 //            tokens and log-probabilities, the count of running rows through the caller's ticket word (an INTEGER atomic; the
 //            workgroup that arrives last writes the count and puts the word back to zero: csrc/token_step.h).
+// fvqa_spec_step_sample is the kernel template with SAMPLE = true (false in fvqa_spec_step, whose instantiation holds none of
+// the sampling code): draft-and-verify under sampling. The pick at row i is not the arg-max but
+// csrc/row_sample.h's row_sample — rules 1 to 5 of fvqa_decode_next_ex with the draw of the token's index,
+// u[(n_generated + i) * n_seq + n] — and a draft is accepted iff it equals the token sampled in front of it: for a point-mass
+// draft that is the rejection rule of speculative sampling, so the ids are the plain sampled call's. The bitmap of the
+// repetition penalty is built once per step and gains one bit per commit. Everything behind the pick is the code above.
 // No float atomics, fixed summation orders: two launches on the same inputs give the same bits.
+#include "row_sample.h"
 #include "token_step.h"
 
 namespace {
@@ -25,7 +32,7 @@ namespace {
 constexpr int TMAX = 16;                 // rows of a sequence per pass (fvqa_attn_suffix's suffix_len limit)
 constexpr int GMAX = 4;                  // the longest n-gram the prompt lookup matches
 
-template <typename T>
+template <typename T, bool SAMPLE>
 __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logits, const T* __restrict__ emb,
                                                   const int32_t* __restrict__ draft_tokens, int G, int eos_id, int stop_at_eos,
                                                   int max_new, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
@@ -35,9 +42,13 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
                                                   int32_t* __restrict__ token_out, float* __restrict__ logprob_out,
                                                   int32_t* __restrict__ n_committed, int32_t* __restrict__ n_drafted,
                                                   int32_t* __restrict__ n_active, unsigned* __restrict__ counter,
-                                                  int64_t* __restrict__ pos64, int B, int Tn, int V, int D, int S, int vec16) {
+                                                  int64_t* __restrict__ pos64, int B, int Tn, int V, int D, int S, int vec16,
+                                                  SampleArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) float erow[];     // SAMPLE: the row's e_i (row_in_lds), then the bitmap
   __shared__ float redf[4];
   __shared__ int redi[4];
+  __shared__ float wtotf[4];             // (SAMPLE: the scans of the walk)
+  __shared__ int wtoti[4];
   __shared__ int cm[TMAX];               // the tokens committed by this step, in order
   __shared__ int wn[TMAX];               // the rows of the next pass: w'_0 .. w'_{m'-1}
   __shared__ int s_len;
@@ -50,13 +61,26 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
   const bool live = verify_live(done[b], p0, S, ngen, max_new);
   int now_done = live ? 0 : 1;
   int p = p0, nc = 0;
+  // ---- SAMPLE: the picks' scratch; under a penalty the bitmap of the ids generated before this step
+  SampleLds sl{};
+  bool pen = false;
+  if constexpr (SAMPLE) {
+    sl = SampleLds{erow, sample_bitmap_at(erow, V, sa.row_in_lds), redf, wtotf, redi, wtoti};
+    pen = sa.rep != 1.f;
+    if (live && pen) sample_bitmap_build(sl.bm, row_ids, sa.gen_start[b], p0, V);
+  }
 
   // ---- verify and commit: row i is scanned only while the drafts keep being accepted
   if (live) {
     for (int i = 0; i < m; ++i) {
       const float* lg = logits + ((size_t)b * Tn + i) * V;
       float lse;
-      const int g = row_verify(lg, V, redf, redi, lse);
+      int g, kept = 1;
+      if constexpr (SAMPLE)                                        // the sampled pick, with the draw of this token's index
+        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa.temperature, sa.top_p, sa.top_k, sa.rep, pen,
+                       sa.row_in_lds, sl, kept, lse);
+      else
+        g = row_verify(lg, V, redf, redi, lse);
       p += 1;
       ngen += 1;
       if (tid == 0) {
@@ -64,6 +88,10 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
         row_ids[p] = g;                                            // (p <= S - 1: checked before every commit)
         token_out[(size_t)b * Tn + nc] = g;
         logprob_out[(size_t)b * Tn + nc] = lg[g] - lse;
+        if constexpr (SAMPLE) sa.n_kept[(size_t)b * Tn + nc] = kept;
+      }
+      if constexpr (SAMPLE) {
+        if (pen) sample_bitmap_add(sl.bm, g);                      // row i + 1 sees what rows 0 .. i committed
       }
       nc += 1;
       if (stop_at_eos && g == eos_id) { now_done = 1; break; }
@@ -133,6 +161,9 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
     start_p[b] = at;
     if (pos64) pos64[b] = at;
     verify_pad(token_out, logprob_out, (size_t)b * Tn, nc, Tn);
+    if constexpr (SAMPLE) {
+      for (int j = nc; j < Tn; ++j) sa.n_kept[(size_t)b * Tn + j] = 0;
+    }
     n_committed[b] = nc;
     n_drafted[b] = live ? m - 1 : 0;
     ticket_arrive(counter, n_active, B, !now_done);
@@ -140,6 +171,61 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
   __syncthreads();
   // ---- the next pass's input rows: emb[w'_j] for j < m' (row 0 always: a row that feeds nothing stays a valid row), zeros behind
   next_pass_rows(x_next, emb, b, Tn, D, vec16, tid, s_len < 1 ? 1 : s_len, [&](int j) { return wn[j]; });
+}
+
+// the operand checks and the launch of both entries; sa: the operands fvqa_spec_step_sample adds (SAMPLE = true), else NULL
+int spec_step_launch(const float* logits, const void* emb, const int32_t* draft_tokens, int lookup_ngram, int eos_id,
+                     int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done, int32_t* n_generated,
+                     int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token, float* logprob, int32_t* n_committed,
+                     int32_t* n_drafted, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int lookahead, int vocab,
+                     int dim, int seq_len, int dtype, void* stream, const SampleArgs* sa) {
+  if (!logits || !emb || !ids || !pos || !done || !n_generated || !w || !len || !start || !x_next || !token || !logprob ||
+      !n_committed || !n_drafted || !n_active || !counter)
+    return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (!draft_tokens && (lookup_ngram < 1 || lookup_ngram > GMAX)) return FVQA_EINVAL;
+  if (sa) {
+    const int rc = fvqa_sample_args_ok(sa->u, sa->temperature, sa->top_p, sa->top_k, sa->rep, sa->gen_start, sa->n_kept);
+    if (rc != FVQA_OK) return rc;
+  }
+  if (n_seq <= 0 || lookahead <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0) return FVQA_ESHAPE;
+  if (lookahead > TMAX || n_seq > 65535 || (int64_t)n_seq * lookahead > 65535) return FVQA_ESHAPE;   // (the ticket counts
+                                                                   // arrivals in 16 bits; the pass's rows are a grid dimension)
+  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) ||
+      !fvqa_aligned(4, logits, draft_tokens, pos, done, n_generated, w, len, start, token, logprob, n_committed, n_drafted,
+                    n_active, counter) ||
+      !fvqa_aligned(8, ids, pos64))
+    return FVQA_EALIGN;
+  if (sa && !fvqa_aligned(4, sa->u, sa->gen_start, sa->n_kept)) return FVQA_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  SampleArgs s = sa ? *sa : SampleArgs{};
+  size_t lds = 0;
+  if (sa) {
+    int fits;
+    lds = fvqa_sample_lds(vocab, s.rep, &s.row_in_lds, &fits);
+    if (!fits) return FVQA_ESHAPE;                                 // (a vocabulary beyond 1.2 million ids under a penalty)
+  }
+  fvqa_by_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    const int vec16 = fvqa_vec16(dim * sizeof(T), emb, x_next);
+    if (sa) {
+      static std::atomic<unsigned long long> attr_done{0};         // one bit per device (fvqa_attr_needed)
+      if (fvqa_attr_needed(attr_done))
+        (void)hipFuncSetAttribute((const void*)spec_step_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(SAMPLE_ROW_LDS_MAX + SAMPLE_BITMAP_LDS_MAX));
+      hipLaunchKernelGGL((spec_step_k<T, true>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, draft_tokens,
+                         lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
+                         (T*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab,
+                         dim, seq_len, vec16, s);
+    } else {
+      hipLaunchKernelGGL((spec_step_k<T, false>), dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, draft_tokens,
+                         lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
+                         (T*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab,
+                         dim, seq_len, vec16, s);
+    }
+  });
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
 }
 
 }  // namespace
@@ -150,27 +236,20 @@ extern "C" int fvqa_spec_step(const float* logits, const void* emb, const int32_
                               float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active, uint32_t* counter,
                               int64_t* pos64, int n_seq, int lookahead, int vocab, int dim, int seq_len, int dtype,
                               void* stream) {
-  if (!logits || !emb || !ids || !pos || !done || !n_generated || !w || !len || !start || !x_next || !token || !logprob ||
-      !n_committed || !n_drafted || !n_active || !counter)
-    return FVQA_EINVAL;
-  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (!draft_tokens && (lookup_ngram < 1 || lookup_ngram > GMAX)) return FVQA_EINVAL;
-  if (n_seq <= 0 || lookahead <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0) return FVQA_ESHAPE;
-  if (lookahead > TMAX || n_seq > 65535 || (int64_t)n_seq * lookahead > 65535) return FVQA_ESHAPE;   // (the ticket counts
-                                                                   // arrivals in 16 bits; the pass's rows are a grid dimension)
-  if (!fvqa_aligned(fvqa_dtype_size(dtype), emb, x_next) ||
-      !fvqa_aligned(4, logits, draft_tokens, pos, done, n_generated, w, len, start, token, logprob, n_committed, n_drafted,
-                    n_active, counter) ||
-      !fvqa_aligned(8, ids, pos64))
-    return FVQA_EALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  fvqa_by_dtype(dtype, [&](auto* t) {
-    using T = std::remove_pointer_t<decltype(t)>;
-    hipLaunchKernelGGL(spec_step_k<T>, dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, draft_tokens, lookup_ngram, eos_id,
-                       stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start, (T*)x_next, token, logprob,
-                       n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab, dim, seq_len,
-                       fvqa_vec16(dim * sizeof(T), emb, x_next));
-  });
-  FVQA_CHECK_LAUNCH();
-  return FVQA_OK;
+  return spec_step_launch(logits, emb, draft_tokens, lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done,
+                          n_generated, w, len, start, x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64,
+                          n_seq, lookahead, vocab, dim, seq_len, dtype, stream, nullptr);
+}
+
+extern "C" int fvqa_spec_step_sample(const float* logits, const float* u, const void* emb, const int32_t* draft_tokens,
+                                     int lookup_ngram, float temperature, float top_p, int top_k, float repetition_penalty,
+                                     int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done,
+                                     int32_t* n_generated, const int32_t* gen_start, int32_t* w, int32_t* len, int32_t* start,
+                                     void* x_next, int32_t* token, int32_t* n_kept, float* logprob, int32_t* n_committed,
+                                     int32_t* n_drafted, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq,
+                                     int lookahead, int vocab, int dim, int seq_len, int dtype, void* stream) {
+  const SampleArgs sa{u, temperature, top_p, top_k, repetition_penalty, gen_start, n_kept, 0};
+  return spec_step_launch(logits, emb, draft_tokens, lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done,
+                          n_generated, w, len, start, x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64,
+                          n_seq, lookahead, vocab, dim, seq_len, dtype, stream, &sa);
 }

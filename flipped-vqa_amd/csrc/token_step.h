@@ -1,6 +1,6 @@
 // What the token-step kernels share (csrc/sample.hip, beam.hip, spec.hip, treespec.hip, jump.hip: one 256-thread workgroup per
 // sequence or sample, everything between the LM head and the next pass's first RMSNorm in one launch), each rule written once: the
-// integer block reductions and the lse of a raw row, the verify scan of the draft-and-verify steps, the view of a trie with its
+// integer block reductions, the block scans and the lse of a raw row, the verify scan of the draft-and-verify steps, the view of a trie with its
 // two clamps, the clamps that keep a finished row's reads inside its arrays, the ticket word that counts running rows across
 // workgroups, the embedding rows of the next pass, and the host side's operand rules (16-byte rows, storage-type dispatch, "no
 // trie or a whole one").
@@ -31,6 +31,39 @@ __device__ __forceinline__ int block_min_int(int v, int* red) {
   return min(min(red[0], red[1]), min(red[2], red[3]));
 }
 __device__ __forceinline__ int block_max_int(int v, int* red) { return -block_min_int(-v, red); }
+
+// exclusive prefix of v over the 256 threads in thread order (fixed tree); *total = the sum over all of them
+__device__ __forceinline__ float block_scan_f(float v, float* wtot, float* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  __syncthreads();
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  float base = 0.f;
+  for (int k = 0; k < w; ++k) base += wtot[k];
+  *total = ((wtot[0] + wtot[1]) + wtot[2]) + wtot[3];
+  return base + (x - v);
+}
+__device__ __forceinline__ int block_scan_i(int v, int* wtot) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  __syncthreads();
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < w; ++k) base += wtot[k];
+  return base + x - v;
+}
 
 // m + log(sum exp(l - m)) of one raw row: the maximum, then the sum of expf over a thread's strided elements in order, a shuffle
 // tree, the four waves in order. Every log-probability of the token steps is taken against this value (row_verify below fuses

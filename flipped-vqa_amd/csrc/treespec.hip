@@ -18,9 +18,13 @@
 // fvqa_kv_tree_commit — the cache append of the accepted path: ONE launch over all layers copies the k | v of the stashed raw rows
 //   path[n, i] to cache row start_old[n] + i, k in the cache's convention (csrc/cache_row.h: the store fvqa_attn_suffix_append
 //   does, so the bits are its bits).
+// fvqa_tree_spec_step_sample — the step kernel with SAMPLE = true (false in fvqa_tree_spec_step, whose instantiation holds none
+//   of the sampling code): every commit of the walk is csrc/row_sample.h's sampled pick with the draw of its token index, and the walk moves
+//   to the child under the sampled token (csrc/spec.hip says why that gives the plain sampled call's ids).
 // No float atomics, fixed summation orders: two launches give the same bits. Every index read from the plan, node, ids or path is
 // clamped or skipped before it is used.
 #include "cache_row.h"
+#include "row_sample.h"
 #include "token_step.h"
 
 namespace {
@@ -31,7 +35,7 @@ constexpr int TILE = 32;                 // rows per tile of the tree attention 
 constexpr int DREL = FVQA_TREE_DEPTH_MAX;
 constexpr int NONE = 0x7fffffff;
 
-template <typename T>
+template <typename T, bool SAMPLE>
 __global__ __launch_bounds__(NT) void tree_spec_step_k(
     const float* __restrict__ logits, const T* __restrict__ emb, const int32_t* __restrict__ plan_n,
     const int32_t* __restrict__ plan_token, const int32_t* __restrict__ plan_depth, const int32_t* __restrict__ plan_end,
@@ -42,9 +46,12 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
     int32_t* __restrict__ n_path, int32_t* __restrict__ start_old, int32_t* __restrict__ token_out,
     float* __restrict__ logprob_out, int32_t* __restrict__ n_committed, int32_t* __restrict__ n_drafted,
     int32_t* __restrict__ n_active, int32_t* __restrict__ n_on_trie, unsigned* __restrict__ counter,
-    int64_t* __restrict__ pos64, int B, int Rin, int Rout, int V, int D, int S, int vec16) {
+    int64_t* __restrict__ pos64, int B, int Rin, int Rout, int V, int D, int S, int vec16, SampleArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) float erow[];     // SAMPLE: the row's e_i (row_in_lds), then the bitmap
   __shared__ float redf[4];
   __shared__ int redi[4];
+  __shared__ float wtotf[4];             // (SAMPLE: the scans of the walk)
+  __shared__ int wtoti[4];
   __shared__ int cm[WALK];               // the tokens committed by this step, in order
   __shared__ int wn[RMAX];               // the input tokens of the next pass's rows
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -65,14 +72,28 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
   const bool live = verify_live(done[b], p0, S, ngen, max_new);
   int now_done = live ? 0 : 1;
   int p = p0, nc = 0, nd = a;
+  // ---- SAMPLE: the picks' scratch; under a penalty the bitmap of the ids generated before this step
+  SampleLds sl{};
+  bool pen = false;
+  if constexpr (SAMPLE) {
+    sl = SampleLds{erow, sample_bitmap_at(erow, V, sa.row_in_lds), redf, wtotf, redi, wtoti};
+    pen = sa.rep != 1.f;
+    if (live && pen) sample_bitmap_build(sl.bm, row_ids, sa.gen_start[b], p0, V);
+  }
 
-  // ---- walk: scan local row j, commit its arg-max, move to the child under that token while this pass fed it
+  // ---- walk: scan local row j, commit its arg-max (SAMPLE: its sampled pick), move to the child under that token while this
+  // pass fed it
   if (live) {
     int j = 0;
     for (;;) {
       const float* lg = logits + ((size_t)b * Rin + j) * V;
       float lse;
-      const int g = row_verify(lg, V, redf, redi, lse);
+      int g, kept = 1;
+      if constexpr (SAMPLE)                                        // the sampled pick, with the draw of this token's index
+        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa.temperature, sa.top_p, sa.top_k, sa.rep, pen,
+                       sa.row_in_lds, sl, kept, lse);
+      else
+        g = row_verify(lg, V, redf, redi, lse);
       p += 1;
       ngen += 1;
       if (tid == 0) {
@@ -81,6 +102,10 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
         token_out[(size_t)b * WALK + nc] = g;
         logprob_out[(size_t)b * WALK + nc] = lg[g] - lse;
         path_o[(size_t)b * WALK + nc] = j;
+        if constexpr (SAMPLE) sa.n_kept[(size_t)b * WALK + nc] = kept;
+      }
+      if constexpr (SAMPLE) {
+        if (pen) sample_bitmap_add(sl.bm, g);                      // the next row of the walk sees what this one committed
       }
       nc += 1;
       if ((stop_at_eos && g == eos_id) || ngen >= max_new) { now_done = 1; nd = -1; break; }
@@ -160,6 +185,9 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
     start_p[b] = at;
     if (pos64) pos64[b] = at;
     verify_pad(token_out, logprob_out, (size_t)b * WALK, nc, WALK);
+    if constexpr (SAMPLE) {
+      for (int j = nc; j < WALK; ++j) sa.n_kept[(size_t)b * WALK + j] = 0;
+    }
     for (int j = nc; j < WALK; ++j) path_o[(size_t)b * WALK + j] = 0;
     n_path[b] = nc;
     start_old[b] = valid_pos(p0, S);
@@ -207,21 +235,25 @@ __global__ __launch_bounds__(NT) void kv_tree_commit_k(T* __restrict__ cache, co
   }
 }
 
-}  // namespace
-
-extern "C" int fvqa_tree_spec_step(const float* logits, const void* emb, const int32_t* plan_n, const int32_t* plan_token,
-                                   const int32_t* plan_depth, const int32_t* plan_end, const int32_t* plan_parent, int plan_rows,
-                                   int plan_stride, int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos,
-                                   int32_t* done, int32_t* n_generated, int32_t* node, int32_t* len, int32_t* start, void* x_next,
-                                   int32_t* depth, int32_t* end, int32_t* tile_anc, int32_t* path, int32_t* n_path,
-                                   int32_t* start_old, int32_t* token, float* logprob, int32_t* n_committed, int32_t* n_drafted,
-                                   int32_t* n_active, int32_t* n_on_trie, uint32_t* counter, int64_t* pos64, int n_seq,
-                                   int rows_in, int rows_out, int vocab, int dim, int seq_len, int dtype, void* stream) {
+// the operand checks and the launch of both step entries; sa: the operands fvqa_tree_spec_step_sample adds (SAMPLE = true), else
+// NULL
+int tree_spec_step_launch(const float* logits, const void* emb, const int32_t* plan_n, const int32_t* plan_token,
+                          const int32_t* plan_depth, const int32_t* plan_end, const int32_t* plan_parent, int plan_rows,
+                          int plan_stride, int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos,
+                          int32_t* done, int32_t* n_generated, int32_t* node, int32_t* len, int32_t* start, void* x_next,
+                          int32_t* depth, int32_t* end, int32_t* tile_anc, int32_t* path, int32_t* n_path, int32_t* start_old,
+                          int32_t* token, float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active,
+                          int32_t* n_on_trie, uint32_t* counter, int64_t* pos64, int n_seq, int rows_in, int rows_out, int vocab,
+                          int dim, int seq_len, int dtype, void* stream, const SampleArgs* sa) {
   if (!logits || !emb || !plan_n || !plan_token || !plan_depth || !plan_end || !plan_parent || !ids || !pos || !done ||
       !n_generated || !node || !len || !start || !x_next || !depth || !end || !tile_anc || !path || !n_path || !start_old ||
       !token || !logprob || !n_committed || !n_drafted || !n_active || !n_on_trie || !counter)
     return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (sa) {
+    const int rc = fvqa_sample_args_ok(sa->u, sa->temperature, sa->top_p, sa->top_k, sa->rep, sa->gen_start, sa->n_kept);
+    if (rc != FVQA_OK) return rc;
+  }
   if (n_seq <= 0 || rows_in <= 0 || rows_out <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0 ||
       plan_rows <= 0)
     return FVQA_ESHAPE;
@@ -235,17 +267,72 @@ extern "C" int fvqa_tree_spec_step(const float* logits, const void* emb, const i
                     counter) ||
       !fvqa_aligned(8, ids, pos64))
     return FVQA_EALIGN;
+  if (sa && !fvqa_aligned(4, sa->u, sa->gen_start, sa->n_kept)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
+  SampleArgs s = sa ? *sa : SampleArgs{};
+  size_t lds = 0;
+  if (sa) {
+    int fits;
+    lds = fvqa_sample_lds(vocab, s.rep, &s.row_in_lds, &fits);
+    if (!fits) return FVQA_ESHAPE;                                 // (a vocabulary beyond 1.2 million ids under a penalty)
+  }
   fvqa_by_dtype(dtype, [&](auto* t) {
     using T = std::remove_pointer_t<decltype(t)>;
-    hipLaunchKernelGGL(tree_spec_step_k<T>, dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, plan_n, plan_token, plan_depth,
-                       plan_end, plan_parent, plan_rows, plan_stride, eos_id, stop_at_eos, max_new_tokens, ids, pos, done,
-                       n_generated, node, len, start, (T*)x_next, depth, end, tile_anc, path, n_path, start_old, token, logprob,
-                       n_committed, n_drafted, n_active, n_on_trie, counter, pos64, n_seq, rows_in, rows_out, vocab, dim, seq_len,
-                       fvqa_vec16(dim * sizeof(T), emb, x_next));
+    const int vec16 = fvqa_vec16(dim * sizeof(T), emb, x_next);
+    if (sa) {
+      static std::atomic<unsigned long long> attr_done{0};         // one bit per device (fvqa_attr_needed)
+      if (fvqa_attr_needed(attr_done))
+        (void)hipFuncSetAttribute((const void*)tree_spec_step_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(SAMPLE_ROW_LDS_MAX + SAMPLE_BITMAP_LDS_MAX));
+      hipLaunchKernelGGL((tree_spec_step_k<T, true>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, plan_n, plan_token,
+                         plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id, stop_at_eos, max_new_tokens, ids, pos,
+                         done, n_generated, node, len, start, (T*)x_next, depth, end, tile_anc, path, n_path, start_old, token,
+                         logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64, n_seq, rows_in, rows_out, vocab,
+                         dim, seq_len, vec16, s);
+    } else {
+      hipLaunchKernelGGL((tree_spec_step_k<T, false>), dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, plan_n, plan_token,
+                         plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id, stop_at_eos, max_new_tokens, ids, pos,
+                         done, n_generated, node, len, start, (T*)x_next, depth, end, tile_anc, path, n_path, start_old, token,
+                         logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64, n_seq, rows_in, rows_out, vocab,
+                         dim, seq_len, vec16, s);
+    }
   });
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
+}
+
+}  // namespace
+
+extern "C" int fvqa_tree_spec_step(const float* logits, const void* emb, const int32_t* plan_n, const int32_t* plan_token,
+                                   const int32_t* plan_depth, const int32_t* plan_end, const int32_t* plan_parent, int plan_rows,
+                                   int plan_stride, int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids, int32_t* pos,
+                                   int32_t* done, int32_t* n_generated, int32_t* node, int32_t* len, int32_t* start, void* x_next,
+                                   int32_t* depth, int32_t* end, int32_t* tile_anc, int32_t* path, int32_t* n_path,
+                                   int32_t* start_old, int32_t* token, float* logprob, int32_t* n_committed, int32_t* n_drafted,
+                                   int32_t* n_active, int32_t* n_on_trie, uint32_t* counter, int64_t* pos64, int n_seq,
+                                   int rows_in, int rows_out, int vocab, int dim, int seq_len, int dtype, void* stream) {
+  return tree_spec_step_launch(logits, emb, plan_n, plan_token, plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id,
+                               stop_at_eos, max_new_tokens, ids, pos, done, n_generated, node, len, start, x_next, depth, end,
+                               tile_anc, path, n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie,
+                               counter, pos64, n_seq, rows_in, rows_out, vocab, dim, seq_len, dtype, stream, nullptr);
+}
+
+extern "C" int fvqa_tree_spec_step_sample(const float* logits, const float* u, const void* emb, const int32_t* plan_n,
+                                          const int32_t* plan_token, const int32_t* plan_depth, const int32_t* plan_end,
+                                          const int32_t* plan_parent, int plan_rows, int plan_stride, float temperature,
+                                          float top_p, int top_k, float repetition_penalty, int eos_id, int stop_at_eos,
+                                          int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done, int32_t* n_generated,
+                                          const int32_t* gen_start, int32_t* node, int32_t* len, int32_t* start, void* x_next,
+                                          int32_t* depth, int32_t* end, int32_t* tile_anc, int32_t* path, int32_t* n_path,
+                                          int32_t* start_old, int32_t* token, int32_t* n_kept, float* logprob,
+                                          int32_t* n_committed, int32_t* n_drafted, int32_t* n_active, int32_t* n_on_trie,
+                                          uint32_t* counter, int64_t* pos64, int n_seq, int rows_in, int rows_out, int vocab,
+                                          int dim, int seq_len, int dtype, void* stream) {
+  const SampleArgs sa{u, temperature, top_p, top_k, repetition_penalty, gen_start, n_kept, 0};
+  return tree_spec_step_launch(logits, emb, plan_n, plan_token, plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id,
+                               stop_at_eos, max_new_tokens, ids, pos, done, n_generated, node, len, start, x_next, depth, end,
+                               tile_anc, path, n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie,
+                               counter, pos64, n_seq, rows_in, rows_out, vocab, dim, seq_len, dtype, stream, &sa);
 }
 
 extern "C" int fvqa_kv_tree_commit(void* qkv_cache, const void* qkv_rows, const int32_t* path, const int32_t* n_path,

@@ -64,8 +64,10 @@ SIGNATURES = {
                                 + [_i] * 5 + [_p]),
     "fvqa_slot_seat": (_i, [_p] * 3 + [_i] + [_p] * 5 + [_i] + [_p] * 10 + [_i] * 3 + [_p]),
     "fvqa_spec_step": (_i, [_p, _p, _p, _i, _i, _i, _i] + [_p] * 15 + [_i] * 6 + [_p]),
+    "fvqa_spec_step_sample": (_i, [_p] * 4 + [_i, _f, _f, _i, _f, _i, _i, _i] + [_p] * 17 + [_i] * 6 + [_p]),
     "fvqa_trie_jump_step": (_i, [_p] * 5 + [_i] * 6 + [_p] * 16 + [_i] * 6 + [_p]),
     "fvqa_tree_spec_step": (_i, [_p] * 7 + [_i] * 5 + [_p] * 22 + [_i] * 7 + [_p]),
+    "fvqa_tree_spec_step_sample": (_i, [_p] * 8 + [_i, _i, _f, _f, _i, _f, _i, _i, _i] + [_p] * 24 + [_i] * 7 + [_p]),
     "fvqa_kv_tree_commit": (_i, [_p] * 7 + [_i] * 9 + [_p]),
     "fvqa_beam_step": (_i,[_p, _p, _i, _i, _i] + [_p] * 12 + [_i] * 6 + [_p]),
     "fvqa_beam_step_trie": (_i, [_p, _p, _i, _i, _i] + [_p] * 16 + [_i] * 8 + [_p]),

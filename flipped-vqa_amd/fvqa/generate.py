@@ -260,34 +260,40 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       "n_plausible" (B[, n], steps) int32: |P| at each step, 0 where "tokens" is -1.
       ValueError: a key the batch lacks, a tensor of another shape, contrast_alpha < 0, contrast_beta outside [0, 1],
       num_beams > 1, 2 * B * num_return_sequences > 65535. Not built: a contrastive beam step; negatives whose TEXT differs.
-    lookahead T (0 or 1: every code path above runs untouched): draft-and-verify greedy decoding, `_generate_lookahead` below —
-      several tokens per pass through the layers (prompt-lookup / assisted generation, restricted to greedy). A pass carries up
+    lookahead T (0 or 1: every code path above runs untouched): draft-and-verify decoding, `_generate_lookahead` below —
+      several tokens per pass through the layers (prompt-lookup / assisted generation). A pass carries up
       to T rows per sample: the last committed token and a draft of up to T - 1 tokens behind it; every draft token that equals
-      the greedy choice is committed, so "ids", "n_generated" and "tokens" are those of the plain greedy call, token for token
-      ("tokens" is (B, longest row), padded with -1). The draft: with draft_tokens (B, max_new_tokens) int32 the answer someone
+      the model's own choice is committed, so "ids", "n_generated" and "tokens" are those of the plain call with the same
+      arguments, token for token ("tokens" is (B, longest row), padded with -1). temperature == 0: the choice is greedy's.
+      temperature > 0 (with top_p, top_k, repetition_penalty as in the plain call, and a seed, which is required): the choice at token index t is the
+      plain sampler's with the plain loop's draw u[t] — the draws are the same one torch.rand(max_new_tokens, B) of the seeded
+      generator, read by token index and not by step —, and a draft is kept iff it equals the sampled token: for a deterministic
+      draft that IS the rejection rule of speculative sampling, nothing is approximate. The draft: with draft_tokens (B, max_new_tokens) int32 the answer someone
       else proposes, read at each row's n_generated (an entry outside [0, vocab) ends a draft); without, prompt lookup — the
       longest suffix of up to lookup_ngram (1 .. 4) committed tokens that occurs earlier in the row, most recent occurrence, and
       what followed it (a multiple-choice prompt lists its answers). include/fvqa.h fvqa_spec_step states the rule. "steps" counts
       the token steps launched; the results gain "n_committed" and "n_drafted" (B, steps) int32: the tokens each step committed
       and the draft tokens it was offered. return_logprobs is served as above ("logprobs" (B, longest row), "sum_logprob").
-      ValueError: temperature > 0, num_beams > 1, top_k, repetition_penalty != 1, num_return_sequences > 1, constraints,
-      contrast, lookahead > 16 (ops.SUFFIX_MAX) or < 0, draft_tokens of another shape or without lookahead >= 2, lookup_ngram
-      outside [1, 4], B * T > 65535. Not built: drafts under sampling (they need the rejection rule), under beam search, a trie
-      or a contrastive pick; a draft model.
+      ValueError: temperature > 0 without a seed, num_beams > 1, num_return_sequences > 1 (the pass state sits on the prefill arena, not the fan-out cache),
+      top_k or repetition_penalty != 1 at temperature == 0, constraints, contrast, lookahead > 16 (ops.SUFFIX_MAX) or < 0,
+      draft_tokens of another shape or without lookahead >= 2, lookup_ngram outside [1, 4], B * T > 65535; under sampling also
+      top_p outside (0, 1], top_k < 0, repetition_penalty < 1. Not built: several samples per prompt on a draft pass, drafts
+      under beam search, a trie or a contrastive pick; a draft model (a draft with a distribution of its own).
     draft_answers C (None: every code path above runs untouched; needs lookahead = R, 2 <= R <= 64): the drafts are a TRIE of
       likely answers — what `constraints` accepts: one list of token sequences, or one list per sample —, verified in one tree pass,
-      `_generate_tree_draft` below. The trie is a draft, not a rule: "ids", "n_generated" and "tokens" are the plain greedy call's,
-      token for token, whatever the model says. A pass feeds up to R rows per sample: a pre-order prefix of the subtree under the
+      `_generate_tree_draft` below. The trie is a draft, not a rule: "ids", "n_generated" and "tokens" are the plain call's,
+      token for token, whatever the model says — greedy's at temperature == 0, the plain sampled call's at temperature > 0 (as
+      under lookahead: the pick at token index t is the plain sampler's with the draw u[t], and the walk follows it). A pass feeds up to R rows per sample: a pre-order prefix of the subtree under the
       row's trie node (ops.attn_suffix_tree: a row sees the cache and its ancestors); the token step walks the tree along the
       model's own picks (include/fvqa.h fvqa_tree_spec_step states the rule) and ops.kv_tree_commit appends the accepted path to
       the cache. A row that leaves the trie goes on one token per pass and does not re-enter; once every running row has left
       (known one step late, as the stop is) the passes carry one row per sample and launch what lookahead's loop launches at T = 1.
       The results gain "n_committed", "n_drafted" (B, steps) int32 — rows fed minus one — and "rows_per_pass" (steps,) int32: the
       rows per sample of the pass each step verified (step 0: the prefill's row, 1). return_logprobs is served as under lookahead.
-      ValueError: no lookahead >= 2, R > 64, B * R > 65535, draft_tokens, temperature > 0, top_k, repetition_penalty != 1,
-      num_return_sequences > 1, num_beams > 1, constraints, contrast, jump_forward, frame_attention. Not built: drafts under
-      sampling, beams, constraints or contrast; tree drafts in the stream; a draft root other than the start of the answer;
-      compacting a pass to the live rows of each sample.
+      ValueError: no lookahead >= 2, R > 64, B * R > 65535, draft_tokens, temperature > 0 without a seed, top_k or repetition_penalty != 1 at temperature == 0,
+      num_return_sequences > 1, num_beams > 1, constraints, contrast, jump_forward, frame_attention. Not built: several samples
+      per prompt, beams, constraints or contrast on a tree pass; tree drafts in the stream; a draft root other than the start
+      of the answer; compacting a pass to the live rows of each sample.
     jump_forward T (0 or 1: every code path above runs untouched; needs `constraints`): jump-forward constrained greedy decoding,
       `_generate_jump` below. Once a row's trie node has a single child the next token is fixed whatever the logits say, so a
       token step picks the one token that is a decision and commits the tokens the trie fixes behind it, up to T per step; the
@@ -330,14 +336,16 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
             raise ValueError("generate: draft_answers and draft_tokens are two drafts: one of them")
         if jump_forward >= 2:
             raise ValueError("generate: draft_answers are not built for jump_forward")
-        if temperature > 0 or num_beams != 1:
-            raise ValueError("generate: draft_answers are verified against the GREEDY choice: temperature == 0, num_beams == 1")
-        if top_k != 0 or repetition_penalty != 1 or num_return_sequences != 1:
-            raise ValueError("generate: draft_answers are not built for top_k, repetition_penalty or num_return_sequences")
+        if num_beams != 1:
+            raise ValueError("generate: draft_answers are verified against the model's own pick, not a beam: num_beams == 1")
+        if num_return_sequences != 1:
+            raise ValueError("generate: draft_answers are not built for num_return_sequences (the pass state sits on the "
+                             "prefill's cache)")
         if constraints is not None or contrast is not None:
             raise ValueError("generate: draft_answers are not built for constraints or contrast (a draft is not a rule)")
+        sampling = _draft_sampling("draft_answers", temperature, top_p, top_k, repetition_penalty, seed)
         return _generate_tree_draft(eng, data, R=int(lookahead), draft_answers=draft_answers, max_new_tokens=max_new_tokens,
-                                    stop_at_eos=stop_at_eos, return_logprobs=return_logprobs)
+                                    stop_at_eos=stop_at_eos, return_logprobs=return_logprobs, sampling=sampling, seed=seed)
     if int(lookahead) != lookahead or not 0 <= lookahead <= ops.SUFFIX_MAX:
         raise ValueError(f"generate: 0 <= lookahead <= {ops.SUFFIX_MAX} (0, 1: one token per pass)")
     if int(jump_forward) != jump_forward or not 0 <= jump_forward <= ops.SUFFIX_MAX:
@@ -358,16 +366,19 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if lookahead < 2 and draft_tokens is not None:
         raise ValueError("generate: draft_tokens are verified by lookahead >= 2")
     if lookahead >= 2:
-        if temperature > 0 or num_beams != 1:
-            raise ValueError("generate: lookahead verifies drafts against the GREEDY choice: temperature == 0, num_beams == 1")
-        if top_k != 0 or repetition_penalty != 1 or num_return_sequences != 1:
-            raise ValueError("generate: lookahead is not built for top_k, repetition_penalty or num_return_sequences")
+        if num_beams != 1:
+            raise ValueError("generate: lookahead verifies drafts against the model's own pick, not a beam: num_beams == 1")
+        if num_return_sequences != 1:
+            raise ValueError("generate: lookahead is not built for num_return_sequences (the pass state sits on the prefill's "
+                             "cache)")
         if constraints is not None or contrast is not None:
             raise ValueError("generate: lookahead is not built for constraints or contrast")
         if draft_tokens is None and (int(lookup_ngram) != lookup_ngram or not 1 <= lookup_ngram <= ops.LOOKUP_NGRAM_MAX):
             raise ValueError(f"generate: 1 <= lookup_ngram <= {ops.LOOKUP_NGRAM_MAX}")
+        sampling = _draft_sampling("lookahead", temperature, top_p, top_k, repetition_penalty, seed)
         return _generate_lookahead(eng, data, T=int(lookahead), G=int(lookup_ngram), draft_tokens=draft_tokens,
-                                   max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, return_logprobs=return_logprobs)
+                                   max_new_tokens=max_new_tokens, stop_at_eos=stop_at_eos, return_logprobs=return_logprobs,
+                                   sampling=sampling, seed=seed)
     if int(num_beams) != num_beams or not 1 <= num_beams <= ops.BEAMS_MAX:
         raise ValueError(f"generate: 1 <= num_beams <= {ops.BEAMS_MAX}")
     if num_beams > 1 and temperature > 0:
@@ -434,13 +445,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if trie is not None:                                    # every row starts at its sample's root (n rows per sample: repeated)
         dtrie = trie.to(dev)
         node = torch.as_tensor(trie.roots(NP // n), dtype=torch.int32).repeat_interleave(n).to(dev).contiguous()
-    u = None
-    if temperature > 0:
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(int(seed))
-        u = torch.rand(max_new_tokens, NP, dtype=torch.float32, device=dev, generator=gen)
+    u = _draws(dev, seed, max_new_tokens, NP) if temperature > 0 else None
     kw = dict(pos64=pos64, temperature=temperature, top_p=top_p, eos_id=eng.model.tokenizer.eos_id, stop_at_eos=stop_at_eos)
     kw_ex = dict(kw, top_k=int(top_k), repetition_penalty=float(repetition_penalty))
     # a finished row stays in the batch (it is rectangular): it goes through every layer on the embedding of its last token
@@ -492,7 +497,38 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     return out
 
 
+def _draws(dev, seed, max_new_tokens: int, rows: int) -> torch.Tensor:
+    """The uniforms of a sampled call, (max_new_tokens, rows) fp32: ONE torch.rand from a device generator seeded with `seed`
+    (None: the default generator). Row t belongs to token index t of every row, whichever step commits it."""
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+    return torch.rand(max_new_tokens, rows, dtype=torch.float32, device=dev, generator=gen)
+
+
 # ------------------------------------------------------------------------------- several rows per sample and pass
+def _draft_sampling(keyword: str, temperature, top_p, top_k, repetition_penalty, seed):
+    """The sampling keywords of a draft-and-verify call -> None at temperature == 0 (the greedy entries, launched as ever), else
+    the keywords of the sampled token steps (ops.spec_step_sample, ops.tree_spec_step_sample). Needs no device. The unseeded
+    form (seed None: the default generator) stays refused, as every sampled draft call was: tests/test_lookahead_cpu.py and
+    tests/test_treedraft_cpu.py hold it so. With a seed the call has a plain call to be set against, token for token."""
+    if int(top_k) != top_k or top_k < 0 or not repetition_penalty >= 1:
+        raise ValueError("generate: top_k >= 0 (0: off), repetition_penalty >= 1")
+    if not temperature > 0:
+        if top_k != 0 or repetition_penalty != 1:
+            raise ValueError(f"generate: at temperature == 0 {keyword} verifies against the plain greedy choice: top_k and "
+                             "repetition_penalty need temperature > 0 here")
+        return None
+    if seed is None:
+        raise ValueError(f"generate: {keyword} with temperature > 0 commits the tokens of the plain sampled call with the same "
+                         "seed: pass seed=")
+    if not 0 < top_p <= 1:
+        raise ValueError("generate: 0 < top_p <= 1")
+    return dict(temperature=float(temperature), top_p=float(top_p), top_k=int(top_k),
+                repetition_penalty=float(repetition_penalty))
+
+
 def _pass_checks(data: dict, T: int, max_new_tokens: int, keyword: str) -> int:
     """What a loop of T rows per sample and pass refuses before it reads the batch -> B."""
     _need_prefix(data)
@@ -576,10 +612,11 @@ def _draft_results(out: dict, tokens, logprobs, n_committed, n_drafted, inside, 
 
 @torch.no_grad()
 def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_new_tokens: int, stop_at_eos: bool,
-                        return_logprobs: bool) -> dict:
+                        return_logprobs: bool, sampling=None, seed=None) -> dict:
     """generate(lookahead=T >= 2): `_pass_loop` with fvqa_spec_step as its token step (verify the pass's drafts, commit, draft the
     next pass: one launch). Rejected drafts leave k / v behind a row's position; the next pass overwrites them from its `start`
-    on and reads nothing behind it."""
+    on and reads nothing behind it. sampling (`_draft_sampling`; None: greedy, the launches of every call before the keyword
+    existed): the token step is fvqa_spec_step_sample with the plain loop's draws (`_draws`), read by token index."""
     B = _pass_checks(data, T, max_new_tokens, "lookahead")
     dev = eng.device
     if draft_tokens is not None:
@@ -590,12 +627,22 @@ def _generate_lookahead(eng, data: dict, *, T: int, G: int, draft_tokens, max_ne
     st = _pass_state(eng, data, T, max_new_tokens)
     logprobs = torch.zeros(max_new_tokens, B, T, dtype=torch.float32, device=dev)
     n_committed, n_drafted = (torch.zeros(max_new_tokens, B, dtype=torch.int32, device=dev) for _ in range(2))
+    kw = dict(max_new_tokens=int(max_new_tokens), draft_tokens=draft_tokens, lookup_ngram=G, pos64=st.pos64,
+              eos_id=eng.model.tokenizer.eos_id, stop_at_eos=stop_at_eos)
+
+    if sampling is not None:
+        u = _draws(dev, seed, int(max_new_tokens), B)
+        gen_start = st.p.prefix.to(torch.int32)
+        n_kept = torch.zeros(B, T, dtype=torch.int32, device=dev)
 
     def token_step(t, n_active):
-        ops.spec_step(st.b.lg, eng.pack.emb, st.ids, st.pos, st.done, st.n_gen, st.w, st.length, st.at, st.b.xin, st.tokens[t],
-                      logprobs[t], n_committed[t], n_drafted[t], n_active, st.counter, max_new_tokens=int(max_new_tokens),
-                      draft_tokens=draft_tokens, lookup_ngram=G, pos64=st.pos64, eos_id=eng.model.tokenizer.eos_id,
-                      stop_at_eos=stop_at_eos)
+        if sampling is None:
+            ops.spec_step(st.b.lg, eng.pack.emb, st.ids, st.pos, st.done, st.n_gen, st.w, st.length, st.at, st.b.xin, st.tokens[t],
+                          logprobs[t], n_committed[t], n_drafted[t], n_active, st.counter, **kw)
+        else:                                               # the same step, every pick the plain sampler's
+            ops.spec_step_sample(st.b.lg, eng.pack.emb, st.ids, st.pos, st.done, st.n_gen, gen_start, st.w, st.length, st.at,
+                                 st.b.xin, st.tokens[t], n_kept, logprobs[t], n_committed[t], n_drafted[t], n_active, st.counter,
+                                 u=u, **sampling, **kw)
     out = _pass_loop(eng, st, max_new_tokens, token_step)
     return _draft_results(out, st.tokens, logprobs, n_committed, n_drafted, st.inside, return_logprobs)
 
@@ -618,14 +665,15 @@ class _LagOneNarrow(_LagOneStop):
 
 @torch.no_grad()
 def _generate_tree_draft(eng, data: dict, *, R: int, draft_answers, max_new_tokens: int, stop_at_eos: bool,
-                         return_logprobs: bool) -> dict:
+                         return_logprobs: bool, sampling=None, seed=None) -> dict:
     """generate(lookahead=R, draft_answers=C): the loop of `_pass_loop` with fvqa_tree_spec_step as its token step and two kinds
     of pass. WIDE (R rows per sample): the layers with ops.attn_suffix_tree, which writes no cache row — siblings share a position
     —; every layer's raw q | k | v rows stay in a per-layer buffer (L, B * R, 3 D) — 403 MB at B = 8, R = 64, 7B in 16 bits:
     rowpass.layers is handed layer i + 1's slice by layer i's attention callback, nothing is copied —, and after the NEXT step
     ops.kv_tree_commit appends the accepted path to the cache in one launch: step, commit, layers. NARROW (one row per sample,
     from the step after a snapshot shows no running row on its trie): ops.attn_suffix_append at T = 1 and no commit, what
-    lookahead's loop launches at T = 1."""
+    lookahead's loop launches at T = 1. sampling (`_draft_sampling`; None: greedy, the launches of every call before the keyword
+    existed): the token step is fvqa_tree_spec_step_sample with the plain loop's draws (`_draws`), read by token index."""
     from . import vocab
     B = _pass_checks(data, R, max_new_tokens, "lookahead")
     eos = eng.model.tokenizer.eos_id
@@ -654,6 +702,10 @@ def _generate_tree_draft(eng, data: dict, *, R: int, draft_answers, max_new_toke
     n_active, n_on_trie = torch.zeros(max_new_tokens, **i32), torch.zeros(max_new_tokens, **i32)
     counter = torch.zeros(2, **i32)
     rope, gates = (eng.cos, eng.sin), eng.model.gate_views
+    if sampling is not None:
+        u = _draws(dev, seed, int(max_new_tokens), B)
+        gen_start = p.prefix.to(torch.int32)
+        n_kept = torch.zeros(B, W, **i32)
 
     def attn_tree(i, qkv, o):
         ops.attn_suffix_tree(qkv, p.ar.qkv[i], o, *gates(i), p.vstart, at, length, *tree[R], rope, B, R, S, eng.H, eng.Dh, eng.A,
@@ -671,9 +723,17 @@ def _generate_tree_draft(eng, data: dict, *, R: int, draft_answers, max_new_toke
         if r_out > 1 and stop.off_trie(t):
             r_out = 1
         nxt = wide if r_out > 1 else narrow
-        ops.tree_spec_step(cur.lg, eng.pack.emb, plan, ids, pos, done, n_gen, node, length, at, nxt.xin, *tree[r_out], path, n_path,
-                           start_old, tokens[t], logprobs[t], n_committed[t], n_drafted[t], n_active[t:t + 1], n_on_trie[t:t + 1],
-                           counter, max_new_tokens=int(max_new_tokens), pos64=pos64, eos_id=eos, stop_at_eos=stop_at_eos)
+        if sampling is None:
+            ops.tree_spec_step(cur.lg, eng.pack.emb, plan, ids, pos, done, n_gen, node, length, at, nxt.xin, *tree[r_out], path,
+                               n_path, start_old, tokens[t], logprobs[t], n_committed[t], n_drafted[t], n_active[t:t + 1],
+                               n_on_trie[t:t + 1], counter, max_new_tokens=int(max_new_tokens), pos64=pos64, eos_id=eos,
+                               stop_at_eos=stop_at_eos)
+        else:
+            ops.tree_spec_step_sample(cur.lg, eng.pack.emb, plan, ids, pos, done, n_gen, gen_start, node, length, at, nxt.xin,
+                                      *tree[r_out], path, n_path, start_old, tokens[t], n_kept, logprobs[t], n_committed[t],
+                                      n_drafted[t], n_active[t:t + 1], n_on_trie[t:t + 1], counter, u=u,
+                                      max_new_tokens=int(max_new_tokens), pos64=pos64, eos_id=eos, stop_at_eos=stop_at_eos,
+                                      **sampling)
         stop.queued(t, n_active[t:t + 1], n_on_trie[t:t + 1])
         widths.append(fed)
         steps = t + 1

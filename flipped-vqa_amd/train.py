@@ -192,13 +192,22 @@ class ArgumentParser(argparse.ArgumentParser):
                     or int(getattr(a, "slots", 0) or 0) >= 1 or getattr(a, "val_vocab", False)
                     or getattr(a, "gen_frame_attention", False) or getattr(a, "frame_attention", False)
                     or int(getattr(a, "rank", 0) or 0) or int(getattr(a, "num_samples", 1) or 1) > 1
-                    or float(getattr(a, "temperature", 0.0) or 0.0) > 0):
-                self.error(f"--{flag} verifies a draft trie against the greedy choice: not with --num_beams > 1, constrained or "
-                           "contrastive decoding, jump-forward, a stream, --val_vocab / --rank, frame attention or sampling")
+                    or (float(getattr(a, "temperature", 0.0) or 0.0) > 0 and getattr(a, "seed", None) is None)):
+                self.error(f"--{flag} verifies a draft trie against the model's own pick: not with --num_beams > 1, constrained "
+                           "or contrastive decoding, jump-forward, a stream, --val_vocab / --rank, frame attention, several "
+                           "samples per prompt or sampling without a --seed")
         if la > 1:
             if int(getattr(a, "num_beams", 1) or 1) > 1 or getattr(a, "gen_constrain", None) or getattr(a, "contrast", None):
-                self.error("--lookahead verifies drafts against the greedy choice: not with --num_beams > 1, --gen_constrain "
+                self.error("--lookahead verifies drafts against the model's own pick: not with --num_beams > 1, --gen_constrain "
                            "or --contrast")
+            if int(getattr(a, "num_samples", 1) or 1) > 1:
+                self.error("--lookahead keeps its pass state on the prefill's cache: not with --num_samples > 1")
+            if float(getattr(a, "temperature", 0.0) or 0.0) > 0 and getattr(a, "seed", None) is None:
+                self.error("--lookahead with --temperature > 0 gives the plain sampled answer of the same --seed: it needs --seed")
+            if not float(getattr(a, "temperature", 0.0) or 0.0) > 0 and (
+                    int(getattr(a, "top_k", 0) or 0) != 0 or float(getattr(a, "repetition_penalty", 1.0) or 1.0) != 1.0):
+                self.error("--lookahead without --temperature > 0 verifies drafts against the plain greedy choice: --top_k and "
+                           "--repetition_penalty need --temperature > 0 here")
             if not 1 <= int(getattr(a, "lookup_ngram", 2)) <= 4:
                 self.error("1 <= --lookup_ngram <= 4")
         for flag, constrained in (("gen_jump_forward", getattr(a, "gen_constrain", None)),

@@ -602,6 +602,36 @@ int fvqa_spec_step(const float* logits, const void* emb, const int32_t* draft_to
                    int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token, float* logprob, int32_t* n_committed,
                    int32_t* n_drafted, int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int lookahead, int vocab,
                    int dim, int seq_len, int dtype, void* stream);
+/* fvqa_spec_step under sampling (the same kernel template in csrc/spec.hip with SAMPLE = true, the pick in csrc/row_sample.h;
+ * generate(lookahead=T, temperature > 0)). Every draft of this project is deterministic, a point mass d; speculative sampling
+ * then accepts d with probability p(d) and else draws from p with d removed and renormalised — the distribution of drawing
+ * t ~ p ONCE with the plain sampler and accepting the draft iff t == d. So the step draws each token with fvqa_decode_next_ex's
+ * rule and the draw the plain loop would have used for it, and the ids are those of the plain sampled call, token for token.
+ * The operands, the liveness rule, the commit, the next pass's draft, the outputs and the errors of fvqa_spec_step hold; in
+ * addition: u (max_new_tokens, n_seq) fp32 in [0, 1) — the plain loop's one array of draws, row t for token index t —,
+ * temperature > 0, top_p, top_k, repetition_penalty and gen_start (n_seq) int32 as in fvqa_decode_next_ex, n_kept (n_seq, T) int32
+ * out. Per live row, with g0 = n_generated before the step:
+ *   1. the pick at row L_i, i = 0, 1, ..: rules 1 to 5 of fvqa_decode_next_ex on the raw row with the draw
+ *      u[min(g0 + i, max_new_tokens - 1) * n_seq + n] — the draw belongs to the TOKEN INDEX, not to the step — and with R = the
+ *      distinct ids at positions max(gen_start, 0) .. pos of the row INCLUDING the tokens rows 0 .. i - 1 of this step committed
+ *      (the bitmap is built once per step and gains one bit per commit). The same summation orders and bisections as
+ *      fvqa_decode_next_ex: e_i staged in LDS when 4 * vocab bytes fit, recomputed from the logits when not.
+ *   2. verify: the draft w_{i+1} is accepted iff it equals the token sampled at row L_i (a draft outside the kept set has
+ *      probability 0 and is never accepted); row L_{i+1} is picked from only then. The token committed at row i is the sampled
+ *      one whether it was drafted or not. n_kept[n, i] = the size of the kept set of the i-th commit, 0 behind the commits;
+ *      logprob is rule 5's, on the raw row.
+ * With T == 1 (and max_new_tokens never reached) token, n_kept, logprob, ids, pos, pos64, done, x_next and n_active are those of
+ * fvqa_decode_next_ex with u's row n_generated, bit for bit. No float atomics, fixed summation orders: bitwise repeatable.
+ * FVQA_EINVAL also for a null u / gen_start / n_kept, temperature <= 0 or NaN, top_p outside (0, 1], top_k < 0,
+ * repetition_penalty < 1 or NaN; FVQA_ESHAPE also for a vocab beyond 1216512 when repetition_penalty != 1 (the bitmap of R
+ * lives in LDS); FVQA_EALIGN also for one of the three off its 4-byte boundary. */
+int fvqa_spec_step_sample(const float* logits, const float* u, const void* emb, const int32_t* draft_tokens, int lookup_ngram,
+                          float temperature, float top_p, int top_k, float repetition_penalty, int eos_id, int stop_at_eos,
+                          int max_new_tokens, int64_t* ids, int32_t* pos, int32_t* done, int32_t* n_generated,
+                          const int32_t* gen_start, int32_t* w, int32_t* len, int32_t* start, void* x_next, int32_t* token,
+                          int32_t* n_kept, float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active,
+                          uint32_t* counter, int64_t* pos64, int n_seq, int lookahead, int vocab, int dim, int seq_len, int dtype,
+                          void* stream);
 /* The token step of jump-forward constrained greedy decoding (csrc/jump.hip; generate(constraints=C, jump_forward=T)): one launch
  * where fvqa_spec_step sits, one 256-thread workgroup per sequence. Under the trie of fvqa_decode_next_trie a row whose node has a
  * single edge has nothing to decide, so a step picks ONE token from the logits and then commits the tokens the trie fixes behind
@@ -703,6 +733,27 @@ int fvqa_tree_spec_step(const float* logits, const void* emb, const int32_t* pla
                         int32_t* token, float* logprob, int32_t* n_committed, int32_t* n_drafted, int32_t* n_active,
                         int32_t* n_on_trie, uint32_t* counter, int64_t* pos64, int n_seq, int rows_in, int rows_out, int vocab,
                         int dim, int seq_len, int dtype, void* stream);
+/* fvqa_tree_spec_step under sampling (the same kernel template in csrc/treespec.hip with SAMPLE = true;
+ * generate(lookahead=R, draft_answers=C, temperature > 0)): what fvqa_spec_step_sample is to fvqa_spec_step. The operands, the
+ * walk, the cut, the outputs and the errors of fvqa_tree_spec_step hold with "g = argmax L_j" read as "g = the token sampled at
+ * L_j": the i-th commit of a step (i = 0, 1, .., at most 32) is rules 1 to 5 of fvqa_decode_next_ex on the raw row the walk
+ * stands at, with the draw u[min(g0 + i, max_new_tokens - 1) * n_seq + n], g0 = n_generated before the step, and with R including
+ * the step's earlier commits; the walk moves to the child under the SAMPLED token, so the ids are those of the plain sampled call
+ * whatever the plan holds. In addition to fvqa_tree_spec_step's operands: u (max_new_tokens, n_seq) fp32, temperature > 0, top_p,
+ * top_k, repetition_penalty, gen_start (n_seq) int32, n_kept (n_seq, 32) int32 out (0 behind the commits).
+ * With rows_in == rows_out == 1, or every node -1, (and max_new_tokens never reached) token, n_kept, logprob, ids, pos, pos64,
+ * done, x_next and n_active are those of fvqa_decode_next_ex, bit for bit. Bitwise repeatable.
+ * The additional errors are fvqa_spec_step_sample's. */
+int fvqa_tree_spec_step_sample(const float* logits, const float* u, const void* emb, const int32_t* plan_n,
+                               const int32_t* plan_token, const int32_t* plan_depth, const int32_t* plan_end,
+                               const int32_t* plan_parent, int plan_rows, int plan_stride, float temperature, float top_p,
+                               int top_k, float repetition_penalty, int eos_id, int stop_at_eos, int max_new_tokens, int64_t* ids,
+                               int32_t* pos, int32_t* done, int32_t* n_generated, const int32_t* gen_start, int32_t* node,
+                               int32_t* len, int32_t* start, void* x_next, int32_t* depth, int32_t* end, int32_t* tile_anc,
+                               int32_t* path, int32_t* n_path, int32_t* start_old, int32_t* token, int32_t* n_kept, float* logprob,
+                               int32_t* n_committed, int32_t* n_drafted, int32_t* n_active, int32_t* n_on_trie, uint32_t* counter,
+                               int64_t* pos64, int n_seq, int rows_in, int rows_out, int vocab, int dim, int seq_len, int dtype,
+                               void* stream);
 /* The cache append of the accepted path (csrc/treespec.hip). fvqa_attn_suffix_tree writes nothing but o — siblings share a
  * position, so a tree pass must not write its rows into the cache —; the pass keeps every layer's RAW q | k | v rows instead:
  * qkv_rows (n_layers, n_seq*rows, 3*dim). After the token step ONE launch over all layers copies, for sequence n and i <

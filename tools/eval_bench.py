@@ -21,6 +21,8 @@ plain sampling `generate` of the same batch — for N > 1 also N calls of it, wh
 batch of 2 * B rows (the same layer pass as the pairs).
 --tree_draft R [R ...] times tree-shaped draft verification, generate(lookahead=R, draft_answers=...), four arms interleaved with
 the plain call in three pairs each (tree_draft_lines states them).
+--temperature T [--top_p P] with --lookahead or --tree_draft times the SAMPLED arms: every call, the plain one too, samples with
+seed 0, the drafts are built around the plain sampled answer, and each arm is interleaved with the plain sampled call.
 --lookahead T [T ...] times draft-and-verify greedy decoding, generate(lookahead=T, stop_at_eos=False), each arm interleaved
 (--pairs N times, default 3) with the same call without the keyword: the run's own answer as draft (full acceptance: the upper
 bound), drafts that are all wrong (the price of the wasted rows) and prompt lookup (--lookup_ngram G) on the synthetic batch as it
@@ -77,6 +79,10 @@ def main():
     ap.add_argument("--lookahead", type=int, nargs="*", default=[], help="draft-and-verify decoding with up to T rows per pass; "
                                                                          "several T: three arms each, interleaved with plain generate")
     ap.add_argument("--lookup_ngram", type=int, default=2, help="--lookahead: the prompt-lookup arm's longest n-gram")
+    ap.add_argument("--temperature", type=float, default=0.0, help="--lookahead / --tree_draft: > 0 times the SAMPLED arms — every "
+                    "call, the plain one too, draws with this temperature, --top_p and seed 0, and the drafts are built around the "
+                    "plain sampled answer")
+    ap.add_argument("--top_p", type=float, default=1.0, help="--temperature: the nucleus bound")
     ap.add_argument("--tree_draft", type=int, nargs="*", default=[], help="tree-shaped draft verification with up to R rows per "
                     "pass (generate(lookahead=R, draft_answers=...)); several R: the four arms for each")
     ap.add_argument("--jump_forward", type=int, nargs="*", default=[], help="jump-forward constrained decoding with up to T rows "
@@ -250,10 +256,19 @@ def device_us(fn, reps=20):
     return ev[0].elapsed_time(ev[1]) * 1e3 / reps
 
 
+def sampling_of(a):
+    """--temperature / --top_p -> (the keywords every call of a sampled arm gets — the plain one too: the same seed, so the same
+    draws —, the word for the lines)."""
+    if not a.temperature > 0:
+        return {}, "greedy"
+    return dict(temperature=a.temperature, top_p=a.top_p, seed=0), f"sampled temperature={a.temperature} top_p={a.top_p} seed=0"
+
+
 def lookahead_lines(a, eng, b, timed):
     B, N = a.batch_size, generate.N_NEW
-    tag = f"{a.model} L={eng.L} B={B} S=128 greedy"
-    ref = generate.generate(eng, b, stop_at_eos=False)
+    smp, word = sampling_of(a)
+    tag = f"{a.model} L={eng.L} B={B} S=128 {word}"
+    ref = generate.generate(eng, b, stop_at_eos=False, **smp)
     answer = ref["tokens"].to(torch.int32)
     listed = dict(b, text_id={"vqa": b["text_id"]["vqa"].clone()})              # the prompt lists the answer: last token, 12 answer
     for i, pre in enumerate(b["prefix_index"]["vqa"]):                          # tokens, one other token, then the prompt's end
@@ -268,8 +283,8 @@ def lookahead_lines(a, eng, b, timed):
     for T in a.lookahead:
         for name, data, kw in arms:
             out, base = {}, {}
-            plain = lambda: base.update(generate.generate(eng, data, stop_at_eos=False))               # noqa: E731
-            fn = lambda: out.update(generate.generate(eng, data, stop_at_eos=False, lookahead=T, **kw))   # noqa: E731
+            plain = lambda: base.update(generate.generate(eng, data, stop_at_eos=False, **smp))        # noqa: E731
+            fn = lambda: out.update(generate.generate(eng, data, stop_at_eos=False, lookahead=T, **smp, **kw))   # noqa: E731
             timed(plain, reps=1)
             timed(fn, reps=1)
             same = bool(torch.equal(out["ids"], base["ids"]))
@@ -290,7 +305,8 @@ def tree_draft_lines(a, eng, b, model, timed):
     import numpy as np
     ANSWER = 10
     B, V, eos = a.batch_size, eng.V, model.tokenizer.eos_id
-    tag = f"{a.model} L={eng.L} B={B} S=128 greedy to the EOS"
+    smp, word = sampling_of(a)
+    tag = f"{a.model} L={eng.L} B={B} S=128 {word} to the EOS"
     pi = synth.vocab_permutation(V)
     mul, add = int((pi[1] - pi[0]) % V), int(pi[0])
     t = eos
@@ -298,7 +314,7 @@ def tree_draft_lines(a, eng, b, model, timed):
         t = ((t - add) * pow(mul, -1, V)) % V
     for i, pre in enumerate(b["prefix_index"]["vqa"]):
         b["text_id"]["vqa"][i, :, pre - 1] = t
-    ref = generate.generate(eng, b, stop_at_eos=True)
+    ref = generate.generate(eng, b, stop_at_eos=True, **smp)
     rows = [[x for x in r if x >= 0 and x != eos] for r in ref["tokens"].cpu().tolist()]
     rng = np.random.default_rng(3)
     other = lambda n: [int(x) for x in rng.integers(3, V, n)]                   # noqa: E731
@@ -317,8 +333,8 @@ def tree_draft_lines(a, eng, b, model, timed):
                 ("chain lookahead=16, the answer as draft", dict(lookahead=16, draft_tokens=chain)))
         for name, kw in arms:
             out, base = {}, {}
-            plain = lambda: base.update(generate.generate(eng, b, stop_at_eos=True))                   # noqa: E731
-            fn = lambda: out.update(generate.generate(eng, b, stop_at_eos=True, **kw))                 # noqa: E731
+            plain = lambda: base.update(generate.generate(eng, b, stop_at_eos=True, **smp))            # noqa: E731
+            fn = lambda: out.update(generate.generate(eng, b, stop_at_eos=True, **smp, **kw))          # noqa: E731
             timed(plain, reps=1)
             timed(fn, reps=1)
             same = bool(torch.equal(out["ids"], base["ids"]))

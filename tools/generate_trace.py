@@ -175,6 +175,9 @@ def modes(eng, batch, full, drafts):
         ("lookahead=4 draft_answers", drafted("answer", lookahead=4)),
         ("lookahead=64 draft_answers return_logprobs", drafted("answer", lookahead=64, return_logprobs=True)),
         ("lookahead=4 draft_answers without the answer", drafted("none", lookahead=4)),
+        ("lookahead=4 draft_tokens sampled", lambda: generate.generate(eng, batch, lookahead=4, draft_tokens=drafts(),
+                                                                       temperature=0.8, top_p=0.9, seed=0)),
+        ("lookahead=4 draft_answers sampled", drafted("answer", lookahead=4, temperature=0.8, top_p=0.9, seed=0)),
     ]
 
 
