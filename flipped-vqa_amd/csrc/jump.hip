@@ -8,16 +8,18 @@
 //   fed      (want_logprobs) the log-probability of each token w_j, 1 <= j < m, the previous step chained, under the row it
 //            was fed behind: l[w_j] - lse of row j - 1, the lse of fvqa_decode_next_ex's rule 5 (maximum, sum of expf in strided
 //            order, shuffles, the four waves in order). Without want_logprobs the rows 0 .. m - 2 are never read.
-//   pick     on the LAST fed row, m - 1. A row at node == -1: the largest logit over the vocabulary, lowest index on exact ties
-//            (fvqa_decode_next's loop). A row at a node: the same loop over the node's edge list, decode_next_k<.., TRIE>'s at
-//            temperature 0 — the edge range clamped into [0, n_edges], edges whose token lies outside [0, V) skipped, lowest edge
-//            on ties, the child clamped to n_nodes. Then the row's lse for the token's log-probability.
+//   pick     on the LAST fed row, m - 1: csrc/row_sample.h's view of the row (RowElems) and its greedy pick, the code
+//            decode_next_k<.., TRIE> runs at temperature 0. A row at node == -1: the largest logit over the vocabulary, lowest
+//            index on exact ties. A row at a node: the same over the node's edge list — the edge range clamped into
+//            [0, n_edges], edges whose token lies outside [0, V) skipped, lowest edge on ties —, the child clamped to n_nodes.
+//            The row's lse, for the token's log-probability, in front of it.
 //   chain    ONE thread: at most T - 1 dependent steps of "the node's clamped edge range holds exactly one edge, its token is
 //            inside the vocabulary". The committed tokens stay in LDS for the embedding gather.
 //   outputs  the rows of the next pass (embeddings of the committed tokens; zeros behind), start / len for the suffix attention,
 //            the step's tokens and log-probabilities, the count of running rows through the caller's ticket word (an INTEGER
 //            atomic; the workgroup that arrives last writes the count and puts the word back to zero: csrc/token_step.h).
 // No float atomics, fixed summation orders: two launches on the same inputs give the same bits.
+#include "row_sample.h"
 #include "token_step.h"
 
 namespace {
@@ -66,45 +68,19 @@ __global__ __launch_bounds__(NT) void trie_jump_step_k(const float* __restrict__
   }
   if (tid == 0) logprob_fed[(size_t)b * Tn] = 0.f;
 
-  // ---- the pick, on the last fed row: the node's edge list et[0 .. N), every index clamped; N = V and element i = token i at -1
+  // ---- the pick, on the last fed row: greedy over the row's elements (the vocabulary at node -1, else the node's edge list; a
+  // trie that was not given has no nodes)
   const float* lg = logits + ((size_t)b * Tn + m - 1) * V;
-  int N = V, first_ok = 0;
-  bool cons = false;
-  const int32_t* et = nullptr;
-  const int32_t* ec = nullptr;
-  if (live && nd != -1) {
-    cons = true;
-    N = 0;
-    if (tr.node_first && nd >= 0 && nd < tr.n_nodes) {
-      int e0, e1;
-      tr.edges(nd, e0, e1);
-      et = tr.edge_token + e0;
-      ec = tr.edge_child + e0;
-      N = e1 - e0;
-    }
-    int c = 0, f = 0x7fffffff;
-    for (int i = tid; i < N; i += NT)
-      if ((unsigned)et[i] < (unsigned)V) { c += 1; f = min(f, i); }
-    const int n_ok = block_sum_int(c, redi);
-    first_ok = block_min_int(f, redi);
-    if (n_ok == 0) live = false;                                   // no children (or a node outside the trie): the row ends
-  }
+  const RowElems<true> el = row_elems<true>(V, tr, live ? nd : -1, redi);
+  const bool cons = el.cons;
+  if (el.n_ok == 0) live = false;                                  // no children (or a node outside the trie): the row ends
   int tok = -1, child = -1;
   float lse = 0.f;
   if (live) {
     lse = row_lse(lg, V, redf);
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < N; i += NT) {
-      if (cons && (unsigned)et[i] >= (unsigned)V) continue;
-      const float v = lg[cons ? et[i] : i];
-      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-    }
-    const float mx = block_max_256(bv, redf);
-    int sel = block_min_int(bv == mx ? bi : 0x7fffffff, redi);
-    if (sel >= N) sel = first_ok;                                  // (a row of NaNs)
-    tok = cons ? et[sel] : sel;
-    if (cons) child = tr.child(ec[sel]);
+    const int sel = row_pick_greedy(el, [&](int t) { return lg[t]; }, redf, redi);
+    tok = el.tok(sel);
+    if (cons) child = tr.child(el.ec[sel]);
   }
   __syncthreads();                                                 // (every read of pos / done / len / w / node above is over)
 

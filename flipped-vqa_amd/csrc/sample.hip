@@ -3,6 +3,11 @@
 // the reference's rule, llama/generation.py:17-68), write it into the id matrix, advance the position, raise the row's `done`
 // flag (EOS, or the end of the sequence), gather the next input embedding, count the rows still running.
 //
+// The pick is not this file's text: the view of a row's elements, the greedy pick and the sampled pick are csrc/row_sample.h's
+// (RowElems, row_pick_greedy, row_pick_sampled), which csrc/spec.hip, csrc/treespec.hip and csrc/jump.hip call as well. The kernel
+// here decides what a row is (live, its slot, its node, its plausible set), hands the pick the view and the logit it sees
+// (l1) and the draw, and steps the row. What follows states the rule the header implements.
+//
 // Picking with temperature > 0, per row (fp32 throughout, no sort):
 //   pass 1   m = max logit
 //   pass 2   e_i = __expf((l_i - m) / T), kept in LDS in place of the logits when 4*V bytes fit (else recomputed from the
@@ -65,13 +70,22 @@
 // [0, min(budget[r], width)), is not live: it becomes done and nothing of any request's results is written. A live slot picks by
 // the _ex / _trie rule with the draw at u[i * n_req + r] — the request's own, wherever and whenever it sits —, is stepped as
 // before, leaves its token, log-probability and count in the request's result rows, and is also done once i + 1 == budget[r].
+#include "row_sample.h"
 #include "token_step.h"
 
 namespace {
 
-constexpr size_t ROW_LDS_MAX = 144 * 1024;       // beside ~100 bytes of reduction scratch, under the CU's 160 KiB
-
 __device__ unsigned g_ticket = 0;
+
+// a view of a row's elements narrowed to those keep(i) admits as well (PAIR: the plausible set), recounted by the caller
+template <typename E, typename K>
+struct ElemsKept {
+  const E& el;
+  K keep;
+  int N, n_ok, first_ok;
+  __device__ __forceinline__ bool ok(int i) const { return el.ok(i) && keep(i); }
+  __device__ __forceinline__ int tok(int i) const { return el.tok(i); }
+};
 
 // the operands fvqa_decode_next_pair adds (PAIR = true)
 struct PairArgs {
@@ -130,236 +144,70 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     if (seated) ti = (int)i; else live = false;
   }
 
-  // ---- TRIE: the row's node -> its edge list et[0 .. N), every index clamped; N = V and element i = token i without one
-  int N = V, n_ok = V, first_ok = 0, nd = -1;
-  bool cons = false;
-  const int32_t* et = nullptr;
-  const int32_t* ec = nullptr;
-  if constexpr (TRIE) {
-    nd = ta.node[b];
-    if (live && nd != -1) {
-      cons = true;
-      N = 0;
-      if (nd >= 0 && nd < tr.n_nodes) {
-        int e0, e1;
-        tr.edges(nd, e0, e1);
-        et = tr.edge_token + e0;
-        ec = tr.edge_child + e0;
-        N = e1 - e0;
-      }
-      int c = 0, f = 0x7fffffff;
-      for (int i = tid; i < N; i += NT)
-        if ((unsigned)et[i] < (unsigned)V) { c += 1; f = min(f, i); }
-      n_ok = block_sum_int(c, redi);
-      first_ok = block_min_int(f, redi);
-      if (n_ok == 0) live = false;                                 // no children (or a node outside the trie): the row ends
-    }
-  }
-  auto ok0 = [&](int i) -> bool {                                  // element i is allowed (always, without a trie)
-    if constexpr (TRIE) {
-      if (cons) return (unsigned)et[i] < (unsigned)V;
-    }
-    return true;
-  };
-  auto tk = [&](int i) -> int {                                    // the token of element i (ok0(i) holds)
-    if constexpr (TRIE) {
-      if (cons) return et[i];
-    }
-    return i;
-  };
+  // ---- the row's elements: the vocabulary, or (TRIE, a row at a node) the node's edge list
+  int nd = -1;
+  if constexpr (TRIE) nd = ta.node[b];
+  const RowElems<TRIE> el0 = row_elems<TRIE>(V, tr, live ? nd : -1, redi);
+  if (el0.n_ok == 0) live = false;                                 // no children (or a node outside the trie): the row ends
   // ---- PAIR: the plausible set P — the allowed elements whose l+ lies within logf(beta) of the largest allowed l+
   float mxa = 0.f, lbeta = 0.f;
-  int n_plaus = 0;
+  int n_ok = el0.n_ok, first_ok = el0.first_ok, n_plaus = 0;
   if constexpr (PAIR) {
     if (live) {
       lbeta = logf(pr.beta);                                       // (beta == 0: -inf, every finite logit passes)
       float mx = -INFINITY;
-      for (int i = tid; i < N; i += NT)
-        if (ok0(i)) mx = fmaxf(mx, lg[tk(i)]);
+      for (int i = tid; i < el0.N; i += NT)
+        if (el0.ok(i)) mx = fmaxf(mx, lg[el0.tok(i)]);
       mxa = block_max_256(mx, redf);
       int c = 0, f = 0x7fffffff;
-      for (int i = tid; i < N; i += NT)
-        if (ok0(i) && lg[tk(i)] - mxa >= lbeta) { c += 1; f = min(f, i); }
+      for (int i = tid; i < el0.N; i += NT)
+        if (el0.ok(i) && lg[el0.tok(i)] - mxa >= lbeta) { c += 1; f = min(f, i); }
       n_ok = n_plaus = block_sum_int(c, redi);
       first_ok = block_min_int(f, redi);
       if (n_ok == 0) live = false;                                 // (a row of NaNs: the pair ends, as at a node without edges)
     }
   }
-  auto ok = [&](int i) -> bool {                                   // element i takes part: allowed, and (PAIR) inside P
-    if (!ok0(i)) return false;
-    if constexpr (PAIR) return lg[tk(i)] - mxa >= lbeta;
+  auto in_p = [&](int i) -> bool {                                 // (always, without PAIR)
+    if constexpr (PAIR) return lg[el0.tok(i)] - mxa >= lbeta;
     return true;
   };
-  const bool use_lds = row_in_lds && (!TRIE || N <= V);            // (a list longer than V: recomputed, never past the row)
+  const ElemsKept<RowElems<TRIE>, decltype(in_p)> el{el0, in_p, el0.N, n_ok, first_ok};   // what takes part in the pick
+  const bool use_lds = row_in_lds && (!TRIE || el.N <= V);         // (a list longer than V: recomputed, never past the row)
 
   // ---- EX: the raw row's lse; the bitmap of the ids generated so far
   float lse = 0.f, lse_n = 0.f;
   const bool pen = EX && rep != 1.f;
-  unsigned* bm = reinterpret_cast<unsigned*>(erow) + (row_in_lds ? ((V + 3) & ~3) : 0);
+  const SampleLds sl{erow, sample_bitmap_at(erow, V, row_in_lds), redf, wtotf, redi, wtoti};
   if constexpr (EX) {
     if (live) lse = row_lse(lg, V, redf);
     if constexpr (PAIR) {
       if (live) lse_n = row_lse(lgn, V, redf);
     }
-    if (live && pen) {
-      for (int i = tid; i < ((V + 31) >> 5); i += NT) bm[i] = 0u;
-      __syncthreads();
-      const int g0 = gen_start[b];
-      for (int j = (g0 < 0 ? 0 : g0) + tid; j <= p; j += NT) {     // (p <= S - 2)
-        const int64_t t = row_ids[j];
-        if (t >= 0 && t < V) atomicOr(&bm[t >> 5], 1u << (t & 31));
-      }
-      __syncthreads();
-    }
+    if (live && pen) sample_bitmap_build(sl.bm, row_ids, gen_start[b], p, V);   // (p <= S - 2)
   }
-  auto l1 = [&](int i) -> float {                                  // the logit the pick sees
-    float v = lg[i];
-    if constexpr (PAIR) v = v + pr.alpha * ((v - lse) - (lgn[i] - lse_n));   // c_i in place of l_i
+  auto l1 = [&](int t) -> float {                                  // the logit the pick sees at token t
+    float v = lg[t];
+    if constexpr (PAIR) v = v + pr.alpha * ((v - lse) - (lgn[t] - lse_n));   // c_t in place of l_t
     if constexpr (EX) {
-      if (pen && ((bm[i >> 5] >> (i & 31)) & 1u)) v = v > 0.f ? v / rep : v * rep;
+      if (pen) v = sample_penalised(v, t, sl.bm, rep);
     }
     return v;
   };
 
-  // Every loop below runs over the N elements of the row: the vocabulary, or (TRIE, a row at a node) the node's edges, of which
-  // those with ok() take part. `sel` is the element picked.
+  // ---- the pick (csrc/row_sample.h) -> `sel`, the element picked
   int sel = -1;
   if (live && temperature == 0.f) {
-    // ---- greedy: the largest logit, the lowest index on exact ties
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < N; i += NT) {
-      if (!ok(i)) continue;
-      const float v = l1(tk(i));
-      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-    }
-    const float m = block_max_256(bv, redf);
-    sel = block_min_int(bv == m ? bi : 0x7fffffff, redi);
-    if (sel >= N) sel = first_ok;                                  // (a row of NaNs)
+    sel = row_pick_greedy(el, l1, redf, redi);
     kept = 1;
   } else if (live) {
-    // ---- pass 1, 2: max, e_i, Z
-    float mx = -INFINITY;
-    for (int i = tid; i < N; i += NT)
-      if (ok(i)) mx = fmaxf(mx, l1(tk(i)));
-    const float m = block_max_256(mx, redf);
-    float z = 0.f;
-    for (int i = tid; i < N; i += NT) {
-      const float e = ok(i) ? __expf((l1(tk(i)) - m) / temperature) : 0.f;
-      if (use_lds) erow[i] = e;
-      z += e;
-    }
-    const float Z = block_sum_256(z, redf);                        // (its barriers also publish erow)
-    // (an element without ok() has e = 0: no `> t` test below sees it, and every `== t` test asks ok() as well)
-    auto pe = [&](int i) -> float {
-      return use_lds ? erow[i] : (ok(i) ? __expf((l1(tk(i)) - m) / temperature) : 0.f);
-    };
-    // ---- EX, top-k: the smallest t with C(t) <= k - 1 is the value at rank k
-    float Zk = Z;
-    unsigned tkb = 0u;
-    int tie_k = 0;
-    const bool cut_k = EX && top_k >= 1 && top_k < n_ok;
-    if constexpr (EX) {
-      if (cut_k) {
-        unsigned lo = 0u, hi = 0x3f800000u;                        // C(bits(1.0f)) = 0
-        while (lo < hi) {
-          const unsigned mid = lo + ((hi - lo) >> 1);
-          int c = 0;
-          for (int i = tid; i < N; i += NT) c += __float_as_uint(pe(i)) > mid ? 1 : 0;
-          c = block_sum_int(c, redi);
-          if (c < top_k) hi = mid; else lo = mid + 1u;
-        }
-        tkb = lo;
-        float g = 0.f;
-        int c = 0;
-        for (int i = tid; i < N; i += NT) {
-          const float e = pe(i);
-          const bool over = __float_as_uint(e) > tkb;
-          g += over ? e : 0.f;
-          c += over ? 1 : 0;
-        }
-        g = block_sum_256(g, redf);
-        tie_k = top_k - block_sum_int(c, redi);                    // >= 1, and the tie group at tkb has at least as many
-        Zk = g + (float)tie_k * __uint_as_float(tkb);
-      }
-    }
-    // ---- the cut: the smallest t with G(t) <= top_p * Z (Z_k under top-k)
-    const float X = top_p * Zk;
-    unsigned lo = 0u, hi = 0x3f800000u;                            // G(bits(1.0f)) = 0: no e_i exceeds exp(0)
-    if (cut_k && top_p >= 1.f) lo = hi = tkb;                      // every rank < k has at most Z_k in front: the top-k cut
-    while (lo < hi) {
-      const unsigned mid = lo + ((hi - lo) >> 1);
-      float g = 0.f;
-      for (int i = tid; i < N; i += NT) {
-        const float e = pe(i);
-        g += __float_as_uint(e) > mid ? e : 0.f;
-      }
-      g = block_sum_256(g, redf);
-      if (g <= X) hi = mid; else lo = mid + 1u;
-    }
-    unsigned tb = lo;
-    const float tf = __uint_as_float(tb);
-    float g = 0.f;
-    int n_gt = 0, n_eq = 0;
-    for (int i = tid; i < N; i += NT) {
-      const float e = pe(i);
-      const unsigned eb = __float_as_uint(e);
-      g += eb > tb ? e : 0.f;
-      n_gt += eb > tb ? 1 : 0;
-      n_eq += (eb == tb && ok(i)) ? 1 : 0;
-    }
-    g = block_sum_256(g, redf);
-    n_gt = block_sum_int(n_gt, redi);
-    n_eq = block_sum_int(n_eq, redi);
-    int n_tie = n_eq;                                              // of the tie group, the j-th has g + j * t in front
-    if (tf > 0.f) {
-      const float q = (X - g) / tf;
-      if (q < (float)n_eq) n_tie = (int)q + 1;
-    }
-    kept = n_gt + n_tie;
-    if (cut_k && (kept > top_k || top_p >= 1.f)) {                 // the shorter prefix of the one order
-      tb = tkb;
-      n_tie = tie_k;
-      kept = top_k;
-    }
-    // ---- the walk, in index order over contiguous ranges
-    const int chunk = (N + NT - 1) / NT;
-    const int i0 = min(N, tid * chunk), i1 = min(N, i0 + chunk);
-    int c_eq = 0;
-    for (int i = i0; i < i1; ++i) c_eq += (__float_as_uint(pe(i)) == tb && ok(i)) ? 1 : 0;
-    const int rank0 = block_scan_i(c_eq, wtoti);
-    float mass = 0.f;
-    int rank = rank0, last = -1;
-    for (int i = i0; i < i1; ++i) {
-      const float e = pe(i);
-      const unsigned eb = __float_as_uint(e);
-      const bool k = eb > tb || (eb == tb && ok(i) && rank++ < n_tie);
-      if (k) { mass += e; last = i; }
-    }
-    float M;
-    const float before = block_scan_f(mass, wtotf, &M);
-    const float target = (STREAM ? u_p[(size_t)ti * sa.n_req + r] : u_p[b]) * M;
-    float run = before;
-    int cand = 0x7fffffff;
-    rank = rank0;
-    for (int i = i0; i < i1; ++i) {
-      const float e = pe(i);
-      const unsigned eb = __float_as_uint(e);
-      const bool k = eb > tb || (eb == tb && ok(i) && rank++ < n_tie);
-      if (k) {
-        run += e;
-        if (run > target && cand == 0x7fffffff) cand = i;
-      }
-    }
-    cand = block_min_int(cand, redi);
-    last = block_max_int(last, redi);
-    sel = cand < N ? cand : (last >= 0 ? last : first_ok);         // (u * M rounded up to M: the last KEPT element)
+    const float u = STREAM ? u_p[(size_t)ti * sa.n_req + r] : u_p[b];
+    sel = row_pick_sampled<EX>(el, l1, use_lds, sl, u, temperature, top_p, top_k, kept);
   }
   int child = -1;
   if (live) {
-    tok = tk(sel);
+    tok = el0.tok(sel);
     if constexpr (TRIE) {
-      if (cons) child = tr.child(ec[sel]);
+      if (el0.cons) child = tr.child(el0.ec[sel]);
     }
   }
 
@@ -395,7 +243,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     token_out[b] = tok;
     n_kept_out[b] = kept;
     if constexpr (TRIE) {
-      if (live && cons) ta.node[b] = child;
+      if (live && el0.cons) ta.node[b] = child;
     }
     if constexpr (EX) logprob_out[b] = live ? lg[tok] - lse : 0.f;
     if constexpr (STREAM) {
@@ -422,7 +270,6 @@ struct ExArgs {
   float* logprob;
   unsigned* counter;
 };
-constexpr size_t BITMAP_LDS_MAX = ROW_LDS_MAX / 32;                // the bitmap of the largest row that lives in LDS
 
 template <typename T, bool EX, bool TRIE, bool PAIR = false, bool STREAM = false>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
@@ -430,18 +277,10 @@ int launch(const float* logits, const float* u, const void* emb, float temperatu
            int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st,
            PairArgs pr = PairArgs{0.f, 0.f, nullptr},
            StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
-  const size_t row_bytes = (size_t)V * sizeof(float);
-  const int in_lds = temperature > 0.f && row_bytes <= ROW_LDS_MAX;
-  size_t lds = in_lds ? row_bytes : 0;
-  if (EX && ex.rep != 1.f) {                                       // the bitmap: V bits behind the row (on a 16-byte boundary)
-    const size_t bitmap = (((size_t)V + 31) / 32) * 4;
-    lds = in_lds ? (((size_t)V + 3) & ~(size_t)3) * sizeof(float) + bitmap : bitmap;
-    if (lds > ROW_LDS_MAX + BITMAP_LDS_MAX) return FVQA_ESHAPE;    // (a vocabulary beyond 1.2 million ids under a penalty)
-  }
-  static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
-  if (fvqa_attr_needed(attr_done))
-    (void)hipFuncSetAttribute((const void*)decode_next_k<T, EX, TRIE, PAIR, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(ROW_LDS_MAX + (EX ? BITMAP_LDS_MAX : 0)));
+  int in_lds, fits;                                                // (without EX rep is 1: no bitmap)
+  const size_t lds = fvqa_sample_lds(V, ex.rep, temperature > 0.f, &in_lds, &fits);
+  if (!fits) return FVQA_ESHAPE;                                   // (a vocabulary beyond 1.2 million ids under a penalty)
+  fvqa_sample_lds_limit<decode_next_k<T, EX, TRIE, PAIR, STREAM>>(EX);
   const int vec16 = fvqa_vec16((size_t)D * sizeof(T), emb, x_next);   // (PAIR: the twin half follows B * D elements on, whole rows)
   hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR, STREAM>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature,
                      top_p, eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds,

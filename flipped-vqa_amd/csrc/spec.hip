@@ -19,7 +19,7 @@
 //            workgroup that arrives last writes the count and puts the word back to zero: csrc/token_step.h).
 // fvqa_spec_step_sample is the kernel template with SAMPLE = true (false in fvqa_spec_step, whose instantiation holds none of
 // the sampling code): draft-and-verify under sampling. The pick at row i is not the arg-max but
-// csrc/row_sample.h's row_sample — rules 1 to 5 of fvqa_decode_next_ex with the draw of the token's index,
+// csrc/row_sample.h's row_sample — the one sampled pick, decode_next_k's own, on the vocabulary with the draw of the token's index,
 // u[(n_generated + i) * n_seq + n] — and a draft is accepted iff it equals the token sampled in front of it: for a point-mass
 // draft that is the rejection rule of speculative sampling, so the ids are the plain sampled call's. The bitmap of the
 // repetition penalty is built once per step and gains one bit per commit. Everything behind the pick is the code above.
@@ -77,8 +77,7 @@ __global__ __launch_bounds__(NT) void spec_step_k(const float* __restrict__ logi
       float lse;
       int g, kept = 1;
       if constexpr (SAMPLE)                                        // the sampled pick, with the draw of this token's index
-        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa.temperature, sa.top_p, sa.top_k, sa.rep, pen,
-                       sa.row_in_lds, sl, kept, lse);
+        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa, pen, sl, kept, lse);
       else
         g = row_verify(lg, V, redf, redi, lse);
       p += 1;
@@ -184,10 +183,7 @@ int spec_step_launch(const float* logits, const void* emb, const int32_t* draft_
     return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
   if (!draft_tokens && (lookup_ngram < 1 || lookup_ngram > GMAX)) return FVQA_EINVAL;
-  if (sa) {
-    const int rc = fvqa_sample_args_ok(sa->u, sa->temperature, sa->top_p, sa->top_k, sa->rep, sa->gen_start, sa->n_kept);
-    if (rc != FVQA_OK) return rc;
-  }
+  if (const int rc = fvqa_sample_args_ok(sa); rc != FVQA_OK) return rc;
   if (n_seq <= 0 || lookahead <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0) return FVQA_ESHAPE;
   if (lookahead > TMAX || n_seq > 65535 || (int64_t)n_seq * lookahead > 65535) return FVQA_ESHAPE;   // (the ticket counts
                                                                    // arrivals in 16 bits; the pass's rows are a grid dimension)
@@ -196,33 +192,23 @@ int spec_step_launch(const float* logits, const void* emb, const int32_t* draft_
                     n_active, counter) ||
       !fvqa_aligned(8, ids, pos64))
     return FVQA_EALIGN;
-  if (sa && !fvqa_aligned(4, sa->u, sa->gen_start, sa->n_kept)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  SampleArgs s = sa ? *sa : SampleArgs{};
-  size_t lds = 0;
-  if (sa) {
-    int fits;
-    lds = fvqa_sample_lds(vocab, s.rep, &s.row_in_lds, &fits);
-    if (!fits) return FVQA_ESHAPE;                                 // (a vocabulary beyond 1.2 million ids under a penalty)
-  }
+  SampleArgs s;
+  size_t lds;
+  if (const int rc = fvqa_sample_launch_args(sa, vocab, &s, &lds); rc != FVQA_OK) return rc;
   fvqa_by_dtype(dtype, [&](auto* t) {
     using T = std::remove_pointer_t<decltype(t)>;
     const int vec16 = fvqa_vec16(dim * sizeof(T), emb, x_next);
-    if (sa) {
-      static std::atomic<unsigned long long> attr_done{0};         // one bit per device (fvqa_attr_needed)
-      if (fvqa_attr_needed(attr_done))
-        (void)hipFuncSetAttribute((const void*)spec_step_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(SAMPLE_ROW_LDS_MAX + SAMPLE_BITMAP_LDS_MAX));
-      hipLaunchKernelGGL((spec_step_k<T, true>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, draft_tokens,
+    auto launch = [&](auto sample) {                               // SAMPLE = sample.value
+      constexpr bool SAMPLE = decltype(sample)::value;
+      if constexpr (SAMPLE) fvqa_sample_lds_limit<spec_step_k<T, true>>(true);
+      hipLaunchKernelGGL((spec_step_k<T, SAMPLE>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, draft_tokens,
                          lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
                          (T*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab,
                          dim, seq_len, vec16, s);
-    } else {
-      hipLaunchKernelGGL((spec_step_k<T, false>), dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, draft_tokens,
-                         lookup_ngram, eos_id, stop_at_eos, max_new_tokens, ids, pos, done, n_generated, w, len, start,
-                         (T*)x_next, token, logprob, n_committed, n_drafted, n_active, counter, pos64, n_seq, lookahead, vocab,
-                         dim, seq_len, vec16, s);
-    }
+    };
+    if (sa) launch(std::true_type{});
+    else launch(std::false_type{});
   });
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;

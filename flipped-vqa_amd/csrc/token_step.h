@@ -3,7 +3,8 @@
 // integer block reductions, the block scans and the lse of a raw row, the verify scan of the draft-and-verify steps, the view of a trie with its
 // two clamps, the clamps that keep a finished row's reads inside its arrays, the ticket word that counts running rows across
 // workgroups, the embedding rows of the next pass, and the host side's operand rules (16-byte rows, storage-type dispatch, "no
-// trie or a whole one").
+// trie or a whole one"). The pick of a row — the elements that take part, greedy, sampled, the penalty's bitmap, the dynamic LDS
+// — is csrc/row_sample.h, on top of this header; row_verify below stays beside it because its arg-max shares a pass with the lse.
 #pragma once
 #include <type_traits>
 #include "common.h"

@@ -19,7 +19,8 @@
 //   path[n, i] to cache row start_old[n] + i, k in the cache's convention (csrc/cache_row.h: the store fvqa_attn_suffix_append
 //   does, so the bits are its bits).
 // fvqa_tree_spec_step_sample — the step kernel with SAMPLE = true (false in fvqa_tree_spec_step, whose instantiation holds none
-//   of the sampling code): every commit of the walk is csrc/row_sample.h's sampled pick with the draw of its token index, and the walk moves
+//   of the sampling code): every commit of the walk is csrc/row_sample.h's sampled pick (the one fvqa_decode_next_ex runs) with
+//   the draw of its token index, and the walk moves
 //   to the child under the sampled token (csrc/spec.hip says why that gives the plain sampled call's ids).
 // No float atomics, fixed summation orders: two launches give the same bits. Every index read from the plan, node, ids or path is
 // clamped or skipped before it is used.
@@ -90,8 +91,7 @@ __global__ __launch_bounds__(NT) void tree_spec_step_k(
       float lse;
       int g, kept = 1;
       if constexpr (SAMPLE)                                        // the sampled pick, with the draw of this token's index
-        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa.temperature, sa.top_p, sa.top_k, sa.rep, pen,
-                       sa.row_in_lds, sl, kept, lse);
+        g = row_sample(lg, V, sample_draw(sa.u, ngen, max_new, B, b), sa, pen, sl, kept, lse);
       else
         g = row_verify(lg, V, redf, redi, lse);
       p += 1;
@@ -250,10 +250,7 @@ int tree_spec_step_launch(const float* logits, const void* emb, const int32_t* p
       !token || !logprob || !n_committed || !n_drafted || !n_active || !n_on_trie || !counter)
     return FVQA_EINVAL;
   if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
-  if (sa) {
-    const int rc = fvqa_sample_args_ok(sa->u, sa->temperature, sa->top_p, sa->top_k, sa->rep, sa->gen_start, sa->n_kept);
-    if (rc != FVQA_OK) return rc;
-  }
+  if (const int rc = fvqa_sample_args_ok(sa); rc != FVQA_OK) return rc;
   if (n_seq <= 0 || rows_in <= 0 || rows_out <= 0 || vocab <= 0 || dim <= 0 || seq_len <= 0 || max_new_tokens <= 0 ||
       plan_rows <= 0)
     return FVQA_ESHAPE;
@@ -267,35 +264,24 @@ int tree_spec_step_launch(const float* logits, const void* emb, const int32_t* p
                     counter) ||
       !fvqa_aligned(8, ids, pos64))
     return FVQA_EALIGN;
-  if (sa && !fvqa_aligned(4, sa->u, sa->gen_start, sa->n_kept)) return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
-  SampleArgs s = sa ? *sa : SampleArgs{};
-  size_t lds = 0;
-  if (sa) {
-    int fits;
-    lds = fvqa_sample_lds(vocab, s.rep, &s.row_in_lds, &fits);
-    if (!fits) return FVQA_ESHAPE;                                 // (a vocabulary beyond 1.2 million ids under a penalty)
-  }
+  SampleArgs s;
+  size_t lds;
+  if (const int rc = fvqa_sample_launch_args(sa, vocab, &s, &lds); rc != FVQA_OK) return rc;
   fvqa_by_dtype(dtype, [&](auto* t) {
     using T = std::remove_pointer_t<decltype(t)>;
     const int vec16 = fvqa_vec16(dim * sizeof(T), emb, x_next);
-    if (sa) {
-      static std::atomic<unsigned long long> attr_done{0};         // one bit per device (fvqa_attr_needed)
-      if (fvqa_attr_needed(attr_done))
-        (void)hipFuncSetAttribute((const void*)tree_spec_step_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(SAMPLE_ROW_LDS_MAX + SAMPLE_BITMAP_LDS_MAX));
-      hipLaunchKernelGGL((tree_spec_step_k<T, true>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, plan_n, plan_token,
+    auto launch = [&](auto sample) {                               // SAMPLE = sample.value
+      constexpr bool SAMPLE = decltype(sample)::value;
+      if constexpr (SAMPLE) fvqa_sample_lds_limit<tree_spec_step_k<T, true>>(true);
+      hipLaunchKernelGGL((tree_spec_step_k<T, SAMPLE>), dim3(n_seq), dim3(NT), lds, st, logits, (const T*)emb, plan_n, plan_token,
                          plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id, stop_at_eos, max_new_tokens, ids, pos,
                          done, n_generated, node, len, start, (T*)x_next, depth, end, tile_anc, path, n_path, start_old, token,
                          logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64, n_seq, rows_in, rows_out, vocab,
                          dim, seq_len, vec16, s);
-    } else {
-      hipLaunchKernelGGL((tree_spec_step_k<T, false>), dim3(n_seq), dim3(NT), 0, st, logits, (const T*)emb, plan_n, plan_token,
-                         plan_depth, plan_end, plan_parent, plan_rows, plan_stride, eos_id, stop_at_eos, max_new_tokens, ids, pos,
-                         done, n_generated, node, len, start, (T*)x_next, depth, end, tile_anc, path, n_path, start_old, token,
-                         logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64, n_seq, rows_in, rows_out, vocab,
-                         dim, seq_len, vec16, s);
-    }
+    };
+    if (sa) launch(std::true_type{});
+    else launch(std::false_type{});
   });
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;

@@ -924,38 +924,6 @@ def _pass_rows(what: str, w):
     return B, T
 
 
-def spec_step(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted,
-              n_active, counter, *, max_new_tokens: int, draft_tokens=None, lookup_ngram: int = 2, pos64=None, eos_id: int = 2,
-              stop_at_eos: bool = True):
-    """The token step of draft-and-verify greedy decoding (include/fvqa.h fvqa_spec_step states the rule). logits (B*T, V) fp32:
-    row n*T + j was computed at position pos[n] + j on the token w[n, j] (j = 0: the last committed token, ids[n, pos[n]]).
-    In/out: ids (B, S) int64, pos / done / n_generated / length (B,) int32, w (B, T) int32. Out: start (B,) int32, x_next (B*T, D),
-    token (B, T) int32 (-1 padded), logprob (B, T) fp32 (0 padded), n_committed / n_drafted (B,) int32, n_active (1,) int32,
-    pos64 (B,) int64 or None. counter: one int32 word the caller zeroed once. draft_tokens (B, max_new_tokens) int32: the drafts
-    are read from it at each row's n_generated; None: prompt lookup with n-grams of up to lookup_ngram tokens."""
-    _dev(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted, n_active,
-         counter, draft_tokens, pos64)
-    B, T = _pass_rows("spec_step", w)
-    V, D, S = _token_step("spec_step", logits, B * T, emb, x_next, ids, B,
-                          _of(_I32, B, pos=pos, done=done, n_generated=n_generated, len=length, start=start,
-                              n_committed=n_committed, n_drafted=n_drafted) + _of(_I32, 1, n_active=n_active, counter=counter) +
-                          _of(_I32, B * T, token=token) + _of(_F32, B * T, logprob=logprob), pos64=pos64, n_pos64=B)
-    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, "spec_step: max_new_tokens >= 1")
-    if draft_tokens is None:
-        _need(int(lookup_ngram) == lookup_ngram and 1 <= lookup_ngram <= LOOKUP_NGRAM_MAX,
-              f"spec_step: 1 <= lookup_ngram <= {LOOKUP_NGRAM_MAX}")
-    else:
-        _need(draft_tokens.dtype == _I32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
-              "spec_step: draft_tokens (B, max_new_tokens) int32")
-    rc = _lib.load(emb.dtype).fvqa_spec_step(_ptr(logits), _ptr(emb), _ptr(draft_tokens), int(lookup_ngram), int(eos_id),
-                                             1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done),
-                                             _ptr(n_generated), _ptr(w), _ptr(length), _ptr(start), _ptr(x_next), _ptr(token),
-                                             _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(counter),
-                                             _ptr(pos64), B, T, V, D, S, dt_code(emb.dtype), _stream())
-    _lib.check(rc, "fvqa_spec_step")
-    return token
-
-
 def _sample_operands(what, u, gen_start, n_kept, n_slots, B, max_new_tokens, temperature, top_p, top_k, repetition_penalty):
     """The operands the sampled draft-and-verify steps add: u (max_new_tokens, B) fp32, gen_start (B,) int32, n_kept of n_slots
     int32, and fvqa_decode_next_ex's parameters with temperature > 0."""
@@ -967,6 +935,56 @@ def _sample_operands(what, u, gen_start, n_kept, n_slots, B, max_new_tokens, tem
     _table(what, _of(_I32, B, gen_start=gen_start) + _of(_I32, n_slots, n_kept=n_kept))
 
 
+def _spec_step(what, sampling, logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed,
+               n_drafted, n_active, counter, max_new_tokens, draft_tokens, lookup_ngram, pos64, eos_id, stop_at_eos):
+    """spec_step (sampling None) and spec_step_sample (sampling = (u, gen_start, n_kept, temperature, top_p, top_k,
+    repetition_penalty)) under the entry's name `what`: one set of operand checks, then fvqa_<what>."""
+    sampled = sampling is not None
+    u, gen_start, n_kept, temperature, top_p, top_k, repetition_penalty = sampling if sampled else (None,) * 7
+
+    def only(*operands):                 # what the sampled entry has in these places on top of the plain one's
+        return operands if sampled else ()
+    _dev(logits, emb, ids, pos, done, n_generated, *only(gen_start), w, length, start, x_next, token, *only(n_kept), logprob,
+         n_committed, n_drafted, n_active, counter, draft_tokens, pos64, *only(u))
+    B, T = _pass_rows(what, w)
+    V, D, S = _token_step(what, logits, B * T, emb, x_next, ids, B,
+                          _of(_I32, B, pos=pos, done=done, n_generated=n_generated, len=length, start=start,
+                              n_committed=n_committed, n_drafted=n_drafted) + _of(_I32, 1, n_active=n_active, counter=counter) +
+                          _of(_I32, B * T, token=token) + _of(_F32, B * T, logprob=logprob), pos64=pos64, n_pos64=B)
+    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
+    if sampled:
+        _sample_operands(what, u, gen_start, n_kept, B * T, B, max_new_tokens, temperature, top_p, top_k, repetition_penalty)
+    if draft_tokens is None:
+        _need(int(lookup_ngram) == lookup_ngram and 1 <= lookup_ngram <= LOOKUP_NGRAM_MAX,
+              f"{what}: 1 <= lookup_ngram <= {LOOKUP_NGRAM_MAX}")
+    else:
+        _need(draft_tokens.dtype == _I32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
+              f"{what}: draft_tokens (B, max_new_tokens) int32")
+    params = (float(temperature), float(top_p), int(top_k), float(repetition_penalty)) if sampled else ()
+    rc = getattr(_lib.load(emb.dtype), "fvqa_" + what)(
+        _ptr(logits), *map(_ptr, only(u)), _ptr(emb), _ptr(draft_tokens), int(lookup_ngram),
+        *params, int(eos_id), 1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated),
+        *map(_ptr, only(gen_start)), _ptr(w), _ptr(length), _ptr(start), _ptr(x_next), _ptr(token), *map(_ptr, only(n_kept)),
+        _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(counter), _ptr(pos64), B, T, V, D, S,
+        dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_" + what)
+    return token
+
+
+def spec_step(logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted,
+              n_active, counter, *, max_new_tokens: int, draft_tokens=None, lookup_ngram: int = 2, pos64=None, eos_id: int = 2,
+              stop_at_eos: bool = True):
+    """The token step of draft-and-verify greedy decoding (include/fvqa.h fvqa_spec_step states the rule). logits (B*T, V) fp32:
+    row n*T + j was computed at position pos[n] + j on the token w[n, j] (j = 0: the last committed token, ids[n, pos[n]]).
+    In/out: ids (B, S) int64, pos / done / n_generated / length (B,) int32, w (B, T) int32. Out: start (B,) int32, x_next (B*T, D),
+    token (B, T) int32 (-1 padded), logprob (B, T) fp32 (0 padded), n_committed / n_drafted (B,) int32, n_active (1,) int32,
+    pos64 (B,) int64 or None. counter: one int32 word the caller zeroed once. draft_tokens (B, max_new_tokens) int32: the drafts
+    are read from it at each row's n_generated; None: prompt lookup with n-grams of up to lookup_ngram tokens."""
+    return _spec_step("spec_step", None, logits, emb, ids, pos, done, n_generated, w, length, start, x_next, token, logprob,
+                      n_committed, n_drafted, n_active, counter, max_new_tokens, draft_tokens, lookup_ngram, pos64, eos_id,
+                      stop_at_eos)
+
+
 def spec_step_sample(logits, emb, ids, pos, done, n_generated, gen_start, w, length, start, x_next, token, n_kept, logprob,
                      n_committed, n_drafted, n_active, counter, *, u, max_new_tokens: int, temperature: float, top_p: float = 1.0,
                      top_k: int = 0, repetition_penalty: float = 1.0, draft_tokens=None, lookup_ngram: int = 2, pos64=None,
@@ -975,30 +993,9 @@ def spec_step_sample(logits, emb, ids, pos, done, n_generated, gen_start, w, len
     decode_next_ex's rule with the draw of its token index, u[n_generated + i, n], and a draft is accepted iff it equals the
     token sampled in front of it. On top of spec_step's operands: u (max_new_tokens, B) fp32 — the plain loop's draws —,
     gen_start (B,) int32, n_kept (B, T) int32 out (0 padded), temperature > 0, top_p, top_k, repetition_penalty."""
-    _dev(logits, emb, ids, pos, done, n_generated, gen_start, w, length, start, x_next, token, n_kept, logprob, n_committed,
-         n_drafted, n_active, counter, draft_tokens, pos64, u)
-    what = "spec_step_sample"
-    B, T = _pass_rows(what, w)
-    V, D, S = _token_step(what, logits, B * T, emb, x_next, ids, B,
-                          _of(_I32, B, pos=pos, done=done, n_generated=n_generated, len=length, start=start,
-                              n_committed=n_committed, n_drafted=n_drafted) + _of(_I32, 1, n_active=n_active, counter=counter) +
-                          _of(_I32, B * T, token=token) + _of(_F32, B * T, logprob=logprob), pos64=pos64, n_pos64=B)
-    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
-    _sample_operands(what, u, gen_start, n_kept, B * T, B, max_new_tokens, temperature, top_p, top_k, repetition_penalty)
-    if draft_tokens is None:
-        _need(int(lookup_ngram) == lookup_ngram and 1 <= lookup_ngram <= LOOKUP_NGRAM_MAX,
-              f"{what}: 1 <= lookup_ngram <= {LOOKUP_NGRAM_MAX}")
-    else:
-        _need(draft_tokens.dtype == _I32 and tuple(draft_tokens.shape) == (B, int(max_new_tokens)),
-              f"{what}: draft_tokens (B, max_new_tokens) int32")
-    rc = _lib.load(emb.dtype).fvqa_spec_step_sample(
-        _ptr(logits), _ptr(u), _ptr(emb), _ptr(draft_tokens), int(lookup_ngram), float(temperature), float(top_p), int(top_k),
-        float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done),
-        _ptr(n_generated), _ptr(gen_start), _ptr(w), _ptr(length), _ptr(start), _ptr(x_next), _ptr(token), _ptr(n_kept),
-        _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(counter), _ptr(pos64), B, T, V, D, S,
-        dt_code(emb.dtype), _stream())
-    _lib.check(rc, "fvqa_spec_step_sample")
-    return token
+    return _spec_step("spec_step_sample", (u, gen_start, n_kept, temperature, top_p, top_k, repetition_penalty), logits, emb,
+                      ids, pos, done, n_generated, w, length, start, x_next, token, logprob, n_committed, n_drafted, n_active,
+                      counter, max_new_tokens, draft_tokens, lookup_ngram, pos64, eos_id, stop_at_eos)
 
 
 def trie_jump_step(logits, emb, ids, pos, done, n_generated, node, w, length, start, x_next, token, logprob_pick, logprob_fed,
@@ -1035,6 +1032,64 @@ TREE_SPEC_ROWS_MAX = 64      # rows of a sequence per pass fvqa_tree_spec_step t
 TREE_SPEC_WALK = 32          # tokens one step commits at the most: columns of token / logprob / path (csrc/treespec.hip WALK)
 
 
+def _tree_spec_step(what, sampling, logits, emb, plan, ids, pos, done, n_generated, node, length, start, x_next, depth, end,
+                    tile_anc, path, n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter,
+                    max_new_tokens, pos64, eos_id, stop_at_eos):
+    """tree_spec_step (sampling None) and tree_spec_step_sample (sampling = (u, gen_start, n_kept, temperature, top_p, top_k,
+    repetition_penalty)) under the entry's name `what`: one set of operand checks, then fvqa_<what>."""
+    sampled = sampling is not None
+    u, gen_start, n_kept, temperature, top_p, top_k, repetition_penalty = sampling if sampled else (None,) * 7
+
+    def only(*operands):                 # what the sampled entry has in these places on top of the plain one's
+        return operands if sampled else ()
+    names = ("n_plan", "token", "depth", "end", "parent")
+    _need(isinstance(plan, dict) and all(torch.is_tensor(plan.get(k)) for k in names), f"{what}: plan holds {names}")
+    pn, pt, pd, pe, pp = (plan[k] for k in names)
+    _dev(logits, emb, pn, pt, pd, pe, pp, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
+         n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64,
+         *only(u, gen_start, n_kept))
+    B = pos.numel()
+    _need(B >= 1 and logits.dim() == 2 and logits.shape[0] % B == 0 and x_next.dim() == 2 and x_next.shape[0] % B == 0,
+          f"{what}: logits (B*R_in, V) and x_next (B*R_out, D) for the B of pos")
+    R_in, R_out = logits.shape[0] // B, x_next.shape[0] // B
+    _need(1 <= R_in <= TREE_SPEC_ROWS_MAX and 1 <= R_out <= TREE_SPEC_ROWS_MAX and B * max(R_in, R_out) <= 65535,
+          f"{what}: 1 <= rows per sequence <= {TREE_SPEC_ROWS_MAX}, B * rows <= 65535")
+    _need(pt.dim() in (1, 2) and pt.shape[-1] >= 1 and (pt.dim() == 1 or pt.shape[0] == B),
+          f"{what}: plan tables are (P,) — shared — or (B, P)")
+    P, per = int(pt.shape[-1]), pt.dim() == 2
+    tiles = (R_out + TREE_TILE - 1) // TREE_TILE
+    W = TREE_SPEC_WALK
+    # (_token_step's checks with x_next at the rows of the NEXT pass: R_out need not be R_in)
+    _need(logits.dtype == _F32, f"{what}: logits ({B * R_in}, V) fp32")
+    V = logits.shape[1]
+    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype and x_next.shape[1] == emb.shape[1],
+          f"{what}: emb (V, D) and x_next ({B * R_out}, D) of one dtype")
+    D = emb.shape[1]
+    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == _I64, f"{what}: ids (B, S) int64, B = {B} rows")
+    S = ids.shape[1]
+    _table(what, _of(_I32, B if per else 1, n_plan=pn) +
+           _of(_I32, (B if per else 1) * P, plan_token=pt, plan_depth=pd, plan_end=pe, plan_parent=pp) +
+           _of(_I32, B, pos=pos, done=done, n_generated=n_generated, node=node, len=length, start=start, n_path=n_path,
+               start_old=start_old, n_committed=n_committed, n_drafted=n_drafted) +
+           _of(_I32, 1, n_active=n_active, n_on_trie=n_on_trie) + _of(_I32, 2, counter=counter) +
+           _of(_I32, B * R_out, depth=depth, end=end) + _of(_I32, B * tiles * TREE_TILE, tile_anc=tile_anc) +
+           _of(_I32, B * W, token=token, path=path) + _of(_F32, B * W, logprob=logprob))
+    _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == B), f"{what}: pos64 ({B},) int64")
+    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
+    if sampled:
+        _sample_operands(what, u, gen_start, n_kept, B * W, B, max_new_tokens, temperature, top_p, top_k, repetition_penalty)
+    params = (float(temperature), float(top_p), int(top_k), float(repetition_penalty)) if sampled else ()
+    rc = getattr(_lib.load(emb.dtype), "fvqa_" + what)(
+        _ptr(logits), *map(_ptr, only(u)), _ptr(emb), _ptr(pn), _ptr(pt), _ptr(pd), _ptr(pe), _ptr(pp), P, P if per else 0,
+        *params, int(eos_id), 1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated),
+        *map(_ptr, only(gen_start)), _ptr(node), _ptr(length), _ptr(start), _ptr(x_next), _ptr(depth), _ptr(end), _ptr(tile_anc),
+        _ptr(path), _ptr(n_path), _ptr(start_old), _ptr(token), *map(_ptr, only(n_kept)), _ptr(logprob), _ptr(n_committed),
+        _ptr(n_drafted), _ptr(n_active), _ptr(n_on_trie), _ptr(counter), _ptr(pos64), B, R_in, R_out, V, D, S,
+        dt_code(emb.dtype), _stream())
+    _lib.check(rc, "fvqa_" + what)
+    return token
+
+
 def tree_spec_step(logits, emb, plan, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
                    n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, *,
                    max_new_tokens: int, pos64=None, eos_id: int = 2, stop_at_eos: bool = True):
@@ -1046,48 +1101,9 @@ def tree_spec_step(logits, emb, plan, ids, pos, done, n_generated, node, length,
     * 32) int32: the next pass's operands of attn_suffix_tree (with `length` as its n_rows); path (B, 32), n_path, start_old (B,)
     int32 for kv_tree_commit; token (B, 32) int32 (-1 padded), logprob (B, 32) fp32 (0 padded), n_committed / n_drafted (B,) int32,
     n_active / n_on_trie (1,) int32, pos64 (B,) int64 or None. counter: TWO int32 words the caller zeroed once."""
-    what = "tree_spec_step"
-    names = ("n_plan", "token", "depth", "end", "parent")
-    _need(isinstance(plan, dict) and all(torch.is_tensor(plan.get(k)) for k in names), f"{what}: plan holds {names}")
-    pn, pt, pd, pe, pp = (plan[k] for k in names)
-    _dev(logits, emb, pn, pt, pd, pe, pp, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
-         n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64)
-    B = pos.numel()
-    _need(B >= 1 and logits.dim() == 2 and logits.shape[0] % B == 0 and x_next.dim() == 2 and x_next.shape[0] % B == 0,
-          f"{what}: logits (B*R_in, V) and x_next (B*R_out, D) for the B of pos")
-    R_in, R_out = logits.shape[0] // B, x_next.shape[0] // B
-    _need(1 <= R_in <= TREE_SPEC_ROWS_MAX and 1 <= R_out <= TREE_SPEC_ROWS_MAX and B * max(R_in, R_out) <= 65535,
-          f"{what}: 1 <= rows per sequence <= {TREE_SPEC_ROWS_MAX}, B * rows <= 65535")
-    _need(pt.dim() in (1, 2) and pt.shape[-1] >= 1 and (pt.dim() == 1 or pt.shape[0] == B),
-          f"{what}: plan tables are (P,) — shared — or (B, P)")
-    P, per = int(pt.shape[-1]), pt.dim() == 2
-    tiles = (R_out + TREE_TILE - 1) // TREE_TILE
-    W = TREE_SPEC_WALK
-    # (_token_step's checks with x_next at the rows of the NEXT pass: R_out need not be R_in)
-    _need(logits.dtype == _F32, f"{what}: logits ({B * R_in}, V) fp32")
-    V = logits.shape[1]
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype and x_next.shape[1] == emb.shape[1],
-          f"{what}: emb (V, D) and x_next ({B * R_out}, D) of one dtype")
-    D = emb.shape[1]
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == _I64, f"{what}: ids (B, S) int64, B = {B} rows")
-    S = ids.shape[1]
-    _table(what, _of(_I32, B if per else 1, n_plan=pn) +
-           _of(_I32, (B if per else 1) * P, plan_token=pt, plan_depth=pd, plan_end=pe, plan_parent=pp) +
-           _of(_I32, B, pos=pos, done=done, n_generated=n_generated, node=node, len=length, start=start, n_path=n_path,
-               start_old=start_old, n_committed=n_committed, n_drafted=n_drafted) +
-           _of(_I32, 1, n_active=n_active, n_on_trie=n_on_trie) + _of(_I32, 2, counter=counter) +
-           _of(_I32, B * R_out, depth=depth, end=end) + _of(_I32, B * tiles * TREE_TILE, tile_anc=tile_anc) +
-           _of(_I32, B * W, token=token, path=path) + _of(_F32, B * W, logprob=logprob))
-    _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == B), f"{what}: pos64 ({B},) int64")
-    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
-    rc = _lib.load(emb.dtype).fvqa_tree_spec_step(
-        _ptr(logits), _ptr(emb), _ptr(pn), _ptr(pt), _ptr(pd), _ptr(pe), _ptr(pp), P, P if per else 0, int(eos_id),
-        1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids), _ptr(pos), _ptr(done), _ptr(n_generated), _ptr(node),
-        _ptr(length), _ptr(start), _ptr(x_next), _ptr(depth), _ptr(end), _ptr(tile_anc), _ptr(path), _ptr(n_path),
-        _ptr(start_old), _ptr(token), _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(n_on_trie),
-        _ptr(counter), _ptr(pos64), B, R_in, R_out, V, D, S, dt_code(emb.dtype), _stream())
-    _lib.check(rc, "fvqa_tree_spec_step")
-    return token
+    return _tree_spec_step("tree_spec_step", None, logits, emb, plan, ids, pos, done, n_generated, node, length, start, x_next,
+                           depth, end, tile_anc, path, n_path, start_old, token, logprob, n_committed, n_drafted, n_active,
+                           n_on_trie, counter, max_new_tokens, pos64, eos_id, stop_at_eos)
 
 
 def tree_spec_step_sample(logits, emb, plan, ids, pos, done, n_generated, gen_start, node, length, start, x_next, depth, end,
@@ -1098,50 +1114,10 @@ def tree_spec_step_sample(logits, emb, plan, ids, pos, done, n_generated, gen_st
     picked by decode_next_ex's rule with the draw of its token index, u[n_generated + i, n], and the walk moves to the child
     under the sampled token. On top of tree_spec_step's operands: u (max_new_tokens, B) fp32, gen_start (B,) int32, n_kept
     (B, 32) int32 out (0 padded), temperature > 0, top_p, top_k, repetition_penalty."""
-    what = "tree_spec_step_sample"
-    names = ("n_plan", "token", "depth", "end", "parent")
-    _need(isinstance(plan, dict) and all(torch.is_tensor(plan.get(k)) for k in names), f"{what}: plan holds {names}")
-    pn, pt, pd, pe, pp = (plan[k] for k in names)
-    _dev(logits, emb, pn, pt, pd, pe, pp, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path,
-         n_path, start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, pos64, u, gen_start, n_kept)
-    B = pos.numel()
-    _need(B >= 1 and logits.dim() == 2 and logits.shape[0] % B == 0 and x_next.dim() == 2 and x_next.shape[0] % B == 0,
-          f"{what}: logits (B*R_in, V) and x_next (B*R_out, D) for the B of pos")
-    R_in, R_out = logits.shape[0] // B, x_next.shape[0] // B
-    _need(1 <= R_in <= TREE_SPEC_ROWS_MAX and 1 <= R_out <= TREE_SPEC_ROWS_MAX and B * max(R_in, R_out) <= 65535,
-          f"{what}: 1 <= rows per sequence <= {TREE_SPEC_ROWS_MAX}, B * rows <= 65535")
-    _need(pt.dim() in (1, 2) and pt.shape[-1] >= 1 and (pt.dim() == 1 or pt.shape[0] == B),
-          f"{what}: plan tables are (P,) — shared — or (B, P)")
-    P, per = int(pt.shape[-1]), pt.dim() == 2
-    tiles = (R_out + TREE_TILE - 1) // TREE_TILE
-    W = TREE_SPEC_WALK
-    # (_token_step's checks with x_next at the rows of the NEXT pass: R_out need not be R_in)
-    _need(logits.dtype == _F32, f"{what}: logits ({B * R_in}, V) fp32")
-    V = logits.shape[1]
-    _need(emb.dim() == 2 and emb.shape[0] == V and x_next.dtype == emb.dtype and x_next.shape[1] == emb.shape[1],
-          f"{what}: emb (V, D) and x_next ({B * R_out}, D) of one dtype")
-    D = emb.shape[1]
-    _need(ids.dim() == 2 and ids.shape[0] == B and ids.dtype == _I64, f"{what}: ids (B, S) int64, B = {B} rows")
-    S = ids.shape[1]
-    _table(what, _of(_I32, B if per else 1, n_plan=pn) +
-           _of(_I32, (B if per else 1) * P, plan_token=pt, plan_depth=pd, plan_end=pe, plan_parent=pp) +
-           _of(_I32, B, pos=pos, done=done, n_generated=n_generated, node=node, len=length, start=start, n_path=n_path,
-               start_old=start_old, n_committed=n_committed, n_drafted=n_drafted) +
-           _of(_I32, 1, n_active=n_active, n_on_trie=n_on_trie) + _of(_I32, 2, counter=counter) +
-           _of(_I32, B * R_out, depth=depth, end=end) + _of(_I32, B * tiles * TREE_TILE, tile_anc=tile_anc) +
-           _of(_I32, B * W, token=token, path=path) + _of(_F32, B * W, logprob=logprob))
-    _need(pos64 is None or (pos64.dtype == _I64 and pos64.numel() == B), f"{what}: pos64 ({B},) int64")
-    _need(int(max_new_tokens) == max_new_tokens and max_new_tokens >= 1, f"{what}: max_new_tokens >= 1")
-    _sample_operands(what, u, gen_start, n_kept, B * W, B, max_new_tokens, temperature, top_p, top_k, repetition_penalty)
-    rc = _lib.load(emb.dtype).fvqa_tree_spec_step_sample(
-        _ptr(logits), _ptr(u), _ptr(emb), _ptr(pn), _ptr(pt), _ptr(pd), _ptr(pe), _ptr(pp), P, P if per else 0, float(temperature),
-        float(top_p), int(top_k), float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0, int(max_new_tokens), _ptr(ids),
-        _ptr(pos), _ptr(done), _ptr(n_generated), _ptr(gen_start), _ptr(node), _ptr(length), _ptr(start), _ptr(x_next),
-        _ptr(depth), _ptr(end), _ptr(tile_anc), _ptr(path), _ptr(n_path), _ptr(start_old), _ptr(token), _ptr(n_kept),
-        _ptr(logprob), _ptr(n_committed), _ptr(n_drafted), _ptr(n_active), _ptr(n_on_trie), _ptr(counter), _ptr(pos64), B, R_in,
-        R_out, V, D, S, dt_code(emb.dtype), _stream())
-    _lib.check(rc, "fvqa_tree_spec_step_sample")
-    return token
+    return _tree_spec_step("tree_spec_step_sample", (u, gen_start, n_kept, temperature, top_p, top_k, repetition_penalty), logits,
+                           emb, plan, ids, pos, done, n_generated, node, length, start, x_next, depth, end, tile_anc, path, n_path,
+                           start_old, token, logprob, n_committed, n_drafted, n_active, n_on_trie, counter, max_new_tokens, pos64,
+                           eos_id, stop_at_eos)
 
 
 def kv_tree_commit(qkv_cache, qkv_rows, path, n_path, start_old, rope, *, n_seq: int, S: int, H: int, Dh: int, A: int,

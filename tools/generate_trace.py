@@ -14,8 +14,9 @@ evaluation call makes its video_start tensor anew, so whether a prefill finds th
 allocator put eight bytes. The tool drops the kept plans in front of every forward of a recorded call (a call may hold several:
 the twin's pass, one prompt pass per task): each prefill then builds its plan, and no address decides what the trace holds.
 
-  python tools/generate_trace.py [--out FILE] [--modes TEXT] [--rehearse]
-  (--modes: only the modes whose name holds TEXT; --rehearse: build the modes and their inputs, launch nothing)"""
+  python tools/generate_trace.py [--out FILE] [--modes TEXT] [--rehearse] [--skip NAMES]
+  (--modes: only the modes whose name holds TEXT; --rehearse: build the modes and their inputs, launch nothing; --skip: functions
+  of fvqa.ops that stay unrecorded, for comparing against a tree that does not have them)"""
 import argparse
 import hashlib
 import os
@@ -54,8 +55,8 @@ class Trace:
     """Every callable of fvqa.ops replaced by a recording wrapper while a mode runs (the library's entries are looked up on the
     module at call time), torch's dispatches counted."""
 
-    def __init__(self):
-        self.calls, self.sha, self.torch = 0, hashlib.sha256(), 0
+    def __init__(self, skip=()):
+        self.calls, self.sha, self.torch, self.skip = 0, hashlib.sha256(), 0, set(skip)
 
     def run(self, fn):
         trace = self
@@ -72,8 +73,8 @@ class Trace:
                 return real(*a, **k)
             return call
 
-        saved = {n: f for n, f in vars(ops).items()
-                 if callable(f) and getattr(f, "__module__", None) == ops.__name__ and not isinstance(f, type)}
+        saved = {n: f for n, f in vars(ops).items() if n not in self.skip
+                 and callable(f) and getattr(f, "__module__", None) == ops.__name__ and not isinstance(f, type)}
         for n, f in saved.items():
             setattr(ops, n, recorded(n, f))
         try:
@@ -197,6 +198,8 @@ def main():
     ap.add_argument("--out", default="", help="also write the lines to this file")
     ap.add_argument("--modes", default="", help="only the modes whose name holds this text")
     ap.add_argument("--rehearse", action="store_true", help="stop in front of the first device call")
+    ap.add_argument("--skip", default="", help="names of fvqa.ops, comma-separated, that are not recorded: a body one tree puts "
+                    "between an entry and its checks and the other tree does not have; what it calls is recorded as before")
     a = ap.parse_args()
     from tests import flipped_util as FU
     from tests.test_beam_gpu import ROWS, eos_batch
@@ -236,7 +239,7 @@ def main():
             forgetful(e)
         for name, fn, _ in todo:
             fn()                                            # once unrecorded: caches of the engine's own (arenas, beam cache) exist
-            tr = Trace()
+            tr = Trace(filter(None, a.skip.split(",")))
             out = tr.run(fn)
             lines.append(f"{str(dtype)[6:]:9s}| {name:46s}| ops calls {tr.calls:5d} {tr.sha.hexdigest()[:16]} | torch dispatches "
                          f"{tr.torch:5d} | result {result_hash(out)[:16]}")
