@@ -28,6 +28,12 @@ a pass of their own, up to T per step, and prints the tokens committed per step 
 sum, the video mass (fvqa.generate.generate(frame_attention=True), fvqa.attribution.summarize: mean over the answer's tokens, the
 layers and the heads); `--json FILE` writes the answers — and those numbers — as a JSON list. Not with beams, --contrast,
 --lookahead, --jump_forward or --slots.
+`--min_p P`, `--no_repeat_ngram N`, `--min_new_tokens M`: three more pick rules (fvqa.generate.generate(min_p=, no_repeat_ngram_size=,
+min_new_tokens=)) — sample only tokens at least P times as likely as the most likely one, never repeat an N-gram among the
+generated tokens, no EOS before the M-th token. Not with beams, --constrain / --answer_vocab, --contrast, --lookahead,
+--jump_forward or --slots.
+`--vote` with `--num_samples N --temperature T`: self-consistency — the N samples with equal tokens form a group; each group, its
+count and the winner are printed (fvqa.generate.generate(vote=True)).
 `--questions FILE --slots N [--admit M]`: one question per line about the given clip, one answer per line, through in-flight
 batching (fvqa.stream.generate_stream): a decode batch of N rows in which a finished answer hands its slot to the next question.
 The sampling flags and --constrain / --answer_vocab apply; beams, --contrast, --lookahead, --jump_forward and --num_samples do not.
@@ -73,6 +79,14 @@ def get_args_parser():
                    help="answers drawn per question from one prefill (needs --temperature > 0)")
     p.add_argument("--logprobs", action="store_true",
                    help="print each answer's log-probability under the model and its per-token geometric mean probability")
+    p.add_argument("--min_p", type=float, default=0.0,
+                   help="sample only tokens whose probability is at least P times the most likely token's (0: off; in [0, 1))")
+    p.add_argument("--no_repeat_ngram", type=int, default=0, metavar="N",
+                   help="no N-gram occurs twice among the generated tokens (0: off); the prompt is not scanned")
+    p.add_argument("--min_new_tokens", type=int, default=0, metavar="M", help="the EOS is banned before the M-th token (0: off)")
+    p.add_argument("--vote", action="store_true",
+                   help="with --num_samples N (2 .. 64): group the samples by their tokens and print each group, its count and "
+                        "the winner — the largest group, ties by the mean log-probability per token")
     p.add_argument("--constrain", action="store_true",
                    help="with --options: the answer is one of the options (constrained decoding); its index is printed")
     p.add_argument("--jump_forward", type=int, default=0,
@@ -200,6 +214,10 @@ def main(args):
         kw.update(jump_forward=args.jump_forward)
     if args.frame_attention:
         kw.update(frame_attention=True)
+    if args.min_p or args.no_repeat_ngram or args.min_new_tokens:
+        kw.update(min_p=args.min_p, no_repeat_ngram_size=args.no_repeat_ngram, min_new_tokens=args.min_new_tokens)
+    if args.vote:
+        return vote_report(model, batch, allowed, args, kw)
     answer = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
                             seed=args.seed, num_beams=args.num_beams, length_penalty=args.length_penalty, top_k=args.top_k,
                             repetition_penalty=args.repetition_penalty, return_logprobs=args.logprobs,
@@ -239,6 +257,32 @@ def main(args):
         with open(args.json, "w") as f:
             json.dump(records, f)
     return answer
+
+
+def vote_report(model, batch, allowed, args, kw):
+    """--vote: the samples of the one question, grouped by their tokens — each group with its count, the winner marked."""
+    best = model.generate(batch, max_new_tokens=args.max_new_tokens, temperature=args.temperature, top_p=args.top_p,
+                          seed=args.seed, top_k=args.top_k, repetition_penalty=args.repetition_penalty,
+                          num_return_sequences=args.num_samples, vote=True, **kw)[0]
+    g = model.last_generation
+    v = {k: t[0].cpu() for k, t in g["vote"].items()}
+    win = int(v["winner"])
+    print(f"[{args.num_samples} samples, {int(v['n_groups'])} groups, {g['steps']} steps, winner's share {float(v['share']):.2f}]")
+    records = []
+    for k, a in enumerate(g["answers"][0]):       # a group is printed at its first sample
+        if int(v["votes"][k]) == 0:
+            continue
+        line = f"{int(v['votes'][k])}\t" + (a if isinstance(a, str) else " ".join(str(t) for t in a))
+        if allowed is not None:
+            c = int(g["choice"][0, k])
+            line += f"\t[choice {c}: {allowed[c]}]" if c >= 0 else "\t[choice -1]"
+        print(line + ("\t<- winner" if k == win else ""))
+        records.append({"answer": a, "votes": int(v["votes"][k]), "winner": k == win})
+    if args.json:
+        import json
+        with open(args.json, "w") as f:
+            json.dump(records, f)
+    return best
 
 
 if __name__ == "__main__":

@@ -19,6 +19,10 @@
 //   bitmap   R, the ids generated so far: built from ids[gen_start .. pos] (sample_bitmap_build); a step that commits several
 //            tokens adds one bit after every commit (sample_bitmap_add), so that row i + 1 sees the tokens rows 0 .. i committed.
 //            Only under a penalty (rep != 1): without one no bitmap exists and none is read.
+//   ban set  X (fvqa_decode_next_rules, rule 0): a second bitmap of V bits behind R's (sample_ban_at), built from the same ids once
+//            per step (sample_ban_build). The pick does not know it: the caller's view answers ok(i) = false for a banned token,
+//            so it takes part nowhere — exactly as an edge outside [0, V) or a token outside the plausible set takes none.
+//   min-p    MINP = true: rule 3' — one counting pass behind the nucleus cut; false (every other caller): none of its code exists.
 #pragma once
 #include "token_step.h"
 
@@ -67,6 +71,32 @@ __device__ __forceinline__ void sample_bitmap_add(unsigned* bm, int t) {
   if (threadIdx.x == 0) bm[t >> 5] |= 1u << (t & 31);
   __syncthreads();
 }
+// the ban set's place in the dynamic block: behind the bitmap of R when there is one (pen), else in its place
+__device__ __forceinline__ unsigned* sample_ban_at(unsigned* bm, int V, bool pen) { return bm + (pen ? ((V + 31) >> 5) : 0); }
+// X of a row (fvqa_decode_next_rules, rule 0), from the generated ids at positions g0c = max(g0, 0) .. p (p <= S - 2: the row is
+// live; every index read lies in [g0c, p]): the EOS while the token index p + 1 - g0 is below min_new; with ngram = n >= 1 the
+// token behind every earlier occurrence, inside the generated ids, of the last n - 1 of them. Ids outside [0, V) are ignored.
+__device__ __forceinline__ void sample_ban_build(unsigned* ban, const int64_t* row_ids, int g0, int p, int V, int ngram,
+                                                 int min_new, int eos_id) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < ((V + 31) >> 5); i += NT) ban[i] = 0u;
+  __syncthreads();
+  if (tid == 0 && (long long)p + 1 - (long long)g0 < (long long)min_new && eos_id >= 0 && eos_id < V)
+    atomicOr(&ban[eos_id >> 5], 1u << (eos_id & 31));
+  const long long g0c = g0 < 0 ? 0 : g0;
+  const long long n1 = (long long)ngram - 1;                       // the suffix s = ids[p - n1 + 1 .. p]
+  if (ngram >= 1 && (long long)p - n1 + 1 >= g0c) {
+    const int64_t* s = row_ids + ((long long)p - n1 + 1);
+    for (long long j = g0c + tid; j + n1 <= (long long)p; j += NT) {
+      bool eq = true;
+      for (long long k = 0; k < n1 && eq; ++k) eq = row_ids[j + k] == s[k];
+      const int64_t t = row_ids[j + n1];
+      if (eq && t >= 0 && t < V) atomicOr(&ban[t >> 5], 1u << (t & 31));
+    }
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ bool sample_banned(const unsigned* ban, int t) { return (ban[t >> 5] >> (t & 31)) & 1u; }
 // the penalty's read of the logit v of token t: l / r or l * r where the bit is set. The logits are not written.
 __device__ __forceinline__ float sample_penalised(float v, int t, const unsigned* bm, float rep) {
   if ((bm[t >> 5] >> (t & 31)) & 1u) v = v > 0.f ? v / rep : v * rep;
@@ -146,9 +176,10 @@ __device__ __forceinline__ int row_pick_greedy(const E& el, L l1, float* redf, i
 
 // The sampled pick -> the element; kept = n_kept. TOPK = false: an entry without top-k (fvqa_decode_next), whose instantiation
 // holds none of its code. use_lds: the row of e_i lives in s.erow (N <= the floats sized for it), else every pass recomputes it.
-template <bool TOPK, typename E, typename L>
+// MINP = true (fvqa_decode_next_rules): rule 3' with min_p in [0, 1) — false everywhere else, and none of its code exists.
+template <bool TOPK, bool MINP = false, typename E, typename L>
 __device__ __forceinline__ int row_pick_sampled(const E& el, L l1, bool use_lds, const SampleLds& s, float u, float temperature,
-                                                float top_p, int top_k, int& kept) {
+                                                float top_p, int top_k, int& kept, float min_p = 0.f) {
   const int tid = threadIdx.x;
   const int N = el.N;
   float* erow = s.erow;
@@ -238,6 +269,21 @@ __device__ __forceinline__ int row_pick_sampled(const E& el, L l1, bool use_lds,
     n_tie = tie_k;
     kept = top_k;
   }
+  // ---- min-p: the elements with e >= min_p are a prefix of the same order made of whole tie groups (the maximum has e == 1 >
+  // min_p: never empty); where it is the shortest of the prefixes it is the kept set — every e at or above bits(min_p)
+  if constexpr (MINP) {
+    if (min_p > 0.f) {
+      const unsigned mpb = __float_as_uint(min_p);                 // (non-negative floats order as their bits do)
+      int c = 0;
+      for (int i = tid; i < N; i += NT) c += (el.ok(i) && __float_as_uint(pe(i)) >= mpb) ? 1 : 0;
+      c = block_sum_int(c, redi);
+      if (c < kept) {
+        tb = mpb;
+        n_tie = 0x7fffffff;
+        kept = c;
+      }
+    }
+  }
   // ---- the walk, in index order over contiguous ranges
   const int chunk = (N + NT - 1) / NT;
   const int i0 = min(N, tid * chunk), i1 = min(N, i0 + chunk);
@@ -283,28 +329,30 @@ __device__ __forceinline__ int row_sample(const float* lg, int V, float u, const
 }
 
 // ---- host side
-// the dynamic LDS of a launch that picks (keep_row: may the row of e_i live there — a greedy launch keeps none) -> bytes, with
-// *row_in_lds; 0 and *ok = 0 when the bitmap of a penalty does not fit (a vocabulary beyond 1.2 million ids)
-inline size_t fvqa_sample_lds(int V, float rep, bool keep_row, int* row_in_lds, int* ok) {
+// the dynamic LDS of a launch that picks (keep_row: may the row of e_i live there — a greedy launch keeps none; ban: a ban set
+// follows, fvqa_decode_next_rules) -> bytes, with *row_in_lds; 0 and *ok = 0 when the bitmaps do not fit: one bitmap (a penalty,
+// or a ban set without one) beyond 1216512 ids, the two together beyond 626688
+inline size_t fvqa_sample_lds(int V, float rep, bool keep_row, int* row_in_lds, int* ok, bool ban = false) {
   const size_t row_bytes = (size_t)V * sizeof(float);
   const int in_lds = keep_row && row_bytes <= ROW_LDS_MAX;
   size_t lds = in_lds ? row_bytes : 0;
   *ok = 1;
-  if (rep != 1.f) {                                                // the bitmap: V bits behind the row (on a 16-byte boundary)
-    const size_t bitmap = (((size_t)V + 31) / 32) * 4;
+  const size_t n_bitmaps = (rep != 1.f ? 1 : 0) + (ban ? 1 : 0);
+  if (n_bitmaps) {                                                 // the bitmaps: V bits each behind the row (on a 16-byte boundary)
+    const size_t bitmap = (((size_t)V + 31) / 32) * 4 * n_bitmaps;
     lds = in_lds ? (((size_t)V + 3) & ~(size_t)3) * sizeof(float) + bitmap : bitmap;
-    if (lds > ROW_LDS_MAX + BITMAP_LDS_MAX) *ok = 0;
+    if (lds > ROW_LDS_MAX + n_bitmaps * BITMAP_LDS_MAX) *ok = 0;
   }
   *row_in_lds = in_lds;
   return lds;
 }
-// the dynamic-LDS limit of kernel K, once per device: the largest row, and (bitmap) the largest bitmap behind it
+// the dynamic-LDS limit of kernel K, once per device: the largest row, and the largest bitmaps behind it (0, 1 or 2 of them)
 template <auto K>
-inline void fvqa_sample_lds_limit(bool bitmap) {
+inline void fvqa_sample_lds_limit(int n_bitmaps) {
   static std::atomic<unsigned long long> attr_done{0};             // one bit per device (fvqa_attr_needed)
   if (fvqa_attr_needed(attr_done))
     (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(ROW_LDS_MAX + (bitmap ? BITMAP_LDS_MAX : 0)));
+                              (int)(ROW_LDS_MAX + (size_t)n_bitmaps * BITMAP_LDS_MAX));
 }
 // The operands and parameters a sampled draft-and-verify entry adds, in the two places of its checks (the order of an entry's
 // outcomes is part of the ABI): among the FVQA_EINVAL checks ...

@@ -70,6 +70,16 @@
 // [0, min(budget[r], width)), is not live: it becomes done and nothing of any request's results is written. A live slot picks by
 // the _ex / _trie rule with the draw at u[i * n_req + r] — the request's own, wherever and whenever it sits —, is stepped as
 // before, leaves its token, log-probability and count in the request's result rows, and is also done once i + 1 == budget[r].
+//
+// fvqa_decode_next_rules is the template with RULES = true (false in the five entries above, in which none of the following
+// exists), on the vocabulary alone (TRIE = PAIR = STREAM = false): three more pick rules, include/fvqa.h states them.
+//   ban set  X, a second bitmap of V bits behind R's, built once per step from the row's generated ids: the EOS while the token
+//            index is below min_new_tokens; with no_repeat_ngram = n the token behind every earlier occurrence, inside the
+//            generated ids, of the last n - 1 of them. The view answers ok(i) = false for a banned token — the place where PAIR
+//            narrows to the plausible set —, so it enters no maximum, sum, count, tie group or walk, n_ok (what top-k is cut
+//            against) counts the others, and a row with none left ends as a trie row at a node without edges does.
+//   min-p    e_i >= min_p, with e = 1 at the non-banned maximum: a third prefix of the one order, whole tie groups; the kept set
+//            is the shortest of the three. One counting pass behind the nucleus cut (csrc/row_sample.h, MINP).
 #include "row_sample.h"
 #include "token_step.h"
 
@@ -103,7 +113,13 @@ struct StreamArgs {
   int32_t* out_n_generated;
 };
 
-template <typename T, bool EX, bool TRIE, bool PAIR, bool STREAM>
+// the operands fvqa_decode_next_rules adds (RULES = true)
+struct RulesArgs {
+  float min_p;
+  int no_repeat_ngram, min_new_tokens;
+};
+
+template <typename T, bool EX, bool TRIE, bool PAIR, bool STREAM, bool RULES>
 __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ logits, const float* __restrict__ u_p,
                                                     const T* __restrict__ emb, float temperature, float top_p, int eos_id,
                                                     int stop_at_eos, int64_t* __restrict__ ids, int32_t* __restrict__ pos,
@@ -113,12 +129,13 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
                                                     int D, int S, int row_in_lds, int vec16, int top_k, float rep,
                                                     const int32_t* __restrict__ gen_start,
                                                     float* __restrict__ logprob_out, unsigned* __restrict__ counter,
-                                                    TrieArgs ta, PairArgs pr, StreamArgs sa) {
+                                                    TrieArgs ta, PairArgs pr, StreamArgs sa, RulesArgs ru) {
   const Trie& tr = ta.trie;
   static_assert(EX || !TRIE, "the trie entry extends the EX entry");
   static_assert(EX || !PAIR, "the pair entry extends the EX entry");
   static_assert((EX && !PAIR) || !STREAM, "the stream entry extends the EX entry, one row per slot");
-  extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX)
+  static_assert((EX && !TRIE && !PAIR && !STREAM) || !RULES, "the rules entry extends the EX entry on the vocabulary");
+  extern __shared__ __attribute__((aligned(16))) float erow[];     // the row's e_i (row_in_lds), then the bitmap (EX), then X (RULES)
   __shared__ float redf[4], wtotf[4];
   __shared__ int redi[4], wtoti[4];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -167,8 +184,24 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
       if (n_ok == 0) live = false;                                 // (a row of NaNs: the pair ends, as at a node without edges)
     }
   }
-  auto in_p = [&](int i) -> bool {                                 // (always, without PAIR)
+  // ---- RULES: the ban set X, from the row's generated ids; what is not banned is what takes part (element i = token i)
+  const unsigned* ban = nullptr;
+  if constexpr (RULES) {
+    if (live) {
+      unsigned* bw = sample_ban_at(sample_bitmap_at(erow, V, row_in_lds), V, rep != 1.f);
+      sample_ban_build(bw, row_ids, gen_start[b], p, V, ru.no_repeat_ngram, ru.min_new_tokens, eos_id);   // (p <= S - 2)
+      ban = bw;
+      int c = 0, f = 0x7fffffff;
+      for (int i = tid; i < V; i += NT)
+        if (!sample_banned(bw, i)) { c += 1; f = min(f, i); }
+      n_ok = block_sum_int(c, redi);
+      first_ok = block_min_int(f, redi);
+      if (n_ok == 0) live = false;                                 // (every token banned: the row ends, as at a node without edges)
+    }
+  }
+  auto in_p = [&](int i) -> bool {                                 // (always, without PAIR and RULES)
     if constexpr (PAIR) return lg[el0.tok(i)] - mxa >= lbeta;
+    if constexpr (RULES) return !sample_banned(ban, i);
     return true;
   };
   const ElemsKept<RowElems<TRIE>, decltype(in_p)> el{el0, in_p, el0.N, n_ok, first_ok};   // what takes part in the pick
@@ -201,7 +234,7 @@ __global__ __launch_bounds__(NT) void decode_next_k(const float* __restrict__ lo
     kept = 1;
   } else if (live) {
     const float u = STREAM ? u_p[(size_t)ti * sa.n_req + r] : u_p[b];
-    sel = row_pick_sampled<EX>(el, l1, use_lds, sl, u, temperature, top_p, top_k, kept);
+    sel = row_pick_sampled<EX, RULES>(el, l1, use_lds, sl, u, temperature, top_p, top_k, kept, RULES ? ru.min_p : 0.f);
   }
   int child = -1;
   if (live) {
@@ -271,32 +304,33 @@ struct ExArgs {
   unsigned* counter;
 };
 
-template <typename T, bool EX, bool TRIE, bool PAIR = false, bool STREAM = false>
+template <typename T, bool EX, bool TRIE, bool PAIR = false, bool STREAM = false, bool RULES = false>
 int launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id, int stop_at_eos,
            int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept, int32_t* n_active,
            int64_t* pos64, int B, int V, int D, int S, ExArgs ex, TrieArgs tr, hipStream_t st,
            PairArgs pr = PairArgs{0.f, 0.f, nullptr},
-           StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
+           StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}, RulesArgs ru = RulesArgs{0.f, 0, 0}) {
   int in_lds, fits;                                                // (without EX rep is 1: no bitmap)
-  const size_t lds = fvqa_sample_lds(V, ex.rep, temperature > 0.f, &in_lds, &fits);
+  const size_t lds = fvqa_sample_lds(V, ex.rep, temperature > 0.f, &in_lds, &fits, RULES);
   if (!fits) return FVQA_ESHAPE;                                   // (a vocabulary beyond 1.2 million ids under a penalty)
-  fvqa_sample_lds_limit<decode_next_k<T, EX, TRIE, PAIR, STREAM>>(EX);
+  fvqa_sample_lds_limit<decode_next_k<T, EX, TRIE, PAIR, STREAM, RULES>>((EX ? 1 : 0) + (RULES ? 1 : 0));
   const int vec16 = fvqa_vec16((size_t)D * sizeof(T), emb, x_next);   // (PAIR: the twin half follows B * D elements on, whole rows)
-  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR, STREAM>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature,
+  hipLaunchKernelGGL((decode_next_k<T, EX, TRIE, PAIR, STREAM, RULES>), dim3(B), dim3(NT), lds, st, logits, u, (const T*)emb, temperature,
                      top_p, eos_id, stop_at_eos, ids, pos, done, (T*)x_next, token, n_kept, n_active, pos64, B, V, D, S, in_lds,
-                     vec16, ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr, sa);
+                     vec16, ex.top_k, ex.rep, ex.gen_start, ex.logprob, ex.counter, tr, pr, sa, ru);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }
 
 // the operand checks the entries share; then the launch
-template <bool EX, bool TRIE = false, bool PAIR = false, bool STREAM = false>
+template <bool EX, bool TRIE = false, bool PAIR = false, bool STREAM = false, bool RULES = false>
 int checked_launch(const float* logits, const float* u, const void* emb, float temperature, float top_p, int eos_id,
                    int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done, void* x_next, int32_t* token, int32_t* n_kept,
                    int32_t* n_active, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len, int dtype, ExArgs ex,
                    void* stream, TrieArgs tr = TrieArgs{},
                    PairArgs pr = PairArgs{0.f, 0.f, nullptr},
-                   StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr}) {
+                   StreamArgs sa = StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr},
+                   RulesArgs ru = RulesArgs{0.f, 0, 0}) {
   if (!logits || !emb || !ids || !pos || !done || !x_next || !token || !n_kept || !n_active) return FVQA_EINVAL;
   if (EX && (!ex.gen_start || !ex.logprob || !ex.counter)) return FVQA_EINVAL;
   if (TRIE && fvqa_trie_given(tr.node, tr.trie.node_first, tr.trie.edge_token, tr.trie.edge_child) != 1) return FVQA_EINVAL;
@@ -305,6 +339,8 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
   if (!(top_p > 0.f && top_p <= 1.f)) return FVQA_EINVAL;
   if (EX && (!(ex.rep >= 1.f) || ex.top_k < 0)) return FVQA_EINVAL;
   if (PAIR && (!pr.n_plausible || !(pr.alpha >= 0.f) || !(pr.beta >= 0.f && pr.beta <= 1.f))) return FVQA_EINVAL;
+  if (RULES && (!(ru.min_p >= 0.f && ru.min_p < 1.f) || ru.no_repeat_ngram < 0 || ru.min_new_tokens < 0)) return FVQA_EINVAL;
+  if (RULES && ru.min_new_tokens > 0 && !stop_at_eos) return FVQA_EINVAL;   // (the EOS ends nothing: no length to hold back)
   if (temperature > 0.f && !u) return FVQA_EINVAL;
   if (STREAM && (!sa.req || !sa.budget || !sa.out_tokens || !sa.out_n_generated)) return FVQA_EINVAL;
   if (STREAM && (sa.n_req <= 0 || sa.width <= 0)) return FVQA_ESHAPE;
@@ -319,11 +355,12 @@ int checked_launch(const float* logits, const float* u, const void* emb, float t
     return FVQA_EALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FVQA_H16)
-    return launch<bf16_t, EX, TRIE, PAIR, STREAM>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
-                                                  x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr,
-                                                  st, pr, sa);
-  return launch<float, EX, TRIE, PAIR, STREAM>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next,
-                                               token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr, st, pr, sa);
+    return launch<bf16_t, EX, TRIE, PAIR, STREAM, RULES>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
+                                                         x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex,
+                                                         tr, st, pr, sa, ru);
+  return launch<float, EX, TRIE, PAIR, STREAM, RULES>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done,
+                                                      x_next, token, n_kept, n_active, pos64, n_seq, vocab, dim, seq_len, ex, tr,
+                                                      st, pr, sa, ru);
 }
 
 }  // namespace
@@ -345,6 +382,19 @@ extern "C" int fvqa_decode_next_ex(const float* logits, const float* u, const vo
   return checked_launch<true>(logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept,
                               n_active, pos64, n_seq, vocab, dim, seq_len, dtype,
                               ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream);
+}
+
+extern "C" int fvqa_decode_next_rules(const float* logits, const float* u, const void* emb, float temperature, float top_p,
+                                      int top_k, float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids,
+                                      int32_t* pos, int32_t* done, const int32_t* gen_start, void* x_next, int32_t* token,
+                                      int32_t* n_kept, float* logprob, int32_t* n_active, uint32_t* counter, int64_t* pos64,
+                                      int n_seq, int vocab, int dim, int seq_len, int dtype, void* stream, float min_p,
+                                      int no_repeat_ngram, int min_new_tokens) {
+  return checked_launch<true, false, false, false, true>(
+      logits, u, emb, temperature, top_p, eos_id, stop_at_eos, ids, pos, done, x_next, token, n_kept, n_active, pos64, n_seq,
+      vocab, dim, seq_len, dtype, ExArgs{top_k, repetition_penalty, gen_start, logprob, counter}, stream, TrieArgs{},
+      PairArgs{0.f, 0.f, nullptr}, StreamArgs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr},
+      RulesArgs{min_p, no_repeat_ngram, min_new_tokens});
 }
 
 extern "C" int fvqa_decode_next_trie(const float* logits, const float* u, const void* emb, float temperature, float top_p,

@@ -186,7 +186,9 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
     gold answer's -log posterior, over the samples whose gold answer is in the vocabulary — and `gold_in_vocab` come from the
     batch's one host read. Nothing is decoded.
     `--gen_frame_attention` (generation task, through `generate`): a `video_mass` meter — the weight the answer rows' text softmax
-    puts on the frame keys (fvqa/attribution.py) — and `frame_share` in every entry of the extracted-answers file."""
+    puts on the frame keys (fvqa/attribution.py) — and `frame_share` in every entry of the extracted-answers file.
+    `--gen_vote N` (generation task): every row decodes N samples and the vote's winner is the answer (llama/model.py); a
+    `vote_share` meter — the winner's share of the samples, mean over the batch — is read with the hits in the batch's one host read."""
     gen = bool(getattr(args, "is_generation_task", False))
     owner = None
     if not gen:
@@ -274,7 +276,16 @@ def val_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: torc
             hit = answer.to(best.device) == best
         misc.log_qtype(data, hit, log, args)
         log.update(lr=optimizer.param_groups[0]["lr"])
-        log.update(n=bsz, acc=hit.sum().item() / bsz)
+        share = None
+        if int(getattr(args, "gen_vote", 0) or 0) > 1:      # --gen_vote N: the winner's share rides behind the hits
+            last = next((m.last_generation for m in (model, getattr(model, "module", None))
+                         if isinstance(getattr(m, "last_generation", None), dict)), {})
+            share = last.get("vote_share")
+        if share is not None:
+            packed = torch.stack([hit.sum().to(torch.float64), share.to(hit.device).to(torch.float64).mean()]).cpu()
+            log.update(n=bsz, acc=float(packed[0]) / bsz, vote_share=float(packed[1]))
+        else:
+            log.update(n=bsz, acc=hit.sum().item() / bsz)
         if getattr(args, "debug", False):
             break
     log.synchronize_between_processes()

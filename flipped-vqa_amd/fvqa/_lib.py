@@ -58,6 +58,8 @@ SIGNATURES = {
     "fvqa_trie_score": (_i, [_p] * 2 + [_i] * 2 + [_p] * 14 + [_i] * 9 + [_p]),
     "fvqa_decode_next": (_i, [_p, _p, _p, _f, _f, _i, _i] + [_p] * 8 + [_i] * 5 + [_p]),
     "fvqa_decode_next_ex": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p]),
+    "fvqa_decode_next_rules": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 11 + [_i] * 5 + [_p] + [_f, _i, _i]),
+    "fvqa_sample_vote": (_i, [_p] * 7 + [_i] * 3 + [_p]),
     "fvqa_decode_next_trie": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 7 + [_p]),
     "fvqa_decode_next_pair": (_i, [_p, _p, _p, _f, _f, _i, _f, _f, _f, _i, _i] + [_p] * 16 + [_i] * 7 + [_p]),
     "fvqa_decode_next_stream": (_i, [_p, _p, _p, _f, _f, _i, _f, _i, _i] + [_p] * 15 + [_i] * 2 + [_p] * 2 + [_i] * 2 + [_p] * 3

@@ -204,7 +204,8 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
              repetition_penalty: float = 1.0, return_logprobs: bool = False, num_return_sequences: int = 1,
              constraints=None, contrast=None, contrast_alpha: float = 1.0, contrast_beta: float = 0.1,
              lookahead: int = 0, lookup_ngram: int = 2, draft_tokens=None, jump_forward: int = 0,
-             frame_attention: bool = False, draft_answers=None) -> dict:
+             frame_attention: bool = False, draft_answers=None, min_p: float = 0.0, no_repeat_ngram_size: int = 0,
+             min_new_tokens: int = 0, vote: bool = False) -> dict:
     """A prompt in, tokens out: greedy (temperature == 0) or temperature / nucleus sampling with the reference's rule
     (llama/generation.py:17-68), each row ended by its EOS. `data` is a validation batch or one of `prompt_batch`. The prefill
     and the per-layer kernel sequence are those of `greedy_decode`; the token step — pick, write, advance, raise `done`, gather
@@ -319,7 +320,44 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
       call without the keyword). Zero where "tokens" is -1. attribution.summarize reduces it to a frame profile per answer.
       Served with greedy and sampled decoding, top_k, repetition_penalty, return_logprobs, num_return_sequences and constraints.
       ValueError: num_beams > 1, contrast, lookahead >= 2, jump_forward >= 2. Not built: the summary for option scoring (the
-      suffix kernel's online softmax keeps no probabilities), under beams, twins, several rows per pass and the stream."""
+      suffix kernel's online softmax keeps no probabilities), under beams, twins, several rows per pass and the stream.
+    min_p, no_repeat_ngram_size, min_new_tokens (0, 0, 0: every code path above runs untouched): three more pick rules; any of
+      them off its default sends the plain token loop's step through ops.decode_next_rules, still one launch per token
+      (include/fvqa.h fvqa_decode_next_rules states the rule).
+      min_p in [0, 1): a token is sampled only if its probability is at least min_p times the most likely token's — on top of
+        top_k and top_p: the kept set is the shortest of the three cuts, which is what Hugging Face's warpers give in sequence
+        (the ratio to the maximum survives every renormalisation, and every cut keeps the maximum). Ignored at temperature == 0.
+      no_repeat_ngram_size n >= 1: no n-gram occurs twice among the GENERATED tokens of a row — the tokens that would complete a
+        repeat are banned before the pick. The prompt is not scanned, for the reason given for repetition_penalty: it lists the
+        answer options and the answer is meant to copy one (Hugging Face's processor scans the prompt too).
+      min_new_tokens m >= 1: the EOS is banned while a row has generated fewer than m tokens (needs stop_at_eos).
+      A banned token takes no part in the pick at all — greedy returns the best of the others, a sampled row renormalises over
+      them, top_k counts them —; "logprobs" stay the raw row's. A row whose every token is banned ends (token -1).
+      Served with top_k, top_p, repetition_penalty, return_logprobs, num_return_sequences and frame_attention.
+      ValueError: min_p outside [0, 1), a negative n or m, m > max_new_tokens, m > 0 with stop_at_eos=False, num_beams > 1,
+      constraints, contrast, lookahead >= 2, draft_tokens, draft_answers, jump_forward >= 2. Not built: the rules under a trie,
+      a twin, a draft pass or the stream; typical, eta and epsilon sampling.
+    vote (False: every code path above runs untouched; needs 2 <= num_return_sequences <= ops.VOTE_SAMPLES_MAX): self-consistency
+      — the samples of a prompt whose token rows are equal form a group and the largest group wins; ties go to the group whose
+      first sample has the larger mean raw log-probability per generated token, then to the lower index (include/fvqa.h
+      fvqa_sample_vote; one launch behind the token loop, ops.sample_vote). Served wherever num_return_sequences is — constraints
+      (a group is then a `choice`) and contrast included —: it only reads the token rows. The log-probabilities are collected
+      whether or not return_logprobs asks for them. The results gain "vote": {"winner" (B,), "group" (B, n), "votes" (B, n),
+      "n_groups" (B,) int32, "share" (B,) fp32 = votes[winner] / n}. Not built: probability-weighted votes, votes over
+      normalised answer strings."""
+    rules = _pick_rules(min_p, no_repeat_ngram_size, min_new_tokens, max_new_tokens, stop_at_eos)
+    if rules is not None:
+        if num_beams != 1:
+            raise ValueError("generate: min_p, no_repeat_ngram_size and min_new_tokens are not built for num_beams > 1")
+        if constraints is not None or contrast is not None:
+            raise ValueError("generate: min_p, no_repeat_ngram_size and min_new_tokens are not built for constraints or contrast")
+        if lookahead >= 2 or draft_tokens is not None or draft_answers is not None:
+            raise ValueError("generate: min_p, no_repeat_ngram_size and min_new_tokens are not built for lookahead or drafts")
+        if jump_forward >= 2:
+            raise ValueError("generate: min_p, no_repeat_ngram_size and min_new_tokens are not built for jump_forward")
+    if vote:
+        if int(num_return_sequences) != num_return_sequences or not 2 <= num_return_sequences <= ops.VOTE_SAMPLES_MAX:
+            raise ValueError(f"generate: vote counts samples: 2 <= num_return_sequences <= {ops.VOTE_SAMPLES_MAX}")
     if frame_attention:
         if num_beams != 1:
             raise ValueError("generate: frame_attention is not built for num_beams > 1")
@@ -390,7 +428,7 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     n = int(num_return_sequences)
     if n > 1 and (num_beams > 1 or not temperature > 0):
         raise ValueError("generate: num_return_sequences > 1 draws samples: temperature > 0 and num_beams == 1")
-    ex = top_k != 0 or repetition_penalty != 1 or bool(return_logprobs) or n > 1
+    ex = top_k != 0 or repetition_penalty != 1 or bool(return_logprobs) or n > 1 or rules is not None
     if num_beams > 1 and ex:
         raise ValueError("generate: top_k, repetition_penalty, return_logprobs and num_return_sequences belong to "
                          "num_beams == 1 (beam search reports \"score\")")
@@ -464,6 +502,9 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
         elif trie is not None:
             ops.decode_next_trie(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t], act, counter,
                                  node, dtrie, u=ut, **kw_ex)
+        elif rules is not None:
+            ops.decode_next_rules(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t], act, counter,
+                                  u=ut, **kw_ex, **rules)
         elif ex:
             ops.decode_next_ex(lg, pk.emb, ids, pos, done, gen_start, xin, tokens[t], n_kept[t], logprobs[t], act, counter,
                                u=ut, **kw_ex)
@@ -488,6 +529,10 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if return_logprobs:
         out["logprobs"] = logprobs[:steps].t().contiguous()
         out["sum_logprob"] = out["logprobs"].sum(1)
+    if vote:                                                # (n >= 2: logprobs exist) the mean raw log-probability per token
+        tk = out["tokens"]
+        score = logprobs[:steps].t().contiguous().sum(1) / (tk != -1).sum(1).clamp(min=1).to(torch.float32)
+        out["vote"] = ops.sample_vote(tk.view(B0, n, steps), score.view(B0, n))
     if n > 1:
         for k in ("ids", "n_generated", "tokens", "logprobs", "sum_logprob", "n_plausible", "frame_attention"):
             if k in out:
@@ -495,6 +540,24 @@ def generate(eng, data: dict, *, max_new_tokens: int = N_NEW, temperature: float
     if trie is not None:
         out["choice"] = torch.as_tensor(constrain.choice_of(trie, out["tokens"]), device=dev)
     return out
+
+
+def _pick_rules(min_p, no_repeat_ngram_size, min_new_tokens, max_new_tokens, stop_at_eos):
+    """The keywords of the three pick rules -> None at their defaults (the entries launched as ever), else the keywords of
+    ops.decode_next_rules. Needs no device."""
+    if not 0 <= min_p < 1:                                  # (a NaN fails the comparison)
+        raise ValueError("generate: 0 <= min_p < 1 (0: off)")
+    if int(no_repeat_ngram_size) != no_repeat_ngram_size or no_repeat_ngram_size < 0:
+        raise ValueError("generate: no_repeat_ngram_size >= 0 (0: off)")
+    if int(min_new_tokens) != min_new_tokens or min_new_tokens < 0:
+        raise ValueError("generate: min_new_tokens >= 0 (0: off)")
+    if min_new_tokens > max_new_tokens:
+        raise ValueError("generate: min_new_tokens <= max_new_tokens")
+    if min_new_tokens > 0 and not stop_at_eos:
+        raise ValueError("generate: min_new_tokens holds the EOS back: it needs stop_at_eos")
+    if min_p == 0 and no_repeat_ngram_size == 0 and min_new_tokens == 0:
+        return None
+    return dict(min_p=float(min_p), no_repeat_ngram=int(no_repeat_ngram_size), min_new_tokens=int(min_new_tokens))
 
 
 def _draws(dev, seed, max_new_tokens: int, rows: int) -> torch.Tensor:

@@ -913,6 +913,54 @@ def decode_next_ex(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept
     return token
 
 
+def decode_next_rules(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, *, u=None,
+                      pos64=None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0,
+                      eos_id: int = 2, stop_at_eos: bool = True, min_p: float = 0.0, no_repeat_ngram: int = 0,
+                      min_new_tokens: int = 0):
+    """decode_next_ex with three more pick rules (include/fvqa.h fvqa_decode_next_rules states them): min_p in [0, 1) — a token
+    is also kept only if its probability is at least min_p times the largest —, no_repeat_ngram n >= 0 — the tokens that would
+    repeat an n-gram of the generated ids are banned —, min_new_tokens m >= 0 — the EOS is banned while fewer than m tokens are
+    generated (needs stop_at_eos). A banned token takes no part in the pick. All three at 0: decode_next_ex's results."""
+    _dev(logits, emb, ids, pos, done, gen_start, x_next, token, n_kept, logprob, n_active, counter, u, pos64)
+    B = _lead(logits)
+    V, D, S = _token_step("decode_next_rules", logits, B, emb, x_next, ids, B,
+                          _ex_table(B, pos, done, gen_start, token, n_kept, logprob, n_active, counter), pos64=pos64, n_pos64=B,
+                          temperature=temperature, u=u, u_shape=(B,), top_k=top_k, repetition_penalty=repetition_penalty)
+    _need(0 <= min_p < 1, "decode_next_rules: 0 <= min_p < 1")
+    _need(int(no_repeat_ngram) == no_repeat_ngram and no_repeat_ngram >= 0, "decode_next_rules: no_repeat_ngram >= 0")
+    _need(int(min_new_tokens) == min_new_tokens and min_new_tokens >= 0, "decode_next_rules: min_new_tokens >= 0")
+    _need(min_new_tokens == 0 or stop_at_eos, "decode_next_rules: min_new_tokens holds the EOS back: it needs stop_at_eos")
+    rc = _lib.load(emb.dtype).fvqa_decode_next_rules(_ptr(logits), _ptr(u), _ptr(emb), float(temperature), float(top_p),
+                                                     int(top_k), float(repetition_penalty), int(eos_id), 1 if stop_at_eos else 0,
+                                                     _ptr(ids), _ptr(pos), _ptr(done), _ptr(gen_start), _ptr(x_next), _ptr(token),
+                                                     _ptr(n_kept), _ptr(logprob), _ptr(n_active), _ptr(counter), _ptr(pos64), B, V,
+                                                     D, S, dt_code(emb.dtype), _stream(), float(min_p), int(no_repeat_ngram),
+                                                     int(min_new_tokens))
+    _lib.check(rc, "fvqa_decode_next_rules")
+    return token
+
+
+VOTE_SAMPLES_MAX = 64    # the most samples per prompt fvqa_sample_vote takes (csrc/vote.hip)
+
+
+def sample_vote(tokens, score):
+    """A vote over the samples of each prompt (include/fvqa.h fvqa_sample_vote): tokens (B, n, steps) int32, -1 padded, score
+    (B, n) fp32 -> {"group", "votes" (B, n) int32, "winner", "n_groups" (B,) int32, "share" (B,) fp32}. Samples with equal token
+    rows form a group; the largest group wins, ties by the larger score of its first sample, then by the lower index."""
+    _dev(tokens, score)
+    _need(tokens.dim() == 3 and tokens.dtype == _I32 and tokens.is_contiguous(), "sample_vote: tokens (B, n, steps) int32")
+    B, n, steps = tokens.shape
+    _need(B >= 1 and 1 <= n <= VOTE_SAMPLES_MAX and steps >= 1, f"sample_vote: 1 <= n <= {VOTE_SAMPLES_MAX}, steps >= 1")
+    _need(tuple(score.shape) == (B, n) and score.dtype == _F32 and score.is_contiguous(), "sample_vote: score (B, n) fp32")
+    i32 = dict(dtype=_I32, device=tokens.device)
+    out = {"group": torch.empty(B, n, **i32), "votes": torch.empty(B, n, **i32), "winner": torch.empty(B, **i32),
+           "n_groups": torch.empty(B, **i32), "share": torch.empty(B, dtype=_F32, device=tokens.device)}
+    rc = _lib.load().fvqa_sample_vote(_ptr(tokens), _ptr(score), _ptr(out["group"]), _ptr(out["votes"]), _ptr(out["winner"]),
+                                      _ptr(out["n_groups"]), _ptr(out["share"]), B, n, steps, _stream())
+    _lib.check(rc, "fvqa_sample_vote")
+    return out
+
+
 LOOKUP_NGRAM_MAX = 4     # the longest n-gram fvqa_spec_step's prompt lookup matches (csrc/spec.hip GMAX)
 
 

@@ -127,6 +127,28 @@ def _frame_attention_kw(args) -> dict:
     return {"frame_attention": True} if getattr(args, "gen_frame_attention", False) else {}
 
 
+def _pick_rules_kw(args) -> dict:
+    """--gen_no_repeat_ngram / --gen_min_new_tokens as generate's keywords ({} without them: the call made before they existed)."""
+    n, m = int(getattr(args, "gen_no_repeat_ngram", 0) or 0), int(getattr(args, "gen_min_new_tokens", 0) or 0)
+    return {"no_repeat_ngram_size": n, "min_new_tokens": m} if n or m else {}
+
+
+def _vote_kw(args) -> dict:
+    """--gen_vote N [--gen_vote_temperature T --gen_vote_top_p P] as generate's keywords ({} without the flag)."""
+    n = int(getattr(args, "gen_vote", 0) or 0)
+    if n < 2:
+        return {}
+    return {"num_return_sequences": n, "vote": True, "temperature": float(getattr(args, "gen_vote_temperature", 1.0)),
+            "top_p": float(getattr(args, "gen_vote_top_p", 1.0)), "seed": int(getattr(args, "seed", 0) or 0)}
+
+
+def _winner_rows(out: dict, key: str):
+    """A voted result's `key` (B, n, ...) -> (B, ...): each row's winning sample."""
+    t = out[key]
+    w = out["vote"]["winner"].to(torch.int64).view(-1, *([1] * (t.dim() - 1))).expand(-1, 1, *t.shape[2:])
+    return t.gather(1, w).squeeze(1)
+
+
 def _report_frame_attention(model, out: dict, extracted) -> None:
     """A result of generate with "frame_attention": the model's `last_generation` gains it, "tokens" and attribution.summarize's
     "frame_share" / "video_mass"; every extracted answer gains its "frame_share" (F numbers) and "video_mass"."""
@@ -267,8 +289,15 @@ class Transformer(nn.Module):
                 raise ValueError("--gen_draft verifies a draft trie against the greedy choice: not with --gen_constrain, "
                                  "--contrast, --num_beams > 1, --gen_jump_forward > 1 or --gen_frame_attention")
             return self._drafted_inference(data, draft)
+        if int(getattr(self.args, "gen_vote", 0) or 0) > 1 and (
+                int(getattr(self.args, "num_beams", 1) or 1) > 1 or int(getattr(self.args, "lookahead", 0) or 0) > 1
+                or int(getattr(self.args, "gen_jump_forward", 0) or 0) > 1 or getattr(self.args, "gen_frame_attention", False)):
+            raise ValueError("--gen_vote draws samples in the plain token loop: not with --num_beams > 1, --lookahead > 1, "
+                             "--gen_jump_forward > 1 or --gen_frame_attention")
         if mode:                                            # --gen_constrain: decode under the allowed answers
             return self._constrained_inference(data, mode)
+        if int(getattr(self.args, "gen_vote", 0) or 0) > 1:     # --gen_vote N: N samples per row, the largest group's answer
+            return self._voted_inference(data)
         if getattr(self.args, "contrast", None):            # --contrast blind: each token from the difference to the blind twin
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
                                     **self._contrast_kw())
@@ -292,7 +321,7 @@ class Transformer(nn.Module):
             ids = out["ids"]
         elif getattr(self.args, "gen_stop_eos", False):     # --gen_stop_eos: the same tokens up to each row's EOS, which is
             out = generate.generate(eng, data, max_new_tokens=generate.N_NEW, temperature=0.0, stop_at_eos=True,
-                                    **_frame_attention_kw(self.args))
+                                    **_frame_attention_kw(self.args), **_pick_rules_kw(self.args))
             ids = out["ids"]                                # where both readers of the ids cut them (match_answers, engine)
         else:
             ids = generate.greedy_decode(eng, data)
@@ -352,6 +381,18 @@ class Transformer(nn.Module):
             lo = hi
         self.last_generation.update(steps=out["steps"], n_prefills=out["n_prefills"], occupancy=out["occupancy"])
         return results
+
+    def _voted_inference(self, data):
+        """--gen_vote N: every row decodes N samples from one prefill (seed = --seed), the vote's winner goes through the unchanged
+        `match_answers`. `last_generation` gains "vote" and "vote_share" (B,), the meter validation reads with its predictions.
+        With --contrast the samples are contrastive ones; --gen_constrain is `_constrained_inference`'s."""
+        from fvqa import generate
+        out = generate.generate(self.ensure_engine(), data, max_new_tokens=generate.N_NEW, stop_at_eos=True, **_vote_kw(self.args),
+                                **self._contrast_kw(), **_pick_rules_kw(self.args))
+        ids = _winner_rows(out, "ids").contiguous()
+        best, sims, extracted = generate.match_answers(self, data, ids)
+        self.last_generation = {"ids": ids, "similarities": sims, "vote": out["vote"], "vote_share": out["vote"]["share"]}
+        return best, extracted
 
     def _contrast_kw(self) -> dict:
         """--contrast / --contrast_alpha / --contrast_beta as generate's keywords ({} without --contrast)."""
@@ -424,14 +465,19 @@ class Transformer(nn.Module):
             raise ValueError(f"gen_constrain: 'options' or 'vocab', not {mode!r}")
         jump = int(getattr(self.args, "gen_jump_forward", 0) or 0)      # --gen_jump_forward T: forced tokens without a pass of
         kw = {"jump_forward": jump} if jump > 1 else {}                 # their own (0, 1: the call made before the flag existed)
-        out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)), temperature=0.0,
+        vote = _vote_kw(self.args)                                      # --gen_vote N: the winner's choice is the prediction
+        out = generate.generate(eng, data, max_new_tokens=max(generate.N_NEW, max(trie.max_len)),
                                 stop_at_eos=True, num_beams=int(getattr(self.args, "num_beams", 1) or 1), constraints=trie,
-                                **self._contrast_kw(), **_frame_attention_kw(self.args), **kw)
+                                **self._contrast_kw(), **_frame_attention_kw(self.args), **kw, **(vote or {"temperature": 0.0}))
         ids, choice = out["ids"], out["choice"]
+        if vote:
+            ids, choice = _winner_rows(out, "ids").contiguous(), _winner_rows(out, "choice")
         best, sims, extracted = generate.match_answers(self, data, ids)
         if mode == "options":
             best = torch.where(choice >= 0, choice.to(best.dtype), best)
         self.last_generation = {"ids": ids, "similarities": sims, "choice": choice}
+        if vote:
+            self.last_generation.update(vote=out["vote"], vote_share=out["vote"]["share"])
         if jump > 1:
             self.last_generation["n_committed"] = out["n_committed"]
         _report_frame_attention(self, out, extracted)
@@ -442,17 +488,17 @@ class Transformer(nn.Module):
         """The generation API on a batch of `fvqa.generate.prompt_batch` (or a validation batch): fvqa.generate.generate's
         keywords (max_new_tokens, temperature, top_p, stop_at_eos, seed, num_beams, length_penalty, top_k, repetition_penalty,
         return_logprobs, num_return_sequences, constraints, contrast, contrast_alpha, contrast_beta, lookahead, lookup_ngram,
-        draft_tokens, draft_answers, jump_forward, frame_attention) -> one answer per row, the
+        draft_tokens, draft_answers, jump_forward, frame_attention, min_p, no_repeat_ngram_size, min_new_tokens, vote) -> one answer per row, the
         generated tokens up to (not including) the EOS: decoded text when the tokenizer has a vocabulary, else the list of token ids. The id matrix, the
         per-row counts and the number of token steps launched are left in `last_generation` (with num_beams > 1 the best
         hypothesis' and, under "score", the sum of its tokens' log-probabilities; with return_logprobs "logprobs" and
         "sum_logprob"; with constraints "choice", the index of each answer in the allowed set; with contrast "n_plausible", the
-        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step, and with draft_answers "rows_per_pass"; with jump_forward >= 2 "n_committed"; with frame_attention "frame_attention" and "tokens", what fvqa.attribution.summarize reads). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis."""
+        size of the plausible set at every token step; with lookahead >= 2 "n_committed" and "n_drafted", per token step, and with draft_answers "rows_per_pass"; with jump_forward >= 2 "n_committed"; with frame_attention "frame_attention" and "tokens", what fvqa.attribution.summarize reads). num_return_sequences = n > 1: a list of n answers per row, and `last_generation` with the sample axis; with vote=True the answer of the vote's winner per row (one answer, not a list), and "vote" and "answers" (every sample's, the list above) in `last_generation`."""
         from fvqa import generate
         out = generate.generate(self.ensure_engine(), data, **kw)
         self.last_generation = {k: out[k] for k in ("ids", "n_generated", "steps", "score", "logprobs", "sum_logprob", "choice",
                                                      "n_plausible", "n_committed", "n_drafted", "rows_per_pass",
-                                                     "frame_attention")
+                                                     "frame_attention", "vote")
                                 if k in out}
         if "frame_attention" in out:
             self.last_generation["tokens"] = out["tokens"]
@@ -469,6 +515,9 @@ class Transformer(nn.Module):
                 answers.append([answer(ids[b, k, int(p): int(p) + int(n[b, k])].tolist()) for k in range(ids.shape[1])])
             else:
                 answers.append(answer(ids[b, int(p): int(p) + int(n[b])].tolist()))
+        if "vote" in out:                                   # the winner's answer per row; every sample's stays in "answers"
+            self.last_generation["answers"] = answers
+            answers = [row[int(k)] for row, k in zip(answers, out["vote"]["winner"].cpu())]
         return answers
 
     @torch.no_grad()

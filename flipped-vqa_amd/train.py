@@ -117,6 +117,23 @@ _FLAGS = [
                                         "text softmax's weight on the frame keys, mean over tokens, layers and heads) and "
                                         "frame_share, the weight per frame, in every entry of the extracted-answers file. Not with "
                                         "--num_beams > 1, --contrast, --lookahead > 1, --gen_jump_forward > 1 or --gen_stream")),
+    ("--gen_vote", dict(type=int, default=0, metavar="N",
+                        help="generation-task validation by self-consistency (fvqa.generate.generate(num_return_sequences=N, "
+                             "vote=True, seed=--seed)): every row decodes N samples (2 .. 64) from one prefill, the samples with "
+                             "equal tokens form a group and the largest group's answer goes through the unchanged answer matching "
+                             "(with --gen_constrain options the winner's choice is the prediction); logs a vote_share meter, the "
+                             "winner's share of the samples. 0: off. Not with --num_beams > 1, --lookahead > 1, "
+                             "--gen_jump_forward > 1, --gen_stream, --val_vocab or --gen_frame_attention")),
+    ("--gen_vote_temperature", dict(type=float, default=1.0, help="--gen_vote: the samples' temperature (> 0)")),
+    ("--gen_vote_top_p", dict(type=float, default=1.0, help="--gen_vote: the samples' nucleus bound, in (0, 1]")),
+    ("--gen_no_repeat_ngram", dict(type=int, default=0, metavar="N",
+                                   help="generation-task validation through fvqa.generate.generate(no_repeat_ngram_size=N) (needs "
+                                        "--gen_stop_eos or --gen_vote): no N-gram occurs twice among a row's generated tokens; the "
+                                        "prompt is not scanned. 0: off. Not with --gen_constrain, --contrast or what --gen_vote refuses")),
+    ("--gen_min_new_tokens", dict(type=int, default=0, metavar="M",
+                                  help="generation-task validation through fvqa.generate.generate(min_new_tokens=M) (needs "
+                                       "--gen_stop_eos or --gen_vote): the EOS is banned before a row's M-th token. 0: off. Not "
+                                       "with --gen_constrain, --contrast or what --gen_vote refuses")),
     ("--log_video_mass", dict(type=int, default=0, metavar="EVERY",
                               help="training: on every EVERY-th iteration log a video_mass meter — the weight the text softmax "
                                    "of the vqa stream's scored rows puts on the frame keys, mean over rows, layers and heads, "
@@ -150,6 +167,51 @@ _FLAGS = [
 ]
 
 
+def _check_pick_rules(self, a, la):
+    """(self: the parser.) The pick rules and the vote, under train.py's names (gen_*) and answer.py's: what fvqa.generate.generate refuses."""
+    beams = int(getattr(a, "num_beams", 1) or 1) > 1
+    jump = int(getattr(a, "gen_jump_forward", 0) or 0) > 1 or int(getattr(a, "jump_forward", 0) or 0) > 1
+    stream = int(getattr(a, "gen_stream", 0) or 0) >= 1 or int(getattr(a, "slots", 0) or 0) >= 1
+    min_p = getattr(a, "min_p", 0.0)
+    ngram = getattr(a, "gen_no_repeat_ngram", 0) or getattr(a, "no_repeat_ngram", 0)
+    m_new = getattr(a, "gen_min_new_tokens", 0) or getattr(a, "min_new_tokens", 0)
+    if not 0 <= min_p < 1:
+        self.error("0 <= --min_p < 1 (0: off)")
+    if ngram < 0 or m_new < 0:
+        self.error("the n-gram size and the minimum length are >= 0 (0: off)")
+    if hasattr(a, "max_new_tokens") and m_new > a.max_new_tokens:
+        self.error("--min_new_tokens <= --max_new_tokens")
+    if min_p > 0 and not float(getattr(a, "temperature", 0.0) or 0.0) > 0:
+        self.error("--min_p cuts a sampled distribution: it needs --temperature > 0")
+    vote_n = int(getattr(a, "gen_vote", 0) or 0)
+    if min_p != 0 or ngram != 0 or m_new != 0:
+        if (beams or la > 1 or jump or stream or getattr(a, "gen_constrain", None) or getattr(a, "constrain", False)
+                or getattr(a, "contrast", None) or getattr(a, "val_vocab", False) or int(getattr(a, "rank", 0) or 0)
+                or (getattr(a, "answer_vocab", None) and hasattr(a, "min_p"))):
+            self.error("the pick rules (min-p, n-gram blocking, minimum length) run in the plain token loop: not with "
+                       "--num_beams > 1, constrained or contrastive decoding, --lookahead > 1, drafts, jump-forward, a stream "
+                       "or a vocabulary scoring")
+        if hasattr(a, "gen_no_repeat_ngram") and not hasattr(a, "min_p") and not (getattr(a, "gen_stop_eos", False) or vote_n):
+            self.error("--gen_no_repeat_ngram and --gen_min_new_tokens are served by fvqa.generate.generate: they need "
+                       "--gen_stop_eos or --gen_vote")
+    if vote_n:
+        if not 2 <= vote_n <= 64:
+            self.error("--gen_vote N counts samples: 2 <= N <= 64 (0: off)")
+        if not getattr(a, "is_generation_task", False):
+            self.error("--gen_vote belongs to generation-task validation: it needs --is_generation_task")
+        if not getattr(a, "gen_vote_temperature", 1.0) > 0 or not 0 < getattr(a, "gen_vote_top_p", 1.0) <= 1:
+            self.error("--gen_vote_temperature > 0, 0 < --gen_vote_top_p <= 1")
+        if beams or la > 1 or jump or stream or getattr(a, "val_vocab", False) or getattr(a, "gen_frame_attention", False):
+            self.error("--gen_vote draws samples in the plain token loop: not with --num_beams > 1, --lookahead > 1, "
+                       "--gen_jump_forward > 1, --gen_stream, --val_vocab or --gen_frame_attention")
+    if getattr(a, "vote", False):
+        if not 2 <= int(getattr(a, "num_samples", 1) or 1) <= 64 or not float(getattr(a, "temperature", 0.0) or 0.0) > 0:
+            self.error("--vote counts samples: it needs --num_samples N, 2 <= N <= 64, and --temperature > 0")
+        if beams or la > 1 or jump or stream or int(getattr(a, "rank", 0) or 0):
+            self.error("--vote draws samples in the plain token loop: not with --num_beams > 1, --lookahead > 1, jump-forward, "
+                       "a stream or --rank")
+
+
 class ArgumentParser(argparse.ArgumentParser):
     """argparse's parser, which also refuses --gen_constrain vocab without its --answer_vocab file and --contrast with
     --num_beams > 1 (a contrastive beam step is not built) or with parameters out of range, and --lookahead or
@@ -159,7 +221,9 @@ class ArgumentParser(argparse.ArgumentParser):
     with a validation that does not score options or scores them twice, and --val_flipped with a validation that does not
     score options or combines their scores another way, and --val_vocab without its vocabulary and generation prompts or with
     a decode (it runs none), and --gen_draft (answer.py: --draft) without its --lookahead R, its prompts or its vocabulary, or
-    with a decode the tree drafts are not built for; --lookahead may reach 64 only with it."""
+    with a decode the tree drafts are not built for; --lookahead may reach 64 only with it; and the pick rules (--gen_no_repeat_ngram,
+    --gen_min_new_tokens; answer.py: --min_p, --no_repeat_ngram, --min_new_tokens) and the vote (--gen_vote; answer.py: --vote) out
+    of range or with a decode fvqa.generate.generate refuses them with."""
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
@@ -243,6 +307,7 @@ class ArgumentParser(argparse.ArgumentParser):
                     or int(getattr(a, "gen_stream", 0) or 0) >= 1 or int(getattr(a, "slots", 0) or 0) >= 1):
                 self.error(f"--{flag} is served by the plain token loop: not with --num_beams > 1, --contrast, --lookahead > 1, "
                            "jump-forward or a stream")
+        _check_pick_rules(self, a, la)
         if int(getattr(a, "log_video_mass", 0) or 0) < 0:
             self.error("--log_video_mass EVERY >= 0 (0: off)")
         if getattr(a, "val_frame_attention", False):

@@ -58,7 +58,8 @@ extern "C" {
  * interleaved in blocks of 16 in the packed W1|W3 matrix. One MFMA wave of the W1|W3 GEMM then holds a and b of the
  * same hidden unit in the same lane, and SwiGLU becomes that GEMM's epilogue. hidden % 16 == 0. */
 
-int fvqa_version(void);      /* ABI version, bumped on any signature change */
+int fvqa_version(void);      /* ABI version, bumped on any signature change: an entry that is only ADDED (no existing signature,
+                              * message or order of outcomes moves) leaves it where it is */
 /* sha256 (hex) of the kernel sources (csrc/ *.hip, *.h, include/fvqa.h) this library was compiled from, "unknown" for a build
  * outside fvqa/build.py. The host binding compares it with the sources next to the library and refuses a stale binary. */
 const char* fvqa_source_hash(void);
@@ -448,6 +449,52 @@ int fvqa_decode_next_ex(const float* logits, const float* u, const void* emb, fl
                         const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
                         int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
                         int dtype, void* stream);
+/* fvqa_decode_next_ex with three more pick rules (the same kernel template in csrc/sample.hip with one more compile-time switch;
+ * generate(min_p / no_repeat_ngram_size / min_new_tokens)). The operands of fvqa_decode_next_ex in its order, then min_p in
+ * [0, 1) (0: off), no_repeat_ngram n >= 0 (0: off), min_new_tokens m >= 0 (0: off; m > 0 needs stop_at_eos != 0). The row
+ * stepping and the errors of fvqa_decode_next_ex hold. With g0 = max(gen_start, 0), p = pos, the row's generated tokens
+ * ids[g0 .. p] and i = p + 1 - gen_start the index of the token being picked, per live row in fp32, in front of rules 1 to 5:
+ *   0. The ban set X, built from the row's own ids once per step, before the penalty:
+ *      - minimum length: eos_id is in X while i < m;
+ *      - n-gram blocking: s = the last n - 1 generated tokens (empty for n == 1; fewer than n - 1 generated: nothing is banned);
+ *        for every j with g0 <= j and j + n - 1 <= p and ids[j .. j + n - 2] == s, the token ids[j + n - 1] is in X. Only
+ *        generated positions are scanned: a window that reaches into the prompt bans nothing — the prompt lists the answer
+ *        options and the answer is meant to copy one (Hugging Face's processor scans the prompt too);
+ *      - ids outside [0, vocab) are ignored.
+ *      A banned token takes no part anywhere: not in the maximum, Z, the counts and sums of either bisection, the number top-k
+ *      is cut against (the tokens NOT banned), the tie groups or the walk; it is never returned and n_kept never counts it; the
+ *      greedy pick is the best token that is not banned. The penalty's set R is unaffected, and logprob stays l_token - lse of
+ *      the raw, whole row. A row whose every token is banned ends as a trie row at a node without edges does: done, token -1,
+ *      n_kept 0, logprob 0; ids and pos are not written.
+ *   3'. min-p (ignored at temperature == 0): the largest token that is not banned has e = exp(0) = 1 exactly; a token is kept
+ *      iff rule 3 keeps it AND e_i >= min_p, an fp32 comparison on the e_i every other pass sees. That is again a prefix of the
+ *      one order (e descending, index ascending) made of whole tie groups, so the kept set is the shortest of three prefixes and
+ *      holds the top token. It equals Hugging Face's warpers in sequence (top-k, then top-p, then min-p, each renormalising):
+ *      the ratio of a probability to the largest one does not change under renormalisation, and every earlier cut keeps the
+ *      largest.
+ * min_p == 0, n == 0, m == 0: fvqa_decode_next_ex's results bit for bit. The method: X is a second bitmap of vocab bits in LDS
+ * behind R's; min-p is one counting pass behind the nucleus cut. Fixed summation orders, no float atomics: bitwise repeatable.
+ * FVQA_EINVAL also for min_p outside [0, 1) or NaN, n < 0, m < 0, m > 0 with stop_at_eos == 0; FVQA_ESHAPE also for a vocab
+ * beyond 1216512 (one bitmap: repetition_penalty == 1) or beyond 626688 (both bitmaps: 2 * 4 * ceil(vocab / 32) bytes above
+ * 156672). */
+int fvqa_decode_next_rules(const float* logits, const float* u, const void* emb, float temperature, float top_p, int top_k,
+                           float repetition_penalty, int eos_id, int stop_at_eos, int64_t* ids, int32_t* pos, int32_t* done,
+                           const int32_t* gen_start, void* x_next, int32_t* token, int32_t* n_kept, float* logprob,
+                           int32_t* n_active, uint32_t* counter, int64_t* pos64, int n_seq, int vocab, int dim, int seq_len,
+                           int dtype, void* stream, float min_p, int no_repeat_ngram, int min_new_tokens);
+/* A vote over the samples of a prompt (csrc/vote.hip; generate(num_return_sequences=n, vote=True)): self-consistency by exact
+ * match of the token rows. In: tokens (n_seq, n_samples, steps) int32, -1 padded; score (n_seq, n_samples) fp32. Out: group and
+ * votes (n_seq, n_samples) int32, winner and n_groups (n_seq) int32, share (n_seq) fp32. Per prompt:
+ *   - two samples belong to one group iff their token rows are equal in every column, padding included; group[a] = the lowest
+ *     sample index of a's group (its representative); votes = the group's size at the representative, 0 elsewhere; n_groups =
+ *     the number of representatives;
+ *   - winner = the representative with the most votes; ties go to the larger score of the representative (a NaN counts as
+ *     -inf), remaining ties to the lower index; share = votes[winner] / n_samples.
+ * One workgroup per prompt, integer compares and one float compare in a fixed order: bitwise repeatable.
+ * FVQA_EINVAL: a null pointer; FVQA_ESHAPE: n_seq outside [1, 65535], n_samples outside [1, 64], steps < 1, more than 2^31 - 1
+ * tokens; FVQA_EALIGN: a pointer off its 4-byte boundary. */
+int fvqa_sample_vote(const int32_t* tokens, const float* score, int32_t* group, int32_t* votes, int32_t* winner,
+                     int32_t* n_groups, float* share, int n_seq, int n_samples, int steps, void* stream);
 /* fvqa_decode_next_ex under a trie of allowed answers (the same kernel template in csrc/sample.hip; generate(constraints=...);
  * fvqa/constrain.py builds the arrays). The operands, the row stepping and the errors of fvqa_decode_next_ex hold; in addition:
  * node (n_seq) int32, in and out — the trie node each row stands at, -1 for an unconstrained row —, and the trie in CSR form,

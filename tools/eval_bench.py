@@ -57,6 +57,64 @@ from fvqa import generate, synth  # noqa: E402
 from llama_vqa import LLaMA_VQA  # noqa: E402
 
 
+def pick_rules_lines(a, eng, b, model, timed):
+    """--pick_rules: end to end, then the pick and the vote alone."""
+    from fvqa import ops
+    B, T, V = a.batch_size, generate.N_NEW, model.vocab_size
+    tag = f"{a.model} L={eng.L} B={B} S=128 V={V} temperature=0.8 top_p=0.9"
+    rules = dict(min_p=0.05, no_repeat_ngram_size=3, min_new_tokens=4)
+    runs = (("plain sampled", lambda: generate.generate(eng, b, temperature=0.8, top_p=0.9, stop_at_eos=True, seed=0)),
+            ("min_p=0.05 no_repeat_ngram_size=3 min_new_tokens=4",
+             lambda: generate.generate(eng, b, temperature=0.8, top_p=0.9, stop_at_eos=True, seed=0, **rules)))
+    for _, fn in runs:
+        timed(fn, reps=1)
+    for k in range(a.pairs or 3):
+        t = [timed(fn, warm=0) for _, fn in runs]
+        print(f"{tag} round {k}: " + " | ".join(f"{name}: {x * 1e3:7.1f} ms/batch" for (name, _), x in zip(runs, t))
+              + f" | rules / plain {t[1] / t[0]:6.3f}", flush=True)
+    dev, S = eng.device, 128
+    gen = torch.Generator(device=dev).manual_seed(0)
+    lg = 6.0 * torch.randn(B, V, device=dev, generator=gen)
+    u = torch.rand(B, device=dev, generator=gen)
+    ids0 = torch.randint(3, V, (B, S), device=dev, generator=gen)
+    i32 = lambda *s, v=0: torch.full(s, v, dtype=torch.int32, device=dev)   # noqa: E731
+    emb = eng.pack.emb
+
+    def event_timed(fn, n=50):
+        for _ in range(5):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n * 1e3
+
+    st = dict(ids=ids0.clone(), pos=i32(B, v=90), done=i32(B), gs=i32(B, v=60), x=torch.empty(B, emb.shape[1], dtype=emb.dtype, device=dev),
+              tok=i32(B), kept=i32(B), lp=torch.zeros(B, device=dev), act=i32(1), cnt=i32(1))
+
+    def step(entry, **kw):
+        def fn():
+            st["pos"].fill_(90)
+            st["done"].zero_()
+            entry(lg, emb, st["ids"], st["pos"], st["done"], st["gs"], st["x"], st["tok"], st["kept"], st["lp"], st["act"], st["cnt"],
+                  u=u, temperature=0.8, **kw)
+        return fn
+    for name, kw in (("top_p 0.9", dict(top_p=0.9)), ("top_k 40 penalty 1.3", dict(top_p=1.0, top_k=40, repetition_penalty=1.3))):
+        t_ex = event_timed(step(ops.decode_next_ex, **kw))
+        t_ru = event_timed(step(ops.decode_next_rules, min_p=0.05, no_repeat_ngram=3, min_new_tokens=4, **kw))
+        t_mp = event_timed(step(ops.decode_next_rules, min_p=0.05, **kw))
+        print(f"pick alone, B={B} V={V}, 31 generated ids, {name} (with two position resets per launch): decode_next_ex {t_ex:7.1f} us | "
+              f"decode_next_rules min_p + n-gram 3 + minimum length {t_ru:7.1f} us | decode_next_rules min_p alone {t_mp:7.1f} us",
+              flush=True)
+    for n in (5, 64):
+        tokens = torch.randint(3, 6, (B, n, T), device=dev, generator=gen, dtype=torch.int32)
+        score = -torch.rand(B, n, device=dev, generator=gen)
+        t_v = event_timed(lambda: ops.sample_vote(tokens, score))
+        print(f"sample_vote, B={B} n={n} steps={T} (with its five output allocations): {t_v:7.1f} us", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="7B")
@@ -93,6 +151,10 @@ def main():
     ap.add_argument("--requests", type=int, default=64, help="--stream: the number of requests")
     ap.add_argument("--frame_attention", action="store_true", help="generate(frame_attention=True) against the call without "
                                                                    "the keyword, interleaved (--pairs rounds, default 3)")
+    ap.add_argument("--pick_rules", action="store_true", help="the plain sampled call against the same call with min_p, "
+                    "no_repeat_ngram_size and min_new_tokens, interleaved (--pairs, default 3); then the pick alone — "
+                    "fvqa_decode_next_rules against fvqa_decode_next_ex on B rows of the model's vocabulary — and fvqa_sample_vote "
+                    "at 5 and 64 samples per prompt, event-timed")
     ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
     if a.val_batch_size:
@@ -190,6 +252,9 @@ def main():
             print(f"{tag} round {k}: " + " | ".join(f"{name}: {x * 1e3:7.1f} ms/batch" for (name, _), x in zip(runs, t))
                   + f" | contrast: {B * T / t[2]:8.1f} answer tokens/s, {t[2] / t[0]:5.2f}x B rows, {t[2] / t[1]:5.2f}x 2B rows",
                   flush=True)
+        return
+    if a.pick_rules:
+        pick_rules_lines(a, eng, b, model, timed)
         return
     if a.top_k or a.samples:
         T = generate.N_NEW

@@ -179,7 +179,15 @@ def modes(eng, batch, full, drafts):
         ("lookahead=4 draft_tokens sampled", lambda: generate.generate(eng, batch, lookahead=4, draft_tokens=drafts(),
                                                                        temperature=0.8, top_p=0.9, seed=0)),
         ("lookahead=4 draft_answers sampled", drafted("answer", lookahead=4, temperature=0.8, top_p=0.9, seed=0)),
-    ]
+    ] + ([                                                  # (a tree without the pick rules and the vote has none of these)
+        ("no_repeat_ngram_size=2 min_new_tokens=4", g(no_repeat_ngram_size=2, min_new_tokens=4)),
+        ("min_p=0.1 sampled", g(temperature=1.5, min_p=0.1, seed=0)),
+        ("min_p + top_k + repetition_penalty + num_return_sequences=3", g(temperature=1.5, min_p=0.05, top_k=20, repetition_penalty=1.2,
+                                                                           no_repeat_ngram_size=3, seed=0, num_return_sequences=3)),
+        ("vote num_return_sequences=5", g(temperature=3.0, min_p=0.05, seed=0, num_return_sequences=5, vote=True)),
+        ("vote + constraints", g(temperature=3.0, seed=0, num_return_sequences=5, vote=True, constraints=branchy)),
+        ("vote + contrast", g(temperature=3.0, seed=0, num_return_sequences=4, vote=True, contrast="blind")),
+    ] if hasattr(ops, "sample_vote") else [])
 
 
 FLIPPED, FLIPPED_ROWS = "flipped_tiny", (0, 1, 2)

@@ -5,7 +5,8 @@ synthetic operands, the public fvqa.ops API only (so the tool runs unchanged in 
   case | sha256 over every operand after the launch (outputs and in/out state, in a fixed order)
 
 Entries: decode_next (greedy, sampled), decode_next_ex, _trie, _pair (with and without a trie), _stream (with and without a trie),
-spec_step, spec_step_sample, tree_spec_step, tree_spec_step_sample, trie_jump_step. Shapes: V = 509 (ragged strided tails), 32000
+_rules (min-p alone, a unigram ban with top-k's count, a bigram ban with a minimum length and min-p; its lines come last in each
+group and are new beside a tree without the entry: compare the others), spec_step, spec_step_sample, tree_spec_step, tree_spec_step_sample, trie_jump_step. Shapes: V = 509 (ragged strided tails), 32000
 (the row of e_i in LDS), 40003 (recomputed); 3 sequences or pairs, D = 32; T = 4 and 16 rows per pass for the chain and the jump
 step, R = 4 and 64 for the tree; fp32 and both 16-bit storage types. Rows: one with planted tie groups (a group of equal logits
 across rank k = 6, a larger one where the nucleus cuts), one of NaNs, peaked rows that let a chain or a walk run deep. The hand-made
@@ -37,6 +38,9 @@ DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 PARAMS = {"nucleus": dict(temperature=0.8, top_p=0.9, top_k=0, repetition_penalty=1.0),
           "topk_penalty": dict(temperature=1.3, top_p=1.0, top_k=6, repetition_penalty=1.5),
           "penalty": dict(temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.3)}
+RULES = {"min_p": dict(min_p=0.1, no_repeat_ngram=0, min_new_tokens=0),
+         "ngram1": dict(min_p=0.0, no_repeat_ngram=1, min_new_tokens=0),
+         "ngram2_minlen_min_p": dict(min_p=0.05, no_repeat_ngram=2, min_new_tokens=9)}
 GREEDY = dict(temperature=0.0, top_p=1.0, top_k=0, repetition_penalty=1.0)
 GREEDY_PENALTY = dict(GREEDY, repetition_penalty=1.3)
 ANSWERS = [[10, 11, 12], [10, 11, 13, 14], [10, 15, 16, 17, 18], [20, 21, 22, 23, 24, 25], [20, 26, 27]]
@@ -163,6 +167,14 @@ def decode_cases(V, dtype, emb, trie):
                                            pos64=st["pos64"], **dict(kw, u=uw))
                     return st
                 yield f"decode_next_stream/{name}{tag}/nodes{nodes}", stream_
+            for rname, rules in RULES.items() if hasattr(ops, "decode_next_rules") else ():
+                def rules_(rows=rows, kw=kw, rules=rules):
+                    st = state(V, dtype, rows, B, V, **ex())
+                    st["ids"][:, 7] = st["ids"][:, 5]                # (rows 0 and 2: the token at pos occurred before — a bigram to ban)
+                    ops.decode_next_rules(st["logits"], emb, st["ids"], st["pos"], st["done"], g0, st["x"], st["token"],
+                                          st["n_kept"], st["logprob"], st["n_active"], st["counter"], pos64=st["pos64"], **kw, **rules)
+                    return st
+                yield f"decode_next_rules/{name}{tag}/{rname}", rules_
 
 
 def chain_cases(V, dtype, emb, trie):
