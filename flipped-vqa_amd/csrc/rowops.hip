@@ -116,6 +116,75 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const T* __restrict__ g, co
   }
 }
 
+// ---- RMSNorm weight gradient: dw[c] (+)= sum_r g[r,c] * round_to<T>(x[r,c] * rstd[r]) -----------------------------------------
+// The grid splits the columns (512 per workgroup: 64 lanes x one 16-byte load of 8 elements) AND the rows (DW_CHUNK per
+// workgroup): dim = 4096 alone would give 8 workgroups for 256 CUs. Wave w of a workgroup takes rows w, w + 4, .. of its chunk,
+// four rows at a time with all their eight loads issued before the first use; the four waves' sums meet in LDS in wave order, and
+// the chunk's partial row goes to the workspace. The finish launch adds the chunks — four interleaved groups of them per column,
+// each in ascending order, the groups joined in order: fp32 products and sums in one fixed order, no atomics, so two launches
+// give the same bits.
+#ifndef FVQA_DW_CHUNK
+#define FVQA_DW_CHUNK 16              // (tuning builds: -DFVQA_DW_CHUNK=32 ...; a multiple of 16)
+#endif
+constexpr int DW_CHUNK = FVQA_DW_CHUNK;   // rows per workgroup
+constexpr int DW_COLS = 512;              // columns per workgroup
+static_assert(DW_CHUNK % 16 == 0, "four waves x batches of four rows");
+
+template <typename T>
+__global__ __launch_bounds__(256) void rmsnorm_dw_part_k(const T* __restrict__ g, const T* __restrict__ x,
+                                                         const float* __restrict__ rstd, float* __restrict__ part,
+                                                         int rows, int dim) {
+  __shared__ float red[4][DW_COLS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c0 = blockIdx.x * DW_COLS, c = c0 + lane * 8;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (c < dim) {
+    for (int b = 0; b < DW_CHUNK; b += 16) {
+      const int r0 = blockIdx.y * DW_CHUNK + b + wave;
+      float gv[4][8], xv[4][8], rs[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int r = r0 + 4 * k;
+        if (r < rows) {
+          load8<T>(g + (size_t)r * dim + c, gv[k]);
+          load8<T>(x + (size_t)r * dim + c, xv[k]);
+          rs[k] = rstd[r];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (r0 + 4 * k < rows) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[i] += gv[k][i] * round_to<T>(xv[k][i] * rs[k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = acc[i];
+  __syncthreads();
+  for (int j = tid; j < DW_COLS; j += 256) {
+    if (c0 + j < dim) part[(size_t)blockIdx.y * dim + c0 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+  }
+}
+
+// 64 columns per workgroup; wave q adds the chunks q, q + 4, .. of its columns, the four sums meet in LDS in wave order
+__global__ __launch_bounds__(256) void rmsnorm_dw_finish_k(const float* __restrict__ part, float* __restrict__ dw,
+                                                           int n_chunks, int dim, int accumulate) {
+  __shared__ float red[4][64];
+  const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (c < dim)
+    for (int k = q; k < n_chunks; k += 4) s += part[(size_t)k * dim + c];
+  red[q][lane] = s;
+  __syncthreads();
+  if (q == 0 && c < dim) {
+    const float t = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    dw[c] = accumulate ? dw[c] + t : t;
+  }
+}
+
 // ---- RoPE on q,k of the fused qkv rows (reference llama/model.py:61-67) ---------------------
 // one 256-thread workgroup per row, 8 elements (4 rotation pairs, 16 B of bf16) per thread
 template <typename T>
@@ -324,6 +393,30 @@ extern "C" int fvqa_rmsnorm_bwd(const void* g, const void* x, const void* w, con
   if (!fvqa_aligned(16, g, x, w, resid, dx) || !fvqa_aligned(4, rstd)) return FVQA_EALIGN;
   DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_bwd_k<T>), dim3(rows), dim3(256), 0, (hipStream_t)stream,
                                        (const T*)g, (const T*)x, (const T*)w, rstd, (const T*)resid, (T*)dx, dim));
+  FVQA_CHECK_LAUNCH();
+  return FVQA_OK;
+}
+
+extern "C" size_t fvqa_rmsnorm_dw_workspace(int rows, int dim) {
+  if (!norm_dims_ok(rows, dim)) return 0;
+  return (size_t)((rows + DW_CHUNK - 1) / DW_CHUNK) * (size_t)dim * sizeof(float);
+}
+
+extern "C" int fvqa_rmsnorm_dw(const void* g, const void* x, const float* rstd, float* dw, void* workspace,
+                               size_t workspace_bytes, int rows, int dim, int accumulate, int dtype, void* stream) {
+  if (!g || !x || !rstd || !dw || !workspace) return FVQA_EINVAL;
+  if (!fvqa_dtype_ok(dtype)) return FVQA_EINVAL;
+  if (!norm_dims_ok(rows, dim)) return FVQA_ESHAPE;
+  if (!fvqa_aligned(16, g, x, workspace) || !fvqa_aligned(4, rstd, dw)) return FVQA_EALIGN;
+  if (workspace_bytes < fvqa_rmsnorm_dw_workspace(rows, dim)) return FVQA_EALIGN;
+  const int n_chunks = (rows + DW_CHUNK - 1) / DW_CHUNK;
+  if (n_chunks > 65535) return FVQA_ESHAPE;                               // (the grid's y extent)
+  const dim3 grid((dim + DW_COLS - 1) / DW_COLS, n_chunks);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_dw_part_k<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)g,
+                                       (const T*)x, rstd, (float*)workspace, rows, dim));
+  FVQA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rmsnorm_dw_finish_k, dim3((dim + 63) / 64), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)workspace, dw, n_chunks, dim, accumulate ? 1 : 0);
   FVQA_CHECK_LAUNCH();
   return FVQA_OK;
 }

@@ -211,13 +211,25 @@ extern "C" int fvqa_layers_fwd(const fvqa_layer_plan* p, void* stream) {
   return FVQA_OK;
 }
 
-// dxnf: gradient w.r.t. the final-norm output (R, D). On return *d_x0 points at the gradient w.r.t.
-// the layer-0 input (one of the plan's two ping-pong buffers).
-extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void** d_x0, void* stream) {
+// `ng` (--train_norm; null: the frozen-norm walk, launch for launch what it was): the norm weights' gradients, one
+// fvqa_rmsnorm_dw in front of each fvqa_rmsnorm_bwd on the same g, x and rstd (g is the scratch `t`: read before its next writer)
+static int layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void** d_x0, const fvqa_norm_grads* ng, void* stream) {
   RUN(check_plan(p));
   if (!dxnf || !d_x0 || !p->dcur || !p->dnxt || !p->dz || !p->dab || !p->dh || !p->d_o || !p->dqkv || !p->attn_ws ||
       !p->dgate1 || !p->dgate2 || !p->d_adapter)
     return FVQA_EINVAL;
+  if (ng) {
+    if (!ng->d_an || !ng->d_fn || !ng->d_norm || !ng->dw_ws) return FVQA_EINVAL;
+    for (int i = 0; i < p->n_layers; ++i)
+      if (!ng->d_an[i] || !ng->d_fn[i]) return FVQA_EINVAL;
+    const int R_all = p->n_seq * p->seq_len;
+    const size_t need = fvqa_rmsnorm_dw_workspace(p->tail.rows > R_all ? p->tail.rows : R_all, p->dim);
+    if (need == 0) return FVQA_ESHAPE;
+    if (ng->dw_ws_bytes < need || ((uintptr_t)ng->dw_ws & 15)) return FVQA_EALIGN;
+  }
+  auto norm_dw = [&](const void* g, const void* x, const float* rstd, float* dw, int rows) {
+    return ng ? fvqa_rmsnorm_dw(g, x, rstd, dw, ng->dw_ws, ng->dw_ws_bytes, rows, p->dim, 1, p->dtype, stream) : FVQA_OK;
+  };
   const int dt = p->dtype, L = p->n_layers, D = p->dim, Hf = p->hidden, H = p->n_heads, Dh = p->head_dim;
   const int A = p->adapter_len, S = p->seq_len, n_seq = p->n_seq;
   const int R = n_seq * S, Ra = R + A;
@@ -232,8 +244,10 @@ extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void*
   if (tail) {
     const auto& t = p->tail;
     if (!t.dcur || !t.dab || !t.dt || !t.dh || !t.d_o) return FVQA_EINVAL;
+    RUN(norm_dw(dxnf, t.xl, t.rstdN, ng ? ng->d_norm : nullptr, t.rows));
     RUN(fvqa_rmsnorm_bwd(dxnf, t.xl, p->norm_w, t.rstdN, nullptr, t.dcur, t.rows, D, dt, stream));      // dxnf: (rows, D)
   } else {
+    RUN(norm_dw(dxnf, at(p->xs, (size_t)L * R * D, es), p->rstdN, ng ? ng->d_norm : nullptr, R));
     RUN(fvqa_rmsnorm_bwd(dxnf, at(p->xs, (size_t)L * R * D, es), p->norm_w, p->rstdN, nullptr, cur, R, D, dt, stream));
   }
   for (int i = L - 1; i >= 0; --i) {
@@ -255,6 +269,7 @@ extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void*
                        p->gemm_ws, p->gemm_ws_bytes, stream));
       RUN(fvqa_gemm_nt(tr.dab, p->w13_t[i], tr.dt, nullptr, nullptr, M, D, 2 * Hf, 2 * Hf, 2 * Hf, D, M, dt, dt,
                        FVQA_EPI_NONE, 0, p->gemm_ws, p->gemm_ws_bytes, stream));
+      RUN(norm_dw(tr.dt, tr.h, tr.rstd2, ng ? ng->d_fn[i] : nullptr, M));
       RUN(fvqa_rmsnorm_bwd(tr.dt, tr.h, p->fn[i], tr.rstd2, tr.dcur, tr.dh, M, D, dt, stream));
       RUN(fvqa_gemm_nt(tr.dh, p->wo_t[i], tr.d_o, nullptr, nullptr, M, D, D, D, D, D, M, dt, dt, FVQA_EPI_NONE, 0,
                        p->gemm_ws, p->gemm_ws_bytes, stream));
@@ -271,6 +286,7 @@ extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void*
     }
     RUN(fvqa_gemm_nt(p->dab, p->w13_t[i], t, nullptr, nullptr, R, D, 2 * Hf, 2 * Hf, 2 * Hf, D, R, dt, dt,
                      FVQA_EPI_NONE, 0, p->gemm_ws, p->gemm_ws_bytes, stream));
+    RUN(norm_dw(t, h, p->rstd2 + (size_t)i * R, ng ? ng->d_fn[i] : nullptr, R));
     RUN(fvqa_rmsnorm_bwd(t, h, p->fn[i], p->rstd2 + (size_t)i * R, cur, p->dh, R, D, dt, stream));
     RUN(fvqa_gemm_nt(p->dh, p->wo_t[i], p->d_o, nullptr, nullptr, R, D, D, D, D, D, R, dt, dt, FVQA_EPI_NONE, 0,
                      p->gemm_ws, p->gemm_ws_bytes, stream));
@@ -291,6 +307,7 @@ extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void*
     }
     RUN(fvqa_gemm_nt(p->dqkv, p->wqkv_t[i], t, nullptr, nullptr, R, D, 3 * D, 3 * D, 3 * D, D, R, dt, dt,
                      FVQA_EPI_NONE, 0, p->gemm_ws, p->gemm_ws_bytes, stream));
+    RUN(norm_dw(t, x, p->rstd1 + (size_t)i * R, ng ? ng->d_an[i] : nullptr, R));
     RUN(fvqa_rmsnorm_bwd(t, x, p->an[i], p->rstd1 + (size_t)i * R, p->dh, nxt, R, D, dt, stream));
     void* sw = cur; cur = nxt; nxt = sw;
   }
@@ -301,4 +318,15 @@ extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void*
   }
   *d_x0 = cur;
   return FVQA_OK;
+}
+
+// dxnf: gradient w.r.t. the final-norm output (R, D). On return *d_x0 points at the gradient w.r.t.
+// the layer-0 input (one of the plan's two ping-pong buffers).
+extern "C" int fvqa_layers_bwd(const fvqa_layer_plan* p, const void* dxnf, void** d_x0, void* stream) {
+  return layers_bwd(p, dxnf, d_x0, nullptr, stream);
+}
+
+extern "C" int fvqa_layers_bwd_norm(const fvqa_layer_plan* p, const void* dxnf, void** d_x0, const fvqa_norm_grads* ng,
+                                    void* stream) {
+  return layers_bwd(p, dxnf, d_x0, ng, stream);
 }

@@ -37,6 +37,8 @@ SIGNATURES = {
     "fvqa_gemm_timing_read": (_i, [_i, _p, _p, _p]),
     "fvqa_rmsnorm_fwd": (_i, [_p, _p, _p, _p, _i, _i, _f, _i, _p]),
     "fvqa_rmsnorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "fvqa_rmsnorm_dw_workspace": (_sz, [_i, _i]),
+    "fvqa_rmsnorm_dw": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),
     "fvqa_rope_qk": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fvqa_swiglu_fwd": (_i, [_p, _p, _i, _i, _i, _p]),
     "fvqa_swiglu_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
@@ -102,6 +104,7 @@ SIGNATURES = {
     "fvqa_layers_gemm_workspace": (_sz, [_p]),
     "fvqa_layers_fwd": (_i, [_p, _p]),
     "fvqa_layers_bwd": (_i, [_p, _p, _p, _p]),
+    "fvqa_layers_bwd_norm": (_i, [_p, _p, _p, _p, _p]),
 }
 
 _pp = C.POINTER(C.c_void_p)
@@ -148,6 +151,11 @@ class LayerPlan(C.Structure):
                                      "vstart", "dcur", "dnxt", "dz", "dab", "dh", "d_o", "dqkv", "attn_ws")]
         + [("attn_ws_bytes", C.c_size_t), ("gemm_ws", C.c_void_p), ("gemm_ws_bytes", C.c_size_t), ("tail", TailRows)]
     )
+
+
+class NormGrads(C.Structure):
+    """Mirror of `fvqa_norm_grads` (include/fvqa.h)."""
+    _fields_ = [("d_an", _pp), ("d_fn", _pp), ("d_norm", C.c_void_p), ("dw_ws", C.c_void_p), ("dw_ws_bytes", C.c_size_t)]
 
 
 ERRORS = {-1: "FVQA_EINVAL (null pointer / bad enum)", -2: "FVQA_ESHAPE (unsupported dimension)",

@@ -357,6 +357,31 @@ def rmsnorm_bwd(g, x, w, rstd, dx, resid=None, rows: Optional[int] = None):
     return dx
 
 
+def rmsnorm_dw_workspace(rows: int, dim: int, dtype=None) -> int:
+    """Bytes of workspace fvqa_rmsnorm_dw needs for (rows, dim); 0: a shape it refuses."""
+    return int(_lib.load(dtype).fvqa_rmsnorm_dw_workspace(int(rows), int(dim)))
+
+
+def rmsnorm_dw(g, x, rstd, dw, ws, accumulate: bool = True, rows: Optional[int] = None):
+    """dw (dim,) fp32 (+)= sum_r g[r] * round_to_storage(x[r] * rstd[r]): the gradient of an RMSNorm's weight (include/fvqa.h).
+    ws: a uint8 device buffer of at least rmsnorm_dw_workspace(rows, dim) bytes."""
+    _dev(g, x, rstd, dw, ws)
+    dim = x.shape[-1]
+    rows = rows if rows is not None else x.numel() // dim
+    _need(g.dtype == x.dtype, "rmsnorm_dw: dtype")
+    for t in (g, x):
+        _need(t.shape[-1] == dim and t.numel() >= rows * dim, "rmsnorm_dw: shape")
+    _need(rstd.dtype == torch.float32 and rstd.numel() >= rows, "rmsnorm_dw: rstd")
+    _need(dw.dtype == torch.float32 and dw.numel() == dim, "rmsnorm_dw: dw")
+    lib = _lib.load(g.dtype)
+    need = int(lib.fvqa_rmsnorm_dw_workspace(rows, dim))
+    _need(ws.dtype == torch.uint8 and (need == 0 or ws.numel() >= need), "rmsnorm_dw: workspace")
+    rc = lib.fvqa_rmsnorm_dw(_ptr(g), _ptr(x), _ptr(rstd), _ptr(dw), _ptr(ws), ws.numel(), rows, dim, int(bool(accumulate)),
+                             dt_code(x.dtype), _stream())
+    _lib.check(rc, "fvqa_rmsnorm_dw")
+    return dw
+
+
 def rope_qk(qkv, cos_t, sin_t, n_seq: int, seq_len: int, n_heads: int, head_dim: int, inverse: bool = False):
     _dev(qkv, cos_t, sin_t)
     dim = n_heads * head_dim

@@ -80,6 +80,8 @@ class FusedAdamW(torch.optim.Optimizer):
             for lo, hi in ranges:
                 ops.adamw_step(f.flat[lo:hi], f.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
                                g["lr"], b1, b2, g["eps"], g["weight_decay"], self.step_dev, fi)
+        if hasattr(f, "after_update"):           # --train_norm: the norm weights' working copies follow their masters (a skipped
+            f.after_update()                     # step leaves the masters, and so the copies, as they were)
         if found_inf is None:                    # stand-alone use: advance the step here
             self.found_inf.zero_()
             ops.scaler_update(self.step_dev, None, None, self.found_inf)

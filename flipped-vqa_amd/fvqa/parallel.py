@@ -81,6 +81,8 @@ class DataParallel(torch.nn.Module):
         of the audio modes (audio_proj, the cross-attention): randomly initialised, outside every checkpoint and — seeded
         seed+rank — different on every rank until here. torch DDP's constructor broadcasts frozen parameters too."""
         self._bcast(self.module.flat_params().flat)
+        if getattr(self.module, "train_norm", False):          # --train_norm: the norm masters came with the flat buffer; the
+            self.module.refresh_norm_working()                 # storage-dtype working copies the kernels read follow them
         if getattr(self.module, "train_audio", False):         # --train_audio: they are segments of the flat buffer
             return
         eng = getattr(self.module, "_engine", None)

@@ -232,6 +232,7 @@ class StepEngine:
         if self.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise TypeError(f"frozen weights must be float32, bfloat16 or float16, got {self.dtype}")
         self.pack = FrozenPack(model, self.layer_ids)
+        self._pack_norm(model)
         cos, sin = model.rope_tables()
         self.cos = cos.to(self.device).contiguous()
         self.sin = sin.to(self.device).contiguous()
@@ -247,6 +248,30 @@ class StepEngine:
         self.lm_head_rows = "all" if os.environ.get("FVQA_LM_HEAD", "scored") == "all" else "scored"
         self.audio = model.audio_mode
         self._pack_front(model)
+
+    # ------------------------------------------------------------------ --train_norm: masters and working copies
+    def _pack_norm(self, model):
+        """--train_norm: the norm weights' fp32 masters are one (2L + 1, D) block of the flat buffer (an | fn | the final norm);
+        the kernels — the step, generation, option scoring, the stream: all read pack.an / fn / norm — keep reading storage-dtype
+        rows, here the rows of ONE working block that `refresh_norm` rewrites from the masters in one launch. In the fp32 build
+        the working block is the masters themselves. No launch may read a working copy older than its master: whoever writes
+        the masters calls Transformer.refresh_norm_working (FusedAdamW.step, misc.load_model, DataParallel.broadcast_params)."""
+        self.train_norm = bool(getattr(model, "train_norm", False))
+        self.norm_master = self.norm_work = None
+        if not self.train_norm:
+            return
+        L = self.L
+        self.norm_master = model._flat.norm_block(model._flat.flat)
+        self.norm_work = self.norm_master if self.dtype == torch.float32 else \
+            torch.empty(2 * L + 1, self.D, dtype=self.dtype, device=self.device)
+        self.pack.an = [self.norm_work[i] for i in range(L)]
+        self.pack.fn = [self.norm_work[L + i] for i in range(L)]
+        self.pack.norm = self.norm_work[2 * L]
+        self.refresh_norm()
+
+    def refresh_norm(self):
+        if self.train_norm and self.norm_work is not self.norm_master:
+            ops.cast_rows(self.norm_master, self.norm_work)
 
     # ------------------------------------------------------------------ front end (llama/model.py:306-324)
     def _pack_front(self, model):
@@ -414,6 +439,31 @@ class StepEngine:
         plan.gemm_ws, plan.gemm_ws_bytes = ws.data_ptr(), ws.numel()
         ar._plan, ar._plan_keep, ar._plan_key = plan, keep + [ws], key
         return plan
+
+    def dw_workspace(self, ar: "Arena") -> torch.Tensor:
+        """The arena's workspace of fvqa_rmsnorm_dw (--train_norm only: made on first use)."""
+        if getattr(ar, "dw_ws", None) is None:
+            # (R + 16: the tail rows carry one pad row per stream, so a batch scored on every row has a few more than R)
+            ar.dw_ws = torch.empty(ops.rmsnorm_dw_workspace(ar.R + 16, self.D, self.dtype), dtype=torch.uint8, device=self.device)
+        return ar.dw_ws
+
+    def norm_grad_rows(self, grads: "FlatParams"):
+        """(d_an rows, d_fn rows, d_norm) of the flat gradient's norm block."""
+        g, L = grads.norm_block(grads.flat_grad), self.L
+        return [g[i] for i in range(L)], [g[L + i] for i in range(L)], g[2 * L]
+
+    def norm_grads(self, ar: "Arena", grads: "FlatParams"):
+        """fvqa_norm_grads for this arena and gradient buffer (built once, cached on the arena)."""
+        key = grads.flat_grad.data_ptr()
+        if getattr(ar, "_ng_key", None) == key:
+            return ar._ng
+        d_an, d_fn, d_norm = self.norm_grad_rows(grads)
+        ws = self.dw_workspace(ar)
+        tabs = [(C.c_void_p * self.L)(*[t.data_ptr() for t in rows]) for rows in (d_an, d_fn)]
+        ng = _lib.NormGrads(C.cast(tabs[0], C.POINTER(C.c_void_p)), C.cast(tabs[1], C.POINTER(C.c_void_p)), d_norm.data_ptr(),
+                            ws.data_ptr(), ws.numel())
+        ar._ng, ar._ng_keep, ar._ng_key = ng, tabs, key
+        return ng
 
     @staticmethod
     def use_native_schedule() -> bool:
@@ -655,8 +705,14 @@ class StepEngine:
             plan = self.layer_plan(ar, grads, sv["vstart"])
             self._plan_tail(plan, ar, tl)
             out = C.c_void_p()
-            _lib.check(_lib.load(self.dtype).fvqa_layers_bwd(C.addressof(plan), dxnf.data_ptr(), C.addressof(out),
-                                                   torch.cuda.current_stream().cuda_stream), "fvqa_layers_bwd")
+            if self.train_norm:
+                ng = self.norm_grads(ar, grads)
+                _lib.check(_lib.load(self.dtype).fvqa_layers_bwd_norm(C.addressof(plan), dxnf.data_ptr(), C.addressof(out),
+                                                                       C.addressof(ng), torch.cuda.current_stream().cuda_stream),
+                           "fvqa_layers_bwd_norm")
+            else:
+                _lib.check(_lib.load(self.dtype).fvqa_layers_bwd(C.addressof(plan), dxnf.data_ptr(), C.addressof(out),
+                                                       torch.cuda.current_stream().cuda_stream), "fvqa_layers_bwd")
             cur = ar.da if out.value == ar.da.data_ptr() else ar.db
         else:
             cur = self._layers_bwd_py(ar, grads, sv, n_seq, S, tl)
@@ -676,10 +732,16 @@ class StepEngine:
         R = ar.R
         cur, nxt = ar.da, ar.db
         t = ar.dz.view(-1)[: R * D].view(R, D)
+        # --train_norm: one rmsnorm_dw (+=) in front of each rmsnorm_bwd, on its g, x and rstd (csrc/schedule.hip, same calls)
+        dw = (lambda g, x, rstd, out, rows: None) if not self.train_norm else \
+            (lambda g, x, rstd, out, rows, ws=self.dw_workspace(ar): ops.rmsnorm_dw(g, x, rstd, out, ws, True, rows=rows))
+        d_an, d_fn, d_norm = self.norm_grad_rows(grads) if self.train_norm else (None, None, None)
         if tl is not None:
             M = tl.M
+            dw(ar.dxnf_c[:M], ar.xl_c[:M], ar.rstdN_c[:M], d_norm, M)
             ops.rmsnorm_bwd(ar.dxnf_c[:M], ar.xl_c[:M], pk.norm, ar.rstdN_c[:M], ar.dcur_c[:M], rows=M)
         else:
+            dw(ar.dxnf, ar.xs[L], ar.rstdN, d_norm, R)
             ops.rmsnorm_bwd(ar.dxnf, ar.xs[L], pk.norm, ar.rstdN, cur, rows=R)
         g_adapter = grads.grad_view("adapter_query.weight").view(-1, A, D)
         st = ops.swiglu_st()                 # (FVQA_SWIGLU_AB=1 switches BOTH schedules to the a, b form)
@@ -688,6 +750,7 @@ class StepEngine:
                 M = tl.M
                 ops.gemm_nt_swiglu_bwd(ar.dcur_c[:M], pk.w2_t[i], ar.ab_c[:M], ar.dab_c[:M], st=st)
                 ops.gemm_nt(ar.dab_c[:M], pk.w13_t[i], ar.dt_c[:M])
+                dw(ar.dt_c[:M], ar.h_c[:M], ar.rstd2_c[:M], d_fn[i] if d_fn else None, M)
                 ops.rmsnorm_bwd(ar.dt_c[:M], ar.h_c[:M], pk.fn[i], ar.rstd2_c[:M], ar.dh_c[:M], resid=ar.dcur_c[:M], rows=M)
                 ops.gemm_nt(ar.dh_c[:M], pk.wo_t[i], ar.do_c[:M])
                 ops.scatter_rows(ar.do_c[:M], ar.do, tl.scatter)
@@ -699,6 +762,7 @@ class StepEngine:
                 else:
                     ops.gemm_nt_swiglu_bwd(cur, pk.w2_t[i], ar.ab[i], ar.dab, st=st)
                 ops.gemm_nt(ar.dab, pk.w13_t[i], t)
+                dw(t, ar.h[i], ar.rstd2[i], d_fn[i] if d_fn else None, R)
                 ops.rmsnorm_bwd(t, ar.h[i], pk.fn[i], ar.rstd2[i], ar.dh, resid=cur, rows=R)
                 ops.gemm_nt(ar.dh, pk.wo_t[i], ar.do)
             g1, g2 = m.gate_views(i)
@@ -712,6 +776,7 @@ class StepEngine:
                              dg2, ar.attn_ws, n_seq, S, H, Dh, A, F)
                 ops.rope_qk(ar.dqkv, self.cos, self.sin, n_seq, S, H, Dh, inverse=True)
             ops.gemm_nt(ar.dqkv[:R], pk.wqkv_t[i], t)
+            dw(t, ar.xs[i], ar.rstd1[i], d_an[i] if d_an else None, R)
             ops.rmsnorm_bwd(t, ar.xs[i], pk.an[i], ar.rstd1[i], nxt, resid=ar.dh, rows=R)
             cur, nxt = nxt, cur
         # layer 0's adapter-query gradient rows (+=): nothing left to ride on
@@ -786,6 +851,20 @@ class FlatParams:
                 raise ValueError(f"flat segments {names} are not adjacent and alike")
             off += sz
         return buf[off0:off].view((len(names) * shape[0],) + tuple(shape[1:]))
+
+    def norm_block(self, buf):
+        """--train_norm: the (2L + 1, D) block of `buf` (the flat parameter or gradient buffer) that holds the walked layers'
+        attention_norm rows, their ffn_norm rows and the final norm — one contiguous range, 16-byte aligned."""
+        from . import synth
+        names = synth.norm_train_names(self.model.engine_layer_ids())
+        blk = self.span(names, buf).view(len(names), -1)
+        if blk.data_ptr() % 16:
+            raise ValueError("the norm block of the flat buffer is not 16-byte aligned")
+        return blk
+
+    def after_update(self):
+        """The flat parameter buffer was written (an optimizer step, a load, a broadcast): what is derived from it follows."""
+        self.model.refresh_norm_working()
 
     def gate_grad_views(self, i):
         li = self.model.engine_layer_ids()[i]

@@ -175,10 +175,21 @@ TRAINABLE_MARKS = ("gate", "adapter", "temporal_emb", "visual_proj")   # referen
 AUDIO_TRAIN_PREFIXES = ("audio_proj.", "video_audio_cross_attn.")    # what --train_audio adds: the filter above misses them
 
 
-def is_trainable(name: str, train_audio: bool = False) -> bool:
+def norm_train_names(layer_ids) -> list:
+    """What --train_norm adds, in the order of the flat buffer's (2L + 1, D) block: attention_norm of the walked layers, their
+    ffn_norm, the final norm."""
+    return [f"layers.{i}.attention_norm.weight" for i in layer_ids] + [f"layers.{i}.ffn_norm.weight" for i in layer_ids] + \
+        ["norm.weight"]
+
+
+def is_trainable(name: str, train_audio: bool = False, train_norm=None) -> bool:
     """The reference's freeze filter; with `train_audio` (--train_audio, a deviation from the reference) the audio half of the
-    front end trains as well."""
-    return any(m in name for m in TRAINABLE_MARKS) or (train_audio and name.startswith(AUDIO_TRAIN_PREFIXES))
+    front end trains as well; with `train_norm` (--train_norm, another one: the ids of the layers the engine walks,
+    Transformer.engine_layer_ids()) the RMSNorm weights of those layers and the final norm do. A layer the reference never
+    walks gets no gradient there either: its norms stay frozen."""
+    if any(m in name for m in TRAINABLE_MARKS) or (train_audio and name.startswith(AUDIO_TRAIN_PREFIXES)):
+        return True
+    return train_norm is not None and train_norm is not False and name in norm_train_names(train_norm)
 
 
 def make_tensor(cfg: SynthConfig, name: str, shape, kind: str, device="cpu") -> torch.Tensor:

@@ -177,6 +177,10 @@ class Transformer(nn.Module):
         # (`concat` and the video-only model have no frozen audio part: nothing changes there)
         self.train_audio = bool(getattr(args, "train_audio", False)) and self.audio_mode in ("only", "sum", "attention")
 
+        # --train_norm: the RMSNorm weights of the walked layers and the final norm train: fp32 masters in the flat buffer, the
+        # kernels read a storage-dtype working block the step engine refreshes after every update (fvqa/step.py)
+        self.train_norm = bool(getattr(args, "train_norm", False))
+
         self.tokenizer = Tokenizer(model_path=f"{args.llama_model_path}./tokenizer.model", args=args)
         self.eos_id = self.tokenizer.eos_id
         self.answer_token_id = self.tokenizer.a_token_id
@@ -229,9 +233,9 @@ class Transformer(nn.Module):
         return g[li, 0], g[li, 1]
 
     def is_trainable(self, name: str) -> bool:
-        """The freeze policy of THIS model: the reference's name filter, widened by --train_audio."""
+        """The freeze policy of THIS model: the reference's name filter, widened by --train_audio and --train_norm."""
         from fvqa import synth
-        return synth.is_trainable(name, self.train_audio)
+        return synth.is_trainable(name, self.train_audio, self.engine_layer_ids() if self.train_norm else None)
 
     def flat_trainable_names(self):
         """The trainables FlatParams lays out ahead of the gates, in buffer order (no visual_proj in the audio-only model). With
@@ -243,7 +247,17 @@ class Transformer(nn.Module):
             names.append("audio_proj.weight")
             if self.audio_mode == "attention":
                 names += [f"video_audio_cross_attn.{m}.{w}" for w in ("weight", "bias") for m in ("query", "key", "value")]
+        if self.train_norm:         # last ahead of the gates: one contiguous (2L + 1, D) block, an | fn | the final norm
+            from fvqa import synth
+            names += synth.norm_train_names(self.engine_layer_ids())
         return names
+
+    def refresh_norm_working(self):
+        """--train_norm: the storage-dtype working copies of the norm weights <- their fp32 masters. Called wherever the masters
+        are written: the optimizer step, a checkpoint load, the data-parallel broadcast (a no-op without the flag or before the
+        engine exists — its construction makes the first copies)."""
+        if self.train_norm and self._engine is not None:
+            self._engine.refresh_norm()
 
     def trainable_parameters(self):
         return [p for p in self.parameters() if p.requires_grad]

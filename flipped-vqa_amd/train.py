@@ -67,6 +67,9 @@ _FLAGS = [
     # MI355X build additions
     ("--train_audio", dict(action="store_true", help="train (and checkpoint) audio_proj and the audio-video cross-attention, "
                                                      "which the reference's freeze filter leaves at their random initialisation")),
+    ("--train_norm", dict(action="store_true", help="train (and checkpoint) the RMSNorm weights of the layers the adapter walks and "
+                                                    "the final norm, which the reference's freeze filter keeps frozen: fp32 masters "
+                                                    "beside the other trainables, no weight decay (they are 1-D)")),
     ("--gen_stop_eos", dict(action="store_true", help="generation-task validation decodes through fvqa.generate.generate: each "
                                                       "sample stops at its EOS and the batch stops when every sample has")),
     ("--num_beams", dict(type=int, default=1, help="generation-task validation: beam search with N slots per sample "
@@ -400,8 +403,13 @@ def main(args):
     print("accumulate grad iterations: %d" % args.accum_iter)
     print("effective batch size: %d" % eff_batch_size)
 
-    optimizer = FusedAdamW(param_groups_weight_decay(model_without_ddp, args.weight_decay), lr=args.lr,
-                           betas=(0.9, 0.95), flat=model_without_ddp.flat_params())
+    groups = param_groups_weight_decay(model_without_ddp, args.weight_decay)
+    if getattr(model_without_ddp, "train_norm", False):       # the norm weights are 1-D: the rule above leaves them undecayed
+        own = dict(model_without_ddp.named_parameters())
+        no_decay = {id(p) for p in groups[0]["params"]}
+        assert all(id(own[n]) in no_decay for n in synth.norm_train_names(model_without_ddp.engine_layer_ids())), \
+            "--train_norm: a norm weight landed in the weight-decay group"
+    optimizer = FusedAdamW(groups, lr=args.lr, betas=(0.9, 0.95), flat=model_without_ddp.flat_params())
     if args.distributed:
         model = DataParallel(model)
         optimizer.grad_sync = model.sync_grads

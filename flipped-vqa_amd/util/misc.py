@@ -334,6 +334,8 @@ def load_model(args, model_without_ddp, optimizer, loss_scaler):
         for n, t in ckpt["model"].items():
             if n in own:
                 own[n].copy_(t.to(own[n].device, own[n].dtype))
+    if hasattr(model_without_ddp, "refresh_norm_working"):       # --train_norm: the working copies follow the loaded masters
+        model_without_ddp.refresh_norm_working()
     print(f"Resume checkpoint {args.resume}")
     if "optimizer" in ckpt and "epoch" in ckpt and not getattr(args, "eval", False):
         optimizer.load_state_dict(ckpt["optimizer"])

@@ -183,9 +183,22 @@ int fvqa_gemm_timing_read(int max, float* us, double* flops, int* kind);
 /* ---- RMSNorm (llama/model.py:37-42; used :185,186,347) -------------------------------- */
 int fvqa_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int rows, int dim,
                      float eps, int dtype, void* stream);
-/* dx = (resid ? resid : 0) + rmsnorm_bwd(g; x, w, rstd)   (weight frozen ⇒ no dw) */
+/* dx = (resid ? resid : 0) + rmsnorm_bwd(g; x, w, rstd)   (no dw here: fvqa_rmsnorm_dw below, when the weight trains) */
 int fvqa_rmsnorm_bwd(const void* g, const void* x, const void* w, const float* rstd,
                      const void* resid, void* dx, int rows, int dim, int dtype, void* stream);
+/* The gradient of an RMSNorm's weight (--train_norm; the reference's autograd of llama/model.py:41-42 with the weight
+ * unfrozen). Operands as fvqa_rmsnorm_bwd: g (rows, dim) the gradient w.r.t. the norm's output, x (rows, dim) its input,
+ * rstd (rows) fp32 as fvqa_rmsnorm_fwd left it; dw (dim) fp32:
+ *     dw[c] (+)= sum_r  g[r,c] * round_to<T>(x[r,c] * rstd[r])
+ * — the rounding of the normalised value to the storage type T is the forward's own (`.type_as(x) * weight`) and part of
+ * the definition (identity in the fp32 build). accumulate != 0: +=, else =. Products and sums are fp32 in one fixed order
+ * without atomics: two launches give the same bits. The rows are split into chunks whose partial sums go through
+ * `workspace` (>= fvqa_rmsnorm_dw_workspace(rows, dim) bytes, 16-byte aligned, caller-owned, no initial state); a second
+ * launch adds the chunks in order. Shapes as fvqa_rmsnorm_bwd: dim % 8 == 0, dim <= 8192 (the workspace query returns 0
+ * for a shape the entry refuses). */
+size_t fvqa_rmsnorm_dw_workspace(int rows, int dim);
+int fvqa_rmsnorm_dw(const void* g, const void* x, const float* rstd, float* dw, void* workspace,
+                    size_t workspace_bytes, int rows, int dim, int accumulate, int dtype, void* stream);
 
 /* ---- RoPE on the q and k column blocks of a fused qkv buffer (llama/model.py:61-67,96).
  * qkv is (rows, 3*dim) with q at cols [0,dim), k at [dim,2dim). cos/sin are (S, head_dim/2)
@@ -1123,6 +1136,23 @@ int fvqa_layers_fwd(const fvqa_layer_plan* plan, void* stream);
 /* dxnf (R, D): gradient w.r.t. xnf. *d_x0 <- device pointer (plan->dcur or plan->dnxt) holding the
  * gradient w.r.t. xs[0]; gate / adapter gradients are accumulated into the plan's buffers. */
 int fvqa_layers_bwd(const fvqa_layer_plan* plan, const void* dxnf, void** d_x0, void* stream);
+
+/* --train_norm: where the RMSNorm weights' gradients go. d_an[i] / d_fn[i] (dim) fp32: attention_norm / ffn_norm of walked
+ * layer i; d_norm (dim): the final norm; all += (segments of the flat gradient buffer). dw_ws: the workspace of
+ * fvqa_rmsnorm_dw, >= fvqa_rmsnorm_dw_workspace(n_seq * seq_len, dim) bytes. */
+typedef struct fvqa_norm_grads {
+  float* const* d_an;        /* [n_layers] */
+  float* const* d_fn;        /* [n_layers] */
+  float* d_norm;
+  void* dw_ws;
+  size_t dw_ws_bytes;
+} fvqa_norm_grads;
+/* fvqa_layers_bwd with one fvqa_rmsnorm_dw (accumulate) queued beside each of its fvqa_rmsnorm_bwd calls, on the same g, x
+ * and rstd: the final norm, then per walked layer ffn_norm and attention_norm. With tail rows the final norm and the last
+ * layer's ffn_norm reduce over the compact rows — every other row's gradient is zero. norm_grads == NULL: exactly
+ * fvqa_layers_bwd (the same launches in the same order). */
+int fvqa_layers_bwd_norm(const fvqa_layer_plan* plan, const void* dxnf, void** d_x0, const fvqa_norm_grads* norm_grads,
+                         void* stream);
 
 /* ---- small utilities -------------------------------------------------------------------
  * dst rows [row0, row0+n_rows) of a (.., dim) storage-dtype matrix <- fp32 src (n_rows, dim)
